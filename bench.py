@@ -21,24 +21,33 @@ assembly) over that collection.
           classification, all-gather of the branching-node facts and of the SP code, all_to_all of the blue entries,
           local blue sort and assembly, final concatenation of the row ranges on rank 0.
 `value` = bases / wall time of a step with the packed text resident in HBM (on every GPU) and the result left in
-HBM (rank 0), barrier + device synchronisation on both sides, slowest rank.  Extra keys:
+HBM (rank 0), barrier + device synchronisation on both sides, slowest rank.
+
+A plain run does only what `value` needs: it generates the text, loads it, builds once cold (first_build_s) and
+--warmup - 1 times more, times --steps builds and prints the line.  Extra keys of every run:
+  first_build_s -- the cold first build (allocates the workspace);
+  link_probe    -- N > 1: all_to_all rate per peer pair measured on this node before the first build, fed to the
+                   key-path cost model (debwt_shard_key_mode) in place of its assumed link rate;
+  roofline      -- the dominant kernel (one 8-bit radix scatter pass over the keys of a range): algorithmic bytes
+                   (16 B per key: 8 read + 8 written) / mean launch time from hipEvents recorded around every such
+                   launch of the first key range on the stream it runs on, against the 8 TB/s HBM peak.
+--full adds the rest (a plain run carries these keys as null or leaves them out):
+  one_shot      -- N = 1: the cold first build as a one-shot host runs it, host text to rows in host memory;
   host_to_host  -- N = 1: the same build from the page-locked host text to the BWT and its '#'/'$' rows back in
                    page-locked host memory (SURVEY 8d's region: load + build + fetch), MEAN over as many consecutive
                    steps as `steps`;
-  link_probe    -- N > 1: all_to_all rate per peer pair measured on this node before the first build, fed to the
-                   key-path cost model (debwt_shard_key_mode) in place of its assumed link rate;
   key_modes_ms  -- N > 1, --mode auto: ms per build of the chosen key path (the timed steps) AND of the other one;
-  first_build_s -- the cold first build (allocates the workspace);
+  host_c        -- N > 1 over gloo: the C host on the same collection (on real GPUs it runs in a plain run too, and
+                   its line becomes the line of the bench when it comes back whole);
   check         -- outside the timed region: symbol census of the result against the text's (device kernel), '#' rows
                    ascending, and the inverse BWT on the device (one LF walk per text segment, debwt_verify_device);
-  roofline      -- the dominant kernel (one 8-bit radix scatter pass over the keys of a range): algorithmic bytes
-                   (16 B per key: 8 read + 8 written) / mean launch time from hipEvents recorded around every such
-                   launch of the first key range on the stream it runs on, against the 8 TB/s HBM peak;
-  cpu_baseline  -- the reference's own stage functions (oracle/_ref, compiled from /root/reference/src in the build
-                   container) on this box's host cores on a bounded prefix of record 0 (rank 0, N = 1 only);
+  cpu_baseline  -- the reference's own stage functions (oracle/_ref, compiled from the reference's sources where
+                   they lie) on this box's host cores on a bounded prefix of record 0 (rank 0, N = 1 only);
   cpu_port      -- the single-threaded CPU oracle on a prefix of the same record;
   cpu_baseline_at_configs -- the reference on the whole ecoli_4.6M and chr1_250M collections (BASELINE configs[0] and [1];
                    --no-cpu-configs leaves out the second, a minute of CPU).
+--dump-outputs DIR writes what the last timed step computed as .npy files (dump_outputs); the inputs depend on the
+arguments alone, so two builds of the project can be compared output for output.
 """
 import argparse
 import json
@@ -117,6 +126,44 @@ def cpu_reference(codes, k, threads):
         shutil.rmtree(d, ignore_errors=True)
 
 
+DUMP_SAMPLE_ROWS = 1 << 20          # rows of the BWT dumped symbol by symbol
+DUMP_BLOCK_WORDS = 1 << 16          # packed words per block sum (2^16 x 2^32 < 2^53: the sums are exact in float64)
+DUMP_SEED = 0xD0B5
+
+
+def dump_outputs(directory, words, hash_rows, dollar_row, n):
+    """--dump-outputs: the result of the last timed step, as a caller of the build receives it (packed BWT words, '#'
+    rows, '$' row), in float64 / float32 .npy files of about 12 MB at any size:
+      hash_rows.npy, dollar_row.npy -- the rows of the '#' separators and of '$' (float64: exact below 2^53);
+      bwt_sample_rows.npy           -- up to 2^20 rows drawn from [0, n) with a fixed seed, sorted, without repeats
+                                       (every row when n is smaller);
+      bwt_sample_symbols.npy        -- the 2-bit code the BWT holds at each of those rows (float32; '#' and '$' rows hold 3);
+      bwt_block_sums.npy            -- (blocks, 2): the low and the high 32 bits of the packed words summed over blocks of
+                                       2^16 words, so that every word of the result is in the dump."""
+    os.makedirs(directory, exist_ok=True)
+    nw = (n + 31) // 32
+    words = np.asarray(words)[:nw].view(np.uint64)
+    if n <= DUMP_SAMPLE_ROWS:
+        rows = np.arange(n, dtype=np.uint64)
+    else:
+        rows = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE_ROWS, dtype=np.uint64))
+    shift = (np.uint64(31) - (rows & np.uint64(31))) * np.uint64(2)
+    symbols = (words[rows >> np.uint64(5)] >> shift) & np.uint64(3)
+    sums = np.zeros(((nw + DUMP_BLOCK_WORDS - 1) // DUMP_BLOCK_WORDS, 2), dtype=np.float64)
+    chunk = DUMP_BLOCK_WORDS * 256
+    for a in range(0, nw, chunk):
+        x = words[a:a + chunk]
+        at = np.arange(0, len(x), DUMP_BLOCK_WORDS)
+        b = a // DUMP_BLOCK_WORDS
+        sums[b:b + len(at), 0] = np.add.reduceat(x & np.uint64(0xFFFFFFFF), at)
+        sums[b:b + len(at), 1] = np.add.reduceat(x >> np.uint64(32), at)
+    out = {"hash_rows": np.asarray(hash_rows, dtype=np.float64), "dollar_row": np.array([dollar_row], dtype=np.float64),
+           "bwt_sample_rows": rows.astype(np.float64), "bwt_sample_symbols": symbols.astype(np.float32),
+           "bwt_block_sums": sums}
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def emit_line(line):
     """The one JSON line, object and newline in a single write (print() issues two: another process on the same pipe can
     get in between)."""
@@ -180,6 +227,8 @@ def run_c_host(args):
         m.build()                                          # synchronous: returns when every shard's stream has drained
     dt = time.perf_counter() - t0
     ms, s0 = m.stats()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, *m.fetch(), n)
     check = None
     if not args.no_check:
         rep = m.verify_device()                            # inverse BWT of the concatenated result on the first GPU
@@ -360,7 +409,9 @@ def launch_ranks(n_ranks, args):
     if held is None:
         return rc if rc else 1
     want_other = (not nested and rc == 0 and args.mode == "auto" and not args.no_other_mode and held.get("exchange") is not None)
-    want_c = not nested and rc == 0 and args.host in (None, "both")
+    # on real GPUs the C host may give the line of the bench (promote_c_host); elsewhere it is extra information (--full)
+    real = args.backend == "nccl" and not args.launch_probe
+    want_c = not nested and rc == 0 and args.host in (None, "both") and (real or args.full)
     if not (want_other or want_c):
         emit_line(held)
         return rc
@@ -381,7 +432,7 @@ def launch_ranks(n_ranks, args):
     old = {sg: signal.signal(sg, flush_held) for sg in (signal.SIGTERM, signal.SIGINT)}
     deadline = time.perf_counter() + args.extras_timeout
     env2 = dict(env, DEBWT_BENCH_NESTED="1")
-    base = _strip_flags(own, ("--steps", "--warmup", "--mode", "--extras-timeout", "--cpu-sample", "--port-sample"))
+    base = _strip_flags(own, ("--steps", "--warmup", "--mode", "--extras-timeout", "--cpu-sample", "--port-sample", "--dump-outputs"))
     no_check = ["--no-check"] if "--no-check" in base else []
     base = [a_ for a_ in base if a_ not in ("--no-check", "--no-cpu-baseline", "--no-other-mode")]
     steps = str(max(1, min(3, held.get("steps", 1))))
@@ -414,7 +465,6 @@ def launch_ranks(n_ranks, args):
             left = deadline - time.perf_counter()
             # on real GPUs (RCCL between the ranks) the C host runs the SAME steps over RCCL -- its line becomes the line of the
             # bench when it comes back whole (promote_c_host); on the one-GPU test box (gloo) it stays a short extra over peer copies
-            real = args.backend == "nccl" and not args.launch_probe
             c_steps = [str(held.get("steps", 1)), str(held.get("warmup", 1))] if real else [steps, "1"]
             child = ([sys.executable, os.path.abspath(__file__)] + base + ["--host", "c", "--steps", c_steps[0], "--warmup", c_steps[1], "--no-cpu-baseline"]
                      + (["--exchange", "rccl"] if real and "--exchange" not in base else []) + no_check)
@@ -489,9 +539,16 @@ def main():
                          "key range); 'rescan' = every GPU reads its own copy of the text once per key range instead; "
                          "'auto' (default) = the cheaper of the two by the library's cost model (debwt_shard_key_mode); "
                          "'scan' = no bulk exchange at all; 'replicas' = N independent collections (no collective)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what `value` does not need: the one-shot first build, host_to_host, the "
+                         "checks of the result, the CPU baselines; at N > 1 the other key path and, over gloo, the C host")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if not args.full:                       # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_check, args.no_cpu_baseline, args.no_other_mode, args.h2h_reps = True, True, True, 0
     if os.environ.get("DEBWT_BENCH_NESTED") == "1" and ("WORLD_SIZE" in os.environ or args.host == "c"):
         # test hooks, seen by the extras only (an extra = a child launch that carries DEBWT_BENCH_NESTED): fail, or be slow
         if os.environ.get("DEBWT_BENCH_FAIL_EXTRA"):
@@ -554,8 +611,10 @@ def main():
     d = api.DeBWT(k=args.k, device=local_rank, sort_algo=args.sort_algo, tune=args.tune)
     # one GPU: the workspace is allocated on a thread of its own while the text is still being produced (debwt_reserve) --
     # what a one-shot host does while it reads its input.  The driver clears device memory another process released at
-    # ~33 GiB/s (profiles/r04_alloc_probe.txt); a 30 Gbp build holds ~250 GB.
-    one_shot_mode = world == 1 and not sharded and not args.no_reserve
+    # ~33 GiB/s (profiles/r04_alloc_probe.txt); a 30 Gbp build holds ~250 GB.  --full: the first build is then timed as
+    # a one-shot host runs it (`one_shot`); a plain run makes it a plain build.
+    reserve_mode = world == 1 and not sharded and not args.no_reserve
+    one_shot_mode = reserve_mode and args.full
     reserve = {"s": 0.0, "error": None}
 
     def _reserve():
@@ -567,7 +626,7 @@ def main():
         reserve["s"] = time.perf_counter() - t_r
 
     import threading
-    rthread = threading.Thread(target=_reserve) if one_shot_mode else None
+    rthread = threading.Thread(target=_reserve) if reserve_mode else None
     if rthread:
         rthread.start()
     text = SN.PinnedArray(nwords)
@@ -651,6 +710,10 @@ def main():
     total_bases = float(n) if (sharded or world == 1) else D.sum_over_ranks(n, tensor_device=tdev)
     pass_ms, pass_launches, stage = acc["pass_ms"], acc["pass_launches"], acc["stage"]
     st = d.stats()
+    if args.dump_outputs:                                  # the rows of the last timed step, before anything else runs
+        res = SH.gather_bwt(d, n, shard_ws) if sharded else (d.fetch() if rank == 0 else None)
+        if rank == 0 and res is not None:
+            dump_outputs(args.dump_outputs, *res, n)
 
     # ---- outside the timed region: checks, host-to-host figure, CPU baselines ----------------------------------------
     check = None
@@ -823,7 +886,7 @@ def main():
             child = [sys.executable, os.path.abspath(__file__), "--gpus", str(args.gpus), "--host", "c", "--backend", args.backend,
                      "--exchange", "rccl" if args.backend == "nccl" else "peer",
                      "--steps", str(args.steps), "--warmup", str(args.warmup), "--workload", args.workload, "--k", str(args.k),
-                     "--mode", args.mode if args.mode in ("auto", "exchange", "rescan") else "auto", "--no-cpu-baseline"] + (["--no-check"] if args.no_check else [])
+                     "--mode", args.mode if args.mode in ("auto", "exchange", "rescan") else "auto", "--no-cpu-baseline"] + (["--no-check"] if args.no_check else []) + (["--full"] if args.full else [])
             sys.stderr.write("bench.py: measured line of the ranks (held back for the C host): " + json.dumps(line) + "\n")
             sys.stderr.flush()
             rc3, j = _run_child(child, env2, timeout=args.extras_timeout)

@@ -162,6 +162,8 @@ def test_bench_starts_its_own_ranks_when_run_directly():
     assert len(lines) == 1, r.stdout                     # exactly one line on stdout; the ranks' chatter is on stderr
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["ranks_joined"] == 2 and "rank 1 joined" in r.stderr
+    # a plain run (no --full) starts no extras: one launch of the ranks, no other key path, no C host
+    assert r.stderr.count("rank 1 joined") == 1 and "key_modes_ms" not in j and "host_c" not in j, j
     # a launcher that started the wrong number of ranks is an error message and a non-zero exit, not an assert
     env2 = dict(env, WORLD_SIZE="3", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-check"],
@@ -177,10 +179,10 @@ def _probe(extra, env_extra=None, timeout=300):
 
 
 def test_bench_extras_are_child_launches_that_cannot_own_the_exit_code():
-    """The N > 1 extras of bench.py (the other key path, the C host) are fresh child launches after the measurement's ranks
-    have exited (--launch-probe: rendezvous only).  Recorded when they come back; text in the line and exit code 0 when they
+    """The N > 1 extras of bench.py --full (the other key path, the C host) are fresh child launches after the measurement's
+    ranks have exited (--launch-probe: rendezvous only).  Recorded when they come back; text in the line and exit code 0 when they
     fail or are not back in time; `--host=both` (one argument) is taken like `--host both` and does not recurse."""
-    r = _probe(["--host=both"])
+    r = _probe(["--host=both", "--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -188,14 +190,14 @@ def test_bench_extras_are_child_launches_that_cannot_own_the_exit_code():
     assert j["ranks_joined"] == 2 and set(j["key_modes_ms"]) >= {"exchange", "rescan"} and j["host_c"]["host"] == "c", j
     assert r.stderr.count("rank 1 joined") == 2          # the measurement's launch and the other key path's, nothing nested
 
-    r = _probe([], env_extra={"DEBWT_BENCH_FAIL_EXTRA": "1"})
+    r = _probe(["--full"], env_extra={"DEBWT_BENCH_FAIL_EXTRA": "1"})
     assert r.returncode == 0, r.stderr[-2000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
     assert "exit code" in j["key_modes_ms"]["exchange"] and "exit code" in j["host_c"]["error"], j
     assert "injected failure" in r.stderr
 
     t0 = time.perf_counter()
-    r = _probe(["--extras-timeout", "2"], env_extra={"DEBWT_BENCH_EXTRA_SLEEP": "60"})
+    r = _probe(["--full", "--extras-timeout", "2"], env_extra={"DEBWT_BENCH_EXTRA_SLEEP": "60"})
     assert r.returncode == 0 and time.perf_counter() - t0 < 50, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout
@@ -203,7 +205,7 @@ def test_bench_extras_are_child_launches_that_cannot_own_the_exit_code():
     assert "not back within" in j["key_modes_ms"]["exchange"] and "not back within" in j["host_c"]["error"], j
 
     # started by a launcher (WORLD_SIZE set): no extras at all; --host python / --no-other-mode: none either
-    r = _probe(["--host", "python", "--no-other-mode"])
+    r = _probe(["--full", "--host", "python", "--no-other-mode"])
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
     assert r.returncode == 0 and "key_modes_ms" not in j and "host_c" not in j, j
 
@@ -214,7 +216,7 @@ def test_bench_asked_to_leave_during_the_extras_prints_the_measured_line_first()
     import signal
     env = {k_: v for k_, v in os.environ.items() if k_ not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["DEBWT_BENCH_EXTRA_SLEEP"] = "120"
-    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launch-probe"], env=env,
+    p = subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--launch-probe", "--full"], env=env,
                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     err = []
     for ln in p.stderr:                                   # wait for the measurement to be over and the extras to start

@@ -28,7 +28,7 @@ def test_bench_two_ranks_started_by_bench_itself_gloo():
     collectives go over gloo), builds ONE chr1-sized collection as two k-mer-prefix shards and prints one line whose
     result passed the census and the device inverse BWT."""
     j = _run_bench_direct(["--gpus", "2", "--backend", "gloo", "--workload", "chr1_250M", "--steps", "1", "--warmup", "1",
-                           "--no-cpu-baseline"])
+                           "--no-cpu-baseline", "--full"])
     assert j["n_gpus"] == 2 and j["steps"] == 1 and j["scaling"] == "strong" and j["value"] > 0
     assert j["check"]["census_equals_text"] and j["check"]["inverse_bwt_ok"], j["check"]
     assert "chr1_250M" in j["config"]["workload"] and j["config"]["bases_per_gpu"] * 2 <= j["config"]["bases"]
@@ -42,12 +42,12 @@ def test_bench_c_host_two_shards_on_one_gpu():
     gloo), the line says which host and which exchange its number belongs to; and the default N > 1 run (python ranks first,
     then the C host as a child process) carries the C host's line under `host_c`."""
     j = _run_bench_direct(["--gpus", "2", "--backend", "gloo", "--host", "c", "--workload", "chr1_250M", "--steps", "2", "--warmup", "1",
-                           "--no-cpu-baseline"])
+                           "--no-cpu-baseline", "--full"])
     assert j["host"] == "c" and j["n_gpus"] == 2 and j["steps"] == 2 and j["value"] > 0
     assert j["check"]["inverse_bwt_ok"] and j["check"]["census_equals_text"], j["check"]
     assert "peer copies" in j["exchange"]["backend"] and j["exchange"]["keys"] in ("exchange", "rescan")
     j = _run_bench_direct(["--gpus", "2", "--backend", "gloo", "--workload", "ecoli_4.6M", "--steps", "1", "--warmup", "1",
-                           "--no-cpu-baseline", "--no-other-mode"])
+                           "--no-cpu-baseline", "--full", "--no-other-mode"])
     assert j["n_gpus"] == 2 and j["check"]["inverse_bwt_ok"] and "python" in j["host"]
     hc = j["host_c"]
     assert hc.get("host") == "c" and hc["value"] > 0 and hc["check"]["inverse_bwt_ok"], hc
@@ -70,7 +70,7 @@ def test_bench_extras_cannot_cost_the_result_when_they_are_slow():
     ends with exit code 0 and exactly the measured line, the extras recorded as dropped."""
     import json
     r = _run_bench_raw(["--gpus", "2", "--backend", "gloo", "--workload", "ecoli_4.6M", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline", "--extras-timeout", "3"], env_extra={"DEBWT_BENCH_EXTRA_SLEEP": "30"})
+                        "--no-cpu-baseline", "--full", "--extras-timeout", "3"], env_extra={"DEBWT_BENCH_EXTRA_SLEEP": "30"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -86,7 +86,7 @@ def test_bench_extras_that_fail_are_recorded_and_cost_nothing():
     `dropped: ... exit code` -- and the exit code of the run stays the measurement's: 0."""
     import json
     r = _run_bench_raw(["--gpus", "2", "--backend", "gloo", "--workload", "ecoli_4.6M", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline"], env_extra={"DEBWT_BENCH_FAIL_EXTRA": "1"})
+                        "--no-cpu-baseline", "--full"], env_extra={"DEBWT_BENCH_FAIL_EXTRA": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -105,7 +105,7 @@ def test_bench_two_ranks_started_by_bench_itself_rccl():
         pytest.skip("one GPU on this box: two RCCL ranks need two devices")
     for mode in ("exchange", "rescan"):
         j = _run_bench_direct(["--gpus", "2", "--workload", "chr1_250M", "--steps", "1", "--warmup", "1",
-                               "--no-cpu-baseline", "--mode", mode], env_extra={"DEBWT_BIG_MESSAGE_PROBE": "1"})
+                               "--no-cpu-baseline", "--full", "--mode", mode], env_extra={"DEBWT_BIG_MESSAGE_PROBE": "1"})
         assert j["n_gpus"] == 2 and j["check"]["census_equals_text"] and j["check"]["inverse_bwt_ok"], j
         assert j["link_probe"]["content_ok"] and j["link_probe"]["gbytes_per_s_per_peer"] > 0, j["link_probe"]
 
@@ -129,7 +129,7 @@ def test_bench_under_a_launcher_hands_the_line_to_the_c_host_when_it_comes_back_
     env["DEBWT_BENCH_FORCE_C_AFTER"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "ecoli_4.6M",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -140,9 +140,45 @@ def test_bench_under_a_launcher_hands_the_line_to_the_c_host_when_it_comes_back_
     env["DEBWT_BENCH_FAIL_EXTRA"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--workload", "ecoli_4.6M",
-                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith('{"metric"')]
     assert len(lines) == 1, r.stdout[-2000:]
     j = json.loads(lines[0])
     assert "host_python" not in j and j["check"]["inverse_bwt_ok"] and "exit code" in j["host_c"]["error"], j.get("host_c")
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line of K timed steps and none of the extras;
+    --dump-outputs writes the rows of the last timed step -- the oracle's rows for the same collection -- and a second run
+    with the same arguments writes the same arrays."""
+    import importlib.util
+    import os
+    import numpy as np
+    from conftest import ROOT
+    from debwt_amd import synth_native as SN
+    from oracle import oracle as O
+    got = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        j = _run_bench_direct(["--gpus", "1", "--workload", "ecoli_4.6M", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)])
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0, j
+        assert j["unit"] == "Gbp/s" and j["higher_is_better"] is True and j["dtype"] == "u64", j
+        assert j["check"] is None and j["host_to_host"] is None and j["one_shot"] is None and j["cpu_baseline"] is None, j
+        assert "cpu_port" not in j and "cpu_baseline_at_configs" not in j, j
+        got.append({p.stem: np.load(p) for p in out.glob("*.npy")})
+        assert all(a.dtype in (np.float32, np.float64) for a in got[-1].values())
+        assert sum(a.nbytes for a in got[-1].values()) <= 64 << 20
+    assert got[0].keys() == got[1].keys() and all(np.array_equal(got[0][k], got[1][k]) for k in got[0])
+    syn = SN.Synth.named("ecoli_4.6M")
+    recs = [syn.codes(0)]
+    syn.close()
+    sym = O.sym_from_codes(recs)
+    assert len(sym) == j["config"]["bases"]
+    ow, oh, od, _ = O.build_bwt(sym, 32)
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    B = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(B)
+    B.dump_outputs(str(tmp_path / "oracle"), ow, oh, od, len(sym))
+    want = {p.stem: np.load(p) for p in (tmp_path / "oracle").glob("*.npy")}
+    assert want.keys() == got[0].keys() and all(np.array_equal(want[k], got[0][k]) for k in want), "dumped rows != oracle"
