@@ -1,0 +1,365 @@
+/*
+ * query.c -- deBWT-query: exact pattern search over a BWT that deBWT wrote (OUT, OUT.#, OUT.$), through the FM-index of
+ * libdebwt_hip.so (debwt_fm_*).
+ *
+ *   deBWT-query index  -i OUT [-t T] [--iupac SEED] [--device D] [--sa S] INPUT.fa[.gz]
+ *   deBWT-query count  -i OUT [--device D] PATTERNS.fa|.fq
+ *   deBWT-query locate -i OUT [--device D] [--max-hits M] PATTERNS.fa|.fq
+ *
+ * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
+ * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
+ * OUT is not INPUT's BWT.  count and locate need OUT, OUT.#, OUT.$ and OUT.sa only.  They print one TSV line per pattern:
+ * name, occurrences and (locate) the occurrences as record:offset, ascending -- records are 0-based in file order.
+ * --max-hits M lists the first M occurrences in suffix order (the count column stays the full count).  A pattern with a
+ * letter outside ACGTacgt occurs 0 times.
+ *
+ * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
+ * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
+ * that does not match OUT, OUT.# and OUT.$ is refused.
+ */
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <sys/stat.h>
+
+#include "../include/debwt_hip.h"
+
+#define SA_MAGIC 0x3141534657424544ull   /* "DEBWFSA1" */
+#define SA_HEADER_WORDS 16
+
+static void usage(void) {
+    fprintf(stderr,
+            "usage: deBWT-query index  -i OUT [-t T] [--iupac SEED] [--device D] [--sa S] INPUT.fa[.gz]\n"
+            "       deBWT-query count  -i OUT [--device D] PATTERNS.fa|.fq\n"
+            "       deBWT-query locate -i OUT [--device D] [--max-hits M] PATTERNS.fa|.fq\n"
+            "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
+            "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file\n");
+}
+
+static int parse_u64(const char *s, uint64_t *out) {
+    char *end;
+    if (!s || !*s || *s == '-') return -1;
+    unsigned long long v = strtoull(s, &end, 10);
+    if (*end) return -1;
+    *out = v;
+    return 0;
+}
+
+static char *with_suffix(const char *path, const char *suffix) {
+    size_t a = strlen(path), b = strlen(suffix);
+    char *p = malloc(a + b + 1);
+    if (!p) return NULL;
+    memcpy(p, path, a); memcpy(p + a, suffix, b + 1);
+    return p;
+}
+
+/* a whole file of u64 words; *nwords = its size / 8.  NULL when it cannot be read or its size is not a multiple of 8. */
+static uint64_t *read_words(const char *path, uint64_t *nwords) {
+    struct stat sb;
+    if (stat(path, &sb) || sb.st_size % 8) return NULL;
+    *nwords = (uint64_t)sb.st_size / 8;
+    uint64_t *w = malloc(*nwords ? *nwords * 8 : 8);
+    FILE *f = fopen(path, "rb");
+    if (!w || !f) { free(w); if (f) fclose(f); return NULL; }
+    if (*nwords && fread(w, 8, *nwords, f) != *nwords) { free(w); fclose(f); return NULL; }
+    fclose(f);
+    return w;
+}
+
+/* rows per 2-bit code of the first n rows of packed words (row j at bits 2*(31-(j&31)) of word j>>5) */
+static void census(const uint64_t *w, uint64_t n, uint64_t c[4]) {
+    c[0] = c[1] = c[2] = c[3] = 0;
+    for (uint64_t i = 0; i < (n + 31) / 32; i++) {
+        uint64_t rows = n - i * 32 < 32 ? n - i * 32 : 32;
+        uint64_t valid = rows == 32 ? 0x5555555555555555ull : (0x5555555555555555ull << (2 * (32 - rows)));
+        uint64_t lo = w[i] & valid, hi = (w[i] >> 1) & valid;
+        uint64_t c3 = (uint64_t)__builtin_popcountll(hi & lo), c2 = (uint64_t)__builtin_popcountll(hi & ~lo),
+                 c1 = (uint64_t)__builtin_popcountll(~hi & lo);
+        c[1] += c1; c[2] += c2; c[3] += c3; c[0] += rows - c1 - c2 - c3;
+    }
+}
+
+struct rows { uint64_t *words, nwords, *hash, nhash, dollar; };
+
+static int read_rows(const char *out, struct rows *r) {
+    char *ph = with_suffix(out, ".#"), *pd = with_suffix(out, ".$");
+    uint64_t nd = 0, *d = NULL;
+    memset(r, 0, sizeof *r);
+    r->words = read_words(out, &r->nwords);
+    if (ph) r->hash = read_words(ph, &r->nhash);
+    if (pd) d = read_words(pd, &nd);
+    int ok = r->words && r->hash && d && nd == 1;
+    if (ok) r->dollar = d[0];
+    else fprintf(stderr, "cannot read %s, %s and %s (deBWT's output)\n", out, ph ? ph : "OUT.#", pd ? pd : "OUT.$");
+    free(ph); free(pd); free(d);
+    return ok ? 0 : -1;
+}
+
+/* ---- index ---------------------------------------------------------------------------------------------------------- */
+
+static int cmd_index(const char *out, const char *input, uint64_t threads, int iupac, uint64_t seed, int device, uint64_t s) {
+    debwt_config cfg = {32, device, 0, 0};
+    debwt_ctx *ctx = NULL;
+    int rc = debwt_create(&cfg, &ctx);
+    if (rc) { fprintf(stderr, "debwt_create: %s\n", debwt_strerror(rc)); return 1; }
+    rc = debwt_load_fasta_opts(ctx, input, (int)threads, iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, seed);
+    if (rc) {
+        fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", input,
+                debwt_last_error(ctx));
+        debwt_destroy(ctx);
+        return 1;
+    }
+    debwt_stats st;
+    debwt_get_stats(ctx, &st);
+    struct rows r;
+    if (read_rows(out, &r)) { debwt_destroy(ctx); return 1; }
+    debwt_fm *fm = NULL;
+    if (r.nwords != (st.n + 31) / 32 || r.nhash != st.nrec - 1) {
+        fprintf(stderr, "%s is not the BWT of %s: %llu rows / %llu '#' rows expected\n", out, input,
+                (unsigned long long)st.n, (unsigned long long)(st.nrec - 1));
+        rc = DEBWT_EINVAL;
+    } else {
+        rc = debwt_fm_create(ctx, r.words, r.hash, r.dollar, (uint32_t)s, &fm);
+        if (rc) fprintf(stderr, "%s is not the BWT of %s: %s\n", out, input, debwt_last_error(ctx));
+    }
+    debwt_destroy(ctx);                                   /* the index keeps what it needs */
+    int ret = rc ? 1 : 0;
+    if (!rc) {
+        debwt_fm_info info;
+        debwt_fm_info_get(fm, &info);
+        uint64_t *buf = malloc((SA_HEADER_WORDS + info.samples) * 8);
+        char *psa = with_suffix(out, ".sa");
+        FILE *f = psa ? fopen(psa, "wb") : NULL;
+        if (buf && f) {
+            memset(buf, 0, SA_HEADER_WORDS * 8);
+            buf[0] = SA_MAGIC; buf[1] = info.n; buf[2] = info.nrec; buf[3] = info.sa_sample; buf[4] = r.dollar;
+            memcpy(buf + 5, info.census, 32);
+            buf[9] = info.samples;
+            rc = debwt_fm_samples(fm, buf + SA_HEADER_WORDS, info.samples);
+            if (rc) fprintf(stderr, "debwt_fm_samples: %s\n", debwt_fm_last_error(fm));
+            else if (fwrite(buf, 8, SA_HEADER_WORDS + info.samples, f) != SA_HEADER_WORDS + info.samples) rc = DEBWT_EIO;
+        } else rc = DEBWT_EIO;
+        if (f && fclose(f)) rc = DEBWT_EIO;
+        if (rc == DEBWT_EIO) fprintf(stderr, "cannot write %s\n", psa ? psa : "OUT.sa");
+        if (!rc) fprintf(stderr, "%s: n = %llu, %llu records, %llu samples (every %llu rows), rank %.1f ms, samples %.1f ms\n",
+                         psa, (unsigned long long)info.n, (unsigned long long)info.nrec, (unsigned long long)info.samples,
+                         (unsigned long long)info.sa_sample, info.ms_rank, info.ms_samples);
+        ret = rc ? 1 : 0;
+        free(buf); free(psa);
+        debwt_fm_destroy(fm);
+    }
+    free(r.words); free(r.hash);
+    return ret;
+}
+
+/* ---- patterns ------------------------------------------------------------------------------------------------------- */
+
+struct patterns {
+    char *seq; uint64_t len, cap;          /* sequences concatenated */
+    uint64_t *off; char **name; uint64_t n, ncap;
+};
+
+static int push_char(struct patterns *p, char c) {
+    if (p->len == p->cap) {
+        uint64_t nc = p->cap ? 2 * p->cap : 1 << 16;
+        char *s = realloc(p->seq, nc);
+        if (!s) return -1;
+        p->seq = s; p->cap = nc;
+    }
+    p->seq[p->len++] = c;
+    return 0;
+}
+
+static int push_record(struct patterns *p, const char *header) {
+    if (p->n + 1 >= p->ncap) {
+        uint64_t nc = p->ncap ? 2 * p->ncap : 1024;
+        uint64_t *o = realloc(p->off, nc * 8);
+        if (!o) return -1;
+        p->off = o;
+        char **nm = realloc(p->name, nc * sizeof(char *));
+        if (!nm) return -1;
+        p->name = nm; p->ncap = nc;
+    }
+    size_t l = strcspn(header, " \t\r\n");
+    char *nm = malloc(l + 1);
+    if (!nm) return -1;
+    memcpy(nm, header, l); nm[l] = 0;
+    p->name[p->n] = nm;
+    p->off[p->n] = p->len;
+    p->n++;
+    p->off[p->n] = p->len;
+    return 0;
+}
+
+/* FASTA (sequence over several lines) or FASTQ (4 lines per record), told apart by the first character */
+static int read_patterns(const char *path, struct patterns *p) {
+    FILE *f = fopen(path, "r");
+    if (!f) { fprintf(stderr, "cannot open %s\n", path); return -1; }
+    memset(p, 0, sizeof *p);
+    char *line = NULL;
+    size_t lcap = 0;
+    ssize_t l;
+    int fastq = -1, err = 0;
+    uint64_t lineno = 0;
+    while ((l = getline(&line, &lcap, f)) >= 0) {
+        lineno++;
+        while (l > 0 && (line[l - 1] == '\n' || line[l - 1] == '\r')) line[--l] = 0;
+        if (fastq < 0) {
+            if (!l) continue;
+            if (line[0] != '>' && line[0] != '@') { fprintf(stderr, "%s: not FASTA or FASTQ\n", path); err = 1; break; }
+            fastq = line[0] == '@';
+        }
+        if (fastq) {
+            if (!l && (lineno % 4) == 1) { lineno--; continue; }
+            switch ((int)(lineno % 4)) {
+                case 1:
+                    if (line[0] != '@') { fprintf(stderr, "%s:%llu: '@' expected\n", path, (unsigned long long)lineno); err = 1; }
+                    else err = push_record(p, line + 1) != 0;
+                    break;
+                case 2:
+                    for (ssize_t i = 0; i < l && !err; i++) err = push_char(p, line[i]) != 0;
+                    p->off[p->n] = p->len;
+                    break;
+                case 3:
+                    if (line[0] != '+') { fprintf(stderr, "%s:%llu: '+' expected\n", path, (unsigned long long)lineno); err = 1; }
+                    break;
+                default: break;
+            }
+        } else if (l && line[0] == '>') {
+            err = push_record(p, line + 1) != 0;
+        } else if (p->n) {
+            for (ssize_t i = 0; i < l && !err; i++)
+                if (line[i] != ' ' && line[i] != '\t') err = push_char(p, line[i]) != 0;
+            p->off[p->n] = p->len;
+        } else if (l) { fprintf(stderr, "%s: sequence before the first header\n", path); err = 1; }
+        if (err) break;
+    }
+    free(line);
+    fclose(f);
+    if (!err && !p->off) {                                  /* no record at all: an empty batch */
+        p->off = calloc(1, 8);
+        if (!p->off) err = 1;
+    }
+    return err ? -1 : 0;
+}
+
+static void free_patterns(struct patterns *p) {
+    for (uint64_t i = 0; i < p->n; i++) free(p->name[i]);
+    free(p->name); free(p->off); free(p->seq);
+}
+
+/* ---- count / locate -------------------------------------------------------------------------------------------------- */
+
+static int open_index(const char *out, int device, debwt_fm **fm) {
+    char *psa = with_suffix(out, ".sa");
+    uint64_t nsa = 0, *sa = psa ? read_words(psa, &nsa) : NULL;
+    struct rows r;
+    int ret = 1;
+    if (!sa || nsa < SA_HEADER_WORDS || sa[0] != SA_MAGIC) {
+        fprintf(stderr, "cannot read %s (made by deBWT-query index)\n", psa ? psa : "OUT.sa");
+        free(psa); free(sa);
+        return 1;
+    }
+    if (read_rows(out, &r)) { free(psa); free(sa); return 1; }
+    const uint64_t n = sa[1], nrec = sa[2], s = sa[3], dollar = sa[4], nsamp = sa[9];
+    uint64_t c[4];
+    if (n < 2 || nrec < 1 || !s || nsamp != (n + s - 1) / s || nsa != SA_HEADER_WORDS + nsamp || r.nwords != (n + 31) / 32 ||
+        r.nhash != nrec - 1 || r.dollar != dollar) {
+        fprintf(stderr, "%s does not belong to %s, %s.# and %s.$\n", psa, out, out, out);
+        goto done;
+    }
+    census(r.words, n, c);
+    if (memcmp(c, sa + 5, 32)) { fprintf(stderr, "%s does not belong to %s: the row census differs\n", psa, out); goto done; }
+    int rc = debwt_fm_open(device, r.words, n, r.hash, nrec, dollar, sa + SA_HEADER_WORDS, (uint32_t)s, fm);
+    if (rc) { fprintf(stderr, "debwt_fm_open: %s\n", debwt_strerror(rc)); goto done; }
+    ret = 0;
+done:
+    free(psa); free(sa); free(r.words); free(r.hash);
+    return ret;
+}
+
+static int cmp_u64(const void *a, const void *b) {
+    uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+    return x < y ? -1 : x > y;
+}
+
+static int cmd_query(const char *out, const char *pfile, int device, int locate, uint64_t max_hits) {
+    struct patterns P;
+    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    int ret = 1;
+    uint64_t *ranges = malloc((P.n ? P.n : 1) * 16), *oo = malloc((P.n + 1) * 8), *pos = NULL, *starts = NULL;
+    debwt_fm_info info;
+    debwt_fm_info_get(fm, &info);
+    starts = malloc(info.nrec * 8);
+    if (!ranges || !oo || !starts) { fprintf(stderr, "out of memory\n"); goto done; }
+    int rc = debwt_fm_count(fm, P.seq, P.off, P.n, ranges);
+    if (!rc) rc = debwt_fm_record_starts(fm, starts, info.nrec);
+    if (!rc && locate) {
+        uint64_t total = 0;
+        for (uint64_t i = 0; i < P.n; i++) {
+            uint64_t c = ranges[2 * i + 1] - ranges[2 * i];
+            total += max_hits && c > max_hits ? max_hits : c;
+        }
+        pos = malloc((total ? total : 1) * 8);
+        if (!pos) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_locate(fm, ranges, P.n, max_hits, oo, pos, total);
+    }
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    for (uint64_t i = 0; i < P.n; i++) {
+        printf("%s\t%llu", P.name[i], (unsigned long long)(ranges[2 * i + 1] - ranges[2 * i]));
+        if (locate) {
+            uint64_t *a = pos + oo[i], m = oo[i + 1] - oo[i], rec = 0;
+            qsort(a, m, 8, cmp_u64);
+            putchar('\t');
+            for (uint64_t j = 0; j < m; j++) {
+                while (rec + 1 < info.nrec && starts[rec + 1] <= a[j]) rec++;
+                printf("%s%llu:%llu", j ? "," : "", (unsigned long long)rec, (unsigned long long)(a[j] - starts[rec]));
+            }
+        }
+        putchar('\n');
+    }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(ranges); free(oo); free(pos); free(starts);
+    debwt_fm_destroy(fm);
+    free_patterns(&P);
+    return ret;
+}
+
+int main(int argc, char **argv) {
+    if (argc < 2) { usage(); return 1; }
+    const char *cmd = argv[1];
+    int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : -1;
+    if (mode < 0) { usage(); return 1; }
+    const char *out = NULL, *file = NULL;
+    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0;
+    int iupac = 0;
+    for (int i = 2; i < argc; i++) {
+        const char *a = argv[i];
+        if (a[0] != '-' || !a[1]) {
+            if (file) { usage(); return 1; }
+            file = a;
+            continue;
+        }
+        if (i + 1 >= argc) { usage(); return 1; }
+        const char *v = argv[++i];
+        if (!strcmp(a, "-i")) out = v;
+        else if (!strcmp(a, "--device")) { if (parse_u64(v, &device) || device > 255) { fprintf(stderr, "--device: a GPU ordinal\n"); return 1; } }
+        else if (mode == 0 && !strcmp(a, "-t")) {
+            if (parse_u64(v, &threads) || threads < 1) { fprintf(stderr, "-t: thread number must be a positive integer\n"); return 1; }
+            if (threads > 256) threads = 256;
+        }
+        else if (mode == 0 && !strcmp(a, "--iupac")) { if (parse_u64(v, &seed)) { fprintf(stderr, "--iupac: a seed\n"); return 1; } iupac = 1; }
+        else if (mode == 0 && !strcmp(a, "--sa")) {
+            if (parse_u64(v, &s) || s < 1 || s > 1024 || (s & (s - 1))) { fprintf(stderr, "--sa: a power of two in 1..1024\n"); return 1; }
+        }
+        else if (mode == 2 && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
+        else { usage(); return 1; }
+    }
+    if (!out || !file) { usage(); return 1; }
+    if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
+    return cmd_query(out, file, (int)device, mode == 2, max_hits);
+}

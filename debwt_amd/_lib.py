@@ -54,6 +54,16 @@ class DebwtShardReport(ctypes.Structure):
                 ("blue_rows", ctypes.c_uint64), ("rows", ctypes.c_uint64), ("bin_lo", ctypes.c_uint32), ("bin_hi", ctypes.c_uint32)]
 
 
+class DebwtFmInfo(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("n", "nrec", "sa_sample", "samples", "device_bytes")] +
+                [("ms_rank", ctypes.c_float), ("ms_samples", ctypes.c_float), ("census", ctypes.c_uint64 * 4)])
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["census"] = [int(x) for x in self.census]
+        return d
+
+
 class DebwtMultiStats(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint64), ("nrec", ctypes.c_uint64), ("ngpus", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
                 ("key_bytes_in", ctypes.c_uint64), ("blue_bytes_in", ctypes.c_uint64), ("ms_build", ctypes.c_float),
@@ -79,6 +89,8 @@ SYMBOLS = [
     "debwt_multi_set_key_mode", "debwt_special_compare", "debwt_build_to_host", "debwt_multi_set_exchange", "debwt_reserve",
     "debwt_multi_set_serial", "debwt_multi_get_shard_report", "debwt_multi_step_name", "debwt_get_config",
     "debwt_dump_reference_files", "debwt_shard_scratch",
+    "debwt_fm_create", "debwt_fm_open", "debwt_fm_last_error", "debwt_fm_info_get", "debwt_fm_samples",
+    "debwt_fm_record_starts", "debwt_fm_count", "debwt_fm_locate", "debwt_fm_destroy",
 ]
 
 
@@ -254,5 +266,24 @@ def lib():
     L.debwt_get_config.argtypes = [vp, ctypes.POINTER(DebwtConfig)]
     L.debwt_dump_reference_files.restype = ctypes.c_int
     L.debwt_dump_reference_files.argtypes = [vp, ctypes.c_char_p, ctypes.c_int]
+    L.debwt_fm_create.restype = ctypes.c_int
+    L.debwt_fm_create.argtypes = [vp, u64p, u64p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(vp)]
+    L.debwt_fm_open.restype = ctypes.c_int
+    L.debwt_fm_open.argtypes = [ctypes.c_int, u64p, ctypes.c_uint64, u64p, ctypes.c_uint64, ctypes.c_uint64, u64p,
+                                ctypes.c_uint32, ctypes.POINTER(vp)]
+    L.debwt_fm_last_error.restype = ctypes.c_char_p
+    L.debwt_fm_last_error.argtypes = [vp]
+    L.debwt_fm_info_get.restype = ctypes.c_int
+    L.debwt_fm_info_get.argtypes = [vp, ctypes.POINTER(DebwtFmInfo)]
+    L.debwt_fm_samples.restype = ctypes.c_int
+    L.debwt_fm_samples.argtypes = [vp, u64p, ctypes.c_uint64]
+    L.debwt_fm_record_starts.restype = ctypes.c_int
+    L.debwt_fm_record_starts.argtypes = [vp, u64p, ctypes.c_uint64]
+    L.debwt_fm_count.restype = ctypes.c_int
+    L.debwt_fm_count.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, u64p]
+    L.debwt_fm_locate.restype = ctypes.c_int
+    L.debwt_fm_locate.argtypes = [vp, u64p, ctypes.c_uint64, ctypes.c_uint64, u64p, u64p, ctypes.c_uint64]
+    L.debwt_fm_destroy.restype = None
+    L.debwt_fm_destroy.argtypes = [vp]
     _lib = L
     return L

@@ -182,6 +182,22 @@ class DeBWT:
         return {"inverse_bwt_ok": bool(r["ok"]), "inverse_bwt": {k: (round(v, 2) if isinstance(v, float) else v)
                                                                   for k, v in r.items() if k != "ok"}}
 
+    def fm_index(self, sa_sample=32, rows=None):
+        """FM-index of the rows (debwt_fm_create): the context's own result, or host rows = (words, hash_rows, dollar_row)
+        as fetch() returns them / OUT, OUT.#, OUT.$ hold them.  Rows that are not the BWT of the loaded text raise.  The
+        index outlives this context."""
+        h = ctypes.c_void_p()
+        if rows is None:
+            rc = self._L.debwt_fm_create(self._h, None, None, 0, int(sa_sample), ctypes.byref(h))
+        else:
+            words, hrows, drow = rows
+            words = np.ascontiguousarray(words, dtype=np.uint64)
+            hrows = np.ascontiguousarray(hrows, dtype=np.uint64)
+            rc = self._L.debwt_fm_create(self._h, _p64(words), _p64(hrows) if len(hrows) else None, int(drow),
+                                         int(sa_sample), ctypes.byref(h))
+        self._chk(rc)
+        return FMIndex(h)
+
     def special_compare(self):
         """Special-region tables of the loaded text, device module against host module: mismatching elements of
         (suffix order, keys, BWT symbols, special branches, head nodes, tail nodes) -- all zero when they agree."""
@@ -228,6 +244,109 @@ class DeBWT:
         p = ctypes.c_void_p()
         self._chk(self._L.debwt_bwt_device_ptr(self._h, ctypes.byref(p)))
         return p.value
+
+
+def _patterns(patterns):
+    """(concatenated bytes, offsets) of one str/bytes pattern or a sequence of them"""
+    if isinstance(patterns, (str, bytes, bytearray)):
+        patterns = [patterns]
+    enc = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
+    offs = np.zeros(len(enc) + 1, dtype=np.uint64)
+    if enc:
+        np.cumsum([len(p) for p in enc], out=offs[1:])
+    return b"".join(enc), offs
+
+
+class FMIndex:
+    """FM-index over built rows on one GPU (debwt_fm_*): count and locate exact patterns of A/C/G/T (either case).  Made
+    by DeBWT.fm_index() from a loaded text, or by FMIndex.open() from saved rows and samples alone.  Positions are global
+    text positions (records joined by one separator each); resolve() turns them into (record, offset)."""
+
+    def __init__(self, handle):
+        self._L = _lib.lib()
+        self._h = handle
+        info = self.info()
+        self.n, self.nrec, self.sa_sample = info["n"], info["nrec"], info["sa_sample"]
+        starts = np.empty(max(self.nrec, 1), dtype=np.uint64)
+        self._chk(self._L.debwt_fm_record_starts(self._h, _p64(starts), len(starts)))
+        self._starts = starts[:self.nrec]
+
+    @classmethod
+    def open(cls, words, n, hash_rows, dollar_row, samples, sa_sample=32, device=0):
+        """The index from rows (OUT), the '#' rows (OUT.#), the '$' row (OUT.$) and samples() of an index of them."""
+        L = _lib.lib()
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        hrows = np.ascontiguousarray(hash_rows, dtype=np.uint64)
+        samples = np.ascontiguousarray(samples, dtype=np.uint64)
+        if len(words) < (int(n) + 31) // 32 or len(samples) < (int(n) + sa_sample - 1) // sa_sample:
+            raise ValueError("rows or samples shorter than n asks for")
+        h = ctypes.c_void_p()
+        rc = L.debwt_fm_open(int(device), _p64(words), int(n), _p64(hrows) if len(hrows) else None, len(hrows) + 1,
+                             int(dollar_row), _p64(samples), int(sa_sample), ctypes.byref(h))
+        if rc:
+            raise DebwtError(rc)
+        return cls(h)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.debwt_fm_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+    def _chk(self, rc):
+        if rc:
+            raise DebwtError(rc, self._L.debwt_fm_last_error(self._h).decode())
+
+    def info(self):
+        inf = _lib.DebwtFmInfo()
+        self._chk(self._L.debwt_fm_info_get(self._h, ctypes.byref(inf)))
+        return inf.as_dict()
+
+    def samples(self):
+        """The sampled suffix array: position of row i * sa_sample, ceil(n / sa_sample) words (save it for open())."""
+        out = np.empty(self.info()["samples"], dtype=np.uint64)
+        self._chk(self._L.debwt_fm_samples(self._h, _p64(out), len(out)))
+        return out
+
+    def record_starts(self):
+        return self._starts.copy()
+
+    def ranges(self, patterns):
+        """(npat, 2) uint64 row intervals [lo, hi) of the suffixes that start with each pattern."""
+        buf, offs = _patterns(patterns)
+        out = np.zeros((len(offs) - 1, 2), dtype=np.uint64)
+        if len(out):
+            self._chk(self._L.debwt_fm_count(self._h, buf, _p64(offs), len(out), _p64(out)))
+        return out
+
+    def count(self, patterns):
+        """Occurrences of each pattern (np.uint64); empty patterns and any with a letter outside ACGTacgt: 0."""
+        r = self.ranges(patterns)
+        return r[:, 1] - r[:, 0]
+
+    def locate(self, patterns, max_per_pattern=None):
+        """Global text positions of each pattern's occurrences (the first max_per_pattern rows when capped), one uint64
+        array per pattern, in row (suffix) order."""
+        r = np.ascontiguousarray(self.ranges(patterns))
+        npat = len(r)
+        offs = np.zeros(npat + 1, dtype=np.uint64)
+        cnt = r[:, 1] - r[:, 0]
+        if max_per_pattern is not None:
+            cnt = np.minimum(cnt, np.uint64(max_per_pattern))
+        total = int(cnt.sum())
+        pos = np.empty(max(total, 1), dtype=np.uint64)
+        if npat:
+            self._chk(self._L.debwt_fm_locate(self._h, _p64(r), npat, int(max_per_pattern or 0), _p64(offs), _p64(pos),
+                                              len(pos)))
+        return [pos[int(offs[i]):int(offs[i + 1])] for i in range(npat)]
+
+    def resolve(self, positions):
+        """(record, offset) arrays of global text positions."""
+        p = np.asarray(positions, dtype=np.uint64)
+        rec = np.searchsorted(self._starts, p, side="right").astype(np.int64) - 1
+        return rec, p - self._starts[rec]
 
 
 class MultiDeBWT:

@@ -25,6 +25,7 @@
 #include "stage_kernels.h"
 #include "special_kernels.h"
 #include "verify_kernels.h"
+#include "fm_kernels.h"
 
 namespace {
 
@@ -2813,4 +2814,372 @@ extern "C" int debwt_verify_inverse(const uint64_t *bwt, uint64_t n, const uint6
         w = wk.prev;
     }
     return (p == 0 && w == -1) ? DEBWT_OK : DEBWT_EINTERNAL;
+}
+
+// ---------------------------------------------------------------------------------------------------
+// FM-index over built rows (fm_kernels.h): the verifier's rank structure, a row-sampled suffix array written by the
+// verifier's walk, batched count and locate.  The index owns its memory and stream and outlives the context.
+
+struct debwt_fm {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    std::string err;
+    u64 n = 0, nrec = 0, s = 32, nsamp = 0, dollar_row = 0;
+    u32 sh = 5;
+    u64 census[4]{};
+    DevBuf idx, rowlists, sa;    // rank lines; '#' rows then separator rows; samples
+    DevBuf q_chars, q_off, q_out, q_runs;   // query scratch, bounded by the batch sizes below
+    VIndex V{};
+    std::vector<u64> rec_starts;
+    float ms_rank = 0.f, ms_samples = 0.f;
+};
+
+namespace {
+
+constexpr u64 FM_BATCH_PATTERNS = 1ull << 20;       // patterns per count launch
+constexpr u64 FM_BATCH_CHARS = 64ull << 20;         // pattern bytes per count launch (a longer single pattern goes alone)
+constexpr u64 FM_BATCH_HITS = 1ull << 22;           // occurrences per locate launch
+
+int fm_ensure(debwt_fm *f, DevBuf &b, size_t bytes) {
+    if (bytes <= b.cap) return DEBWT_OK;
+    HIPCHK(f, hipStreamSynchronize(f->stream));
+    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    const size_t want = bytes + bytes / 4 + 256;
+    HIPCHK(f, hipMalloc(&b.p, want));
+    b.cap = want;
+    return DEBWT_OK;
+}
+#define FM_ENSURE(f, b, bytes) do { int r_ = fm_ensure((f), (b), (bytes)); if (r_) return r_; } while (0)
+
+int fm_sync(debwt_fm *f) {
+    HIPCHK(f, hipStreamSynchronize(f->stream));
+    HIPCHK(f, hipGetLastError());
+    return DEBWT_OK;
+}
+
+// a temporary device buffer, released on every way out
+struct FmTmp {
+    void *p = nullptr;
+    ~FmTmp() { if (p) (void)hipFree(p); }
+};
+
+int fm_new(int device, u64 n, u64 nrec, u32 sa_sample, debwt_fm **out, std::string *err) {
+    if (!sa_sample) sa_sample = 32;
+    if (sa_sample > 1024 || (sa_sample & (sa_sample - 1))) { *err = "sa_sample must be a power of two in 1..1024"; return DEBWT_EINVAL; }
+    if (n < 2 || nrec < 1 || nrec > n) { *err = "FM-index: n or nrec out of range"; return DEBWT_EINVAL; }
+    auto *f = new (std::nothrow) debwt_fm;
+    if (!f) return DEBWT_ENOMEM;
+    f->device = device; f->n = n; f->nrec = nrec; f->s = sa_sample;
+    f->sh = 0;
+    while ((1ull << f->sh) < sa_sample) f->sh++;
+    f->nsamp = (n + sa_sample - 1) / sa_sample;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&f->stream, hipStreamNonBlocking);
+    if (e != hipSuccess) { *err = std::string("FM-index stream: ") + hipGetErrorString(e); delete f; return DEBWT_EDEVICE; }
+    *out = f;
+    return DEBWT_OK;
+}
+
+// rank structure of packed rows in HBM (d_words, n rows) with the given '#' rows and '$' row: f->idx, f->rowlists, f->V
+int fm_build_rank(debwt_fm *f, const u64 *d_words, const std::vector<u64> &hr, u64 dollar_row) {
+    const u64 n = f->n, nrec = f->nrec;
+    if (dollar_row >= n) { f->err = "'$' row outside the BWT"; return DEBWT_EINVAL; }
+    if (hr.size() != nrec - 1) { f->err = "'#' rows: nrec - 1 rows expected"; return DEBWT_EINVAL; }
+    for (size_t i = 0; i < hr.size(); i++)
+        if (hr[i] >= n || (i && hr[i] <= hr[i - 1]) || hr[i] == dollar_row) { f->err = "'#' rows are not ascending rows of the BWT"; return DEBWT_EINVAL; }
+    std::vector<u64> sr(hr);
+    sr.insert(std::upper_bound(sr.begin(), sr.end(), dollar_row), dollar_row);
+    const u64 nlines = n / VB_ROWS + 1, nchunks = (nlines + VB_CHUNK - 1) / VB_CHUNK;
+    FM_ENSURE(f, f->idx, (size_t)nlines * VB_LINE * 8);
+    FM_ENSURE(f, f->rowlists, (size_t)(2 * nrec + 1) * 8);
+    u64 *d_hash = f->rowlists.as<u64>(), *d_srows = d_hash + nrec;
+    FmTmp tmp;
+    HIPCHK(f, hipMalloc(&tmp.p, ((size_t)nchunks * 5 + 8) * 8));
+    u64 *csum = reinterpret_cast<u64 *>(tmp.p), *totals = csum + nchunks * 5;
+    if (!hr.empty()) HIPCHK(f, hipMemcpyAsync(d_hash, hr.data(), hr.size() * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(d_srows, sr.data(), sr.size() * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(totals, 0, 64, f->stream));
+    hipEvent_t e0, e1;
+    HIPCHK(f, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    (void)hipEventRecord(e0, f->stream);
+    k_vidx_count<<<(u32)nchunks, VB_CHUNK, 0, f->stream>>>(d_words, n, nlines, d_srows, sr.size(), csum);
+    k_vidx_scan<<<1, 1024, 0, f->stream>>>(csum, nchunks, totals);
+    k_vidx_write<<<(u32)nchunks, VB_CHUNK, 0, f->stream>>>(d_words, n, nlines, d_srows, sr.size(), csum, f->idx.as<u64>());
+    (void)hipEventRecord(e1, f->stream);
+    u64 tot[5];
+    HIPCHK(f, hipMemcpyAsync(tot, totals, 40, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (!rc) (void)hipEventElapsedTime(&f->ms_rank, e0, e1);
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (rc) return rc;
+    if (tot[4] != nrec || tot[0] + tot[1] + tot[2] + tot[3] != n || tot[3] < nrec) {
+        f->err = "rank structure: row census is inconsistent"; return DEBWT_EINVAL;
+    }
+    for (int q = 0; q < 4; q++) f->census[q] = tot[q];
+    VIndex &V = f->V;
+    V = VIndex{};
+    V.idx = f->idx.as<u64>(); V.hash = d_hash; V.srows = d_srows; V.nhash = hr.size(); V.nsep = sr.size(); V.n = n;
+    V.C[0] = 0; V.C[1] = tot[0]; V.C[2] = tot[0] + tot[1]; V.C[3] = V.C[2] + tot[2];
+    V.C[4] = V.C[3] + (tot[3] - nrec); V.C[5] = n - 1;
+    V.dollar_row = dollar_row;
+    f->dollar_row = dollar_row;
+    return DEBWT_OK;
+}
+
+// positions of the rows of `runs` (host: first row, count) into host `out` (sum of the counts), in run order
+int fm_locate_runs(debwt_fm *f, const std::vector<u64> &run_row, const std::vector<u64> &run_cnt, u64 *out) {
+    const u64 nr = run_row.size();
+    if (!nr) return DEBWT_OK;
+    std::vector<u64> run_out(nr + 1, 0);
+    for (u64 k = 0; k < nr; k++) run_out[k + 1] = run_out[k] + run_cnt[k];
+    const u64 total = run_out[nr];
+    if (!total) return DEBWT_OK;
+    FM_ENSURE(f, f->q_runs, (size_t)(2 * nr + 1) * 8);
+    u64 *d_row = f->q_runs.as<u64>(), *d_out_off = d_row + nr;
+    HIPCHK(f, hipMemcpyAsync(d_row, run_row.data(), nr * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(d_out_off, run_out.data(), (nr + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    FM_ENSURE(f, f->q_out, (size_t)std::min(total, FM_BATCH_HITS) * 8);
+    for (u64 g0 = 0; g0 < total; g0 += FM_BATCH_HITS) {
+        const u64 cnt = std::min(total - g0, FM_BATCH_HITS);
+        k_fm_locate<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->V, f->sa.as<u64>(), f->sh, d_row, d_out_off, nr, g0, cnt,
+                                                              f->q_out.as<u64>());
+        HIPCHK(f, hipMemcpyAsync(out + g0, f->q_out.p, cnt * 8, hipMemcpyDeviceToHost, f->stream));
+        int rc = fm_sync(f);
+        if (rc) return rc;
+    }
+    return DEBWT_OK;
+}
+
+// first text position of every record: the rows of the '#' suffixes (C[4] .. C[4] + nrec - 2) located, sorted, + 1
+int fm_record_starts_build(debwt_fm *f) {
+    std::vector<u64> pos(f->nrec - 1);
+    if (f->nrec > 1) {
+        int rc = fm_locate_runs(f, {f->V.C[4]}, {f->nrec - 1}, pos.data());
+        if (rc) return rc;
+    }
+    std::sort(pos.begin(), pos.end());
+    f->rec_starts.assign(1, 0);
+    for (u64 p : pos) {
+        if (p + 1 >= f->n) { f->err = "'#' suffix located outside the text"; return DEBWT_EINVAL; }
+        f->rec_starts.push_back(p + 1);
+    }
+    return DEBWT_OK;
+}
+
+int fm_upload_rows(debwt_fm *f, const uint64_t *rows, FmTmp *tmp, const u64 **d_words) {
+    const size_t bytes = (size_t)((f->n + 31) >> 5) * 8;
+    HIPCHK(f, hipMalloc(&tmp->p, bytes));
+    HIPCHK(f, hipMemcpyAsync(tmp->p, rows, bytes, hipMemcpyHostToDevice, f->stream));
+    *d_words = reinterpret_cast<const u64 *>(tmp->p);
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+static int fm_create_impl(debwt_ctx *c, debwt_fm *f, const uint64_t *rows, std::vector<u64> &hr, u64 dollar_row) {
+    const u64 n = f->n;
+    FmTmp rows_tmp;
+    const u64 *d_words;
+    if (!rows) d_words = c->bwt.as<u64>();
+    else { int rc = fm_upload_rows(f, rows, &rows_tmp, &d_words); if (rc) return rc; }
+    int rc = fm_build_rank(f, d_words, hr, dollar_row);
+    if (rc) return rc;
+    // segment boundaries by backward search of the loaded text (as debwt_verify_device), then the walk with the samples
+    const u64 segments = std::min<u64>(std::max<u64>(n / 16384, 1), 1ull << 20);
+    const u64 gap = std::max<u64>(n / segments, 2);
+    const u64 nbound = n > 2 ? (n - 2) / gap : 0;
+    const u32 maxm = (u32)std::min<u64>(std::max<u64>(gap / 2, 1), 1u << 16);
+    FmTmp small;
+    HIPCHK(f, hipMalloc(&small.p, (size_t)(8 + 2 * (nbound + 2)) * 8));
+    u64 *counters = reinterpret_cast<u64 *>(small.p), *d_bounds = counters + 8;
+    HIPCHK(f, hipMemsetAsync(counters, 0, 64, f->stream));
+    FM_ENSURE(f, f->sa, (size_t)f->nsamp * 8);
+    HIPCHK(f, hipMemsetAsync(f->sa.p, 0xFF, (size_t)f->nsamp * 8, f->stream));
+    hipEvent_t e0, e1;
+    HIPCHK(f, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
+    (void)hipEventRecord(e0, f->stream);
+    std::vector<u64> found(2 * nbound), bounds;
+    if (nbound) {
+        k_vsearch<<<grid_for(nbound, 256), 256, 0, f->stream>>>(f->V, c->text.as<u64>(), c->sepbits.as<u64>(), nbound, gap, maxm,
+                                                               d_bounds, counters);
+        HIPCHK(f, hipMemcpyAsync(found.data(), d_bounds, nbound * 16, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+    }
+    bounds.push_back(0); bounds.push_back(dollar_row);
+    u64 last = 0;
+    for (u64 j = 0; j < nbound; j++)
+        if (found[2 * j] != ~0ull && found[2 * j] > last && found[2 * j] < n - 1) {
+            bounds.push_back(found[2 * j]); bounds.push_back(found[2 * j + 1]);
+            last = found[2 * j];
+        }
+    bounds.push_back(n - 1); bounds.push_back(n - 1);
+    const u64 nseg = bounds.size() / 2 - 1;
+    HIPCHK(f, hipMemcpyAsync(d_bounds, bounds.data(), bounds.size() * 8, hipMemcpyHostToDevice, f->stream));
+    k_fm_walk_samples<<<grid_for(nseg, 256), 256, 0, f->stream>>>(f->V, c->text.as<u64>(), c->sepbits.as<u64>(), d_bounds, nseg,
+                                                                  f->sh, f->sa.as<u64>(), counters);
+    (void)hipEventRecord(e1, f->stream);
+    if (dollar_row % f->s == 0) {                              // the suffix at position 0: no segment's current row
+        const u64 zero = 0;
+        HIPCHK(f, hipMemcpyAsync(f->sa.as<u64>() + dollar_row / f->s, &zero, 8, hipMemcpyHostToDevice, f->stream));
+    }
+    u64 ctr[8];
+    HIPCHK(f, hipMemcpyAsync(ctr, counters, 64, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;                          // bounds and zero are host memory
+    (void)hipEventElapsedTime(&f->ms_samples, e0, e1);
+    if (ctr[0] || ctr[1] || ctr[2] || ctr[4] != n - 1) {
+        f->err = "the rows are not the BWT of the loaded text (" + std::to_string(ctr[0]) + " symbol mismatches, " +
+                 std::to_string(ctr[1]) + " broken links, " + std::to_string(ctr[2]) + " failed searches, " +
+                 std::to_string(ctr[4]) + " of " + std::to_string(n - 1) + " steps)";
+        return DEBWT_EINVAL;
+    }
+    return fm_record_starts_build(f);
+}
+
+extern "C" int debwt_fm_create(debwt_ctx *c, const uint64_t *rows, const uint64_t *hash_rows, uint64_t dollar_row,
+                               uint32_t sa_sample, debwt_fm **out) {
+    if (!c || !out) return DEBWT_EINVAL;
+    *out = nullptr;
+    if (c->stage < ST_LOADED) { c->err = "debwt_fm_create: no text loaded"; return DEBWT_ESTATE; }
+    HIPCHK(c, hipSetDevice(c->cfg.device));
+    std::vector<u64> hr;
+    if (!rows) {                                               // the context's own result
+        if (c->stage < ST_ASSEMBLED || c->shard_world > 1) { c->err = "debwt_fm_create: no result of a one-GPU build"; return DEBWT_ESTATE; }
+        hr.resize(c->nrec);
+        if (c->nrec > 1) HIPCHK(c, hipMemcpy(hr.data(), c->hash_rows.p, (c->nrec - 1) * 8, hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&dollar_row, c->dollar.p, 8, hipMemcpyDeviceToHost));
+        hr.resize(c->nrec - 1);
+    } else {
+        if (c->nrec > 1 && !hash_rows) return DEBWT_EINVAL;
+        if (c->nrec > 1) hr.assign(hash_rows, hash_rows + (c->nrec - 1));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));               // the index's stream reads the context's text (and rows)
+    debwt_fm *f = nullptr;
+    int rc = fm_new(c->cfg.device, c->n, c->nrec, sa_sample, &f, &c->err);
+    if (rc) return rc;
+    rc = fm_create_impl(c, f, rows, hr, dollar_row);
+    if (rc) { c->err = f->err; debwt_fm_destroy(f); return rc; }
+    *out = f;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_open(int device, const uint64_t *rows, uint64_t n, const uint64_t *hash_rows, uint64_t nrec,
+                             uint64_t dollar_row, const uint64_t *samples, uint32_t sa_sample, debwt_fm **out) {
+    if (!out || !rows || !samples || (nrec > 1 && !hash_rows)) return DEBWT_EINVAL;
+    *out = nullptr;
+    std::string err;
+    debwt_fm *f = nullptr;
+    int rc = fm_new(device, n, nrec, sa_sample, &f, &err);
+    if (rc) return rc;
+    std::vector<u64> hr;
+    if (nrec > 1) hr.assign(hash_rows, hash_rows + (nrec - 1));
+    {
+        FmTmp rows_tmp;
+        const u64 *d_words;
+        rc = fm_upload_rows(f, rows, &rows_tmp, &d_words);
+        if (!rc) rc = fm_build_rank(f, d_words, hr, dollar_row);
+    }
+    for (u64 i = 0; !rc && i < f->nsamp; i++)
+        if (samples[i] >= n) { f->err = "a sample is not a text position"; rc = DEBWT_EINVAL; }
+    if (!rc) rc = fm_ensure(f, f->sa, (size_t)f->nsamp * 8);
+    if (!rc && hipMemcpy(f->sa.p, samples, (size_t)f->nsamp * 8, hipMemcpyHostToDevice) != hipSuccess) {
+        f->err = "upload of the samples"; rc = DEBWT_EDEVICE;
+    }
+    if (!rc) rc = fm_record_starts_build(f);
+    if (rc) { debwt_fm_destroy(f); return rc; }
+    *out = f;
+    return DEBWT_OK;
+}
+
+extern "C" const char *debwt_fm_last_error(const debwt_fm *f) { return f ? f->err.c_str() : ""; }
+
+extern "C" int debwt_fm_info_get(const debwt_fm *f, debwt_fm_info *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    memset(out, 0, sizeof *out);
+    out->n = f->n; out->nrec = f->nrec; out->sa_sample = f->s; out->samples = f->nsamp;
+    out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap;
+    out->ms_rank = f->ms_rank; out->ms_samples = f->ms_samples;
+    for (int q = 0; q < 4; q++) out->census[q] = f->census[q];
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_samples(debwt_fm *f, uint64_t *dst, uint64_t capacity) {
+    if (!f || !dst) return DEBWT_EINVAL;
+    if (capacity < f->nsamp) { f->err = "debwt_fm_samples: capacity below the sample count"; return DEBWT_ERANGE; }
+    HIPCHK(f, hipSetDevice(f->device));
+    HIPCHK(f, hipMemcpyAsync(dst, f->sa.p, (size_t)f->nsamp * 8, hipMemcpyDeviceToHost, f->stream));
+    return fm_sync(f);
+}
+
+extern "C" int debwt_fm_record_starts(const debwt_fm *f, uint64_t *dst, uint64_t capacity) {
+    if (!f || !dst) return DEBWT_EINVAL;
+    if (capacity < f->rec_starts.size()) return DEBWT_ERANGE;
+    memcpy(dst, f->rec_starts.data(), f->rec_starts.size() * 8);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_count(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat, uint64_t *ranges) {
+    if (!f || !offsets || (npat && !ranges)) return DEBWT_EINVAL;
+    if (!npat) return DEBWT_OK;
+    for (u64 i = 0; i < npat; i++)
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_count: offsets must not decrease"; return DEBWT_EINVAL; }
+    if (offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    HIPCHK(f, hipSetDevice(f->device));
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 p1 = p0 + 1;                                       // at least one pattern, however long
+        while (p1 < npat && p1 - p0 < FM_BATCH_PATTERNS && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS) p1++;
+        const u64 np = p1 - p0, base = offsets[p0], bytes = offsets[p1] - base;
+        FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
+        FM_ENSURE(f, f->q_off, (size_t)(np + 1) * 8);
+        FM_ENSURE(f, f->q_out, (size_t)np * 16);
+        if (bytes) HIPCHK(f, hipMemcpyAsync(f->q_chars.p, patterns + base, bytes, hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->q_off.p, offsets + p0, (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        k_fm_count<<<grid_for(np, 256), 256, 0, f->stream>>>(f->V, f->q_chars.as<u8>(), f->q_off.as<u64>(), base, np,
+                                                             f->q_out.as<u64>());
+        HIPCHK(f, hipMemcpyAsync(ranges + 2 * p0, f->q_out.p, np * 16, hipMemcpyDeviceToHost, f->stream));
+        int rc = fm_sync(f);                                   // the next batch reuses the scratch
+        if (rc) return rc;
+        p0 = p1;
+    }
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_locate(debwt_fm *f, const uint64_t *ranges, uint64_t npat, uint64_t max_per_pattern,
+                               uint64_t *out_offsets, uint64_t *positions, uint64_t capacity) {
+    if (!f || !out_offsets || (npat && !ranges)) return DEBWT_EINVAL;
+    out_offsets[0] = 0;
+    for (u64 i = 0; i < npat; i++) {
+        const u64 lo = ranges[2 * i], hi = ranges[2 * i + 1];
+        if (hi < lo || hi > f->n) { f->err = "debwt_fm_locate: a range is not a row interval of the index"; return DEBWT_EINVAL; }
+        u64 cnt = hi - lo;
+        if (max_per_pattern && cnt > max_per_pattern) cnt = max_per_pattern;
+        out_offsets[i + 1] = out_offsets[i] + cnt;
+    }
+    const u64 total = out_offsets[npat];
+    if (!total) return DEBWT_OK;
+    if (!positions || capacity < total) { f->err = "debwt_fm_locate: capacity below the reported occurrences"; return DEBWT_ERANGE; }
+    HIPCHK(f, hipSetDevice(f->device));
+    std::vector<u64> rr, rc_;
+    for (u64 p0 = 0; p0 < npat;) {                             // runs uploaded FM_BATCH_PATTERNS patterns at a time
+        const u64 p1 = std::min<u64>(npat, p0 + FM_BATCH_PATTERNS);
+        rr.clear(); rc_.clear();
+        for (u64 i = p0; i < p1; i++)
+            if (out_offsets[i + 1] > out_offsets[i]) { rr.push_back(ranges[2 * i]); rc_.push_back(out_offsets[i + 1] - out_offsets[i]); }
+        int rc = fm_locate_runs(f, rr, rc_, reinterpret_cast<u64 *>(positions) + out_offsets[p0]);
+        if (rc) return rc;
+        p0 = p1;
+    }
+    return DEBWT_OK;
+}
+
+extern "C" void debwt_fm_destroy(debwt_fm *f) {
+    if (!f) return;
+    (void)hipSetDevice(f->device);
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    for (DevBuf *b : {&f->idx, &f->rowlists, &f->sa, &f->q_chars, &f->q_off, &f->q_out, &f->q_runs})
+        if (b->p) (void)hipFree(b->p);
+    if (f->stream) (void)hipStreamDestroy(f->stream);
+    delete f;
 }

@@ -454,6 +454,42 @@ int debwt_verify_device(debwt_ctx *ctx, const uint64_t *d_words, const uint64_t 
 /* the same on the concatenated result of debwt_multi_build (first GPU; every GPU holds the text) */
 int debwt_multi_verify(debwt_multi *m, debwt_verify_report *report);
 
+/* FM-index over built rows: the verifier's rank structure (one 128-byte line per 384 rows), a suffix array sampled every
+ * sa_sample rows (a power of two in 1..1024, 0 = 32; one u64 text position per sample), batched count (one backward
+ * search per pattern) and locate (one LF walk per occurrence to the nearest sampled row: s steps expected, not bounded).
+ * An index owns its device memory and its stream; it is not re-entrant. */
+typedef struct debwt_fm debwt_fm;
+typedef struct {
+    uint64_t n, nrec, sa_sample, samples, device_bytes;
+    float ms_rank, ms_samples;
+    uint64_t census[4];      /* rows per 2-bit code, '#' and '$' rows counted as 3 (as debwt_bwt_census) */
+} debwt_fm_info;
+/* ctx: a text loaded.  rows NULL: the context's own result (after a build); else HOST packed rows (OUT) with hash_rows
+ * (OUT.#, nrec - 1 rows) and dollar_row (OUT.$).  The samples come from the verifier's walk over the loaded text, so an
+ * index is made only of rows that are the BWT of that text: otherwise DEBWT_EINVAL with the reason in debwt_last_error.
+ * The index outlives the context. */
+int debwt_fm_create(debwt_ctx *ctx, const uint64_t *rows, const uint64_t *hash_rows, uint64_t dollar_row,
+                    uint32_t sa_sample, debwt_fm **out);
+/* the same index from saved files alone (no text): rows of n symbols, nrec - 1 '#' rows, the '$' row and the
+ * ceil(n / sa_sample) samples debwt_fm_samples returned.  The rows are not checked against a text. */
+int debwt_fm_open(int device, const uint64_t *rows, uint64_t n, const uint64_t *hash_rows, uint64_t nrec,
+                  uint64_t dollar_row, const uint64_t *samples, uint32_t sa_sample, debwt_fm **out);
+const char *debwt_fm_last_error(const debwt_fm *fm);
+int debwt_fm_info_get(const debwt_fm *fm, debwt_fm_info *out);
+/* the samples (info.samples words) and the first text position of every record (nrec words, ascending) */
+int debwt_fm_samples(debwt_fm *fm, uint64_t *dst, uint64_t capacity);
+int debwt_fm_record_starts(const debwt_fm *fm, uint64_t *dst, uint64_t capacity);
+/* patterns: ASCII concatenated, pattern i = patterns[offsets[i] .. offsets[i + 1]).  ranges[2i] = lo, ranges[2i + 1] = hi:
+ * the rows of the suffixes that start with pattern i, count = hi - lo.  A/C/G/T in either case; an empty pattern or one
+ * with any other character occurs 0 times.  Large batches are cut inside. */
+int debwt_fm_count(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat, uint64_t *ranges);
+/* ranges as debwt_fm_count wrote them.  out_offsets (npat + 1): prefix sums of min(hi - lo, max_per_pattern);
+ * positions[out_offsets[i] ..]: the global text positions of pattern i's first rows, in row order.  DEBWT_ERANGE when
+ * capacity is below out_offsets[npat] (out_offsets is written first).  max_per_pattern 0 = no cap. */
+int debwt_fm_locate(debwt_fm *fm, const uint64_t *ranges, uint64_t npat, uint64_t max_per_pattern,
+                    uint64_t *out_offsets, uint64_t *positions, uint64_t capacity);
+void debwt_fm_destroy(debwt_fm *fm);
+
 #ifdef __cplusplus
 }
 #endif
