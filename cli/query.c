@@ -3,8 +3,8 @@
  * libdebwt_hip.so (debwt_fm_*).
  *
  *   deBWT-query index  -i OUT [-t T] [--iupac SEED] [--device D] [--sa S] INPUT.fa[.gz]
- *   deBWT-query count  -i OUT [--device D] PATTERNS.fa|.fq
- *   deBWT-query locate -i OUT [--device D] [--max-hits M] PATTERNS.fa|.fq
+ *   deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
+ *   deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -12,6 +12,12 @@
  * name, occurrences and (locate) the occurrences as record:offset, ascending -- records are 0-based in file order.
  * --max-hits M lists the first M occurrences in suffix order (the count column stays the full count).  A pattern with a
  * letter outside ACGTacgt occurs 0 times.
+ *
+ * --mismatches K (0..4), --both-strands and --best search with debwt_fm_search: occurrences of strings within Hamming
+ * distance K of the pattern (a letter outside ACGTacgt matches no base), also of its reverse complement, only those of
+ * the smallest distance found.  With any of them, count prints name, total and the occurrences per distance c0,..,cK;
+ * locate prints name, total and record:offset:strand:mismatches (strand + or -), ascending by (record, offset, strand),
+ * the first M of them with --max-hits M.
  *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
@@ -31,10 +37,12 @@
 static void usage(void) {
     fprintf(stderr,
             "usage: deBWT-query index  -i OUT [-t T] [--iupac SEED] [--device D] [--sa S] INPUT.fa[.gz]\n"
-            "       deBWT-query count  -i OUT [--device D] PATTERNS.fa|.fq\n"
-            "       deBWT-query locate -i OUT [--device D] [--max-hits M] PATTERNS.fa|.fq\n"
+            "       deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
+            "       deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
-            "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file\n");
+            "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
+            "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
+            "name<TAB>total<TAB>record:offset:strand:mismatches,... (locate)\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -329,14 +337,91 @@ done:
     return ret;
 }
 
+/* one located occurrence of a search hit */
+struct occ { uint64_t rec, off; uint32_t strand, mm; };
+
+static int cmp_occ(const void *a, const void *b) {
+    const struct occ *x = a, *y = b;
+    if (x->rec != y->rec) return x->rec < y->rec ? -1 : 1;
+    if (x->off != y->off) return x->off < y->off ? -1 : 1;
+    return (x->strand > y->strand) - (x->strand < y->strand);
+}
+
+static int cmd_search(const char *out, const char *pfile, int device, int locate, uint64_t max_hits, uint32_t K,
+                      uint32_t flags) {
+    struct patterns P;
+    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    int ret = 1, rc;
+    uint64_t cap = 4 * P.n + 16, *hoff = malloc((P.n + 1) * 8), *ranges = NULL, *oo = NULL, *pos = NULL, *starts = NULL;
+    uint32_t *info = NULL;
+    struct occ *occ = NULL;
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    starts = malloc(fi.nrec * 8);
+    if (!hoff || !starts) { fprintf(stderr, "out of memory\n"); goto done; }
+    for (;;) {                                            /* grow to the exact hit count on DEBWT_ERANGE */
+        free(ranges); free(info);
+        ranges = malloc(cap * 16); info = malloc(cap * 4);
+        if (!ranges || !info) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_search(fm, P.seq, P.off, P.n, K, flags, hoff, ranges, info, cap);
+        if (rc == DEBWT_ERANGE && hoff[P.n] > cap) { cap = hoff[P.n]; continue; }
+        break;
+    }
+    if (!rc) rc = debwt_fm_record_starts(fm, starts, fi.nrec);
+    const uint64_t nh = rc ? 0 : hoff[P.n];
+    uint64_t total = 0;
+    for (uint64_t h = 0; h < nh; h++) total += ranges[2 * h + 1] - ranges[2 * h];
+    if (!rc && locate) {
+        oo = malloc((nh + 1) * 8); pos = malloc((total ? total : 1) * 8); occ = malloc((total ? total : 1) * sizeof *occ);
+        if (!oo || !pos || !occ) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_locate(fm, ranges, nh, 0, oo, pos, total);
+    }
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    for (uint64_t i = 0; i < P.n; i++) {
+        uint64_t per[5] = {0, 0, 0, 0, 0}, t = 0;
+        for (uint64_t h = hoff[i]; h < hoff[i + 1]; h++) {
+            const uint64_t c = ranges[2 * h + 1] - ranges[2 * h];
+            per[info[h] & 0xFF] += c; t += c;
+        }
+        printf("%s\t%llu\t", P.name[i], (unsigned long long)t);
+        if (!locate) {
+            for (uint32_t k = 0; k <= K; k++) printf("%s%llu", k ? "," : "", (unsigned long long)per[k]);
+        } else {
+            uint64_t m = 0;
+            for (uint64_t h = hoff[i]; h < hoff[i + 1]; h++)
+                for (uint64_t j = oo[h]; j < oo[h + 1]; j++) {
+                    uint64_t lo = 0, hi = fi.nrec;             /* the record: last start <= position */
+                    while (hi - lo > 1) { uint64_t mid = (lo + hi) / 2; if (starts[mid] <= pos[j]) lo = mid; else hi = mid; }
+                    occ[m].rec = lo; occ[m].off = pos[j] - starts[lo]; occ[m].strand = (info[h] >> 8) & 1; occ[m].mm = info[h] & 0xFF;
+                    m++;
+                }
+            qsort(occ, m, sizeof *occ, cmp_occ);
+            if (max_hits && m > max_hits) m = max_hits;
+            for (uint64_t j = 0; j < m; j++)
+                printf("%s%llu:%llu:%c:%u", j ? "," : "", (unsigned long long)occ[j].rec, (unsigned long long)occ[j].off,
+                       occ[j].strand ? '-' : '+', occ[j].mm);
+        }
+        putchar('\n');
+    }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(hoff); free(ranges); free(info); free(oo); free(pos); free(occ); free(starts);
+    debwt_fm_destroy(fm);
+    free_patterns(&P);
+    return ret;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { usage(); return 1; }
     const char *cmd = argv[1];
     int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : -1;
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL;
-    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0;
-    int iupac = 0;
+    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0;
+    int iupac = 0, search = 0;
+    uint32_t flags = 0;
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
         if (a[0] != '-' || !a[1]) {
@@ -344,6 +429,8 @@ int main(int argc, char **argv) {
             file = a;
             continue;
         }
+        if (mode && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
+        if (mode && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
         if (i + 1 >= argc) { usage(); return 1; }
         const char *v = argv[++i];
         if (!strcmp(a, "-i")) out = v;
@@ -356,10 +443,15 @@ int main(int argc, char **argv) {
         else if (mode == 0 && !strcmp(a, "--sa")) {
             if (parse_u64(v, &s) || s < 1 || s > 1024 || (s & (s - 1))) { fprintf(stderr, "--sa: a power of two in 1..1024\n"); return 1; }
         }
+        else if (mode && !strcmp(a, "--mismatches")) {
+            if (parse_u64(v, &K) || K > 4) { fprintf(stderr, "--mismatches: a count in 0..4\n"); return 1; }
+            search = 1;
+        }
         else if (mode == 2 && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
     if (!out || !file) { usage(); return 1; }
     if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
+    if (search) return cmd_search(out, file, (int)device, mode == 2, max_hits, (uint32_t)K, flags);
     return cmd_query(out, file, (int)device, mode == 2, max_hits);
 }

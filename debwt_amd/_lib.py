@@ -64,6 +64,17 @@ class DebwtFmInfo(ctypes.Structure):
         return d
 
 
+class DebwtFmSearchStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("patterns", "batches", "launches", "retries", "hits", "steps", "line_reads",
+                                                 "scratch_bytes")] +
+                [("items", ctypes.c_uint64 * 5), ("ms_kernel", ctypes.c_float), ("ms_wall", ctypes.c_float)])
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["items"] = [int(x) for x in self.items]
+        return d
+
+
 class DebwtMultiStats(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint64), ("nrec", ctypes.c_uint64), ("ngpus", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
                 ("key_bytes_in", ctypes.c_uint64), ("blue_bytes_in", ctypes.c_uint64), ("ms_build", ctypes.c_float),
@@ -91,6 +102,7 @@ SYMBOLS = [
     "debwt_dump_reference_files", "debwt_shard_scratch",
     "debwt_fm_create", "debwt_fm_open", "debwt_fm_last_error", "debwt_fm_info_get", "debwt_fm_samples",
     "debwt_fm_record_starts", "debwt_fm_count", "debwt_fm_locate", "debwt_fm_destroy",
+    "debwt_fm_search", "debwt_fm_search_stats_get",
 ]
 
 
@@ -283,6 +295,11 @@ def lib():
     L.debwt_fm_count.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, u64p]
     L.debwt_fm_locate.restype = ctypes.c_int
     L.debwt_fm_locate.argtypes = [vp, u64p, ctypes.c_uint64, ctypes.c_uint64, u64p, u64p, ctypes.c_uint64]
+    L.debwt_fm_search.restype = ctypes.c_int
+    L.debwt_fm_search.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u64p,
+                                  ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
+    L.debwt_fm_search_stats_get.restype = ctypes.c_int
+    L.debwt_fm_search_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmSearchStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

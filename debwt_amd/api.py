@@ -348,6 +348,100 @@ class FMIndex:
         rec = np.searchsorted(self._starts, p, side="right").astype(np.int64) - 1
         return rec, p - self._starts[rec]
 
+    def search(self, patterns, mismatches=1, strands="forward", best=False):
+        """Hits with up to `mismatches` (0..4) substitutions among A/C/G/T (debwt_fm_search): one hit per distinct text
+        string, as its row interval, mismatch count and strand (0 forward, 1 reverse complement).  strands: "forward" or
+        "both"; best: only each pattern's hits of the smallest mismatch count.  A character outside ACGTacgt matches no
+        base.  Returns a SearchResult."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        flags = (SEARCH_BOTH_STRANDS if strands == "both" else 0) | (SEARCH_BEST_ONLY if best else 0)
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        hoff = np.zeros(npat + 1, dtype=np.uint64)
+        cap = 4 * npat + 16                                   # first estimate; grown to the exact count on DEBWT_ERANGE
+        while True:
+            ranges = np.zeros((cap, 2), dtype=np.uint64)
+            info = np.zeros(cap, dtype=np.uint32)
+            rc = self._L.debwt_fm_search(self._h, buf, _p64(offs), npat, int(mismatches), flags, _p64(hoff), _p64(ranges),
+                                         info.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cap)
+            if rc == -5 and int(hoff[npat]) > cap:
+                cap = int(hoff[npat])
+                continue
+            self._chk(rc)
+            break
+        h = int(hoff[npat])
+        return SearchResult(self, hoff, ranges[:h].copy(), (info[:h] & 0xFF).astype(np.uint8),
+                            ((info[:h] >> 8) & 1).astype(np.uint8))
+
+    def search_stats(self):
+        """What the last search did (debwt_fm_search_stats_get): items per level, rank steps and lines, kernel ms."""
+        st = _lib.DebwtFmSearchStats()
+        self._chk(self._L.debwt_fm_search_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def locate_hits(self, result, max_per_pattern=None):
+        """Text positions of a SearchResult's hits (debwt_fm_locate on its ranges): per pattern a tuple of uint64
+        positions, uint8 strands and uint8 mismatches, ascending by (position, strand).  max_per_pattern caps the rows
+        taken per pattern, in hit order (strand, mismatches, row)."""
+        r = result.ranges
+        cnt = (r[:, 1] - r[:, 0]).astype(np.uint64) if len(r) else np.zeros(0, dtype=np.uint64)
+        npat = len(result.offsets) - 1
+        if max_per_pattern is not None and len(r):
+            pat = np.repeat(np.arange(npat), np.diff(result.offsets).astype(np.int64))
+            excl = np.zeros(len(cnt) + 1, dtype=np.int64)
+            np.cumsum(cnt.astype(np.int64), out=excl[1:])
+            before = excl[:-1] - excl[result.offsets[:-1].astype(np.int64)[pat]]    # rows of the pattern's earlier hits
+            cnt = np.minimum(cnt.astype(np.int64), np.maximum(int(max_per_pattern) - before, 0)).astype(np.uint64)
+        rr = np.ascontiguousarray(np.stack([r[:, 0], r[:, 0] + cnt], axis=1) if len(r) else np.zeros((0, 2), np.uint64),
+                                  dtype=np.uint64)
+        total = int(cnt.sum())
+        offs = np.zeros(len(rr) + 1, dtype=np.uint64)
+        pos = np.empty(max(total, 1), dtype=np.uint64)
+        if len(rr):
+            self._chk(self._L.debwt_fm_locate(self._h, _p64(rr), len(rr), 0, _p64(offs), _p64(pos), len(pos)))
+        pos = pos[:total]
+        per_hit = cnt.astype(np.int64)
+        strand = np.repeat(result.strands, per_hit)
+        mism = np.repeat(result.mismatches, per_hit)
+        out = []
+        for i in range(npat):
+            a, b = int(offs[int(result.offsets[i])]), int(offs[int(result.offsets[i + 1])])
+            p, s, m = pos[a:b], strand[a:b], mism[a:b]
+            o = np.lexsort((s, p))
+            out.append((p[o], s[o], m[o]))
+        return out
+
+
+SEARCH_BOTH_STRANDS, SEARCH_BEST_ONLY = 1, 2
+
+
+class SearchResult:
+    """Hits of FMIndex.search: pattern i's hits are offsets[i] .. offsets[i + 1], ordered by (strand, mismatches, lo).
+    ranges (H x 2) row intervals [lo, hi) as FMIndex.ranges gives them; mismatches and strands per hit."""
+
+    def __init__(self, index, offsets, ranges, mismatches, strands):
+        self.index, self.offsets, self.ranges, self.mismatches, self.strands = index, offsets, ranges, mismatches, strands
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def hits(self, i):
+        """(ranges, mismatches, strands) of pattern i"""
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return self.ranges[a:b], self.mismatches[a:b], self.strands[a:b]
+
+    def count(self):
+        """occurrences per pattern: the sum of hi - lo over its hits (np.uint64)"""
+        occ = (self.ranges[:, 1] - self.ranges[:, 0]).astype(np.uint64)
+        cs = np.zeros(len(occ) + 1, dtype=np.uint64)
+        np.cumsum(occ, out=cs[1:])
+        return cs[self.offsets[1:].astype(np.int64)] - cs[self.offsets[:-1].astype(np.int64)]
+
+    def locate(self, max_per_pattern=None):
+        """FMIndex.locate_hits of this result"""
+        return self.index.locate_hits(self, max_per_pattern)
+
 
 class MultiDeBWT:
     """One BWT over several GPUs from one process (debwt_multi_*): one host thread per GPU, peer-to-peer exchanges.

@@ -26,6 +26,7 @@
 #include "special_kernels.h"
 #include "verify_kernels.h"
 #include "fm_kernels.h"
+#include "fm_search_kernels.h"
 
 namespace {
 
@@ -2829,6 +2830,8 @@ struct debwt_fm {
     u64 census[4]{};
     DevBuf idx, rowlists, sa;    // rank lines; '#' rows then separator rows; samples
     DevBuf q_chars, q_off, q_out, q_runs;   // query scratch, bounded by the batch sizes below
+    DevBuf s_items[FM_SEARCH_MAX_K + 1], s_hits, s_ctr, s_plist;   // search scratch: levels 1..K, hits, counters
+    debwt_fm_search_stats s_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -3174,12 +3177,237 @@ extern "C" int debwt_fm_locate(debwt_fm *f, const uint64_t *ranges, uint64_t npa
     return DEBWT_OK;
 }
 
+// ---- search with mismatches (fm_search_kernels.h) -------------------------------------------------------------------
+// Levels are drained depth first: a chunk of level L writes its children into level L + 1's buffer, which is drained
+// (recursively) before the next chunk of L, so K + 1 buffers of `cap` items bound the scratch whatever the patterns.
+// A chunk whose children or hits exceed a buffer is re-run in a piece sized from the counts it asked for; one item
+// asks for at most 4 * 1024 children and one hit, and the buffers hold at least that, so every chunk finishes.
+
+namespace {
+
+constexpr u64 FM_SEARCH_ITEMS = 1ull << 23;            // items per buffer (24 bytes each): 5 buffers = 960 MiB at K = 4
+
+int fm_search_buf(debwt_fm *f, DevBuf &b, size_t bytes) {  // exactly `bytes`: the documented cap is the allocation
+    if (bytes <= b.cap) return DEBWT_OK;
+    HIPCHK(f, hipStreamSynchronize(f->stream));
+    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.cap = 0; }
+    HIPCHK(f, hipMalloc(&b.p, bytes));
+    b.cap = bytes;
+    return DEBWT_OK;
+}
+
+u64 fm_env_u64(const char *name, u64 dflt) {
+    const char *e = getenv(name);
+    if (!e || !*e) return dflt;
+    const u64 v = strtoull(e, nullptr, 10);
+    return v ? v : dflt;
+}
+
+struct FmSearchRun {
+    debwt_fm *f;
+    const u8 *chars; const u64 *off; u64 base;
+    const u32 *plist; u64 nact;
+    u32 kmax;
+    u64 cap;                                             // items per buffer (children and hits)
+    u64 hint[FM_SEARCH_MAX_K + 1];
+    hipEvent_t e0, e1;
+    std::vector<u64> *hits;                              // (lo, hi, meta) triples
+};
+
+int fm_search_drain(FmSearchRun &r, u32 level, u64 count) {
+    debwt_fm *f = r.f;
+    debwt_fm_search_stats &st = f->s_stats;
+    const u64 *in = level ? f->s_items[level].as<u64>() : nullptr;
+    u64 *out = level < r.kmax ? f->s_items[level + 1].as<u64>() : nullptr;
+    u64 *ctr = f->s_ctr.as<u64>();
+    for (u64 a = 0; a < count;) {
+        const u64 c = std::min(count - a, r.hint[level]);
+        HIPCHK(f, hipMemsetAsync(ctr, 0, 32, f->stream));
+        (void)hipEventRecord(r.e0, f->stream);
+        k_fm_search<<<grid_for(c, 256), 256, 0, f->stream>>>(f->V, r.chars, r.off, r.base, r.plist, r.nact, in, a, c, level,
+                                                             r.kmax, out, out ? r.cap : 0, f->s_hits.as<u64>(), r.cap, ctr);
+        (void)hipEventRecord(r.e1, f->stream);
+        u64 h[4];
+        HIPCHK(f, hipMemcpyAsync(h, ctr, 32, hipMemcpyDeviceToHost, f->stream));
+        int rc = fm_sync(f);
+        if (rc) return rc;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, r.e0, r.e1);
+        st.ms_kernel += ms; st.launches++;
+        if (h[0] > r.cap || h[1] > r.cap) {                 // overflow: nothing of this chunk is kept
+            if (c == 1) { f->err = "debwt_fm_search: one item overflowed the search buffers"; return DEBWT_EINTERNAL; }
+            const double fit = std::min((double)r.cap / (double)std::max<u64>(h[0], 1), (double)r.cap / (double)std::max<u64>(h[1], 1));
+            r.hint[level] = std::max<u64>(1, std::min<u64>(c / 2, (u64)((double)c * fit * 0.9)));
+            st.retries++;
+            continue;
+        }
+        if (h[1]) {
+            const size_t at = r.hits->size();
+            r.hits->resize(at + 3 * h[1]);
+            HIPCHK(f, hipMemcpyAsync(r.hits->data() + at, f->s_hits.p, h[1] * 24, hipMemcpyDeviceToHost, f->stream));
+            if ((rc = fm_sync(f))) return rc;
+        }
+        st.items[level] += c; st.steps += h[2]; st.line_reads += h[3];
+        if (h[0] < r.cap / 4 && h[1] < r.cap / 4 && r.hint[level] < (1ull << 40)) r.hint[level] *= 2;
+        a += c;
+        if (h[0] && (rc = fm_search_drain(r, level + 1, h[0]))) return rc;
+    }
+    return DEBWT_OK;
+}
+
+// hits of host patterns [p0, p1) into `hits` as (lo, hi, meta) with global pattern numbers in meta's low 32 bits
+// replaced by the offset from p0 (the caller adds p0)
+int fm_search_batch(debwt_fm *f, const char *patterns, const uint64_t *offsets, u64 p0, u64 p1, u32 K, u32 flags,
+                    u64 cap, std::vector<u64> *hits) {
+    const u64 np = p1 - p0, base = offsets[p0], bytes = offsets[p1] - base;
+    const u64 nstr = (flags & DEBWT_FM_BOTH_STRANDS) ? 2 : 1;
+    FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
+    FM_ENSURE(f, f->q_off, (size_t)(np + 1) * 8);
+    if (bytes) HIPCHK(f, hipMemcpyAsync(f->q_chars.p, patterns + base, bytes, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->q_off.p, offsets + p0, (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    FmSearchRun r{};
+    r.f = f; r.chars = f->q_chars.as<u8>(); r.off = f->q_off.as<u64>(); r.base = base; r.cap = cap; r.hits = hits;
+    HIPCHK(f, hipEventCreate(&r.e0));
+    if (hipEventCreate(&r.e1) != hipSuccess) { (void)hipEventDestroy(r.e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{r.e0, r.e1};
+    const bool best = flags & DEBWT_FM_BEST_ONLY;
+    std::vector<u32> act;                                  // best only: the patterns without hits yet
+    std::vector<u8> found;
+    if (best) {
+        act.resize(np);
+        for (u64 i = 0; i < np; i++) act[i] = (u32)i;
+        found.assign(np, 0);
+    }
+    for (u32 k = best ? 0 : K; k <= K; k++) {              // one stratum, or 0..K over the patterns still without hits
+        r.kmax = k;
+        for (u32 l = 0; l <= FM_SEARCH_MAX_K; l++) r.hint[l] = ~0ull;
+        if (best) {
+            if (act.empty()) break;
+            FM_ENSURE(f, f->s_plist, act.size() * 4);
+            HIPCHK(f, hipMemcpyAsync(f->s_plist.p, act.data(), act.size() * 4, hipMemcpyHostToDevice, f->stream));
+            r.plist = f->s_plist.as<u32>(); r.nact = act.size();
+        } else {
+            r.plist = nullptr; r.nact = np;
+        }
+        const size_t before = hits->size();
+        int rc = fm_search_drain(r, 0, r.nact * nstr);
+        if (rc) return rc;
+        if (best) {
+            for (size_t h = before; h < hits->size(); h += 3) found[(u32)(*hits)[h + 2]] = 1;
+            size_t w = 0;
+            for (u32 p : act)
+                if (!found[p]) act[w++] = p;
+            act.resize(w);
+        }
+    }
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_search(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                               uint32_t max_mismatches, uint32_t flags, uint64_t *hit_offsets, uint64_t *ranges,
+                               uint32_t *hit_info, uint64_t capacity) {
+    if (!f || !offsets || !hit_offsets) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->s_stats = debwt_fm_search_stats{};
+    if (max_mismatches > FM_SEARCH_MAX_K) { f->err = "debwt_fm_search: max_mismatches must be 0..4"; return DEBWT_EINVAL; }
+    if (flags & ~(DEBWT_FM_BOTH_STRANDS | DEBWT_FM_BEST_ONLY)) { f->err = "debwt_fm_search: unknown flags"; return DEBWT_EINVAL; }
+    if (npat >> 31) { f->err = "debwt_fm_search: too many patterns"; return DEBWT_EINVAL; }
+    u64 maxlen = 0;
+    for (u64 i = 0; i < npat; i++) {
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_search: offsets must not decrease"; return DEBWT_EINVAL; }
+        maxlen = std::max<u64>(maxlen, offsets[i + 1] - offsets[i]);
+    }
+    if (maxlen > FM_SEARCH_MAX_LEN) {
+        f->err = "debwt_fm_search: a pattern is longer than " + std::to_string(FM_SEARCH_MAX_LEN) + " bytes";
+        return DEBWT_EINVAL;
+    }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    hit_offsets[0] = 0;
+    if (!npat) return DEBWT_OK;
+    HIPCHK(f, hipSetDevice(f->device));
+    // per buffer at least what one item can ask for (4 children per step, 1024 steps), so a chunk of one always fits
+    const u64 cap = std::max<u64>(fm_env_u64("DEBWT_FM_SEARCH_ITEMS", FM_SEARCH_ITEMS), 4 * FM_SEARCH_MAX_LEN + 64);
+    const u64 batch = std::min<u64>(fm_env_u64("DEBWT_FM_SEARCH_BATCH", FM_BATCH_PATTERNS), FM_BATCH_PATTERNS);
+    for (u32 l = 1; l <= max_mismatches; l++) { int rc = fm_search_buf(f, f->s_items[l], (size_t)cap * 24); if (rc) return rc; }
+    int rc = fm_search_buf(f, f->s_hits, (size_t)cap * 24);
+    if (!rc) rc = fm_search_buf(f, f->s_ctr, 64);
+    if (rc) return rc;
+    debwt_fm_search_stats &st = f->s_stats;
+    st.patterns = npat;
+    st.scratch_bytes = (u64)(max_mismatches + 1) * cap * 24;   // the buffers this call may fill
+    std::vector<u64> raw;                                  // (lo, hi, meta) with global pattern numbers
+    std::vector<u64> part;
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 p1 = p0 + 1;
+        while (p1 < npat && p1 - p0 < batch && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS) p1++;
+        part.clear();
+        if ((rc = fm_search_batch(f, patterns, offsets, p0, p1, max_mismatches, flags, cap, &part))) return rc;
+        for (size_t h = 0; h < part.size(); h += 3) {
+            const u64 meta = part[h + 2];
+            raw.push_back(part[h]); raw.push_back(part[h + 1]);
+            raw.push_back((meta & ~0xFFFFFFFFull) | ((meta & 0xFFFFFFFFull) + p0));
+        }
+        st.batches++;
+        p0 = p1;
+    }
+    // order: bucket by pattern, then (strand, mismatches, lo) inside each pattern, on up to 16 host threads
+    const u64 nh = raw.size() / 3;
+    st.hits = nh;
+    std::vector<u64> start(npat + 1, 0);
+    for (u64 h = 0; h < nh; h++) start[(u32)raw[3 * h + 2] + 1]++;
+    for (u64 i = 0; i < npat; i++) start[i + 1] += start[i];
+    for (u64 i = 0; i <= npat; i++) hit_offsets[i] = start[i];
+    if (capacity < nh || (nh && (!ranges || !hit_info))) {
+        f->err = "debwt_fm_search: capacity below the hits (hit_offsets[npat] = " + std::to_string(nh) + ")";
+        return DEBWT_ERANGE;
+    }
+    struct Hit { u64 key, lo, hi; };                       // key: strand << 8 | mismatches (hit_info)
+    std::vector<Hit> sorted(nh);
+    {
+        std::vector<u64> at(start.begin(), start.end() - 1);
+        for (u64 h = 0; h < nh; h++) {
+            const u64 meta = raw[3 * h + 2];
+            sorted[at[(u32)meta]++] = Hit{(((meta >> 56) & 1) << 8) | ((meta >> 48) & 0xFF), raw[3 * h], raw[3 * h + 1]};
+        }
+    }
+    std::vector<u64>().swap(raw);
+    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), nh / 65536 + 1}));
+    auto work = [&](unsigned t) {
+        for (u64 i = t; i < npat; i += nt)
+            std::sort(sorted.begin() + start[i], sorted.begin() + start[i + 1],
+                      [](const Hit &x, const Hit &y) { return x.key != y.key ? x.key < y.key : x.lo < y.lo; });
+    };
+    {
+        std::vector<std::thread> th;
+        for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
+        work(0);
+        for (auto &x : th) x.join();
+    }
+    for (u64 h = 0; h < nh; h++) {
+        ranges[2 * h] = sorted[h].lo; ranges[2 * h + 1] = sorted[h].hi;
+        hit_info[h] = (u32)sorted[h].key;
+    }
+    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_search_stats_get(const debwt_fm *f, debwt_fm_search_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->s_stats;
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    for (DevBuf *b : {&f->idx, &f->rowlists, &f->sa, &f->q_chars, &f->q_off, &f->q_out, &f->q_runs})
+    for (DevBuf *b : {&f->idx, &f->rowlists, &f->sa, &f->q_chars, &f->q_off, &f->q_out, &f->q_runs, &f->s_hits, &f->s_ctr,
+                      &f->s_plist})
         if (b->p) (void)hipFree(b->p);
+    for (DevBuf &b : f->s_items)
+        if (b.p) (void)hipFree(b.p);
     if (f->stream) (void)hipStreamDestroy(f->stream);
     delete f;
 }

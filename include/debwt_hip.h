@@ -488,6 +488,33 @@ int debwt_fm_count(debwt_fm *fm, const char *patterns, const uint64_t *offsets, 
  * capacity is below out_offsets[npat] (out_offsets is written first).  max_per_pattern 0 = no cap. */
 int debwt_fm_locate(debwt_fm *fm, const uint64_t *ranges, uint64_t npat, uint64_t max_per_pattern,
                     uint64_t *out_offsets, uint64_t *positions, uint64_t capacity);
+/* Search with up to max_mismatches (0..4) substitutions among A/C/G/T.  A hit is one distinct text string W, |W| = |P|,
+ * Hamming(W, P) <= K, W inside one record; a pattern character outside ACGTacgt matches no base (one mismatch whatever
+ * the text holds).  K = 0 agrees with debwt_fm_count: 0 hits, or 1 hit with count's [lo, hi).  An empty pattern has 0
+ * hits; a pattern longer than 1024 bytes or K > 4 is DEBWT_EINVAL.  DEBWT_FM_BOTH_STRANDS also searches the reverse
+ * complement (A<->T, C<->G; other characters stay mismatch characters), hits of strand 1.  DEBWT_FM_BEST_ONLY keeps per
+ * pattern only the hits of the smallest mismatch count, over both strands when both are searched (searched stratum by
+ * stratum, so deeper strata are not explored once a pattern has hits).
+ * hit_offsets (npat + 1): pattern i's hits are [hit_offsets[i], hit_offsets[i+1]), ascending by (strand, mismatches,
+ * lo).  ranges: 2 words per hit, the same layout debwt_fm_count writes, so they can go straight into debwt_fm_locate
+ * (one "pattern" per hit).  hit_info: per hit, mismatches in bits 0-7, strand in bit 8 (0 forward, 1 reverse
+ * complement).  DEBWT_ERANGE when capacity < hit_offsets[npat]; hit_offsets is written first (same protocol as
+ * debwt_fm_locate).  Device scratch is capped: (K + 1) buffers of DEBWT_FM_SEARCH_ITEMS (environment, read per call;
+ * default 2^23) items of 24 bytes, at most 960 MiB. */
+#define DEBWT_FM_BOTH_STRANDS 1u
+#define DEBWT_FM_BEST_ONLY    2u
+int debwt_fm_search(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                    uint32_t max_mismatches, uint32_t flags,
+                    uint64_t *hit_offsets, uint64_t *ranges, uint32_t *hit_info, uint64_t capacity);
+/* what the last debwt_fm_search did: work items per level (level 0: pattern x strand searches, per stratum with
+ * DEBWT_FM_BEST_ONLY), rank steps (one fm_occ4 each), rank lines read, kernel launches and the launches re-run in smaller
+ * chunks after a buffer overflowed, hits before the final sort, kernel time (events) and host wall time */
+typedef struct {
+    uint64_t patterns, batches, launches, retries, hits, steps, line_reads, scratch_bytes;
+    uint64_t items[5];
+    float ms_kernel, ms_wall;
+} debwt_fm_search_stats;
+int debwt_fm_search_stats_get(const debwt_fm *fm, debwt_fm_search_stats *out);
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
