@@ -5,6 +5,7 @@
  *   deBWT-query index  -i OUT [-t T] [--iupac SEED] [--device D] [--sa S] INPUT.fa[.gz]
  *   deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
+ *   deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -18,6 +19,11 @@
  * the smallest distance found.  With any of them, count prints name, total and the occurrences per distance c0,..,cK;
  * locate prints name, total and record:offset:strand:mismatches (strand + or -), ascending by (record, offset, strand),
  * the first M of them with --max-hits M.
+ *
+ * mems prints the maximal exact matches of at least L bases (default 19, BWA-MEM's -k; debwt_fm_mems) of every read, and
+ * with --both-strands those of its reverse complement: one line per MEM, name, strand (+ or -), qbeg, qend (0-based, end
+ * exclusive, in the read's own coordinates on both strands), occurrences and record:offset ascending.  --max-hits M lists
+ * the first M occurrences in suffix order (the count column stays the full count).  Reads without MEMs print nothing.
  *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
@@ -39,10 +45,13 @@ static void usage(void) {
             "usage: deBWT-query index  -i OUT [-t T] [--iupac SEED] [--device D] [--sa S] INPUT.fa[.gz]\n"
             "       deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
+            "       deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
-            "name<TAB>total<TAB>record:offset:strand:mismatches,... (locate)\n");
+            "name<TAB>total<TAB>record:offset:strand:mismatches,... (locate);\n"
+            "mems prints name<TAB>strand<TAB>qbeg<TAB>qend<TAB>count<TAB>record:offset,... per maximal exact match of at\n"
+            "least L bases (default 19)\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -413,13 +422,67 @@ done:
     return ret;
 }
 
+static int cmd_mems(const char *out, const char *pfile, int device, uint64_t max_hits, uint32_t min_len, uint32_t flags) {
+    struct patterns P;
+    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    int ret = 1, rc;
+    uint64_t cap = 4 * P.n + 16, *moff = malloc((P.n + 1) * 8), *ranges = NULL, *oo = NULL, *pos = NULL, *starts = NULL;
+    uint32_t *spans = NULL;
+    uint8_t *strand = NULL;
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    starts = malloc(fi.nrec * 8);
+    if (!moff || !starts) { fprintf(stderr, "out of memory\n"); goto done; }
+    for (;;) {                                            /* grow to the exact MEM count on DEBWT_ERANGE */
+        free(spans); free(ranges); free(strand);
+        spans = malloc(cap * 8); ranges = malloc(cap * 16); strand = malloc(cap);
+        if (!spans || !ranges || !strand) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_mems(fm, P.seq, P.off, P.n, min_len, flags, moff, spans, ranges, strand, cap);
+        if (rc == DEBWT_ERANGE && moff[P.n] > cap) { cap = moff[P.n]; continue; }
+        break;
+    }
+    if (!rc) rc = debwt_fm_record_starts(fm, starts, fi.nrec);
+    const uint64_t nm = rc ? 0 : moff[P.n];
+    uint64_t total = 0;
+    for (uint64_t h = 0; h < nm; h++) {
+        const uint64_t c = ranges[2 * h + 1] - ranges[2 * h];
+        total += max_hits && c > max_hits ? max_hits : c;
+    }
+    if (!rc) {
+        oo = malloc((nm + 1) * 8); pos = malloc((total ? total : 1) * 8);
+        if (!oo || !pos) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_locate(fm, ranges, nm, max_hits, oo, pos, total);
+    }
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    for (uint64_t i = 0; i < P.n; i++)
+        for (uint64_t h = moff[i]; h < moff[i + 1]; h++) {
+            uint64_t *a = pos + oo[h], m = oo[h + 1] - oo[h], rec = 0;
+            qsort(a, m, 8, cmp_u64);
+            printf("%s\t%c\t%u\t%u\t%llu\t", P.name[i], strand[h] ? '-' : '+', spans[2 * h], spans[2 * h + 1],
+                   (unsigned long long)(ranges[2 * h + 1] - ranges[2 * h]));
+            for (uint64_t j = 0; j < m; j++) {
+                while (rec + 1 < fi.nrec && starts[rec + 1] <= a[j]) rec++;
+                printf("%s%llu:%llu", j ? "," : "", (unsigned long long)rec, (unsigned long long)(a[j] - starts[rec]));
+            }
+            putchar('\n');
+        }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(moff); free(spans); free(ranges); free(strand); free(oo); free(pos); free(starts);
+    debwt_fm_destroy(fm);
+    free_patterns(&P);
+    return ret;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { usage(); return 1; }
     const char *cmd = argv[1];
-    int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : -1;
+    int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 : -1;
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL;
-    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0;
+    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19;
     int iupac = 0, search = 0;
     uint32_t flags = 0;
     for (int i = 2; i < argc; i++) {
@@ -430,7 +493,7 @@ int main(int argc, char **argv) {
             continue;
         }
         if (mode && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
-        if (mode && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
+        if ((mode == 1 || mode == 2) && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
         if (i + 1 >= argc) { usage(); return 1; }
         const char *v = argv[++i];
         if (!strcmp(a, "-i")) out = v;
@@ -443,15 +506,19 @@ int main(int argc, char **argv) {
         else if (mode == 0 && !strcmp(a, "--sa")) {
             if (parse_u64(v, &s) || s < 1 || s > 1024 || (s & (s - 1))) { fprintf(stderr, "--sa: a power of two in 1..1024\n"); return 1; }
         }
-        else if (mode && !strcmp(a, "--mismatches")) {
+        else if ((mode == 1 || mode == 2) && !strcmp(a, "--mismatches")) {
             if (parse_u64(v, &K) || K > 4) { fprintf(stderr, "--mismatches: a count in 0..4\n"); return 1; }
             search = 1;
         }
-        else if (mode == 2 && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
+        else if (mode == 3 && !strcmp(a, "--min-len")) {
+            if (parse_u64(v, &min_len) || min_len < 1 || min_len > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
+        }
+        else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
     if (!out || !file) { usage(); return 1; }
     if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
+    if (mode == 3) return cmd_mems(out, file, (int)device, max_hits, (uint32_t)min_len, flags);
     if (search) return cmd_search(out, file, (int)device, mode == 2, max_hits, (uint32_t)K, flags);
     return cmd_query(out, file, (int)device, mode == 2, max_hits);
 }

@@ -75,6 +75,15 @@ class DebwtFmSearchStats(ctypes.Structure):
         return d
 
 
+class DebwtFmMemsStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("patterns", "batches", "launches", "mems", "steps", "line_reads", "wave_steps",
+                                                 "scratch_bytes")] +
+                [("ms_kernel", ctypes.c_float), ("ms_wall", ctypes.c_float)])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DebwtMultiStats(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint64), ("nrec", ctypes.c_uint64), ("ngpus", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
                 ("key_bytes_in", ctypes.c_uint64), ("blue_bytes_in", ctypes.c_uint64), ("ms_build", ctypes.c_float),
@@ -102,7 +111,7 @@ SYMBOLS = [
     "debwt_dump_reference_files", "debwt_shard_scratch",
     "debwt_fm_create", "debwt_fm_open", "debwt_fm_last_error", "debwt_fm_info_get", "debwt_fm_samples",
     "debwt_fm_record_starts", "debwt_fm_count", "debwt_fm_locate", "debwt_fm_destroy",
-    "debwt_fm_search", "debwt_fm_search_stats_get",
+    "debwt_fm_search", "debwt_fm_search_stats_get", "debwt_fm_mems", "debwt_fm_mems_stats_get",
 ]
 
 
@@ -300,6 +309,11 @@ def lib():
                                   ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
     L.debwt_fm_search_stats_get.restype = ctypes.c_int
     L.debwt_fm_search_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmSearchStats)]
+    L.debwt_fm_mems.restype = ctypes.c_int
+    L.debwt_fm_mems.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p,
+                                ctypes.POINTER(ctypes.c_uint32), u64p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64]
+    L.debwt_fm_mems_stats_get.restype = ctypes.c_int
+    L.debwt_fm_mems_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmMemsStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

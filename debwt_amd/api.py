@@ -380,6 +380,39 @@ class FMIndex:
         self._chk(self._L.debwt_fm_search_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def mems(self, patterns, min_len=19, strands="forward"):
+        """Maximal exact matches of each pattern of at least min_len bases (debwt_fm_mems; 19 is BWA-MEM's -k): spans of
+        the pattern that occur inside one record and cannot be extended by one base on either side and still occur.
+        strands "both" adds those of the reverse complement (strand 1), with spans in the pattern's own coordinates.
+        A character outside ACGTacgt matches nothing.  Returns a MemResult."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        flags = SEARCH_BOTH_STRANDS if strands == "both" else 0
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        moff = np.zeros(npat + 1, dtype=np.uint64)
+        cap = 4 * npat + 16                                   # first estimate; grown to the exact count on DEBWT_ERANGE
+        while True:
+            spans = np.zeros((cap, 2), dtype=np.uint32)
+            ranges = np.zeros((cap, 2), dtype=np.uint64)
+            st = np.zeros(cap, dtype=np.uint8)
+            rc = self._L.debwt_fm_mems(self._h, buf, _p64(offs), npat, int(min_len), flags, _p64(moff),
+                                       spans.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _p64(ranges),
+                                       st.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), cap)
+            if rc == -5 and int(moff[npat]) > cap:
+                cap = int(moff[npat])
+                continue
+            self._chk(rc)
+            break
+        h = int(moff[npat])
+        return MemResult(self, moff, spans[:h].copy(), ranges[:h].copy(), st[:h].copy())
+
+    def mems_stats(self):
+        """What the last mems call did (debwt_fm_mems_stats_get): batches, MEMs, rank steps and lines, wave steps, ms."""
+        st = _lib.DebwtFmMemsStats()
+        self._chk(self._L.debwt_fm_mems_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def locate_hits(self, result, max_per_pattern=None):
         """Text positions of a SearchResult's hits (debwt_fm_locate on its ranges): per pattern a tuple of uint64
         positions, uint8 strands and uint8 mismatches, ascending by (position, strand).  max_per_pattern caps the rows
@@ -441,6 +474,43 @@ class SearchResult:
     def locate(self, max_per_pattern=None):
         """FMIndex.locate_hits of this result"""
         return self.index.locate_hits(self, max_per_pattern)
+
+
+class MemResult:
+    """MEMs of FMIndex.mems: pattern i's MEMs are offsets[i] .. offsets[i + 1], ordered by (strand, qbeg).  spans (M x 2
+    uint32) [qbeg, qend) in the pattern's coordinates (strand 1: the text reads the reverse complement of that span),
+    ranges (M x 2 uint64) row intervals as FMIndex.ranges gives them, strands (uint8) per MEM."""
+
+    def __init__(self, index, offsets, spans, ranges, strands):
+        self.index, self.offsets, self.spans, self.ranges, self.strands = index, offsets, spans, ranges, strands
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def hits(self, i):
+        """(spans, ranges, strands) of pattern i"""
+        a, b = int(self.offsets[i]), int(self.offsets[i + 1])
+        return self.spans[a:b], self.ranges[a:b], self.strands[a:b]
+
+    def count(self):
+        """occurrences per MEM: hi - lo (np.uint64)"""
+        return (self.ranges[:, 1] - self.ranges[:, 0]).astype(np.uint64)
+
+    def locate(self, max_per_mem=None):
+        """global text positions of each MEM's occurrences (the first max_per_mem rows when capped), one uint64 array per
+        MEM in row (suffix) order, through debwt_fm_locate"""
+        r = np.ascontiguousarray(self.ranges, dtype=np.uint64)
+        nm = len(r)
+        cnt = r[:, 1] - r[:, 0]
+        if max_per_mem is not None:
+            cnt = np.minimum(cnt, np.uint64(max_per_mem))
+        total = int(cnt.sum())
+        offs = np.zeros(nm + 1, dtype=np.uint64)
+        pos = np.empty(max(total, 1), dtype=np.uint64)
+        if nm:
+            self.index._chk(self.index._L.debwt_fm_locate(self.index._h, _p64(r), nm, int(max_per_mem or 0), _p64(offs),
+                                                          _p64(pos), len(pos)))
+        return [pos[int(offs[i]):int(offs[i + 1])] for i in range(nm)]
 
 
 class MultiDeBWT:

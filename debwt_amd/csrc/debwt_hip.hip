@@ -27,6 +27,7 @@
 #include "verify_kernels.h"
 #include "fm_kernels.h"
 #include "fm_search_kernels.h"
+#include "fm_mem_kernels.h"
 
 namespace {
 
@@ -2832,6 +2833,8 @@ struct debwt_fm {
     DevBuf q_chars, q_off, q_out, q_runs;   // query scratch, bounded by the batch sizes below
     DevBuf s_items[FM_SEARCH_MAX_K + 1], s_hits, s_ctr, s_plist;   // search scratch: levels 1..K, hits, counters
     debwt_fm_search_stats s_stats{};
+    DevBuf m_slot, m_cnt, m_obase, m_spans, m_ranges, m_cspans, m_cranges;   // MEM scratch: slots, then compacted
+    debwt_fm_mems_stats m_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -3399,12 +3402,166 @@ extern "C" int debwt_fm_search_stats_get(const debwt_fm *f, debwt_fm_search_stat
     return DEBWT_OK;
 }
 
+// ---- maximal exact matches (fm_mem_kernels.h) -----------------------------------------------------------------------
+// A batch of patterns [p0, p1) runs as np x strands items; item g gets max(0, m - min_len + 1) slots from an exclusive
+// prefix sum (a bound on its MEM count: MEM ends strictly increase and each is >= min_len), so the kernel needs no
+// atomics and cannot overflow.  The counts come back, the host lays the MEMs out by (pattern, strand), and
+// k_fm_mems_compact gathers them (reversing strand 0, which the lane emits from the right) for one download.
+
+namespace {
+
+constexpr u64 FM_MEM_SLOTS = 1ull << 24;               // worst-case MEM slots per batch (24 bytes each, twice)
+
+struct FmMemOut {                                      // one batch's MEMs, in (pattern, strand, qbeg) order
+    std::vector<u64> per;                              // MEMs per (pattern, strand): 2 per pattern
+    std::vector<u32> spans;
+    std::vector<u64> ranges;
+};
+
+int fm_mems_batch(debwt_fm *f, const char *patterns, const uint64_t *offsets, u64 p0, u64 p1, u32 min_len, u64 nstr,
+                  hipEvent_t e0, hipEvent_t e1, FmMemOut *out) {
+    debwt_fm_mems_stats &st = f->m_stats;
+    const u64 np = p1 - p0, base = offsets[p0], bytes = offsets[p1] - base, nit = np * nstr;
+    std::vector<u64> slot(nit + 1);
+    slot[0] = 0;
+    for (u64 g = 0; g < nit; g++) {
+        const u64 j = p0 + (g < np ? g : g - np), m = offsets[j + 1] - offsets[j];
+        slot[g + 1] = slot[g] + (m >= min_len ? m - min_len + 1 : 0);
+    }
+    const u64 ns = slot[nit];
+    st.scratch_bytes = std::max<u64>(st.scratch_bytes, ns * 24);
+    FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
+    FM_ENSURE(f, f->q_off, (size_t)(np + 1) * 8);
+    FM_ENSURE(f, f->m_slot, (size_t)(nit + 1) * 8);
+    FM_ENSURE(f, f->m_cnt, (size_t)std::max<u64>(nit, 1) * 4);
+    FM_ENSURE(f, f->m_obase, (size_t)std::max<u64>(nit, 1) * 8);
+    FM_ENSURE(f, f->m_spans, (size_t)std::max<u64>(ns, 1) * 8);
+    FM_ENSURE(f, f->m_ranges, (size_t)std::max<u64>(ns, 1) * 16);
+    FM_ENSURE(f, f->s_ctr, 64);
+    if (bytes) HIPCHK(f, hipMemcpyAsync(f->q_chars.p, patterns + base, bytes, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->q_off.p, offsets + p0, (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->m_slot.p, slot.data(), (nit + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(f->s_ctr.p, 0, 32, f->stream));
+    (void)hipEventRecord(e0, f->stream);
+    k_fm_mems<<<grid_for(nit, 256), 256, 0, f->stream>>>(f->V, f->q_chars.as<u8>(), f->q_off.as<u64>(), base, np, nit,
+                                                         min_len, f->m_slot.as<u64>(), f->m_spans.as<u32>(),
+                                                         f->m_ranges.as<u64>(), f->m_cnt.as<u32>(), f->s_ctr.as<u64>());
+    (void)hipEventRecord(e1, f->stream);
+    std::vector<u32> cnt(nit);
+    u64 h[4];
+    HIPCHK(f, hipMemcpyAsync(cnt.data(), f->m_cnt.p, nit * 4, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(h, f->s_ctr.p, 32, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    st.ms_kernel += ms; st.launches++;
+    st.steps += h[0]; st.line_reads += h[1]; st.wave_steps += h[2];
+    std::vector<u64> ob(nit);                            // output order: pattern, then strand
+    out->per.assign(2 * np, 0);
+    u64 tot = 0;
+    for (u64 j = 0; j < np; j++)
+        for (u64 sd = 0; sd < nstr; sd++) {
+            const u64 g = sd * np + j;
+            if (cnt[g] > slot[g + 1] - slot[g]) { f->err = "debwt_fm_mems: an item wrote more MEMs than its slots"; return DEBWT_EINTERNAL; }
+            ob[g] = tot; tot += cnt[g]; out->per[2 * j + sd] = cnt[g];
+        }
+    out->spans.resize(2 * tot);
+    out->ranges.resize(2 * tot);
+    if (!tot) return DEBWT_OK;
+    FM_ENSURE(f, f->m_cspans, (size_t)tot * 8);
+    FM_ENSURE(f, f->m_cranges, (size_t)tot * 16);
+    HIPCHK(f, hipMemcpyAsync(f->m_obase.p, ob.data(), nit * 8, hipMemcpyHostToDevice, f->stream));
+    k_fm_mems_compact<<<grid_for(nit, 256), 256, 0, f->stream>>>(f->m_slot.as<u64>(), f->m_cnt.as<u32>(),
+                                                                 f->m_obase.as<u64>(), np, nit, f->m_spans.as<u32>(),
+                                                                 f->m_ranges.as<u64>(), f->m_cspans.as<u32>(),
+                                                                 f->m_cranges.as<u64>());
+    st.launches++;
+    HIPCHK(f, hipMemcpyAsync(out->spans.data(), f->m_cspans.p, tot * 8, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(out->ranges.data(), f->m_cranges.p, tot * 16, hipMemcpyDeviceToHost, f->stream));
+    return fm_sync(f);
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_mems(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat, uint32_t min_len,
+                             uint32_t flags, uint64_t *mem_offsets, uint32_t *spans, uint64_t *ranges, uint8_t *strands,
+                             uint64_t capacity) {
+    if (!f || !offsets || !mem_offsets) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->m_stats = debwt_fm_mems_stats{};
+    if (!min_len) { f->err = "debwt_fm_mems: min_len must be at least 1"; return DEBWT_EINVAL; }
+    if (flags & ~DEBWT_FM_BOTH_STRANDS) { f->err = "debwt_fm_mems: unknown flags"; return DEBWT_EINVAL; }
+    for (u64 i = 0; i < npat; i++) {
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_mems: offsets must not decrease"; return DEBWT_EINVAL; }
+        if ((offsets[i + 1] - offsets[i]) >> 32) { f->err = "debwt_fm_mems: a pattern of 2^32 bytes or more"; return DEBWT_EINVAL; }
+    }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    mem_offsets[0] = 0;
+    if (!npat) return DEBWT_OK;
+    HIPCHK(f, hipSetDevice(f->device));
+    const u64 nstr = (flags & DEBWT_FM_BOTH_STRANDS) ? 2 : 1;
+    const u64 slots = fm_env_u64("DEBWT_FM_MEM_SLOTS", FM_MEM_SLOTS);
+    debwt_fm_mems_stats &st = f->m_stats;
+    st.patterns = npat;
+    hipEvent_t e0, e1;
+    HIPCHK(f, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
+    auto worst = [&](u64 i) {
+        const u64 m = offsets[i + 1] - offsets[i];
+        return nstr * (m >= min_len ? m - min_len + 1 : 0);
+    };
+    std::vector<u64> per(2 * npat, 0);                   // MEMs per (pattern, strand)
+    std::vector<u32> all_spans;
+    std::vector<u64> all_ranges;
+    FmMemOut part;
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 p1 = p0 + 1, ws = worst(p0);                  // at least one pattern, however long
+        while (p1 < npat && p1 - p0 < FM_BATCH_PATTERNS && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS &&
+               ws + worst(p1) <= slots)
+            ws += worst(p1++);
+        int rc = fm_mems_batch(f, patterns, offsets, p0, p1, min_len, nstr, e0, e1, &part);
+        if (rc) return rc;
+        std::copy(part.per.begin(), part.per.end(), per.begin() + 2 * p0);
+        all_spans.insert(all_spans.end(), part.spans.begin(), part.spans.end());
+        all_ranges.insert(all_ranges.end(), part.ranges.begin(), part.ranges.end());
+        st.batches++;
+        p0 = p1;
+    }
+    const u64 total = all_spans.size() / 2;
+    st.mems = total;
+    for (u64 i = 0; i < npat; i++) mem_offsets[i + 1] = mem_offsets[i] + per[2 * i] + per[2 * i + 1];
+    if (capacity < total || (total && (!spans || !ranges || !strands))) {
+        f->err = "debwt_fm_mems: capacity below the MEMs (mem_offsets[npat] = " + std::to_string(total) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (total) {
+        memcpy(spans, all_spans.data(), total * 8);
+        memcpy(ranges, all_ranges.data(), total * 16);
+    }
+    for (u64 i = 0; i < npat; i++) {
+        u8 *d = strands + mem_offsets[i];
+        if (per[2 * i]) memset(d, 0, per[2 * i]);
+        if (per[2 * i + 1]) memset(d + per[2 * i], 1, per[2 * i + 1]);
+    }
+    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_mems_stats_get(const debwt_fm *f, debwt_fm_mems_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->m_stats;
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     for (DevBuf *b : {&f->idx, &f->rowlists, &f->sa, &f->q_chars, &f->q_off, &f->q_out, &f->q_runs, &f->s_hits, &f->s_ctr,
-                      &f->s_plist})
+                      &f->s_plist, &f->m_slot, &f->m_cnt, &f->m_obase, &f->m_spans, &f->m_ranges, &f->m_cspans,
+                      &f->m_cranges})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -515,6 +515,31 @@ typedef struct {
     float ms_kernel, ms_wall;
 } debwt_fm_search_stats;
 int debwt_fm_search_stats_get(const debwt_fm *fm, debwt_fm_search_stats *out);
+/* Maximal exact matches of each pattern (and of its reverse complement with DEBWT_FM_BOTH_STRANDS) of length >= min_len
+ * (>= 1).  With s(e) the smallest s such that P[s..e] occurs inside one record (e + 1 when P[e] is outside ACGTacgt or
+ * does not occur), the MEMs are the spans [s(e), e + 1) with s(e) <= e where e = m - 1 or s(e + 1) > s(e): they occur and
+ * cannot be extended by one base on either side.  Exact, with no cap; any pattern length below 2^32 bytes, an empty
+ * pattern has 0 MEMs.
+ * mem_offsets (npat + 1): pattern i's MEMs are [mem_offsets[i], mem_offsets[i+1]), ascending by (strand, qbeg).
+ * spans: 2 u32 per MEM, [qbeg, qend) in the coordinates of the pattern AS GIVEN, also for strand 1 (the text there
+ * reads revcomp(P[qbeg..qend))).  ranges: 2 u64 per MEM, the debwt_fm_count layout (straight into debwt_fm_locate).
+ * strands: 1 byte per MEM.  DEBWT_ERANGE when capacity < mem_offsets[npat], mem_offsets written first.  DEBWT_EINVAL for
+ * min_len 0, flags other than DEBWT_FM_BOTH_STRANDS, decreasing offsets and a pattern of 2^32 bytes or more.
+ * Batches are cut inside the library at 64 MB of pattern bytes and DEBWT_FM_MEM_SLOTS (environment, read per call;
+ * default 2^24) worst-case MEM slots, max(0, m - min_len + 1) per pattern and strand; a pattern with more goes alone.
+ * Device scratch: 24 bytes per slot, 24 per MEM found, 20 per pattern and strand and the pattern bytes, each with up to
+ * 25 % slack: at most about 1.2 GB at the default (more only for a single pattern beyond the slot limit). */
+int debwt_fm_mems(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat, uint32_t min_len,
+                  uint32_t flags, uint64_t *mem_offsets, uint32_t *spans, uint64_t *ranges, uint8_t *strands,
+                  uint64_t capacity);
+/* what the last debwt_fm_mems did: patterns, batches, kernel launches (k_fm_mems and the compaction), MEMs, rank steps
+ * (one fm_occ2 each), rank lines read, wave steps (64 x the longest lane per wave: steps / wave_steps is the share of
+ * lanes busy), the largest slot scratch of a batch, k_fm_mems time (events) and host wall time */
+typedef struct {
+    uint64_t patterns, batches, launches, mems, steps, line_reads, wave_steps, scratch_bytes;
+    float ms_kernel, ms_wall;
+} debwt_fm_mems_stats;
+int debwt_fm_mems_stats_get(const debwt_fm *fm, debwt_fm_mems_stats *out);
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
