@@ -6,6 +6,8 @@
  *   deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq
+ *   deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]
+ *                      [--max-occ N] [--min-score S] READS.fa|.fq
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -24,6 +26,13 @@
  * with --both-strands those of its reverse complement: one line per MEM, name, strand (+ or -), qbeg, qend (0-based, end
  * exclusive, in the read's own coordinates on both strands), occurrences and record:offset ascending.  --max-hits M lists
  * the first M occurrences in suffix order (the count column stays the full count).  Reads without MEMs print nothing.
+ *
+ * map aligns every read (debwt_fm_map: MEM seeds of at least L bases, at most N occurrences of each, clustered by diagonal,
+ * banded affine-gap extension with half-width W, 0..63; a plain heuristic, not BWA-MEM's).  The index holds no text, so
+ * --ref names the input again; it is packed as index packs it (same -t, same --iupac SEED) and refused when it is not
+ * the text of OUT.  One PAF line per mapped read: name, length, query start and end (on the read's own strand), strand,
+ * record number, record length, target start and end, matching bases, alignment columns, mapping quality, then AS:i:
+ * (score), NM:i: (mismatches + gap bases) and cg:Z: (CIGAR along the text).  Reads that are not mapped print nothing.
  *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
@@ -46,12 +55,16 @@ static void usage(void) {
             "       deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq\n"
+            "       deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]\n"
+            "                          [--max-occ N] [--min-score S] READS.fa|.fq\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
             "name<TAB>total<TAB>record:offset:strand:mismatches,... (locate);\n"
             "mems prints name<TAB>strand<TAB>qbeg<TAB>qend<TAB>count<TAB>record:offset,... per maximal exact match of at\n"
-            "least L bases (default 19)\n");
+            "least L bases (default 19);\n"
+            "map prints one PAF line per mapped read (AS:i: score, NM:i: edits, cg:Z: CIGAR); --ref is the FASTA that OUT\n"
+            "is the BWT of\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -476,13 +489,86 @@ done:
     return ret;
 }
 
+/* ---- map ------------------------------------------------------------------------------------------------------------- */
+
+static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t threads, int iupac, uint64_t seed, int device,
+                   const debwt_fm_map_opts *opts) {
+    struct patterns P;
+    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    int ret = 1, rc;
+    debwt_packed_text pt;
+    char err[256] = "";
+    memset(&pt, 0, sizeof pt);
+    uint64_t cap = 4 * P.n + 16, *coff = malloc((P.n + 1) * 8), *starts = NULL;
+    uint32_t *cig = NULL;
+    debwt_fm_hit *hits = malloc((P.n ? P.n : 1) * sizeof *hits);
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    starts = malloc((fi.nrec + 1) * 8);
+    if (!coff || !hits || !starts) { fprintf(stderr, "out of memory\n"); goto done; }
+    rc = debwt_pack_fasta_opts(ref, (int)threads, iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, seed, &pt, err, sizeof err);
+    if (rc) {
+        fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", ref, err);
+        goto done;
+    }
+    if (pt.n != fi.n || pt.nrec != fi.nrec) {
+        fprintf(stderr, "%s is not the text of %s: %llu symbols in %llu records, the index has %llu in %llu\n", ref, out,
+                (unsigned long long)pt.n, (unsigned long long)pt.nrec, (unsigned long long)fi.n, (unsigned long long)fi.nrec);
+        goto done;
+    }
+    rc = debwt_fm_attach_text(fm, NULL, pt.words, pt.sep);
+    if (rc) { fprintf(stderr, "%s is not the text of %s: %s\n", ref, out, debwt_fm_last_error(fm)); goto done; }
+    for (;;) {                                            /* grow to the exact op count on DEBWT_ERANGE */
+        free(cig);
+        cig = malloc(cap * 4);
+        if (!cig) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_map(fm, P.seq, P.off, P.n, opts, hits, coff, cig, cap);
+        if (rc == DEBWT_ERANGE && coff[P.n] > cap) { cap = coff[P.n]; continue; }
+        break;
+    }
+    if (!rc) rc = debwt_fm_record_starts(fm, starts, fi.nrec);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    starts[fi.nrec] = fi.n;                               /* record r holds starts[r + 1] - 1 - starts[r] bases */
+    for (uint64_t i = 0; i < P.n; i++) {
+        const debwt_fm_hit *h = &hits[i];
+        if (h->flags & DEBWT_FM_MAP_UNMAPPED) continue;
+        const uint64_t m = P.off[i + 1] - P.off[i];
+        const int rev = (h->flags & DEBWT_FM_MAP_REVERSE) != 0;
+        uint64_t cols = 0, gaps = 0, mcols = 0;
+        for (uint64_t k = coff[i]; k < coff[i + 1]; k++) {
+            cols += cig[k] >> 4;
+            if (cig[k] & 15) gaps += cig[k] >> 4; else mcols += cig[k] >> 4;
+        }
+        printf("%s\t%llu\t%llu\t%llu\t%c\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%u\tAS:i:%d\tNM:i:%u\tcg:Z:", P.name[i],
+               (unsigned long long)m, (unsigned long long)(rev ? m - h->qend : h->qbeg),
+               (unsigned long long)(rev ? m - h->qbeg : h->qend), rev ? '-' : '+', h->record,
+               (unsigned long long)(starts[h->record + 1] - 1 - starts[h->record]), (unsigned long long)h->offset,
+               (unsigned long long)(h->offset + (h->tend - h->tbeg)), (unsigned long long)(mcols - (h->edits - gaps)),
+               (unsigned long long)cols, h->mapq, h->score, h->edits);
+        for (uint64_t k = coff[i]; k < coff[i + 1]; k++) printf("%u%c", cig[k] >> 4, "MID"[cig[k] & 3]);
+        putchar('\n');
+    }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    debwt_free_packed(&pt);
+    free(coff); free(cig); free(hits); free(starts);
+    debwt_fm_destroy(fm);
+    free_patterns(&P);
+    return ret;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { usage(); return 1; }
     const char *cmd = argv[1];
-    int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 : -1;
+    int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 :
+               !strcmp(cmd, "map") ? 4 : -1;
     if (mode < 0) { usage(); return 1; }
-    const char *out = NULL, *file = NULL;
-    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19;
+    const char *out = NULL, *file = NULL, *ref = NULL;
+    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, v64 = 0;
+    debwt_fm_map_opts mo;
+    debwt_fm_map_defaults(&mo);
     int iupac = 0, search = 0;
     uint32_t flags = 0;
     for (int i = 2; i < argc; i++) {
@@ -492,17 +578,17 @@ int main(int argc, char **argv) {
             file = a;
             continue;
         }
-        if (mode && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
+        if (mode >= 1 && mode <= 3 && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
         if ((mode == 1 || mode == 2) && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
         if (i + 1 >= argc) { usage(); return 1; }
         const char *v = argv[++i];
         if (!strcmp(a, "-i")) out = v;
         else if (!strcmp(a, "--device")) { if (parse_u64(v, &device) || device > 255) { fprintf(stderr, "--device: a GPU ordinal\n"); return 1; } }
-        else if (mode == 0 && !strcmp(a, "-t")) {
+        else if ((mode == 0 || mode == 4) && !strcmp(a, "-t")) {
             if (parse_u64(v, &threads) || threads < 1) { fprintf(stderr, "-t: thread number must be a positive integer\n"); return 1; }
             if (threads > 256) threads = 256;
         }
-        else if (mode == 0 && !strcmp(a, "--iupac")) { if (parse_u64(v, &seed)) { fprintf(stderr, "--iupac: a seed\n"); return 1; } iupac = 1; }
+        else if ((mode == 0 || mode == 4) && !strcmp(a, "--iupac")) { if (parse_u64(v, &seed)) { fprintf(stderr, "--iupac: a seed\n"); return 1; } iupac = 1; }
         else if (mode == 0 && !strcmp(a, "--sa")) {
             if (parse_u64(v, &s) || s < 1 || s > 1024 || (s & (s - 1))) { fprintf(stderr, "--sa: a power of two in 1..1024\n"); return 1; }
         }
@@ -510,13 +596,31 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &K) || K > 4) { fprintf(stderr, "--mismatches: a count in 0..4\n"); return 1; }
             search = 1;
         }
-        else if (mode == 3 && !strcmp(a, "--min-len")) {
+        else if (mode == 4 && !strcmp(a, "--ref")) ref = v;
+        else if (mode == 4 && !strcmp(a, "--band")) {
+            if (parse_u64(v, &v64) || v64 > 63) { fprintf(stderr, "--band: a half-width in 0..63\n"); return 1; }
+            mo.band = (uint32_t)v64;
+        }
+        else if (mode == 4 && !strcmp(a, "--max-occ")) {
+            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-occ: a count of at least 1\n"); return 1; }
+            mo.max_occ = (uint32_t)v64;
+        }
+        else if (mode == 4 && !strcmp(a, "--min-score")) {
+            if (parse_u64(v, &v64) || v64 > 0x7FFFFFFFull) { fprintf(stderr, "--min-score: a score of at least 0\n"); return 1; }
+            mo.min_score = (int32_t)v64;
+        }
+        else if ((mode == 3 || mode == 4) && !strcmp(a, "--min-len")) {
             if (parse_u64(v, &min_len) || min_len < 1 || min_len > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
         }
         else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
     if (!out || !file) { usage(); return 1; }
+    if (mode == 4) {
+        if (!ref) { fprintf(stderr, "map: --ref INPUT.fa[.gz] (the text OUT is the BWT of) is required\n"); return 1; }
+        mo.min_len = (uint32_t)min_len;
+        return cmd_map(out, ref, file, threads, iupac, seed, (int)device, &mo);
+    }
     if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
     if (mode == 3) return cmd_mems(out, file, (int)device, max_hits, (uint32_t)min_len, flags);
     if (search) return cmd_search(out, file, (int)device, mode == 2, max_hits, (uint32_t)K, flags);

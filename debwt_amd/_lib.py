@@ -84,6 +84,58 @@ class DebwtFmMemsStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmJob(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_uint64), ("diag", ctypes.c_int64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32)]
+
+
+class DebwtFmScoring(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("match", "mismatch", "gap_open", "gap_extend")]
+
+
+class DebwtFmAln(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_int32), ("qbeg", ctypes.c_uint32), ("qend", ctypes.c_uint32), ("edits", ctypes.c_uint32),
+                ("tbeg", ctypes.c_uint64), ("tend", ctypes.c_uint64)]
+
+
+class DebwtFmSeed(ctypes.Structure):
+    _fields_ = [("diag", ctypes.c_int64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32), ("qbeg", ctypes.c_uint32),
+                ("qend", ctypes.c_uint32)]
+
+
+class DebwtFmCand(ctypes.Structure):
+    _fields_ = [("diag", ctypes.c_int64), ("first_diag", ctypes.c_int64), ("record", ctypes.c_uint32),
+                ("strand", ctypes.c_uint32), ("weight", ctypes.c_uint32), ("seeds", ctypes.c_uint32)]
+
+
+class DebwtFmMapOpts(ctypes.Structure):
+    _fields_ = [("min_len", ctypes.c_uint32), ("band", ctypes.c_uint32), ("max_occ", ctypes.c_uint32),
+                ("max_cand", ctypes.c_uint32), ("min_score", ctypes.c_int32), ("flags", ctypes.c_uint32),
+                ("scoring", DebwtFmScoring)]
+
+
+class DebwtFmHit(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_uint64), ("flags", ctypes.c_uint32), ("record", ctypes.c_uint32),
+                ("offset", ctypes.c_uint64), ("qbeg", ctypes.c_uint32), ("qend", ctypes.c_uint32), ("tbeg", ctypes.c_uint64),
+                ("tend", ctypes.c_uint64), ("score", ctypes.c_int32), ("sub", ctypes.c_int32), ("mapq", ctypes.c_uint32),
+                ("edits", ctypes.c_uint32), ("diag", ctypes.c_int64)]
+
+
+class DebwtFmExtendStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("jobs", "batches", "launches", "cells", "wave_steps", "scratch_bytes")] +
+                [(n, ctypes.c_float) for n in ("ms_kernel", "ms_trace", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DebwtFmMapStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("reads", "mapped", "mems", "seeds", "candidates", "jobs", "batches")] +
+                [(n, ctypes.c_float) for n in ("ms_mems", "ms_locate", "ms_candidates", "ms_extend", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DebwtMultiStats(ctypes.Structure):
     _fields_ = [("n", ctypes.c_uint64), ("nrec", ctypes.c_uint64), ("ngpus", ctypes.c_uint32), ("rounds", ctypes.c_uint32),
                 ("key_bytes_in", ctypes.c_uint64), ("blue_bytes_in", ctypes.c_uint64), ("ms_build", ctypes.c_float),
@@ -112,6 +164,8 @@ SYMBOLS = [
     "debwt_fm_create", "debwt_fm_open", "debwt_fm_last_error", "debwt_fm_info_get", "debwt_fm_samples",
     "debwt_fm_record_starts", "debwt_fm_count", "debwt_fm_locate", "debwt_fm_destroy",
     "debwt_fm_search", "debwt_fm_search_stats_get", "debwt_fm_mems", "debwt_fm_mems_stats_get",
+    "debwt_fm_attach_text", "debwt_fm_extend", "debwt_fm_extend_stats_get", "debwt_fm_cluster_seeds",
+    "debwt_fm_map_defaults", "debwt_fm_map", "debwt_fm_map_stats_get",
 ]
 
 
@@ -314,6 +368,24 @@ def lib():
                                 ctypes.POINTER(ctypes.c_uint32), u64p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64]
     L.debwt_fm_mems_stats_get.restype = ctypes.c_int
     L.debwt_fm_mems_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmMemsStats)]
+    L.debwt_fm_attach_text.restype = ctypes.c_int
+    L.debwt_fm_attach_text.argtypes = [vp, vp, u64p, u64p]
+    L.debwt_fm_extend.restype = ctypes.c_int
+    L.debwt_fm_extend.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.POINTER(DebwtFmJob), ctypes.c_uint64,
+                                  ctypes.POINTER(DebwtFmScoring), ctypes.c_uint32, ctypes.POINTER(DebwtFmAln), u64p,
+                                  ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
+    L.debwt_fm_extend_stats_get.restype = ctypes.c_int
+    L.debwt_fm_extend_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmExtendStats)]
+    L.debwt_fm_cluster_seeds.restype = ctypes.c_int
+    L.debwt_fm_cluster_seeds.argtypes = [ctypes.POINTER(DebwtFmSeed), ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                         ctypes.POINTER(DebwtFmCand)]
+    L.debwt_fm_map_defaults.restype = None
+    L.debwt_fm_map_defaults.argtypes = [ctypes.POINTER(DebwtFmMapOpts)]
+    L.debwt_fm_map.restype = ctypes.c_int
+    L.debwt_fm_map.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.POINTER(DebwtFmMapOpts),
+                               ctypes.POINTER(DebwtFmHit), u64p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
+    L.debwt_fm_map_stats_get.restype = ctypes.c_int
+    L.debwt_fm_map_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmMapStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

@@ -413,6 +413,96 @@ class FMIndex:
         self._chk(self._L.debwt_fm_mems_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def attach_text(self, source=None, words=None, sep=None):
+        """Give the index its text (debwt_fm_attach_text; n / 4 bytes of HBM), which extend() and map() read.  source: the
+        DeBWT context the index was made from (device-to-device copy), or None with the host text words / sep as
+        pack_records() and pack_fasta() return them (the path after FMIndex.open).  A text that is not the index's raises."""
+        if source is not None:
+            self._chk(self._L.debwt_fm_attach_text(self._h, source._h, None, None))
+            return
+        if words is None or sep is None:
+            raise ValueError("attach_text needs a DeBWT context or the packed words and separator positions")
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        sep = np.ascontiguousarray(sep, dtype=np.uint64)
+        if len(sep) != self.nrec or len(words) < (self.n + 63) // 32:
+            raise DebwtError(-1, "the text has another number of records or fewer words than the index's n asks for")
+        self._chk(self._L.debwt_fm_attach_text(self._h, None, _p64(words), _p64(sep)))
+
+    def extend(self, patterns, jobs, scoring=(1, 4, 6, 1), band=16, cigar=True):
+        """Banded affine-gap local alignment of jobs (debwt_fm_extend).  jobs: rows of (pattern index, strand, diag, record),
+        diag = text position - query position, the query being the pattern (strand 0) or its reverse complement (strand 1).
+        scoring: (match, mismatch, gap open, gap extend), a gap of length L costs open + L * extend; band: half-width 0..63.
+        cigar=False: scores and alignment ends only (no traceback).  Returns an ExtendResult."""
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        jobs = [tuple(int(x) for x in j) for j in jobs]
+        nj = len(jobs)
+        ja = (_lib.DebwtFmJob * max(nj, 1))()
+        for k, (p, s, d, r) in enumerate(jobs):
+            if p < 0 or s < 0 or r < 0 or r >= 2 ** 32 or s >= 2 ** 32:
+                raise DebwtError(-1, "a job with a negative or oversized field")
+            ja[k].pattern, ja[k].strand, ja[k].diag, ja[k].record = p, s, d, r
+        sc = _lib.DebwtFmScoring(*[int(x) for x in scoring])
+        out = np.zeros(max(nj, 1), dtype=_ALN_DTYPE)
+        outp = out.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmAln))
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        if not cigar:
+            self._chk(self._L.debwt_fm_extend(self._h, buf, _p64(offs), npat, ja, nj, ctypes.byref(sc), int(band), outp, None,
+                                              None, 0))
+            return ExtendResult(out[:nj], None, None)
+        coff = np.zeros(nj + 1, dtype=np.uint64)
+        cap = 4 * nj + 16
+        while True:
+            cg = np.zeros(cap, dtype=np.uint32)
+            rc = self._L.debwt_fm_extend(self._h, buf, _p64(offs), npat, ja, nj, ctypes.byref(sc), int(band), outp, _p64(coff),
+                                         cg.ctypes.data_as(u32p), cap)
+            if rc == -5 and int(coff[nj]) > cap:
+                cap = int(coff[nj])
+                continue
+            self._chk(rc)
+            break
+        return ExtendResult(out[:nj], coff, cg[:int(coff[nj])].copy())
+
+    def extend_stats(self):
+        """What the last extend() (or the extension stage of the last map()) did (debwt_fm_extend_stats_get)."""
+        st = _lib.DebwtFmExtendStats()
+        self._chk(self._L.debwt_fm_extend_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def map(self, patterns, min_len=19, band=16, max_occ=64, max_cand=8, min_score=30, scoring=(1, 4, 6, 1), strands="both"):
+        """Reads to alignments (debwt_fm_map): MEM seeds of at least min_len, at most max_occ occurrences of each, clustered
+        by diagonal within `band`, the max_cand heaviest clusters extended, the best score kept; mapq = 60 * (score - sub) /
+        score.  A plain heuristic, not BWA-MEM's.  Needs attach_text().  Returns a MapResult."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        o = _lib.DebwtFmMapOpts()
+        self._L.debwt_fm_map_defaults(ctypes.byref(o))
+        o.min_len, o.band, o.max_occ, o.max_cand, o.min_score = int(min_len), int(band), int(max_occ), int(max_cand), int(min_score)
+        o.flags = MAP_FORWARD if strands == "forward" else 0
+        o.scoring = _lib.DebwtFmScoring(*[int(x) for x in scoring])
+        hits = np.zeros(max(npat, 1), dtype=_HIT_DTYPE)
+        coff = np.zeros(npat + 1, dtype=np.uint64)
+        cap = 4 * npat + 16
+        while True:
+            cg = np.zeros(cap, dtype=np.uint32)
+            rc = self._L.debwt_fm_map(self._h, buf, _p64(offs), npat, ctypes.byref(o),
+                                      hits.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmHit)), _p64(coff),
+                                      cg.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cap)
+            if rc == -5 and int(coff[npat]) > cap:
+                cap = int(coff[npat])
+                continue
+            self._chk(rc)
+            break
+        return MapResult(hits[:npat], coff, cg[:int(coff[npat])].copy())
+
+    def map_stats(self):
+        """Stage times and counts of the last map() (debwt_fm_map_stats_get)."""
+        st = _lib.DebwtFmMapStats()
+        self._chk(self._L.debwt_fm_map_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def locate_hits(self, result, max_per_pattern=None):
         """Text positions of a SearchResult's hits (debwt_fm_locate on its ranges): per pattern a tuple of uint64
         positions, uint8 strands and uint8 mismatches, ascending by (position, strand).  max_per_pattern caps the rows
@@ -447,6 +537,78 @@ class FMIndex:
 
 
 SEARCH_BOTH_STRANDS, SEARCH_BEST_ONLY = 1, 2
+MAP_REVERSE, MAP_UNMAPPED, MAP_TOO_LONG = 1, 2, 4      # MapResult.flags
+MAP_FORWARD = 1                                        # option flag of debwt_fm_map
+_ALN_DTYPE = np.dtype([("score", np.int32), ("qbeg", np.uint32), ("qend", np.uint32), ("edits", np.uint32),
+                       ("tbeg", np.uint64), ("tend", np.uint64)])
+_HIT_DTYPE = np.dtype([("pattern", np.uint64), ("flags", np.uint32), ("record", np.uint32), ("offset", np.uint64),
+                       ("qbeg", np.uint32), ("qend", np.uint32), ("tbeg", np.uint64), ("tend", np.uint64),
+                       ("score", np.int32), ("sub", np.int32), ("mapq", np.uint32), ("edits", np.uint32),
+                       ("diag", np.int64)])
+
+
+def cigar_string(ops):
+    """BAM-coded ops (len << 4 | op, M 0, I 1, D 2) as text"""
+    return "".join(f"{int(x) >> 4}{'MID'[int(x) & 15]}" for x in ops)
+
+
+def cluster_seeds(seeds, band=16, max_cand=8):
+    """Seeds of one read to extension candidates on the host (debwt_fm_cluster_seeds, no GPU).  seeds: rows of (strand,
+    record, diag, qbeg, qend).  Returns dicts (strand, record, diag, first_diag, weight, seeds), heaviest first."""
+    L = _lib.lib()
+    seeds = list(seeds)
+    sa = (_lib.DebwtFmSeed * max(len(seeds), 1))()
+    for k, (st, rec, dg, qb, qe) in enumerate(seeds):
+        sa[k].strand, sa[k].record, sa[k].diag, sa[k].qbeg, sa[k].qend = int(st), int(rec), int(dg), int(qb), int(qe)
+    out = (_lib.DebwtFmCand * max(int(max_cand), 1))()
+    rc = L.debwt_fm_cluster_seeds(sa, len(seeds), int(band), int(max_cand), out)
+    if rc < 0:
+        raise DebwtError(rc)
+    return [{n: int(getattr(out[k], n)) for n, _ in _lib.DebwtFmCand._fields_} for k in range(rc)]
+
+
+class ExtendResult:
+    """Alignments of FMIndex.extend, one per job: numpy arrays score, qbeg, qend, tbeg, tend, edits ([qbeg, qend) in the
+    query string, i.e. in the reverse complement for strand 1; [tbeg, tend) global text positions); cigar(i) as text and
+    ops(i) as BAM-coded uint32 (None without a traceback).  score 0: no alignment, everything 0."""
+
+    def __init__(self, aln, offsets, cigars):
+        self.aln, self.offsets, self.cigars = aln, offsets, cigars
+        for name in _ALN_DTYPE.names:
+            setattr(self, name, aln[name].copy())
+
+    def __len__(self):
+        return len(self.aln)
+
+    def ops(self, i):
+        if self.offsets is None:
+            return None
+        return self.cigars[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+    def cigar(self, i):
+        return None if self.offsets is None else cigar_string(self.ops(i))
+
+
+class MapResult:
+    """Alignments of FMIndex.map, one per read: numpy arrays pattern, flags (MAP_REVERSE, MAP_UNMAPPED, MAP_TOO_LONG),
+    record, offset (in the record), qbeg, qend (in the read as aligned: its reverse complement with MAP_REVERSE), tbeg,
+    tend, score, sub, mapq, edits, diag (the diagonal of the extension job that won); cigar(i) as text, ops(i)."""
+
+    def __init__(self, hits, offsets, cigars):
+        self.hits, self.offsets, self.cigars = hits, offsets, cigars
+        for name in _HIT_DTYPE.names:
+            setattr(self, name, hits[name].copy())
+        self.mapped = (self.flags & MAP_UNMAPPED) == 0
+        self.strand = (self.flags & MAP_REVERSE).astype(np.uint8)
+
+    def __len__(self):
+        return len(self.hits)
+
+    def ops(self, i):
+        return self.cigars[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+    def cigar(self, i):
+        return cigar_string(self.ops(i))
 
 
 class SearchResult:

@@ -16,6 +16,7 @@
 #include <atomic>
 #include <string>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include "radix_sort.h"
@@ -28,6 +29,7 @@
 #include "fm_kernels.h"
 #include "fm_search_kernels.h"
 #include "fm_mem_kernels.h"
+#include "fm_extend_kernels.h"
 
 namespace {
 
@@ -2835,6 +2837,11 @@ struct debwt_fm {
     debwt_fm_search_stats s_stats{};
     DevBuf m_slot, m_cnt, m_obase, m_spans, m_ranges, m_cspans, m_cranges;   // MEM scratch: slots, then compacted
     debwt_fm_mems_stats m_stats{};
+    DevBuf text;                 // the 2-bit text (debwt_fm_attach_text); has_text: checked against the samples
+    bool has_text = false;
+    DevBuf x_jobs, x_best, x_cells, x_flags, x_tr, x_cigoff, x_cig;   // extension scratch of one batch
+    debwt_fm_extend_stats x_stats{};
+    debwt_fm_map_stats map_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -3105,7 +3112,7 @@ extern "C" int debwt_fm_info_get(const debwt_fm *f, debwt_fm_info *out) {
     if (!f || !out) return DEBWT_EINVAL;
     memset(out, 0, sizeof *out);
     out->n = f->n; out->nrec = f->nrec; out->sa_sample = f->s; out->samples = f->nsamp;
-    out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap;
+    out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap + (f->has_text ? f->text.cap : 0);
     out->ms_rank = f->ms_rank; out->ms_samples = f->ms_samples;
     for (int q = 0; q < 4; q++) out->census[q] = f->census[q];
     return DEBWT_OK;
@@ -3555,13 +3562,509 @@ extern "C" int debwt_fm_mems_stats_get(const debwt_fm *f, debwt_fm_mems_stats *o
     return DEBWT_OK;
 }
 
+// ---- gapped extension of seeds and the read mapper (fm_extend_kernels.h) --------------------------------------------
+// Jobs whose band misses their record never reach the device.  The others run in batches cut at DEBWT_FM_EXTEND_BYTES of
+// traceback flags: the sweep (a group of 16, 32 or 64 lanes per job, by the band), then with a traceback the walk twice
+// with one lane per job -- once to count the CIGAR ops, once to write them at their final offsets.
+
+namespace {
+
+constexpr u64 FM_EXTEND_BYTES = 512ull << 20;          // flag scratch per batch
+constexpr u64 FM_EXTEND_JOBS = 1ull << 20;             // jobs per batch
+constexpr u32 FM_EXT_LDS_BUDGET = 64u << 10;           // staged queries and text windows of one workgroup
+
+// the device form of a job; false: no cell of the band lies inside the record (score 0)
+bool fm_ext_prepare(const debwt_fm *f, u64 m, const debwt_fm_job &jb, u32 w, FmExtJob *d) {
+    const u64 rs = f->rec_starts[jb.record];
+    const u64 re = (jb.record + 1 < f->nrec ? f->rec_starts[jb.record + 1] : f->n) - 1;
+    const __int128 tb = (__int128)jb.diag - (__int128)w;   // text position of band column 0
+    const __int128 ncol = (__int128)m + 2 * w;
+    __int128 lo = (__int128)rs - tb, hi = (__int128)re - tb;
+    if (lo < 0) lo = 0;
+    if (hi > ncol) hi = ncol;
+    if (lo >= hi) return false;
+    const u32 clo = (u32)lo, chi = (u32)hi;
+    const u32 ilo = clo > 2 * w ? clo - 2 * w : 0, ihi = (u32)std::min<u64>(m, chi);
+    d->tbase = (long long)tb;
+    d->m = (u32)m; d->strand = jb.strand; d->clo = clo; d->chi = chi;
+    d->a0 = 2 * ilo; d->nsteps = 2 * (ihi - 1) + 2 * w - d->a0 + 1;
+    d->qoff = 0; d->flag_off = 0;
+    return true;
+}
+
+template <int G>
+void fm_ext_launch(bool trace, u32 grid, u32 block, size_t lds, hipStream_t s, const u64 *text, const u8 *chars,
+                   const FmExtJob *jobs, u32 nj, u32 w, const debwt_fm_scoring &sc, u32 lds_per_job, u8 *flags, u64 *best,
+                   u32 *cells) {
+    if (trace)
+        k_fm_extend<G, true><<<grid, block, lds, s>>>(text, chars, jobs, nj, w, sc.match, sc.mismatch, sc.gap_open,
+                                                      sc.gap_extend, lds_per_job, flags, best, cells);
+    else
+        k_fm_extend<G, false><<<grid, block, lds, s>>>(text, chars, jobs, nj, w, sc.match, sc.mismatch, sc.gap_open,
+                                                       sc.gap_extend, lds_per_job, flags, best, cells);
+}
+
+struct FmExtEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~FmExtEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// jobs [0, njobs) -> out; with `trace` also ops per job (cig_n) and the ops of all jobs in job order (cig).  The
+// arguments were validated by the caller; statistics are added to f->x_stats.
+int fm_extend_run(debwt_fm *f, const char *patterns, const uint64_t *offsets, const debwt_fm_job *jobs, u64 njobs,
+                  const debwt_fm_scoring &sc, u32 w, bool trace, debwt_fm_aln *out, std::vector<u32> *cig_n,
+                  std::vector<u32> *cig) {
+    debwt_fm_extend_stats &st = f->x_stats;
+    st.jobs += njobs;
+    if (trace) { cig_n->assign(njobs, 0); cig->clear(); }
+    if (!njobs) return DEBWT_OK;
+    const u64 limit = fm_env_u64("DEBWT_FM_EXTEND_BYTES", FM_EXTEND_BYTES);
+    const int G = w < 16 ? 16 : w < 32 ? 32 : 64;
+    FmExtEvents ev;
+    HIPCHK(f, hipEventCreate(&ev.a));
+    HIPCHK(f, hipEventCreate(&ev.b));
+    std::vector<FmExtJob> dj;
+    std::vector<u64> src;                                // job index of every device job
+    std::vector<char> chars;
+    std::vector<u64> best;
+    std::vector<u32> cells, tr, ops;
+    std::vector<u64> coff;
+    for (u64 j0 = 0; j0 < njobs;) {
+        dj.clear(); src.clear(); chars.clear();
+        u64 fbytes = 0, j1 = j0, last_pat = ~0ull, last_off = 0;
+        u32 lds_job = 4;
+        for (; j1 < njobs; j1++) {
+            const debwt_fm_job &jb = jobs[j1];
+            const u64 m = offsets[jb.pattern + 1] - offsets[jb.pattern];
+            FmExtJob d;
+            if (!fm_ext_prepare(f, m, jb, w, &d)) { out[j1] = debwt_fm_aln{}; continue; }
+            const u64 fb = trace ? (u64)d.nsteps * (w + 1) : 0;
+            const bool fresh = jb.pattern != last_pat;
+            if (!dj.empty() && (fbytes + fb > limit || dj.size() >= FM_EXTEND_JOBS ||
+                                (fresh && chars.size() + m > FM_BATCH_CHARS)))
+                break;
+            if (fresh) {
+                last_pat = jb.pattern; last_off = chars.size();
+                chars.insert(chars.end(), patterns + offsets[jb.pattern], patterns + offsets[jb.pattern] + m);
+            }
+            d.qoff = last_off; d.flag_off = fbytes;
+            fbytes += fb;
+            lds_job = std::max<u32>(lds_job, (u32)(((m + 1) / 2 + (m + 2 * w + 3) / 4 + 3) & ~3ull));
+            dj.push_back(d); src.push_back(j1);
+        }
+        const u64 nd = dj.size();
+        if (!nd) { j0 = j1; continue; }
+        // the workgroup: as many groups as the staged strings of its jobs leave room for
+        int g = G;
+        u32 block = 256;
+        if ((u64)(block / g) * lds_job > FM_EXT_LDS_BUDGET) block = 64;
+        while ((u64)(block / g) * lds_job > FM_EXT_LDS_BUDGET && g < 64) g *= 2;
+        const u32 jpb = block / g, grid = (u32)((nd + jpb - 1) / jpb);
+        const u32 jpw = 64 / g;                            // wave steps: the longest job of every wave
+        for (u64 a = 0; a < nd; a += jpw) {
+            u32 mx = 0;
+            for (u64 b = a; b < std::min(nd, a + jpw); b++) mx = std::max(mx, (dj[b].nsteps + 1) & ~1u);
+            st.wave_steps += mx;
+        }
+        st.scratch_bytes = std::max<u64>(st.scratch_bytes, fbytes);
+        FM_ENSURE(f, f->q_chars, std::max<size_t>(chars.size(), 1));
+        FM_ENSURE(f, f->x_jobs, nd * sizeof(FmExtJob));
+        FM_ENSURE(f, f->x_best, nd * 8);
+        FM_ENSURE(f, f->x_cells, nd * 4);
+        if (trace) {
+            FM_ENSURE(f, f->x_flags, (size_t)std::max<u64>(fbytes, 1));
+            FM_ENSURE(f, f->x_tr, nd * 16);
+            FM_ENSURE(f, f->x_cigoff, (nd + 1) * 8);
+        }
+        HIPCHK(f, hipMemcpyAsync(f->q_chars.p, chars.data(), chars.size(), hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->x_jobs.p, dj.data(), nd * sizeof(FmExtJob), hipMemcpyHostToDevice, f->stream));
+        (void)hipEventRecord(ev.a, f->stream);
+        const size_t lds = (size_t)jpb * lds_job;
+        auto go = [&](auto tag) {
+            fm_ext_launch<decltype(tag)::value>(trace, grid, block, lds, f->stream, f->text.as<u64>(), f->q_chars.as<u8>(),
+                                                f->x_jobs.as<FmExtJob>(), (u32)nd, w, sc, lds_job, f->x_flags.as<u8>(),
+                                                f->x_best.as<u64>(), f->x_cells.as<u32>());
+        };
+        if (g == 16) go(std::integral_constant<int, 16>{});
+        else if (g == 32) go(std::integral_constant<int, 32>{});
+        else go(std::integral_constant<int, 64>{});
+        (void)hipEventRecord(ev.b, f->stream);
+        st.launches++;
+        best.resize(nd); cells.resize(nd);
+        HIPCHK(f, hipMemcpyAsync(best.data(), f->x_best.p, nd * 8, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(f, hipMemcpyAsync(cells.data(), f->x_cells.p, nd * 4, hipMemcpyDeviceToHost, f->stream));
+        if (trace) {
+            k_fm_extend_trace<<<grid_for(nd, 256), 256, 0, f->stream>>>(f->x_jobs.as<FmExtJob>(), (u32)nd, w, f->x_flags.as<u8>(),
+                                                                        f->x_best.as<u64>(), nullptr, nullptr, f->x_tr.as<u32>());
+            st.launches++;
+            tr.resize(4 * nd);
+            HIPCHK(f, hipMemcpyAsync(tr.data(), f->x_tr.p, nd * 16, hipMemcpyDeviceToHost, f->stream));
+        }
+        int rc = fm_sync(f);
+        if (rc) return rc;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+        st.ms_kernel += ms;
+        for (u64 a = 0; a < nd; a++) st.cells += cells[a];
+        u64 total = 0;
+        if (trace) {
+            coff.resize(nd + 1);
+            coff[0] = 0;
+            for (u64 a = 0; a < nd; a++) coff[a + 1] = coff[a] + tr[4 * a + 3];
+            total = coff[nd];
+            ops.resize(total);
+            if (total) {
+                FM_ENSURE(f, f->x_cig, (size_t)total * 4);
+                HIPCHK(f, hipMemcpyAsync(f->x_cigoff.p, coff.data(), (nd + 1) * 8, hipMemcpyHostToDevice, f->stream));
+                (void)hipEventRecord(ev.a, f->stream);
+                k_fm_extend_trace<<<grid_for(nd, 256), 256, 0, f->stream>>>(f->x_jobs.as<FmExtJob>(), (u32)nd, w,
+                                                                            f->x_flags.as<u8>(), f->x_best.as<u64>(),
+                                                                            f->x_cigoff.as<u64>(), f->x_cig.as<u32>(),
+                                                                            f->x_tr.as<u32>());
+                (void)hipEventRecord(ev.b, f->stream);
+                st.launches++;
+                HIPCHK(f, hipMemcpyAsync(ops.data(), f->x_cig.p, total * 4, hipMemcpyDeviceToHost, f->stream));
+                if ((rc = fm_sync(f))) return rc;
+                (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+                st.ms_trace += ms;
+            }
+        }
+        for (u64 a = 0; a < nd; a++) {
+            debwt_fm_aln &o = out[src[a]];
+            o = debwt_fm_aln{};
+            const u64 key = best[a];
+            if (!(key >> 32)) continue;
+            const u32 i = 65535u - (u32)((key >> 8) & 0xFFFFu), k = 127u - (u32)(key & 0xFFu);
+            o.score = (int32_t)(key >> 32);
+            o.qend = i + 1;
+            o.tend = (u64)(dj[a].tbase + (long long)(i + k)) + 1;
+            if (trace) {
+                o.qbeg = tr[4 * a]; o.tbeg = (u64)(dj[a].tbase + (long long)tr[4 * a + 1]); o.edits = tr[4 * a + 2];
+                (*cig_n)[src[a]] = tr[4 * a + 3];
+            }
+        }
+        if (trace) cig->insert(cig->end(), ops.begin(), ops.end());   // device jobs are in job order
+        st.batches++;
+        j0 = j1;
+    }
+    return DEBWT_OK;
+}
+
+int fm_ext_check(debwt_fm *f, const debwt_fm_scoring *sc, u32 band, const char *who) {
+    if (!f->has_text) { f->err = std::string(who) + ": no text attached (debwt_fm_attach_text)"; return DEBWT_ESTATE; }
+    if (band > FM_EXT_MAX_BAND) { f->err = std::string(who) + ": band above 63"; return DEBWT_EINVAL; }
+    if (sc->match < 1 || sc->match > 255 || sc->mismatch < 1 || sc->mismatch > 255 || sc->gap_open < 0 || sc->gap_open > 255 ||
+        sc->gap_extend < 1 || sc->gap_extend > 255) {
+        f->err = std::string(who) + ": scoring outside match 1..255, mismatch 1..255, gap open 0..255, gap extend 1..255";
+        return DEBWT_EINVAL;
+    }
+    return DEBWT_OK;
+}
+
+double fm_ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_attach_text(debwt_fm *f, debwt_ctx *c, const uint64_t *packed, const uint64_t *sep) {
+    if (!f) return DEBWT_EINVAL;
+    const u64 n = f->n, nrec = f->nrec;
+    if (c) {
+        if (c->stage < ST_LOADED) { f->err = "debwt_fm_attach_text: the context holds no text"; return DEBWT_ESTATE; }
+        if (c->n != n || c->nrec != nrec) { f->err = "debwt_fm_attach_text: the context's text has another n or nrec"; return DEBWT_EINVAL; }
+        sep = c->h_sep.data();
+    } else if (!packed || !sep) return DEBWT_EINVAL;
+    for (u64 r = 0; r < nrec; r++) {
+        const u64 want = (r + 1 < nrec ? f->rec_starts[r + 1] : n) - 1;
+        if (sep[r] != want) {
+            f->err = "debwt_fm_attach_text: separator " + std::to_string(r) + " is at " + std::to_string(sep[r]) +
+                     ", the index has it at " + std::to_string(want);
+            return DEBWT_EINVAL;
+        }
+    }
+    HIPCHK(f, hipSetDevice(f->device));
+    f->has_text = false;
+    const size_t words = (size_t)((n + 63) >> 5), tw = words + 2;
+    FM_ENSURE(f, f->text, tw * 8);
+    FM_ENSURE(f, f->s_ctr, 64);
+    if (c) {
+        HIPCHK(f, hipStreamSynchronize(c->stream));          // the load may still be in flight on the context's stream
+        HIPCHK(f, hipMemcpyAsync(f->text.p, c->text.p, words * 8, hipMemcpyDeviceToDevice, f->stream));
+    } else {
+        HIPCHK(f, hipMemcpyAsync(f->text.p, packed, words * 8, hipMemcpyHostToDevice, f->stream));
+    }
+    HIPCHK(f, hipMemsetAsync(f->text.as<u64>() + words, 0, (tw - words) * 8, f->stream));
+    HIPCHK(f, hipMemsetAsync(f->s_ctr.p, 0, 8, f->stream));
+    k_fm_text_check<<<grid_for(f->nsamp, 256), 256, 0, f->stream>>>(f->V, f->sa.as<u64>(), f->nsamp, f->sh, f->text.as<u64>(),
+                                                                   f->s_ctr.as<u64>());
+    u64 bad = 0;
+    HIPCHK(f, hipMemcpyAsync(&bad, f->s_ctr.p, 8, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    if (bad) {
+        f->err = "debwt_fm_attach_text: not the text of the index (" + std::to_string(bad) + " of " + std::to_string(f->nsamp) +
+                 " sampled rows hold another symbol than the text before their suffix)";
+        return DEBWT_EINVAL;
+    }
+    f->has_text = true;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_extend(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                               const debwt_fm_job *jobs, uint64_t njobs, const debwt_fm_scoring *sc, uint32_t band,
+                               debwt_fm_aln *out, uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity) {
+    if (!f || !sc || !offsets || (njobs && (!jobs || !out))) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->x_stats = debwt_fm_extend_stats{};
+    int rc = fm_ext_check(f, sc, band, "debwt_fm_extend");
+    if (rc) return rc;
+    for (u64 i = 0; i < npat; i++)
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_extend: offsets must not decrease"; return DEBWT_EINVAL; }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    for (u64 j = 0; j < njobs; j++) {
+        const debwt_fm_job &jb = jobs[j];
+        if (jb.pattern >= npat || jb.strand > 1 || jb.record >= f->nrec) {
+            f->err = "debwt_fm_extend: job " + std::to_string(j) + " names a pattern, strand or record that does not exist";
+            return DEBWT_EINVAL;
+        }
+        const u64 m = offsets[jb.pattern + 1] - offsets[jb.pattern];
+        if (m < 1 || m > FM_EXT_MAX_LEN) {
+            f->err = "debwt_fm_extend: job " + std::to_string(j) + " has a pattern of " + std::to_string(m) + " bytes (1..65535)";
+            return DEBWT_EINVAL;
+        }
+    }
+    HIPCHK(f, hipSetDevice(f->device));
+    const bool trace = cigar_offsets != nullptr;
+    std::vector<u32> cig_n, cig;
+    rc = fm_extend_run(f, patterns, offsets, jobs, njobs, *sc, band, trace, out, &cig_n, &cig);
+    if (rc) return rc;
+    f->x_stats.ms_wall = (float)fm_ms_since(t0);
+    if (!trace) return DEBWT_OK;
+    cigar_offsets[0] = 0;
+    for (u64 j = 0; j < njobs; j++) cigar_offsets[j + 1] = cigar_offsets[j] + cig_n[j];
+    if (capacity < cig.size() || (!cig.empty() && !cigar)) {
+        f->err = "debwt_fm_extend: capacity below the CIGAR ops (cigar_offsets[njobs] = " + std::to_string(cig.size()) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (!cig.empty()) memcpy(cigar, cig.data(), cig.size() * 4);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_extend_stats_get(const debwt_fm *f, debwt_fm_extend_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->x_stats;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_cluster_seeds(const debwt_fm_seed *seeds, uint64_t nseeds, uint32_t band, uint32_t max_cand,
+                                      debwt_fm_cand *out) {
+    if ((nseeds && !seeds) || (max_cand && !out)) return DEBWT_EINVAL;
+    for (u64 i = 0; i < nseeds; i++)
+        if (seeds[i].qend <= seeds[i].qbeg) return DEBWT_EINVAL;
+    std::vector<u64> ord(nseeds);
+    for (u64 i = 0; i < nseeds; i++) ord[i] = i;
+    auto key = [&](u64 i) { return std::make_tuple(seeds[i].strand, seeds[i].record, seeds[i].diag, seeds[i].qbeg, seeds[i].qend); };
+    std::sort(ord.begin(), ord.end(), [&](u64 a, u64 b) { return key(a) < key(b); });
+    std::vector<debwt_fm_cand> cl;
+    std::vector<std::pair<u32, u32>> iv;
+    auto close = [&](debwt_fm_cand &c) {                   // weight: the union of the cluster's query intervals
+        std::sort(iv.begin(), iv.end());
+        u32 end = 0, wgt = 0;
+        for (auto &p : iv) {
+            const u32 a = std::max(p.first, end);
+            if (p.second > a) { wgt += p.second - a; end = p.second; }
+        }
+        c.weight = wgt;
+        iv.clear();
+    };
+    u32 best_len = 0, best_qbeg = 0;
+    for (u64 x = 0; x < nseeds; x++) {
+        const debwt_fm_seed &s = seeds[ord[x]];
+        const bool join = !cl.empty() && cl.back().strand == s.strand && cl.back().record == s.record &&
+                          (__int128)s.diag - (__int128)cl.back().first_diag <= (__int128)band;
+        if (!join) {
+            if (!cl.empty()) close(cl.back());
+            cl.push_back(debwt_fm_cand{s.diag, s.diag, s.record, s.strand, 0, 0});
+            best_len = 0;
+        }
+        debwt_fm_cand &c = cl.back();
+        c.seeds++;
+        iv.emplace_back(s.qbeg, s.qend);
+        const u32 len = s.qend - s.qbeg;
+        if (len > best_len || (len == best_len && s.qbeg < best_qbeg)) { best_len = len; best_qbeg = s.qbeg; c.diag = s.diag; }
+    }
+    if (!cl.empty()) close(cl.back());
+    std::stable_sort(cl.begin(), cl.end(), [](const debwt_fm_cand &a, const debwt_fm_cand &b) {
+        if (a.weight != b.weight) return a.weight > b.weight;
+        return std::make_tuple(a.strand, a.record, a.first_diag) < std::make_tuple(b.strand, b.record, b.first_diag);
+    });
+    const u64 k = std::min<u64>(cl.size(), max_cand);
+    for (u64 i = 0; i < k; i++) out[i] = cl[i];
+    return (int)k;
+}
+
+extern "C" void debwt_fm_map_defaults(debwt_fm_map_opts *o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    o->min_len = 19; o->band = 16; o->max_occ = 64; o->max_cand = 8; o->min_score = 30; o->flags = 0;
+    o->scoring = debwt_fm_scoring{1, 4, 6, 1};
+}
+
+extern "C" int debwt_fm_map(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                            const debwt_fm_map_opts *opts, debwt_fm_hit *hits, uint64_t *cigar_offsets, uint32_t *cigar,
+                            uint64_t capacity) {
+    if (!f || !offsets || !cigar_offsets || (npat && !hits)) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    debwt_fm_map_opts o;
+    debwt_fm_map_defaults(&o);
+    if (opts) o = *opts;
+    f->map_stats = debwt_fm_map_stats{};
+    f->x_stats = debwt_fm_extend_stats{};
+    int rc = fm_ext_check(f, &o.scoring, o.band, "debwt_fm_map");
+    if (rc) return rc;
+    if (!o.min_len || !o.max_occ || !o.max_cand || o.max_cand > 4096 || (o.flags & ~DEBWT_FM_MAP_FORWARD)) {
+        f->err = "debwt_fm_map: min_len, max_occ and max_cand must be positive (max_cand <= 4096), flags known";
+        return DEBWT_EINVAL;
+    }
+    for (u64 i = 0; i < npat; i++)
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_map: offsets must not decrease"; return DEBWT_EINVAL; }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    debwt_fm_map_stats &ms = f->map_stats;
+    ms.reads = npat;
+    cigar_offsets[0] = 0;
+    std::vector<u32> all_cig;
+    std::vector<uint64_t> moff, ranges, loff, pos;
+    std::vector<u32> spans, cig_n, cig;
+    std::vector<u8> strands;
+    std::vector<debwt_fm_seed> seeds;
+    std::vector<debwt_fm_cand> cand(o.max_cand);
+    std::vector<debwt_fm_job> jobs;
+    std::vector<u64> job_first;
+    std::vector<debwt_fm_aln> aln;
+    const u32 mflags = (o.flags & DEBWT_FM_MAP_FORWARD) ? 0u : DEBWT_FM_BOTH_STRANDS;
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 p1 = p0 + 1;
+        while (p1 < npat && p1 - p0 < (1ull << 18) && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS) p1++;
+        const u64 np = p1 - p0;
+        // 1. MEMs of the batch (the existing path, as any caller uses it)
+        auto t = std::chrono::steady_clock::now();
+        moff.assign(np + 1, 0);
+        u64 cap = std::max<u64>(spans.size() / 2, 4 * np + 16);
+        for (;;) {
+            spans.resize(2 * cap); ranges.resize(2 * cap); strands.resize(cap);
+            rc = debwt_fm_mems(f, patterns, offsets + p0, np, o.min_len, mflags, moff.data(), spans.data(), ranges.data(),
+                               strands.data(), cap);
+            if (rc == DEBWT_ERANGE && moff[np] > cap) { cap = moff[np]; continue; }
+            if (rc) return rc;
+            break;
+        }
+        const u64 nmem = moff[np];
+        ms.mems += nmem;
+        ms.ms_mems += (float)fm_ms_since(t);
+        // 2. their first max_occ rows located
+        t = std::chrono::steady_clock::now();
+        loff.assign(nmem + 1, 0);
+        u64 nocc = 0;
+        for (u64 i = 0; i < nmem; i++) nocc += std::min<u64>(ranges[2 * i + 1] - ranges[2 * i], o.max_occ);
+        pos.resize(std::max<u64>(nocc, 1));
+        rc = debwt_fm_locate(f, ranges.data(), nmem, o.max_occ, loff.data(), pos.data(), pos.size());
+        if (rc) return rc;
+        ms.seeds += nocc;
+        ms.ms_locate += (float)fm_ms_since(t);
+        // 3. seeds -> candidates -> jobs, read by read
+        t = std::chrono::steady_clock::now();
+        jobs.clear();
+        job_first.assign(np + 1, 0);
+        for (u64 r = 0; r < np; r++) {
+            job_first[r] = jobs.size();
+            const u64 m = offsets[p0 + r + 1] - offsets[p0 + r];
+            if (m < 1 || m > FM_EXT_MAX_LEN) continue;
+            seeds.clear();
+            for (u64 i = moff[r]; i < moff[r + 1]; i++) {
+                const u32 qb = strands[i] ? (u32)m - spans[2 * i + 1] : spans[2 * i];      // in Q
+                const u32 qe = strands[i] ? (u32)m - spans[2 * i] : spans[2 * i + 1];
+                for (u64 x = loff[i]; x < loff[i + 1]; x++) {
+                    const u64 tp = pos[x];
+                    const u64 rec = (u64)(std::upper_bound(f->rec_starts.begin(), f->rec_starts.end(), tp) - f->rec_starts.begin()) - 1;
+                    seeds.push_back(debwt_fm_seed{(int64_t)tp - (int64_t)qb, (u32)rec, strands[i], qb, qe});
+                }
+            }
+            if (seeds.empty()) continue;
+            const int nc = debwt_fm_cluster_seeds(seeds.data(), seeds.size(), o.band, o.max_cand, cand.data());
+            if (nc < 0) { f->err = "debwt_fm_map: a MEM with an empty span"; return DEBWT_EINTERNAL; }
+            for (int k = 0; k < nc; k++) jobs.push_back(debwt_fm_job{p0 + r, cand[k].diag, cand[k].record, cand[k].strand});
+        }
+        job_first[np] = jobs.size();
+        ms.candidates += jobs.size();
+        ms.jobs += jobs.size();
+        ms.ms_candidates += (float)fm_ms_since(t);
+        // 4. every job extended, with its traceback: the tie rule and `sub` need the text interval of each
+        t = std::chrono::steady_clock::now();
+        aln.resize(jobs.size());
+        HIPCHK(f, hipSetDevice(f->device));
+        rc = fm_extend_run(f, patterns, offsets, jobs.data(), jobs.size(), o.scoring, o.band, true, aln.data(), &cig_n, &cig);
+        if (rc) return rc;
+        ms.ms_extend += (float)fm_ms_since(t);
+        // 5. the winner of every read
+        std::vector<u64> cfirst(jobs.size() + 1, 0);
+        for (u64 j = 0; j < jobs.size(); j++) cfirst[j + 1] = cfirst[j] + cig_n[j];
+        for (u64 r = 0; r < np; r++) {
+            const u64 m = offsets[p0 + r + 1] - offsets[p0 + r];
+            debwt_fm_hit &h = hits[p0 + r];
+            memset(&h, 0, sizeof h);
+            h.pattern = p0 + r;
+            h.flags = DEBWT_FM_MAP_UNMAPPED | (m > FM_EXT_MAX_LEN ? DEBWT_FM_MAP_TOO_LONG : 0u);
+            cigar_offsets[p0 + r + 1] = cigar_offsets[p0 + r];
+            u64 w = ~0ull;
+            for (u64 j = job_first[r]; j < job_first[r + 1]; j++) {
+                if (aln[j].score <= 0) continue;
+                if (w == ~0ull || aln[j].score > aln[w].score ||
+                    (aln[j].score == aln[w].score && std::make_tuple(jobs[j].strand, jobs[j].record, aln[j].tbeg) <
+                                                         std::make_tuple(jobs[w].strand, jobs[w].record, aln[w].tbeg)))
+                    w = j;
+            }
+            if (w == ~0ull || aln[w].score < o.min_score) continue;
+            int32_t sub = 0;
+            for (u64 j = job_first[r]; j < job_first[r + 1]; j++)
+                if (j != w && aln[j].score > sub && (aln[j].tend <= aln[w].tbeg || aln[j].tbeg >= aln[w].tend)) sub = aln[j].score;
+            const debwt_fm_aln &a = aln[w];
+            h.flags = jobs[w].strand ? DEBWT_FM_MAP_REVERSE : 0u;
+            h.record = jobs[w].record; h.offset = a.tbeg - f->rec_starts[jobs[w].record];
+            h.qbeg = a.qbeg; h.qend = a.qend; h.tbeg = a.tbeg; h.tend = a.tend;
+            h.score = a.score; h.sub = sub; h.mapq = (u32)(60 * (int64_t)(a.score - sub) / a.score); h.edits = a.edits;
+            h.diag = jobs[w].diag;
+            all_cig.insert(all_cig.end(), cig.begin() + cfirst[w], cig.begin() + cfirst[w + 1]);
+            cigar_offsets[p0 + r + 1] = all_cig.size();
+            ms.mapped++;
+        }
+        ms.batches++;
+        p0 = p1;
+    }
+    f->x_stats.ms_wall = ms.ms_extend;
+    ms.ms_wall = (float)fm_ms_since(t0);
+    if (capacity < all_cig.size() || (!all_cig.empty() && !cigar)) {
+        f->err = "debwt_fm_map: capacity below the CIGAR ops (cigar_offsets[npat] = " + std::to_string(all_cig.size()) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (!all_cig.empty()) memcpy(cigar, all_cig.data(), all_cig.size() * 4);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_map_stats_get(const debwt_fm *f, debwt_fm_map_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->map_stats;
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
     for (DevBuf *b : {&f->idx, &f->rowlists, &f->sa, &f->q_chars, &f->q_off, &f->q_out, &f->q_runs, &f->s_hits, &f->s_ctr,
                       &f->s_plist, &f->m_slot, &f->m_cnt, &f->m_obase, &f->m_spans, &f->m_ranges, &f->m_cspans,
-                      &f->m_cranges})
+                      &f->m_cranges, &f->text, &f->x_jobs, &f->x_best, &f->x_cells, &f->x_flags, &f->x_tr, &f->x_cigoff,
+                      &f->x_cig})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -540,6 +540,132 @@ typedef struct {
     float ms_kernel, ms_wall;
 } debwt_fm_mems_stats;
 int debwt_fm_mems_stats_get(const debwt_fm *fm, debwt_fm_mems_stats *out);
+
+/* ---- gapped extension of seeds and a read mapper (fm_extend_kernels.h) -------------------------------------------
+ * An index holds no text; the two entry points below read the text next to a seed, so it is attached first (n / 4 bytes
+ * of HBM, counted in debwt_fm_info.device_bytes).  Without it they answer DEBWT_ESTATE; count, locate, search and mems
+ * never need it.
+ *   ctx given: device-to-device copy of the context's loaded text (same n and nrec, else DEBWT_EINVAL); packed / sep are
+ *              ignored.  The path after debwt_fm_create.
+ *   ctx NULL:  packed (host words in the format of debwt_load_text) and sep (the nrec separator positions) are uploaded.
+ *              The path after debwt_fm_open; a host gets them from debwt_pack_fasta.
+ * The text must be the index's text: the separators must be the record starts - 1 (and n - 1), and for every sample i
+ * with p = sa[i] > 0 the 2-bit code of row i * sa_sample must be the text's code at p - 1 (checked on the device);
+ * otherwise DEBWT_EINVAL with the reason in debwt_fm_last_error, and no text is attached. */
+int debwt_fm_attach_text(debwt_fm *fm, debwt_ctx *ctx, const uint64_t *packed, const uint64_t *sep);
+
+/* Banded affine-gap local alignment of jobs.  A job aligns the query string Q (length m, 1..65535) of pattern `pattern`
+ * -- the pattern itself (strand 0) or its reverse complement (strand 1); a character outside ACGTacgt mismatches every
+ * base -- against record `record` around the diagonal `diag` = text position - query position.  Scoring: match a > 0,
+ * mismatch b > 0, gap open o >= 0, gap extend e > 0, each at most 255; a gap of length L costs o + L * e.  band: the
+ * half-width w, 0..63.  With [rs, re) the text positions of the record's bases, a cell (i, t) is allowed iff
+ * 0 <= i < m, rs <= t < re and |t - i - diag| <= w; over allowed cells, with -inf for every value at any other cell:
+ *     E(i,t) = max(H(i,t-1) - o - e, E(i,t-1) - e)                  deletion: consumes text t
+ *     F(i,t) = max(H(i-1,t) - o - e, F(i-1,t) - e)                  insertion: consumes query i
+ *     H(i,t) = max(0 + s(i,t), H(i-1,t-1) + s(i,t), E(i,t), F(i,t)),   s = +a if Q[i] == T[t] else -b
+ *     score  = max(0, max over allowed cells of H)
+ * out[j]: score, and for score > 0 one optimal alignment: [qbeg, qend) IN Q -- for strand 1 these are coordinates of the
+ * reverse complement, unlike the spans of debwt_fm_mems (which are in the pattern as given): a CIGAR reads left to right
+ * along the text --, [tbeg, tend) global text positions, edits = mismatch columns + gap bases.  cigar_offsets (njobs + 1)
+ * and cigar: job j's ops are cigar[cigar_offsets[j] .. cigar_offsets[j + 1]), BAM-coded (len << 4 | op, M 0, I 1, D 2);
+ * DEBWT_ERANGE when capacity < cigar_offsets[njobs] (cigar_offsets and out are written first, as debwt_fm_locate does).
+ * score 0: empty CIGAR, coordinates 0.  cigar_offsets NULL: score only -- no traceback is stored; qend and tend are the
+ * end of the best alignment, qbeg = tbeg = edits = 0.
+ * Among optimal alignments: the end cell is the one with the smallest query index, then the smallest text position; walking
+ * back, H prefers the diagonal (and stops where H(i-1,t-1) <= 0) to E to F, and a gap is opened rather than continued on a
+ * tie.  The result does not depend on how the jobs are batched.
+ * DEBWT_EINVAL: band > 63, a scoring value out of range, a job with pattern >= npat, strand > 1, record >= nrec or a
+ * pattern length outside 1..65535.  Device scratch: (2m + 2w - 1 or fewer) x (w + 1) flag bytes per job with a traceback;
+ * batches are cut at DEBWT_FM_EXTEND_BYTES of it (environment, read per call; default 512 MiB; a job above it goes alone). */
+typedef struct {
+    uint64_t pattern;
+    int64_t diag;
+    uint32_t record, strand;
+} debwt_fm_job;
+typedef struct {
+    int32_t match, mismatch, gap_open, gap_extend;
+} debwt_fm_scoring;
+typedef struct {
+    int32_t score;
+    uint32_t qbeg, qend, edits;
+    uint64_t tbeg, tend;
+} debwt_fm_aln;
+int debwt_fm_extend(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat, const debwt_fm_job *jobs,
+                    uint64_t njobs, const debwt_fm_scoring *scoring, uint32_t band, debwt_fm_aln *out,
+                    uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity);
+/* what the last debwt_fm_extend (or the extension stage of the last debwt_fm_map) did: jobs, batches, kernel launches,
+ * allowed cells computed, steps of the waves (one anti-diagonal each: cells / (64 x wave_steps) is the share of lanes
+ * busy), the largest flag scratch of a batch, kernel time (events: sweep, traceback) and host wall time */
+typedef struct {
+    uint64_t jobs, batches, launches, cells, wave_steps, scratch_bytes;
+    float ms_kernel, ms_trace, ms_wall;
+} debwt_fm_extend_stats;
+int debwt_fm_extend_stats_get(const debwt_fm *fm, debwt_fm_extend_stats *out);
+
+/* Seeds of ONE read to extension candidates (host only, no GPU; the clustering step of debwt_fm_map).  A seed is an exact
+ * match Q[qbeg, qend) = T[diag + qbeg, diag + qend) inside `record`.  Sorted by (strand, record, diag), a seed joins the
+ * open cluster when strand and record agree and its diag is at most `band` above the diag of the cluster's first seed,
+ * otherwise it opens a new one.  weight = distinct query positions the cluster's seeds cover.  The max_cand heaviest
+ * clusters are written, heaviest first, ties by smaller (strand, record, first seed's diag).  A candidate's diag is that
+ * of its longest seed (ties: smallest qbeg, then smallest diag).  Returns the number written (<= max_cand), or
+ * DEBWT_EINVAL (a seed with qend <= qbeg). */
+typedef struct {
+    int64_t diag;
+    uint32_t record, strand, qbeg, qend;
+} debwt_fm_seed;
+typedef struct {
+    int64_t diag, first_diag;
+    uint32_t record, strand, weight, seeds;
+} debwt_fm_cand;
+int debwt_fm_cluster_seeds(const debwt_fm_seed *seeds, uint64_t nseeds, uint32_t band, uint32_t max_cand,
+                           debwt_fm_cand *out);
+
+/* Reads to alignments: MEMs of every read (debwt_fm_mems, min_len, both strands unless DEBWT_FM_MAP_FORWARD), each MEM
+ * located for at most max_occ rows (the first rows in suffix order), the seeds clustered per read
+ * (debwt_fm_cluster_seeds with `band` and max_cand), one extension job per candidate, all jobs of a batch of reads in one
+ * extension pass.  Per read the best score wins (ties by smaller (strand, record, tbeg)); sub = the best score of
+ * another job of the read whose text interval does not intersect the winner's (0: none); mapq = 60 * (score - sub) /
+ * score in integers.  A read without a seed or with a best score below min_score is unmapped (score 0,
+ * DEBWT_FM_MAP_UNMAPPED); a read above 65535 bases is not extended (DEBWT_FM_MAP_UNMAPPED | DEBWT_FM_MAP_TOO_LONG).
+ * A plain heuristic: neither the seeding strategy nor the mapping quality is BWA-MEM's.
+ * hits[i]: read i.  qbeg .. tend, edits as debwt_fm_extend gives them (qbeg, qend in the read's reverse complement when
+ * DEBWT_FM_MAP_REVERSE is set); offset = tbeg - first position of `record`; diag: the diagonal of the job that won, so a
+ * caller can re-derive the band.  CIGARs through cigar_offsets (npat + 1) / cigar / capacity as in debwt_fm_extend
+ * (DEBWT_ERANGE after hits and cigar_offsets are written). */
+#define DEBWT_FM_MAP_REVERSE  1u   /* hit flag: aligned as the reverse complement */
+#define DEBWT_FM_MAP_UNMAPPED 2u   /* hit flag */
+#define DEBWT_FM_MAP_TOO_LONG 4u   /* hit flag */
+#define DEBWT_FM_MAP_FORWARD  1u   /* option flag: seed and align the reads as given only */
+typedef struct {
+    uint32_t min_len;      /* shortest MEM used as a seed (19) */
+    uint32_t band;         /* w of clustering and extension (16) */
+    uint32_t max_occ;      /* rows located per MEM (64) */
+    uint32_t max_cand;     /* candidates extended per read (8) */
+    int32_t min_score;     /* below it a read is unmapped (30) */
+    uint32_t flags;        /* DEBWT_FM_MAP_FORWARD */
+    debwt_fm_scoring scoring;   /* (1, 4, 6, 1) */
+} debwt_fm_map_opts;
+typedef struct {
+    uint64_t pattern;
+    uint32_t flags, record;
+    uint64_t offset;
+    uint32_t qbeg, qend;
+    uint64_t tbeg, tend;
+    int32_t score, sub;
+    uint32_t mapq, edits;
+    int64_t diag;
+} debwt_fm_hit;
+void debwt_fm_map_defaults(debwt_fm_map_opts *opts);
+/* opts NULL: the defaults */
+int debwt_fm_map(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat, const debwt_fm_map_opts *opts,
+                 debwt_fm_hit *hits, uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity);
+/* the last debwt_fm_map: reads, reads mapped, seeds (located MEM occurrences), candidates kept (= extension jobs), and host
+ * wall milliseconds per stage: MEMs, locate, candidate building, extension, and the whole call */
+typedef struct {
+    uint64_t reads, mapped, mems, seeds, candidates, jobs, batches;
+    float ms_mems, ms_locate, ms_candidates, ms_extend, ms_wall;
+} debwt_fm_map_stats;
+int debwt_fm_map_stats_get(const debwt_fm *fm, debwt_fm_map_stats *out);
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
