@@ -7,7 +7,7 @@
  *   deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq
  *   deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]
- *                      [--max-occ N] [--min-score S] READS.fa|.fq
+ *                      [--max-occ N] [--min-score S] [--chain [--max-gap G]] READS.fa|.fq
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -33,6 +33,9 @@
  * the text of OUT.  One PAF line per mapped read: name, length, query start and end (on the read's own strand), strand,
  * record number, record length, target start and end, matching bases, alignment columns, mapping quality, then AS:i:
  * (score), NM:i: (mismatches + gap bases) and cg:Z: (CIGAR along the text).  Reads that are not mapped print nothing.
+ * --chain maps with debwt_fm_map_chained instead: the seeds of a read are chained across diagonals (steps of at most W,
+ * stretches of at most G bases between two seeds, default 5000) and the band follows the chain, so a read whose indels
+ * add up to more than W is still aligned end to end.  The PAF columns are the same.
  *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
@@ -56,7 +59,7 @@ static void usage(void) {
             "       deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq\n"
             "       deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]\n"
-            "                          [--max-occ N] [--min-score S] READS.fa|.fq\n"
+            "                          [--max-occ N] [--min-score S] [--chain [--max-gap G]] READS.fa|.fq\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
@@ -64,7 +67,8 @@ static void usage(void) {
             "mems prints name<TAB>strand<TAB>qbeg<TAB>qend<TAB>count<TAB>record:offset,... per maximal exact match of at\n"
             "least L bases (default 19);\n"
             "map prints one PAF line per mapped read (AS:i: score, NM:i: edits, cg:Z: CIGAR); --ref is the FASTA that OUT\n"
-            "is the BWT of\n");
+            "is the BWT of; --chain chains the seeds of a read across diagonals and aligns along the chain (stretches of\n"
+            "at most G bases between two seeds, default 5000)\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -492,7 +496,7 @@ done:
 /* ---- map ------------------------------------------------------------------------------------------------------------- */
 
 static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t threads, int iupac, uint64_t seed, int device,
-                   const debwt_fm_map_opts *opts) {
+                   const debwt_fm_map_opts *opts, int chain, uint32_t max_gap) {
     struct patterns P;
     if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
@@ -524,7 +528,15 @@ static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t
         free(cig);
         cig = malloc(cap * 4);
         if (!cig) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = debwt_fm_map(fm, P.seq, P.off, P.n, opts, hits, coff, cig, cap);
+        if (chain) {
+            debwt_fm_chain_opts co;
+            debwt_fm_chain_defaults(&co);
+            co.map = *opts;
+            co.max_gap = max_gap;
+            rc = debwt_fm_map_chained(fm, P.seq, P.off, P.n, &co, hits, coff, cig, cap, NULL, NULL, 0);
+        } else {
+            rc = debwt_fm_map(fm, P.seq, P.off, P.n, opts, hits, coff, cig, cap);
+        }
         if (rc == DEBWT_ERANGE && coff[P.n] > cap) { cap = coff[P.n]; continue; }
         break;
     }
@@ -569,7 +581,9 @@ int main(int argc, char **argv) {
     uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, v64 = 0;
     debwt_fm_map_opts mo;
     debwt_fm_map_defaults(&mo);
-    int iupac = 0, search = 0;
+    debwt_fm_chain_opts co;
+    debwt_fm_chain_defaults(&co);
+    int iupac = 0, search = 0, chain = 0, gap_given = 0;
     uint32_t flags = 0;
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
@@ -580,6 +594,7 @@ int main(int argc, char **argv) {
         }
         if (mode >= 1 && mode <= 3 && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
         if ((mode == 1 || mode == 2) && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
+        if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (i + 1 >= argc) { usage(); return 1; }
         const char *v = argv[++i];
         if (!strcmp(a, "-i")) out = v;
@@ -609,6 +624,10 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &v64) || v64 > 0x7FFFFFFFull) { fprintf(stderr, "--min-score: a score of at least 0\n"); return 1; }
             mo.min_score = (int32_t)v64;
         }
+        else if (mode == 4 && !strcmp(a, "--max-gap")) {
+            if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-gap: a length of at least 0\n"); return 1; }
+            co.max_gap = (uint32_t)v64; gap_given = 1;
+        }
         else if ((mode == 3 || mode == 4) && !strcmp(a, "--min-len")) {
             if (parse_u64(v, &min_len) || min_len < 1 || min_len > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
         }
@@ -618,8 +637,9 @@ int main(int argc, char **argv) {
     if (!out || !file) { usage(); return 1; }
     if (mode == 4) {
         if (!ref) { fprintf(stderr, "map: --ref INPUT.fa[.gz] (the text OUT is the BWT of) is required\n"); return 1; }
+        if (gap_given && !chain) { fprintf(stderr, "--max-gap: only with --chain\n"); return 1; }
         mo.min_len = (uint32_t)min_len;
-        return cmd_map(out, ref, file, threads, iupac, seed, (int)device, &mo);
+        return cmd_map(out, ref, file, threads, iupac, seed, (int)device, &mo, chain, co.max_gap);
     }
     if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
     if (mode == 3) return cmd_mems(out, file, (int)device, max_hits, (uint32_t)min_len, flags);

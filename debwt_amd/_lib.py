@@ -120,6 +120,24 @@ class DebwtFmHit(ctypes.Structure):
                 ("edits", ctypes.c_uint32), ("diag", ctypes.c_int64)]
 
 
+class DebwtFmAnchor(ctypes.Structure):
+    _fields_ = [("qbeg", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("diag", ctypes.c_int64)]
+
+
+class DebwtFmChain(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_int32), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32),
+                ("n_anchors", ctypes.c_uint32), ("first_anchor", ctypes.c_uint64)]
+
+
+class DebwtFmChainJob(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_uint64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32),
+                ("first_anchor", ctypes.c_uint64), ("n_anchors", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class DebwtFmChainOpts(ctypes.Structure):
+    _fields_ = [("map", DebwtFmMapOpts), ("max_gap", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class DebwtFmExtendStats(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_uint64) for n in ("jobs", "batches", "launches", "cells", "wave_steps", "scratch_bytes")] +
                 [(n, ctypes.c_float) for n in ("ms_kernel", "ms_trace", "ms_wall")])
@@ -166,6 +184,7 @@ SYMBOLS = [
     "debwt_fm_search", "debwt_fm_search_stats_get", "debwt_fm_mems", "debwt_fm_mems_stats_get",
     "debwt_fm_attach_text", "debwt_fm_extend", "debwt_fm_extend_stats_get", "debwt_fm_cluster_seeds",
     "debwt_fm_map_defaults", "debwt_fm_map", "debwt_fm_map_stats_get",
+    "debwt_fm_chain_seeds", "debwt_fm_extend_chain", "debwt_fm_chain_defaults", "debwt_fm_map_chained",
 ]
 
 
@@ -386,6 +405,21 @@ def lib():
                                ctypes.POINTER(DebwtFmHit), u64p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
     L.debwt_fm_map_stats_get.restype = ctypes.c_int
     L.debwt_fm_map_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmMapStats)]
+    L.debwt_fm_chain_seeds.restype = ctypes.c_int
+    L.debwt_fm_chain_seeds.argtypes = [ctypes.POINTER(DebwtFmSeed), ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.POINTER(DebwtFmChain), ctypes.POINTER(DebwtFmAnchor),
+                                       ctypes.c_uint64, u64p]
+    L.debwt_fm_extend_chain.restype = ctypes.c_int
+    L.debwt_fm_extend_chain.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.POINTER(DebwtFmChainJob),
+                                        ctypes.c_uint64, ctypes.POINTER(DebwtFmAnchor), ctypes.c_uint64,
+                                        ctypes.POINTER(DebwtFmScoring), ctypes.c_uint32, ctypes.POINTER(DebwtFmAln), u64p,
+                                        ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64]
+    L.debwt_fm_chain_defaults.restype = None
+    L.debwt_fm_chain_defaults.argtypes = [ctypes.POINTER(DebwtFmChainOpts)]
+    L.debwt_fm_map_chained.restype = ctypes.c_int
+    L.debwt_fm_map_chained.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.POINTER(DebwtFmChainOpts),
+                                       ctypes.POINTER(DebwtFmHit), u64p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64,
+                                       u64p, ctypes.POINTER(DebwtFmAnchor), ctypes.c_uint64]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

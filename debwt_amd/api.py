@@ -497,8 +497,84 @@ class FMIndex:
             break
         return MapResult(hits[:npat], coff, cg[:int(coff[npat])].copy())
 
+    def extend_chain(self, patterns, jobs, anchors, scoring=(1, 4, 6, 1), band=16, cigar=True):
+        """Banded affine-gap local alignment along chains (debwt_fm_extend_chain): as extend(), but the band of query row i
+        is centred on the diagonal of the job's last anchor at or before i.  jobs: rows of (pattern index, strand, record,
+        first anchor, number of anchors); anchors: rows of (qbeg, diag), qbeg strictly increasing inside a job and
+        consecutive diag at most `band` apart.  A job with one anchor is an extend() job.  Returns an ExtendResult."""
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        jobs = [tuple(int(x) for x in j) for j in jobs]
+        anchors = [tuple(int(x) for x in a) for a in anchors]
+        nj, na = len(jobs), len(anchors)
+        ja = (_lib.DebwtFmChainJob * max(nj, 1))()
+        for k, (p, s, r, fa, n) in enumerate(jobs):
+            if min(p, s, r, fa, n) < 0 or max(s, r, n) >= 2 ** 32:
+                raise DebwtError(-1, "a job with a negative or oversized field")
+            ja[k].pattern, ja[k].strand, ja[k].record, ja[k].first_anchor, ja[k].n_anchors = p, s, r, fa, n
+        aa = (_lib.DebwtFmAnchor * max(na, 1))()
+        for k, (q, d) in enumerate(anchors):
+            if q < 0 or q >= 2 ** 32:
+                raise DebwtError(-1, "an anchor with a negative or oversized qbeg")
+            aa[k].qbeg, aa[k].diag = q, d
+        sc = _lib.DebwtFmScoring(*[int(x) for x in scoring])
+        out = np.zeros(max(nj, 1), dtype=_ALN_DTYPE)
+        outp = out.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmAln))
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        if not cigar:
+            self._chk(self._L.debwt_fm_extend_chain(self._h, buf, _p64(offs), npat, ja, nj, aa, na, ctypes.byref(sc), int(band),
+                                                    outp, None, None, 0))
+            return ExtendResult(out[:nj], None, None)
+        coff = np.zeros(nj + 1, dtype=np.uint64)
+        cap = 4 * nj + 16
+        while True:
+            cg = np.zeros(cap, dtype=np.uint32)
+            rc = self._L.debwt_fm_extend_chain(self._h, buf, _p64(offs), npat, ja, nj, aa, na, ctypes.byref(sc), int(band), outp,
+                                               _p64(coff), cg.ctypes.data_as(u32p), cap)
+            if rc == -5 and int(coff[nj]) > cap:
+                cap = int(coff[nj])
+                continue
+            self._chk(rc)
+            break
+        return ExtendResult(out[:nj], coff, cg[:int(coff[nj])].copy())
+
+    def map_chained(self, patterns, min_len=19, band=16, max_occ=64, max_cand=8, min_score=30, scoring=(1, 4, 6, 1),
+                    strands="both", max_gap=None):
+        """Reads to alignments through chains (debwt_fm_map_chained): as map(), but the seeds of a read are chained across
+        diagonals (chain_seeds with `band` and max_gap, the max_cand best chains kept) and each chain is extended with a
+        band that follows it (extend_chain).  Returns a MapResult whose anchors(i) are the winning chain's (qbeg, diag)."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        co = _lib.DebwtFmChainOpts()
+        self._L.debwt_fm_chain_defaults(ctypes.byref(co))
+        o = co.map
+        o.min_len, o.band, o.max_occ, o.max_cand, o.min_score = int(min_len), int(band), int(max_occ), int(max_cand), int(min_score)
+        o.flags = MAP_FORWARD if strands == "forward" else 0
+        o.scoring = _lib.DebwtFmScoring(*[int(x) for x in scoring])
+        if max_gap is not None:
+            co.max_gap = int(max_gap)
+        hits = np.zeros(max(npat, 1), dtype=_HIT_DTYPE)
+        coff = np.zeros(npat + 1, dtype=np.uint64)
+        aoff = np.zeros(npat + 1, dtype=np.uint64)
+        cap, acap = 4 * npat + 16, 4 * npat + 16
+        while True:
+            cg = np.zeros(cap, dtype=np.uint32)
+            an = np.zeros(acap, dtype=_ANCHOR_DTYPE)
+            rc = self._L.debwt_fm_map_chained(self._h, buf, _p64(offs), npat, ctypes.byref(co),
+                                              hits.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmHit)), _p64(coff),
+                                              cg.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cap, _p64(aoff),
+                                              an.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmAnchor)), acap)
+            if rc == -5 and (int(coff[npat]) > cap or int(aoff[npat]) > acap):
+                cap, acap = max(cap, int(coff[npat])), max(acap, int(aoff[npat]))
+                continue
+            self._chk(rc)
+            break
+        return MapResult(hits[:npat], coff, cg[:int(coff[npat])].copy(), aoff, an[:int(aoff[npat])].copy())
+
     def map_stats(self):
-        """Stage times and counts of the last map() (debwt_fm_map_stats_get)."""
+        """Stage times and counts of the last map() or map_chained() (debwt_fm_map_stats_get)."""
         st = _lib.DebwtFmMapStats()
         self._chk(self._L.debwt_fm_map_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
@@ -545,6 +621,7 @@ _HIT_DTYPE = np.dtype([("pattern", np.uint64), ("flags", np.uint32), ("record", 
                        ("qbeg", np.uint32), ("qend", np.uint32), ("tbeg", np.uint64), ("tend", np.uint64),
                        ("score", np.int32), ("sub", np.int32), ("mapq", np.uint32), ("edits", np.uint32),
                        ("diag", np.int64)])
+_ANCHOR_DTYPE = np.dtype([("qbeg", np.uint32), ("reserved", np.uint32), ("diag", np.int64)])
 
 
 def cigar_string(ops):
@@ -565,6 +642,27 @@ def cluster_seeds(seeds, band=16, max_cand=8):
     if rc < 0:
         raise DebwtError(rc)
     return [{n: int(getattr(out[k], n)) for n, _ in _lib.DebwtFmCand._fields_} for k in range(rc)]
+
+
+def chain_seeds(seeds, band=16, max_gap=5000, max_chains=8):
+    """Seeds of one read to colinear chains on the host (debwt_fm_chain_seeds, no GPU).  seeds: rows of (strand, record,
+    diag, qbeg, qend).  Returns dicts (score, strand, record, anchors: the chain's (qbeg, diag) in ascending qbeg), the
+    best score first."""
+    L = _lib.lib()
+    seeds = list(seeds)
+    sa = (_lib.DebwtFmSeed * max(len(seeds), 1))()
+    for k, (st, rec, dg, qb, qe) in enumerate(seeds):
+        sa[k].strand, sa[k].record, sa[k].diag, sa[k].qbeg, sa[k].qend = int(st), int(rec), int(dg), int(qb), int(qe)
+    ch = (_lib.DebwtFmChain * max(int(max_chains), 1))()
+    an = (_lib.DebwtFmAnchor * max(len(seeds), 1))()                       # chains share no seed
+    need = ctypes.c_uint64(0)
+    rc = L.debwt_fm_chain_seeds(sa, len(seeds), int(band), int(max_gap), int(max_chains), ch, an, len(seeds), ctypes.byref(need))
+    if rc < 0:
+        raise DebwtError(rc)
+    return [{"score": int(ch[k].score), "strand": int(ch[k].strand), "record": int(ch[k].record),
+             "anchors": [(int(an[x].qbeg), int(an[x].diag))
+                         for x in range(int(ch[k].first_anchor), int(ch[k].first_anchor) + int(ch[k].n_anchors))]}
+            for k in range(rc)]
 
 
 class ExtendResult:
@@ -592,10 +690,12 @@ class ExtendResult:
 class MapResult:
     """Alignments of FMIndex.map, one per read: numpy arrays pattern, flags (MAP_REVERSE, MAP_UNMAPPED, MAP_TOO_LONG),
     record, offset (in the record), qbeg, qend (in the read as aligned: its reverse complement with MAP_REVERSE), tbeg,
-    tend, score, sub, mapq, edits, diag (the diagonal of the extension job that won); cigar(i) as text, ops(i)."""
+    tend, score, sub, mapq, edits, diag (the diagonal of the extension job that won); cigar(i) as text, ops(i).  From
+    FMIndex.map_chained also anchors(i): the winning chain as (qbeg, diag) pairs, diag[i] being the first one's."""
 
-    def __init__(self, hits, offsets, cigars):
+    def __init__(self, hits, offsets, cigars, anchor_offsets=None, anchor_rows=None):
         self.hits, self.offsets, self.cigars = hits, offsets, cigars
+        self.anchor_offsets, self.anchor_rows = anchor_offsets, anchor_rows
         for name in _HIT_DTYPE.names:
             setattr(self, name, hits[name].copy())
         self.mapped = (self.flags & MAP_UNMAPPED) == 0
@@ -609,6 +709,12 @@ class MapResult:
 
     def cigar(self, i):
         return cigar_string(self.ops(i))
+
+    def anchors(self, i):
+        if self.anchor_offsets is None:
+            return None
+        a = self.anchor_rows[int(self.anchor_offsets[i]):int(self.anchor_offsets[i + 1])]
+        return [(int(q), int(d)) for q, d in zip(a["qbeg"], a["diag"])]
 
 
 class SearchResult:

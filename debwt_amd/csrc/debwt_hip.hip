@@ -30,6 +30,7 @@
 #include "fm_search_kernels.h"
 #include "fm_mem_kernels.h"
 #include "fm_extend_kernels.h"
+#include "fm_chain_kernels.h"
 
 namespace {
 
@@ -2840,6 +2841,7 @@ struct debwt_fm {
     DevBuf text;                 // the 2-bit text (debwt_fm_attach_text); has_text: checked against the samples
     bool has_text = false;
     DevBuf x_jobs, x_best, x_cells, x_flags, x_tr, x_cigoff, x_cig;   // extension scratch of one batch
+    DevBuf x_anchors;            // the anchors of one batch of chain jobs
     debwt_fm_extend_stats x_stats{};
     debwt_fm_map_stats map_stats{};
     VIndex V{};
@@ -4057,6 +4059,546 @@ extern "C" int debwt_fm_map_stats_get(const debwt_fm *f, debwt_fm_map_stats *out
     return DEBWT_OK;
 }
 
+// ---- chains: seeds of a read chained across diagonals, extension along a chain, the mapper on both (fm_chain_kernels.h) --
+// The batches, the two traceback passes and the statistics are those of fm_extend_run; a job carries its anchors, and its
+// flag scratch is one row of 2w + 1 bytes per query row that holds an allowed cell.
+
+namespace {
+
+// the device form of a chain job; false: no cell of the band lies inside the record (score 0)
+bool fm_chain_prepare(const debwt_fm *f, u64 m, const debwt_fm_chain_job &jb, const debwt_fm_anchor *an, u32 w, FmChainJob *d) {
+    const u64 rs = f->rec_starts[jb.record];
+    const u64 re = (jb.record + 1 < f->nrec ? f->rec_starts[jb.record + 1] : f->n) - 1;
+    const __int128 tb = (__int128)an[0].diag - (__int128)w;   // text position of column 0
+    const __int128 lim = (__int128)1 << 30;                   // columns of allowed cells stay far inside it
+    const long long clo = (long long)std::max(-lim, std::min(lim, (__int128)rs - tb));
+    const long long chi = (long long)std::max(-lim, std::min(lim, (__int128)re - tb));
+    long long i0 = -1, i1 = -1, wmin = 0, wmax = 0;
+    u32 a0 = 0;
+    for (u32 a = 0; a < jb.n_anchors; a++) {                  // the rows [ra, rb) share the centre of anchor a
+        const long long ra = a ? (long long)an[a].qbeg : 0, rb = a + 1 < jb.n_anchors ? (long long)an[a + 1].qbeg : (long long)m;
+        const long long dc = (long long)(an[a].diag - an[0].diag);
+        const long long lo = std::max(ra, clo - dc - 2 * (long long)w), hi = std::min(rb - 1, chi - 1 - dc);
+        if (lo > hi) continue;
+        const long long c0 = std::max(clo, lo + dc), c1 = std::min(chi - 1, hi + dc + 2 * (long long)w);
+        if (i0 < 0) { i0 = lo; a0 = a; wmin = c0; wmax = c1; }
+        i1 = hi + 1;
+        wmin = std::min(wmin, c0); wmax = std::max(wmax, c1);
+    }
+    if (i0 < 0) return false;
+    d->tbase = (long long)tb;
+    d->m = (u32)m; d->strand = jb.strand; d->na = jb.n_anchors; d->a0 = a0;
+    d->clo = (int)clo; d->chi = (int)chi;
+    d->wlo = (int)wmin; d->wn = (u32)(wmax - wmin + 1);
+    d->i0 = (u32)i0; d->nrows = (u32)(i1 - i0);
+    d->qoff = 0; d->flag_off = 0; d->aoff = 0;
+    return true;
+}
+
+template <int G, int S>
+void fm_chain_launch(bool trace, u32 grid, u32 block, size_t lds, hipStream_t s, const u64 *text, const u8 *chars,
+                     const FmChainJob *jobs, const FmChainAnchor *anchors, u32 nj, u32 w, const debwt_fm_scoring &sc,
+                     u32 lds_per_job, u8 *flags, u64 *best, u32 *cells) {
+    if (trace)
+        k_fm_extend_chain<G, S, true><<<grid, block, lds, s>>>(text, chars, jobs, anchors, nj, w, sc.match, sc.mismatch,
+                                                               sc.gap_open, sc.gap_extend, lds_per_job, flags, best, cells);
+    else
+        k_fm_extend_chain<G, S, false><<<grid, block, lds, s>>>(text, chars, jobs, anchors, nj, w, sc.match, sc.mismatch,
+                                                                sc.gap_open, sc.gap_extend, lds_per_job, flags, best, cells);
+}
+
+// chain jobs [0, njobs) -> out; with `trace` also ops per job (cig_n) and the ops of all jobs in job order (cig).  The
+// arguments were validated by the caller; statistics are added to f->x_stats (wave steps: rows).
+int fm_chain_run(debwt_fm *f, const char *patterns, const uint64_t *offsets, const debwt_fm_chain_job *jobs, u64 njobs,
+                 const debwt_fm_anchor *anchors, const debwt_fm_scoring &sc, u32 w, bool trace, debwt_fm_aln *out,
+                 std::vector<u32> *cig_n, std::vector<u32> *cig) {
+    debwt_fm_extend_stats &st = f->x_stats;
+    st.jobs += njobs;
+    if (trace) { cig_n->assign(njobs, 0); cig->clear(); }
+    if (!njobs) return DEBWT_OK;
+    const u64 limit = fm_env_u64("DEBWT_FM_EXTEND_BYTES", FM_EXTEND_BYTES);
+    const int G = 2 * w + 1 <= 16 ? 16 : 2 * w + 1 <= 32 ? 32 : 64;
+    FmExtEvents ev;
+    HIPCHK(f, hipEventCreate(&ev.a));
+    HIPCHK(f, hipEventCreate(&ev.b));
+    std::vector<FmChainJob> dj;
+    std::vector<FmChainAnchor> da;
+    std::vector<u64> src;                                // job index of every device job
+    std::vector<char> chars;
+    std::vector<u64> best;
+    std::vector<u32> cells, tr, ops;
+    std::vector<u64> coff;
+    for (u64 j0 = 0; j0 < njobs;) {
+        dj.clear(); da.clear(); src.clear(); chars.clear();
+        u64 fbytes = 0, j1 = j0, last_pat = ~0ull, last_off = 0;
+        u32 lds_job = 4;
+        for (; j1 < njobs; j1++) {
+            const debwt_fm_chain_job &jb = jobs[j1];
+            const debwt_fm_anchor *an = anchors + jb.first_anchor;
+            const u64 m = offsets[jb.pattern + 1] - offsets[jb.pattern];
+            FmChainJob d;
+            if (!fm_chain_prepare(f, m, jb, an, w, &d)) { out[j1] = debwt_fm_aln{}; continue; }
+            const u64 fb = trace ? (u64)d.nrows * (2 * w + 1) : 0;
+            const bool fresh = jb.pattern != last_pat;
+            if (!dj.empty() && (fbytes + fb > limit || dj.size() >= FM_EXTEND_JOBS ||
+                                (fresh && chars.size() + m > FM_BATCH_CHARS)))
+                break;
+            if (fresh) {
+                last_pat = jb.pattern; last_off = chars.size();
+                chars.insert(chars.end(), patterns + offsets[jb.pattern], patterns + offsets[jb.pattern] + m);
+            }
+            d.qoff = last_off; d.flag_off = fbytes; d.aoff = da.size();
+            fbytes += fb;
+            for (u32 a = 0; a < jb.n_anchors; a++) da.push_back(FmChainAnchor{an[a].qbeg, (int)(an[a].diag - an[0].diag)});
+            // a text window that leaves no room beside the query is not staged: the sweep reads the text itself
+            if ((m + 1) / 2 + ((u64)d.wn + 3) / 4 + 3 > FM_EXT_LDS_BUDGET) d.wn = 0;
+            lds_job = std::max<u32>(lds_job, (u32)(((m + 1) / 2 + ((u64)d.wn + 3) / 4 + 3) & ~3ull));
+            dj.push_back(d); src.push_back(j1);
+        }
+        const u64 nd = dj.size();
+        if (!nd) { j0 = j1; continue; }
+        // the workgroup: as many groups as the staged strings of its jobs leave room for
+        int g = G;
+        u32 block = 256;
+        if ((u64)(block / g) * lds_job > FM_EXT_LDS_BUDGET) block = 64;
+        while ((u64)(block / g) * lds_job > FM_EXT_LDS_BUDGET && g < 64) g *= 2;
+        const u32 jpb = block / g, grid = (u32)((nd + jpb - 1) / jpb);
+        const u32 jpw = 64 / g;                            // wave steps: the rows of the longest job of every wave
+        for (u64 a = 0; a < nd; a += jpw) {
+            u32 mx = 0;
+            for (u64 b = a; b < std::min(nd, a + jpw); b++) mx = std::max(mx, dj[b].nrows);
+            st.wave_steps += mx;
+        }
+        st.scratch_bytes = std::max<u64>(st.scratch_bytes, fbytes);
+        FM_ENSURE(f, f->q_chars, std::max<size_t>(chars.size(), 1));
+        FM_ENSURE(f, f->x_jobs, nd * sizeof(FmChainJob));
+        FM_ENSURE(f, f->x_anchors, da.size() * sizeof(FmChainAnchor));
+        FM_ENSURE(f, f->x_best, nd * 8);
+        FM_ENSURE(f, f->x_cells, nd * 4);
+        if (trace) {
+            FM_ENSURE(f, f->x_flags, (size_t)std::max<u64>(fbytes, 1));
+            FM_ENSURE(f, f->x_tr, nd * 16);
+            FM_ENSURE(f, f->x_cigoff, (nd + 1) * 8);
+        }
+        HIPCHK(f, hipMemcpyAsync(f->q_chars.p, chars.data(), chars.size(), hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->x_jobs.p, dj.data(), nd * sizeof(FmChainJob), hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->x_anchors.p, da.data(), da.size() * sizeof(FmChainAnchor), hipMemcpyHostToDevice, f->stream));
+        (void)hipEventRecord(ev.a, f->stream);
+        const size_t lds = (size_t)jpb * lds_job;
+        auto go = [&](auto gt, auto stag) {
+            fm_chain_launch<decltype(gt)::value, decltype(stag)::value>(
+                trace, grid, block, lds, f->stream, f->text.as<u64>(), f->q_chars.as<u8>(), f->x_jobs.as<FmChainJob>(),
+                f->x_anchors.as<FmChainAnchor>(), (u32)nd, w, sc, lds_job, f->x_flags.as<u8>(), f->x_best.as<u64>(),
+                f->x_cells.as<u32>());
+        };
+        if (w > 31) go(std::integral_constant<int, 64>{}, std::integral_constant<int, 2>{});
+        else if (g == 16) go(std::integral_constant<int, 16>{}, std::integral_constant<int, 1>{});
+        else if (g == 32) go(std::integral_constant<int, 32>{}, std::integral_constant<int, 1>{});
+        else go(std::integral_constant<int, 64>{}, std::integral_constant<int, 1>{});
+        (void)hipEventRecord(ev.b, f->stream);
+        st.launches++;
+        best.resize(nd); cells.resize(nd);
+        HIPCHK(f, hipMemcpyAsync(best.data(), f->x_best.p, nd * 8, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(f, hipMemcpyAsync(cells.data(), f->x_cells.p, nd * 4, hipMemcpyDeviceToHost, f->stream));
+        if (trace) {
+            k_fm_chain_trace<<<grid_for(nd, 256), 256, 0, f->stream>>>(f->x_jobs.as<FmChainJob>(), f->x_anchors.as<FmChainAnchor>(),
+                                                                       (u32)nd, w, f->x_flags.as<u8>(), f->x_best.as<u64>(),
+                                                                       nullptr, nullptr, f->x_tr.as<u32>());
+            st.launches++;
+            tr.resize(4 * nd);
+            HIPCHK(f, hipMemcpyAsync(tr.data(), f->x_tr.p, nd * 16, hipMemcpyDeviceToHost, f->stream));
+        }
+        int rc = fm_sync(f);
+        if (rc) return rc;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+        st.ms_kernel += ms;
+        for (u64 a = 0; a < nd; a++) st.cells += cells[a];
+        u64 total = 0;
+        if (trace) {
+            coff.resize(nd + 1);
+            coff[0] = 0;
+            for (u64 a = 0; a < nd; a++) coff[a + 1] = coff[a] + tr[4 * a + 3];
+            total = coff[nd];
+            ops.resize(total);
+            if (total) {
+                FM_ENSURE(f, f->x_cig, (size_t)total * 4);
+                HIPCHK(f, hipMemcpyAsync(f->x_cigoff.p, coff.data(), (nd + 1) * 8, hipMemcpyHostToDevice, f->stream));
+                (void)hipEventRecord(ev.a, f->stream);
+                k_fm_chain_trace<<<grid_for(nd, 256), 256, 0, f->stream>>>(f->x_jobs.as<FmChainJob>(),
+                                                                           f->x_anchors.as<FmChainAnchor>(), (u32)nd, w,
+                                                                           f->x_flags.as<u8>(), f->x_best.as<u64>(),
+                                                                           f->x_cigoff.as<u64>(), f->x_cig.as<u32>(),
+                                                                           f->x_tr.as<u32>());
+                (void)hipEventRecord(ev.b, f->stream);
+                st.launches++;
+                HIPCHK(f, hipMemcpyAsync(ops.data(), f->x_cig.p, total * 4, hipMemcpyDeviceToHost, f->stream));
+                if ((rc = fm_sync(f))) return rc;
+                (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+                st.ms_trace += ms;
+            }
+        }
+        for (u64 a = 0; a < nd; a++) {
+            debwt_fm_aln &o = out[src[a]];
+            o = debwt_fm_aln{};
+            const u64 key = best[a];
+            if (!(key >> 32)) continue;
+            const u32 i = 65535u - (u32)((key >> 8) & 0xFFFFu), k = 127u - (u32)(key & 0xFFu);
+            const FmChainAnchor *an = da.data() + dj[a].aoff;
+            u32 x = dj[a].na - 1;                            // the anchor in effect at the end row
+            while (x > 0 && an[x].q > i) x--;
+            o.score = (int32_t)(key >> 32);
+            o.qend = i + 1;
+            o.tend = (u64)(dj[a].tbase + (long long)i + an[x].dc + (long long)k) + 1;
+            if (trace) {
+                o.qbeg = tr[4 * a]; o.tbeg = (u64)(dj[a].tbase + (long long)(int32_t)tr[4 * a + 1]); o.edits = tr[4 * a + 2];
+                (*cig_n)[src[a]] = tr[4 * a + 3];
+            }
+        }
+        if (trace) cig->insert(cig->end(), ops.begin(), ops.end());   // device jobs are in job order
+        st.batches++;
+        j0 = j1;
+    }
+    return DEBWT_OK;
+}
+
+// |a - b| <= band, for any two diagonals
+bool fm_diag_near(int64_t a, int64_t b, u32 band) {
+    const __int128 d = (__int128)a - (__int128)b;
+    return (d < 0 ? -d : d) <= (__int128)band;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_chain_seeds(const debwt_fm_seed *seeds, uint64_t nseeds, uint32_t band, uint32_t max_gap,
+                                    uint32_t max_chains, debwt_fm_chain *chains, debwt_fm_anchor *anchors,
+                                    uint64_t anchor_capacity, uint64_t *anchors_needed) {
+    if ((nseeds && !seeds) || (max_chains && !chains) || !anchors_needed || band > FM_EXT_MAX_BAND) return DEBWT_EINVAL;
+    for (u64 i = 0; i < nseeds; i++)
+        if (seeds[i].qend <= seeds[i].qbeg) return DEBWT_EINVAL;
+    *anchors_needed = 0;
+    typedef __int128 wide;
+    struct S { wide tb, te; int64_t diag; u32 strand, record, qb, qe; };
+    std::vector<S> s(nseeds);
+    u32 longest = 0;
+    for (u64 i = 0; i < nseeds; i++) {
+        const debwt_fm_seed &x = seeds[i];
+        s[i] = S{(wide)x.diag + x.qbeg, (wide)x.diag + x.qend, x.diag, x.strand, x.record, x.qbeg, x.qend};
+        longest = std::max(longest, x.qend - x.qbeg);
+    }
+    std::sort(s.begin(), s.end(), [](const S &a, const S &b) {
+        return std::make_tuple(a.strand, a.record, a.tb, a.qb, a.qe) < std::make_tuple(b.strand, b.record, b.tb, b.qb, b.qe);
+    });
+    std::vector<int64_t> fv(nseeds), pred(nseeds, -1);
+    const wide reach = (wide)max_gap + longest;
+    for (u64 j = 0; j < nseeds; j++) {
+        const S &b = s[j];
+        const int64_t len = b.qe - b.qb;
+        bool have = false;
+        int64_t top = 0, who = -1;
+        for (u64 i = j; i-- > 0;) {
+            const S &a = s[i];
+            if (a.strand != b.strand || a.record != b.record || b.tb - a.tb > reach) break;
+            if (!(a.qb < b.qb && a.qe < b.qe && a.tb < b.tb && a.te < b.te) || !fm_diag_near(a.diag, b.diag, band)) continue;
+            if ((int64_t)b.qb - (int64_t)a.qe > (int64_t)max_gap || b.tb - a.te > (wide)max_gap) continue;
+            const wide dd = (wide)b.diag - (wide)a.diag;
+            const int64_t gain = std::min<int64_t>(len, std::min<int64_t>(b.qe - a.qe, (int64_t)(b.te - a.te))) -
+                                 (int64_t)(dd < 0 ? -dd : dd);
+            const int64_t v = fv[i] + gain;
+            if (!have || v > top) { have = true; top = v; who = (int64_t)i; }   // going down: the largest i of a tie stays
+        }
+        if (have && top >= len) { fv[j] = top; pred[j] = who; } else fv[j] = len;
+    }
+    std::vector<u64> ord(nseeds);
+    for (u64 i = 0; i < nseeds; i++) ord[i] = i;
+    std::stable_sort(ord.begin(), ord.end(), [&](u64 a, u64 b) { return fv[a] > fv[b]; });
+    struct C { int64_t score; u64 first, n; };             // first: the chain's seeds in `walk`, end first
+    std::vector<C> cs;
+    std::vector<u64> walk;
+    std::vector<char> used(nseeds, 0);
+    for (u64 e : ord) {
+        if (used[e]) continue;
+        C c{fv[e], walk.size(), 0};
+        int64_t p = (int64_t)e;
+        for (; p >= 0 && !used[p]; p = pred[p]) { walk.push_back((u64)p); c.n++; }
+        if (p >= 0) c.score -= fv[p];
+        for (u64 x = c.first; x < c.first + c.n; x++) used[walk[x]] = 1;
+        cs.push_back(c);
+    }
+    auto head = [&](const C &c) -> const S & { return s[walk[c.first + c.n - 1]]; };
+    std::stable_sort(cs.begin(), cs.end(), [&](const C &a, const C &b) {
+        if (a.score != b.score) return a.score > b.score;
+        const S &x = head(a), &y = head(b);
+        return std::make_tuple(x.strand, x.record, x.diag, x.qb) < std::make_tuple(y.strand, y.record, y.diag, y.qb);
+    });
+    const u64 k = std::min<u64>(cs.size(), max_chains);
+    u64 need = 0;
+    for (u64 c = 0; c < k; c++) {
+        chains[c] = debwt_fm_chain{(int32_t)cs[c].score, head(cs[c]).record, head(cs[c]).strand, (u32)cs[c].n, need};
+        need += cs[c].n;
+    }
+    *anchors_needed = need;
+    if (anchor_capacity < need || (need && !anchors)) return DEBWT_ERANGE;
+    for (u64 c = 0; c < k; c++)
+        for (u64 x = 0; x < cs[c].n; x++) {
+            const S &y = s[walk[cs[c].first + cs[c].n - 1 - x]];
+            anchors[chains[c].first_anchor + x] = debwt_fm_anchor{y.qb, 0, y.diag};
+        }
+    return (int)k;
+}
+
+extern "C" int debwt_fm_extend_chain(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                                     const debwt_fm_chain_job *jobs, uint64_t njobs, const debwt_fm_anchor *anchors,
+                                     uint64_t nanchors, const debwt_fm_scoring *sc, uint32_t band, debwt_fm_aln *out,
+                                     uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity) {
+    if (!f || !sc || !offsets || (njobs && (!jobs || !out)) || (nanchors && !anchors)) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->x_stats = debwt_fm_extend_stats{};
+    int rc = fm_ext_check(f, sc, band, "debwt_fm_extend_chain");
+    if (rc) return rc;
+    for (u64 i = 0; i < npat; i++)
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_extend_chain: offsets must not decrease"; return DEBWT_EINVAL; }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    for (u64 j = 0; j < njobs; j++) {
+        const debwt_fm_chain_job &jb = jobs[j];
+        const std::string who = "debwt_fm_extend_chain: job " + std::to_string(j);
+        if (jb.pattern >= npat || jb.strand > 1 || jb.record >= f->nrec) {
+            f->err = who + " names a pattern, strand or record that does not exist";
+            return DEBWT_EINVAL;
+        }
+        const u64 m = offsets[jb.pattern + 1] - offsets[jb.pattern];
+        if (m < 1 || m > FM_EXT_MAX_LEN) {
+            f->err = who + " has a pattern of " + std::to_string(m) + " bytes (1..65535)";
+            return DEBWT_EINVAL;
+        }
+        if (!jb.n_anchors || jb.first_anchor > nanchors || jb.n_anchors > nanchors - jb.first_anchor) {
+            f->err = who + " has no anchor, or anchors outside the " + std::to_string(nanchors) + " given";
+            return DEBWT_EINVAL;
+        }
+        const debwt_fm_anchor *an = anchors + jb.first_anchor;
+        for (u32 a = 0; a < jb.n_anchors; a++) {
+            if (an[a].qbeg >= m || (a && an[a].qbeg <= an[a - 1].qbeg)) {
+                f->err = who + ": the qbeg of its anchors must increase strictly and stay below the pattern length";
+                return DEBWT_EINVAL;
+            }
+            if (a && !fm_diag_near(an[a].diag, an[a - 1].diag, band)) {
+                f->err = who + ": consecutive anchors lie further apart than the band";
+                return DEBWT_EINVAL;
+            }
+        }
+    }
+    HIPCHK(f, hipSetDevice(f->device));
+    const bool trace = cigar_offsets != nullptr;
+    std::vector<u32> cig_n, cig;
+    rc = fm_chain_run(f, patterns, offsets, jobs, njobs, anchors, *sc, band, trace, out, &cig_n, &cig);
+    if (rc) return rc;
+    f->x_stats.ms_wall = (float)fm_ms_since(t0);
+    if (!trace) return DEBWT_OK;
+    cigar_offsets[0] = 0;
+    for (u64 j = 0; j < njobs; j++) cigar_offsets[j + 1] = cigar_offsets[j] + cig_n[j];
+    if (capacity < cig.size() || (!cig.empty() && !cigar)) {
+        f->err = "debwt_fm_extend_chain: capacity below the CIGAR ops (cigar_offsets[njobs] = " + std::to_string(cig.size()) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (!cig.empty()) memcpy(cigar, cig.data(), cig.size() * 4);
+    return DEBWT_OK;
+}
+
+extern "C" void debwt_fm_chain_defaults(debwt_fm_chain_opts *o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    debwt_fm_map_defaults(&o->map);
+    o->max_gap = 5000;
+}
+
+extern "C" int debwt_fm_map_chained(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                                    const debwt_fm_chain_opts *opts, debwt_fm_hit *hits, uint64_t *cigar_offsets,
+                                    uint32_t *cigar, uint64_t capacity, uint64_t *anchor_offsets,
+                                    debwt_fm_anchor *hit_anchors, uint64_t anchor_capacity) {
+    if (!f || !offsets || !cigar_offsets || (npat && !hits)) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    debwt_fm_chain_opts co;
+    debwt_fm_chain_defaults(&co);
+    if (opts) co = *opts;
+    const debwt_fm_map_opts &o = co.map;
+    f->map_stats = debwt_fm_map_stats{};
+    f->x_stats = debwt_fm_extend_stats{};
+    int rc = fm_ext_check(f, &o.scoring, o.band, "debwt_fm_map_chained");
+    if (rc) return rc;
+    if (!o.min_len || !o.max_occ || !o.max_cand || o.max_cand > 4096 || (o.flags & ~DEBWT_FM_MAP_FORWARD)) {
+        f->err = "debwt_fm_map_chained: min_len, max_occ and max_cand must be positive (max_cand <= 4096), flags known";
+        return DEBWT_EINVAL;
+    }
+    for (u64 i = 0; i < npat; i++)
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_map_chained: offsets must not decrease"; return DEBWT_EINVAL; }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    debwt_fm_map_stats &ms = f->map_stats;
+    ms.reads = npat;
+    cigar_offsets[0] = 0;
+    if (anchor_offsets) anchor_offsets[0] = 0;
+    std::vector<u32> all_cig;
+    std::vector<debwt_fm_anchor> all_anchors;
+    std::vector<uint64_t> moff, ranges, loff, pos;
+    std::vector<u32> spans, cig_n, cig;
+    std::vector<u8> strands;
+    std::vector<debwt_fm_chain_job> jobs;
+    std::vector<debwt_fm_anchor> anchors;
+    std::vector<u64> job_first;
+    std::vector<debwt_fm_aln> aln;
+    const u32 mflags = (o.flags & DEBWT_FM_MAP_FORWARD) ? 0u : DEBWT_FM_BOTH_STRANDS;
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 p1 = p0 + 1;
+        while (p1 < npat && p1 - p0 < (1ull << 18) && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS) p1++;
+        const u64 np = p1 - p0;
+        // 1. MEMs of the batch
+        auto t = std::chrono::steady_clock::now();
+        moff.assign(np + 1, 0);
+        u64 cap = std::max<u64>(spans.size() / 2, 4 * np + 16);
+        for (;;) {
+            spans.resize(2 * cap); ranges.resize(2 * cap); strands.resize(cap);
+            rc = debwt_fm_mems(f, patterns, offsets + p0, np, o.min_len, mflags, moff.data(), spans.data(), ranges.data(),
+                               strands.data(), cap);
+            if (rc == DEBWT_ERANGE && moff[np] > cap) { cap = moff[np]; continue; }
+            if (rc) return rc;
+            break;
+        }
+        const u64 nmem = moff[np];
+        ms.mems += nmem;
+        ms.ms_mems += (float)fm_ms_since(t);
+        // 2. their first max_occ rows located
+        t = std::chrono::steady_clock::now();
+        loff.assign(nmem + 1, 0);
+        u64 nocc = 0;
+        for (u64 i = 0; i < nmem; i++) nocc += std::min<u64>(ranges[2 * i + 1] - ranges[2 * i], o.max_occ);
+        pos.resize(std::max<u64>(nocc, 1));
+        rc = debwt_fm_locate(f, ranges.data(), nmem, o.max_occ, loff.data(), pos.data(), pos.size());
+        if (rc) return rc;
+        ms.seeds += nocc;
+        ms.ms_locate += (float)fm_ms_since(t);
+        // 3. seeds -> chains -> jobs: every read on its own, the reads spread over at most 16 threads
+        t = std::chrono::steady_clock::now();
+        struct PerRead { std::vector<debwt_fm_chain> chains; std::vector<debwt_fm_anchor> anchors; };
+        std::vector<PerRead> per(np);
+        std::atomic<u64> next{0};
+        std::atomic<int> bad{0};
+        auto worker = [&]() {
+            std::vector<debwt_fm_seed> seeds;
+            for (;;) {
+                const u64 r0 = next.fetch_add(64);
+                if (r0 >= np) return;
+                for (u64 r = r0; r < std::min(np, r0 + 64); r++) {
+                    const u64 m = offsets[p0 + r + 1] - offsets[p0 + r];
+                    if (m < 1 || m > FM_EXT_MAX_LEN) continue;
+                    seeds.clear();
+                    for (u64 i = moff[r]; i < moff[r + 1]; i++) {
+                        const u32 qb = strands[i] ? (u32)m - spans[2 * i + 1] : spans[2 * i];      // in Q
+                        const u32 qe = strands[i] ? (u32)m - spans[2 * i] : spans[2 * i + 1];
+                        for (u64 x = loff[i]; x < loff[i + 1]; x++) {
+                            const u64 tp = pos[x];
+                            const u64 rec = (u64)(std::upper_bound(f->rec_starts.begin(), f->rec_starts.end(), tp) - f->rec_starts.begin()) - 1;
+                            seeds.push_back(debwt_fm_seed{(int64_t)tp - (int64_t)qb, (u32)rec, strands[i], qb, qe});
+                        }
+                    }
+                    if (seeds.empty()) continue;
+                    PerRead &pr = per[r];
+                    pr.chains.resize(o.max_cand);
+                    pr.anchors.resize(seeds.size());                       // chains share no seed
+                    uint64_t need = 0;
+                    const int nc = debwt_fm_chain_seeds(seeds.data(), seeds.size(), o.band, co.max_gap, o.max_cand,
+                                                        pr.chains.data(), pr.anchors.data(), pr.anchors.size(), &need);
+                    if (nc < 0) { bad.store(1); pr.chains.clear(); continue; }
+                    pr.chains.resize((size_t)nc);
+                    pr.anchors.resize(need);
+                }
+            }
+        };
+        {
+            const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, (u64)std::thread::hardware_concurrency(), (np + 63) / 64}));
+            std::vector<std::thread> th;
+            for (unsigned x = 1; x < nt; x++) th.emplace_back(worker);
+            worker();
+            for (auto &x : th) x.join();
+        }
+        if (bad.load()) { f->err = "debwt_fm_map_chained: a MEM with an empty span"; return DEBWT_EINTERNAL; }
+        jobs.clear(); anchors.clear();
+        job_first.assign(np + 1, 0);
+        for (u64 r = 0; r < np; r++) {
+            job_first[r] = jobs.size();
+            for (const debwt_fm_chain &c : per[r].chains) {
+                jobs.push_back(debwt_fm_chain_job{p0 + r, c.record, c.strand, anchors.size() + c.first_anchor, c.n_anchors, 0});
+            }
+            anchors.insert(anchors.end(), per[r].anchors.begin(), per[r].anchors.end());
+        }
+        job_first[np] = jobs.size();
+        ms.candidates += jobs.size();
+        ms.jobs += jobs.size();
+        ms.ms_candidates += (float)fm_ms_since(t);
+        // 4. every chain extended, with its traceback: the tie rule and `sub` need the text interval of each
+        t = std::chrono::steady_clock::now();
+        aln.resize(jobs.size());
+        HIPCHK(f, hipSetDevice(f->device));
+        rc = fm_chain_run(f, patterns, offsets, jobs.data(), jobs.size(), anchors.data(), o.scoring, o.band, true, aln.data(),
+                          &cig_n, &cig);
+        if (rc) return rc;
+        ms.ms_extend += (float)fm_ms_since(t);
+        // 5. the winner of every read
+        std::vector<u64> cfirst(jobs.size() + 1, 0);
+        for (u64 j = 0; j < jobs.size(); j++) cfirst[j + 1] = cfirst[j] + cig_n[j];
+        for (u64 r = 0; r < np; r++) {
+            const u64 m = offsets[p0 + r + 1] - offsets[p0 + r];
+            debwt_fm_hit &h = hits[p0 + r];
+            memset(&h, 0, sizeof h);
+            h.pattern = p0 + r;
+            h.flags = DEBWT_FM_MAP_UNMAPPED | (m > FM_EXT_MAX_LEN ? DEBWT_FM_MAP_TOO_LONG : 0u);
+            cigar_offsets[p0 + r + 1] = cigar_offsets[p0 + r];
+            if (anchor_offsets) anchor_offsets[p0 + r + 1] = anchor_offsets[p0 + r];
+            u64 w = ~0ull;
+            for (u64 j = job_first[r]; j < job_first[r + 1]; j++) {
+                if (aln[j].score <= 0) continue;
+                if (w == ~0ull || aln[j].score > aln[w].score ||
+                    (aln[j].score == aln[w].score && std::make_tuple(jobs[j].strand, jobs[j].record, aln[j].tbeg) <
+                                                         std::make_tuple(jobs[w].strand, jobs[w].record, aln[w].tbeg)))
+                    w = j;
+            }
+            if (w == ~0ull || aln[w].score < o.min_score) continue;
+            int32_t sub = 0;
+            for (u64 j = job_first[r]; j < job_first[r + 1]; j++)
+                if (j != w && aln[j].score > sub && (aln[j].tend <= aln[w].tbeg || aln[j].tbeg >= aln[w].tend)) sub = aln[j].score;
+            const debwt_fm_aln &a = aln[w];
+            h.flags = jobs[w].strand ? DEBWT_FM_MAP_REVERSE : 0u;
+            h.record = jobs[w].record; h.offset = a.tbeg - f->rec_starts[jobs[w].record];
+            h.qbeg = a.qbeg; h.qend = a.qend; h.tbeg = a.tbeg; h.tend = a.tend;
+            h.score = a.score; h.sub = sub; h.mapq = (u32)(60 * (int64_t)(a.score - sub) / a.score); h.edits = a.edits;
+            h.diag = anchors[jobs[w].first_anchor].diag;
+            all_cig.insert(all_cig.end(), cig.begin() + cfirst[w], cig.begin() + cfirst[w + 1]);
+            cigar_offsets[p0 + r + 1] = all_cig.size();
+            if (anchor_offsets) {
+                all_anchors.insert(all_anchors.end(), anchors.begin() + jobs[w].first_anchor,
+                                   anchors.begin() + jobs[w].first_anchor + jobs[w].n_anchors);
+                anchor_offsets[p0 + r + 1] = all_anchors.size();
+            }
+            ms.mapped++;
+        }
+        ms.batches++;
+        p0 = p1;
+    }
+    f->x_stats.ms_wall = ms.ms_extend;
+    ms.ms_wall = (float)fm_ms_since(t0);
+    rc = DEBWT_OK;
+    if (capacity < all_cig.size() || (!all_cig.empty() && !cigar)) {
+        f->err = "debwt_fm_map_chained: capacity below the CIGAR ops (cigar_offsets[npat] = " + std::to_string(all_cig.size()) + ")";
+        rc = DEBWT_ERANGE;
+    }
+    if (anchor_offsets && (anchor_capacity < all_anchors.size() || (!all_anchors.empty() && !hit_anchors))) {
+        f->err = "debwt_fm_map_chained: anchor capacity below the anchors (anchor_offsets[npat] = " + std::to_string(all_anchors.size()) + ")";
+        rc = DEBWT_ERANGE;
+    }
+    if (rc) return rc;
+    if (!all_cig.empty()) memcpy(cigar, all_cig.data(), all_cig.size() * 4);
+    if (anchor_offsets && !all_anchors.empty()) memcpy(hit_anchors, all_anchors.data(), all_anchors.size() * sizeof(debwt_fm_anchor));
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
@@ -4064,7 +4606,7 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
     for (DevBuf *b : {&f->idx, &f->rowlists, &f->sa, &f->q_chars, &f->q_off, &f->q_out, &f->q_runs, &f->s_hits, &f->s_ctr,
                       &f->s_plist, &f->m_slot, &f->m_cnt, &f->m_obase, &f->m_spans, &f->m_ranges, &f->m_cspans,
                       &f->m_cranges, &f->text, &f->x_jobs, &f->x_best, &f->x_cells, &f->x_flags, &f->x_tr, &f->x_cigoff,
-                      &f->x_cig})
+                      &f->x_cig, &f->x_anchors})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -666,6 +666,89 @@ typedef struct {
     float ms_mems, ms_locate, ms_candidates, ms_extend, ms_wall;
 } debwt_fm_map_stats;
 int debwt_fm_map_stats_get(const debwt_fm *fm, debwt_fm_map_stats *out);
+
+/* ---- chaining of seeds across diagonals, extension along a chain, and a mapper on both (fm_chain_kernels.h) ---------
+ * Seeds of ONE read to colinear chains (host only, no GPU; the chaining step of debwt_fm_map_chained).
+ * Seed quantities.  For seed x: len = qend - qbeg, tbeg = diag + qbeg, tend = diag + qend.  The seeds are sorted by
+ * (strand, record, tbeg, qbeg, qend).  Indices below are positions in that order.
+ * Valid predecessor.  i < j is a valid predecessor of j iff all of these hold: strand and record agree;
+ * qbeg_i < qbeg_j, qend_i < qend_j, tbeg_i < tbeg_j, tend_i < tend_j; |diag_j - diag_i| <= band;
+ * qbeg_j - qend_i <= max_gap and tbeg_j - tend_i <= max_gap, as signed values.  Overlaps are allowed.
+ * Gain and DP.  gain(i,j) = min(len_j, qend_j - qend_i, tend_j - tend_i) - |diag_j - diag_i|;
+ * f(j) = max(len_j, max over valid i of f(i) + gain(i,j)).
+ * Predecessor tie rule.  The predecessor is the i that reaches the maximum.  Among several, the largest i wins.  "No
+ * predecessor" is taken only when it is strictly better than every i.
+ * Chain extraction.  Take the seeds in descending f, ties by smaller index.  A seed not yet used ends a chain.  Walk its
+ * predecessors back until there is none, or until the next one is already used.  The used one is not part of the chain.
+ * Mark the chain's seeds used.  score = f(end) - f(first used seed met), or f(end) when none was met.
+ * Output.  The max_chains chains of the largest score are written, largest first, ties by smaller (strand, record, first
+ * anchor's diag, first anchor's qbeg), then by the order of extraction.  A chain's anchors are its seeds in ascending
+ * qbeg, as (qbeg, diag), at anchors[first_anchor .. first_anchor + n_anchors).  By the validity rule qbeg strictly
+ * increases and consecutive diag differ by at most band.  The function returns the number of chains written.
+ * *anchors_needed (the anchors of the chains written) is written first, then the chains; DEBWT_ERANGE when
+ * anchor_capacity is smaller than *anchors_needed (no anchor is written then), following the protocol of
+ * debwt_fm_locate.  DEBWT_EINVAL for a seed with qend <= qbeg, or for band > 63.
+ * The sort order lets the inner loop stop early: going back from j, once tbeg_j - tbeg_i exceeds max_gap plus the longest
+ * seed no earlier i can be valid.  No result depends on that. */
+typedef struct {
+    uint32_t qbeg;
+    uint32_t reserved;
+    int64_t diag;
+} debwt_fm_anchor;
+typedef struct {
+    int32_t score;
+    uint32_t record, strand, n_anchors;
+    uint64_t first_anchor;
+} debwt_fm_chain;
+int debwt_fm_chain_seeds(const debwt_fm_seed *seeds, uint64_t nseeds, uint32_t band, uint32_t max_gap,
+                         uint32_t max_chains, debwt_fm_chain *chains, debwt_fm_anchor *anchors,
+                         uint64_t anchor_capacity, uint64_t *anchors_needed);
+
+/* Banded affine-gap local alignment of jobs along chains.  Everything is as debwt_fm_extend documents it -- the
+ * recurrence for E, F, H and the score, the scoring limits and Q, strand handling and out[], the CIGAR coding, the
+ * DEBWT_ERANGE protocol and the score-only mode, the rule for the end cell and the traceback tie rule -- except the set
+ * of allowed cells.  With the job's anchors (q_0, d_0) .. (q_{r-1}, d_{r-1}) = anchors[first_anchor .. first_anchor +
+ * n_anchors), the band centre of query row i is c(i) = d_a for the largest a with q_a <= i, and c(i) = d_0 for i < q_0.
+ * Cell (i, t) is allowed iff 0 <= i < m, rs <= t < re and |t - i - c(i)| <= w.  A job with one anchor is exactly a
+ * debwt_fm_extend job with diag = d_0: the same out, the same CIGAR and the same offsets, bit for bit.  The total drift
+ * d_{r-1} - d_0 is not limited.  The result does not depend on how the jobs are batched.
+ * DEBWT_EINVAL in addition to the cases of debwt_fm_extend: n_anchors == 0, anchors out of range of the `anchors` array,
+ * qbeg not strictly increasing or >= m, consecutive diagonals further apart than band.  DEBWT_ESTATE without an attached
+ * text.  Device scratch: (rows that hold an allowed cell) x (2w + 1) flag bytes per job with a traceback; batches are cut
+ * at DEBWT_FM_EXTEND_BYTES of it, as in debwt_fm_extend.  debwt_fm_extend_stats_get reports the last chain extension
+ * too; its "wave steps" are then query rows (one row of 2w + 1 band indices each), not anti-diagonals. */
+typedef struct {
+    uint64_t pattern;
+    uint32_t record, strand;
+    uint64_t first_anchor;
+    uint32_t n_anchors, reserved;
+} debwt_fm_chain_job;
+int debwt_fm_extend_chain(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                          const debwt_fm_chain_job *jobs, uint64_t njobs, const debwt_fm_anchor *anchors, uint64_t nanchors,
+                          const debwt_fm_scoring *scoring, uint32_t band, debwt_fm_aln *out,
+                          uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity);
+
+/* Reads to alignments through chains: the stages of debwt_fm_map with debwt_fm_chain_seeds (band, max_gap, max_cand
+ * chains kept) in place of debwt_fm_cluster_seeds and one debwt_fm_extend_chain job per chain, so a read whose indels
+ * move it more than `band` diagonals away from a seed is still aligned end to end, as long as seeds on the way let the
+ * band follow it in steps of at most `band`.  The winner, sub, mapq, the flags, the unmapped / too-long rules and the
+ * DEBWT_ERANGE protocol are those of debwt_fm_map; hits[i].diag is the first anchor's diagonal of the winning chain.
+ * anchor_offsets (npat + 1) and hit_anchors return the winning chain's anchors per read (none for an unmapped read), so
+ * that a caller can rebuild the band; both may be NULL; DEBWT_ERANGE when anchor_capacity < anchor_offsets[npat], after
+ * anchor_offsets is written.  debwt_fm_map_stats_get describes the last mapping call of either kind; ms_candidates then
+ * holds the chaining time (host, at most 16 threads across reads) and candidates the chains kept.
+ * max_gap: the longest stretch, in the read or in the text, between two consecutive seeds of a chain (5000). */
+typedef struct {
+    debwt_fm_map_opts map;
+    uint32_t max_gap;
+    uint32_t reserved;
+} debwt_fm_chain_opts;
+void debwt_fm_chain_defaults(debwt_fm_chain_opts *opts);
+/* opts NULL: the defaults */
+int debwt_fm_map_chained(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                         const debwt_fm_chain_opts *opts, debwt_fm_hit *hits,
+                         uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity,
+                         uint64_t *anchor_offsets, debwt_fm_anchor *hit_anchors, uint64_t anchor_capacity);
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
