@@ -60,10 +60,14 @@ class RefDP:
         return sc[0] if q[i] in "ACGT" and q[i] == self.text[t] else -sc[1]
 
     def score(self, p, strand, diag, rec, w, sc):
+        return self.score_end(p, strand, diag, rec, w, sc)[0]
+
+    def score_end(self, p, strand, diag, rec, w, sc):
+        """(score, end row, end text position): the largest H, then the smallest row, then the smallest text position"""
         q = self.query(p, strand)
         m, (a, b, o, e) = len(q), sc
         H, E, F = {}, {}, {}
-        best = 0
+        best, bi, bt = 0, 0, 0
         for i in range(m):
             for t in range(max(self.rs[rec], i + diag - w), min(self.re[rec], i + diag + w + 1)):
                 ev = max(H.get((i, t - 1), NEG) - o - e, E.get((i, t - 1), NEG) - e)
@@ -71,8 +75,9 @@ class RefDP:
                 s = self.sub(q, i, t, sc)
                 hv = max(0 + s, H.get((i - 1, t - 1), NEG) + s, ev, fv)
                 H[(i, t)], E[(i, t)], F[(i, t)] = hv, ev, fv
-                best = max(best, hv)
-        return best
+                if hv > best:                                             # rows ascend, then text positions
+                    best, bi, bt = hv, i, t
+        return best, bi, bt
 
     def check(self, p, job, w, sc, score, qbeg, qend, tbeg, tend, edits, ops):
         """a valid alignment of score `score`: lengths, first and last op M, every visited cell allowed, re-scored, edits"""
@@ -176,8 +181,10 @@ def check_all(R, pats, jobs, w, sc, res):
     assert len(res) == len(jobs)
     for j, job in enumerate(jobs):
         p = pats[job[0]]
-        want = R.score(p, job[1], job[2], job[3], w, sc)
+        want, ei, et = R.score_end(p, job[1], job[2], job[3], w, sc)
         assert int(res.score[j]) == want, (job, w, sc, int(res.score[j]), want)
+        if want:
+            assert (int(res.qend[j]) - 1, int(res.tend[j]) - 1) == (ei, et), (job, w, sc)
         R.check(p, job, w, sc, want, int(res.qbeg[j]), int(res.qend[j]), int(res.tbeg[j]), int(res.tend[j]),
                 int(res.edits[j]), res.ops(j))
 
