@@ -7,7 +7,8 @@
  *   deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq
  *   deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]
- *                      [--max-occ N] [--min-score S] [--chain [--max-gap G]] READS.fa|.fq
+ *                      [--max-occ N] [--min-score S] [--chain [--max-gap G]]
+ *                      [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -36,6 +37,13 @@
  * --chain maps with debwt_fm_map_chained instead: the seeds of a read are chained across diagonals (steps of at most W,
  * stretches of at most G bases between two seeds, default 5000) and the band follows the chain, so a read whose indels
  * add up to more than W is still aligned end to end.  The PAF columns are the same.
+ * --mate READS2 maps paired ends with debwt_fm_map_pairs: read i of READS and read i of READS2 are the mates of pair i (the
+ * files must hold the same number of reads; not with --chain).  --insert LO,HI gives the bounds of the template length
+ * (LO <= HI <= 16384) instead of estimating them from the pairs that map uniquely; --no-rescue keeps a mate without a
+ * seed unmapped instead of aligning it in the window its partner leaves it.  Output: mate 1's line, then mate 2's, for
+ * every pair, mapped mates only, with three more tags: pr:A:P on both mates of a proper pair and pr:A:U otherwise, tl:i:
+ * (the template length, positive on the forward mate and negative on the reverse one; proper pairs only) and rs:i:1 on a
+ * mate that was placed by the rescue.
  *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
@@ -59,7 +67,8 @@ static void usage(void) {
             "       deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq\n"
             "       deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]\n"
-            "                          [--max-occ N] [--min-score S] [--chain [--max-gap G]] READS.fa|.fq\n"
+            "                          [--max-occ N] [--min-score S] [--chain [--max-gap G]]\n"
+            "                          [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
@@ -68,7 +77,9 @@ static void usage(void) {
             "least L bases (default 19);\n"
             "map prints one PAF line per mapped read (AS:i: score, NM:i: edits, cg:Z: CIGAR); --ref is the FASTA that OUT\n"
             "is the BWT of; --chain chains the seeds of a read across diagonals and aligns along the chain (stretches of\n"
-            "at most G bases between two seeds, default 5000)\n");
+            "at most G bases between two seeds, default 5000); --mate maps paired ends, read i of READS2 being the mate of\n"
+            "read i of READS (tags pr:A:P|U, tl:i: template length, rs:i:1 rescued mate), --insert LO,HI bounds the template\n"
+            "length instead of estimating it, --no-rescue leaves a mate without a seed unmapped\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -495,6 +506,24 @@ done:
 
 /* ---- map ------------------------------------------------------------------------------------------------------------- */
 
+/* the PAF columns and the tags AS, NM, cg of a mapped read, without the line's end */
+static void paf_line(const char *name, uint64_t m, const debwt_fm_hit *h, const uint64_t *starts, const uint32_t *cig,
+                     uint64_t c0, uint64_t c1) {
+    const int rev = (h->flags & DEBWT_FM_MAP_REVERSE) != 0;
+    uint64_t cols = 0, gaps = 0, mcols = 0;
+    for (uint64_t k = c0; k < c1; k++) {
+        cols += cig[k] >> 4;
+        if (cig[k] & 15) gaps += cig[k] >> 4; else mcols += cig[k] >> 4;
+    }
+    printf("%s\t%llu\t%llu\t%llu\t%c\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%u\tAS:i:%d\tNM:i:%u\tcg:Z:", name,
+           (unsigned long long)m, (unsigned long long)(rev ? m - h->qend : h->qbeg),
+           (unsigned long long)(rev ? m - h->qbeg : h->qend), rev ? '-' : '+', h->record,
+           (unsigned long long)(starts[h->record + 1] - 1 - starts[h->record]), (unsigned long long)h->offset,
+           (unsigned long long)(h->offset + (h->tend - h->tbeg)), (unsigned long long)(mcols - (h->edits - gaps)),
+           (unsigned long long)cols, h->mapq, h->score, h->edits);
+    for (uint64_t k = c0; k < c1; k++) printf("%u%c", cig[k] >> 4, "MID"[cig[k] & 3]);
+}
+
 static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t threads, int iupac, uint64_t seed, int device,
                    const debwt_fm_map_opts *opts, int chain, uint32_t max_gap) {
     struct patterns P;
@@ -544,22 +573,8 @@ static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     starts[fi.nrec] = fi.n;                               /* record r holds starts[r + 1] - 1 - starts[r] bases */
     for (uint64_t i = 0; i < P.n; i++) {
-        const debwt_fm_hit *h = &hits[i];
-        if (h->flags & DEBWT_FM_MAP_UNMAPPED) continue;
-        const uint64_t m = P.off[i + 1] - P.off[i];
-        const int rev = (h->flags & DEBWT_FM_MAP_REVERSE) != 0;
-        uint64_t cols = 0, gaps = 0, mcols = 0;
-        for (uint64_t k = coff[i]; k < coff[i + 1]; k++) {
-            cols += cig[k] >> 4;
-            if (cig[k] & 15) gaps += cig[k] >> 4; else mcols += cig[k] >> 4;
-        }
-        printf("%s\t%llu\t%llu\t%llu\t%c\t%u\t%llu\t%llu\t%llu\t%llu\t%llu\t%u\tAS:i:%d\tNM:i:%u\tcg:Z:", P.name[i],
-               (unsigned long long)m, (unsigned long long)(rev ? m - h->qend : h->qbeg),
-               (unsigned long long)(rev ? m - h->qbeg : h->qend), rev ? '-' : '+', h->record,
-               (unsigned long long)(starts[h->record + 1] - 1 - starts[h->record]), (unsigned long long)h->offset,
-               (unsigned long long)(h->offset + (h->tend - h->tbeg)), (unsigned long long)(mcols - (h->edits - gaps)),
-               (unsigned long long)cols, h->mapq, h->score, h->edits);
-        for (uint64_t k = coff[i]; k < coff[i + 1]; k++) printf("%u%c", cig[k] >> 4, "MID"[cig[k] & 3]);
+        if (hits[i].flags & DEBWT_FM_MAP_UNMAPPED) continue;
+        paf_line(P.name[i], P.off[i + 1] - P.off[i], &hits[i], starts, cig, coff[i], coff[i + 1]);
         putchar('\n');
     }
     ret = fflush(stdout) ? 1 : 0;
@@ -568,6 +583,88 @@ done:
     free(coff); free(cig); free(hits); free(starts);
     debwt_fm_destroy(fm);
     free_patterns(&P);
+    return ret;
+}
+
+/* ---- map --mate: paired ends ----------------------------------------------------------------------------------------- */
+
+static int cmd_map_pairs(const char *out, const char *ref, const char *pfile, const char *mfile, uint64_t threads, int iupac,
+                         uint64_t seed, int device, const debwt_fm_pair_opts *opts) {
+    struct patterns P, M, B;                              /* mates 1, mates 2, both interleaved (names stay in P and M) */
+    memset(&P, 0, sizeof P); memset(&M, 0, sizeof M); memset(&B, 0, sizeof B);
+    if (read_patterns(pfile, &P)) return 1;
+    if (read_patterns(mfile, &M)) { free_patterns(&P); return 1; }
+    if (P.n != M.n) {
+        fprintf(stderr, "--mate: %s holds %llu reads, %s holds %llu: read i of one is the mate of read i of the other\n", mfile,
+                (unsigned long long)M.n, pfile, (unsigned long long)P.n);
+        free_patterns(&P); free_patterns(&M);
+        return 1;
+    }
+    const uint64_t np = P.n, nr = 2 * np;
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); free_patterns(&M); return 1; }
+    int ret = 1, rc;
+    debwt_packed_text pt;
+    char err[256] = "";
+    memset(&pt, 0, sizeof pt);
+    uint64_t cap = 4 * nr + 16, *coff = malloc((nr + 1) * 8), *starts = NULL;
+    uint32_t *cig = NULL;
+    debwt_fm_hit *hits = malloc((nr ? nr : 1) * sizeof *hits);
+    debwt_fm_pair_info *info = malloc((np ? np : 1) * sizeof *info);
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    starts = malloc((fi.nrec + 1) * 8);
+    B.seq = malloc(P.len + M.len + 1);
+    B.off = malloc((nr + 1) * 8);
+    if (!coff || !hits || !info || !starts || !B.seq || !B.off) { fprintf(stderr, "out of memory\n"); goto done; }
+    B.off[0] = 0;
+    for (uint64_t i = 0; i < np; i++) {
+        const uint64_t l1 = P.off[i + 1] - P.off[i], l2 = M.off[i + 1] - M.off[i];
+        memcpy(B.seq + B.off[2 * i], P.seq + P.off[i], l1);
+        B.off[2 * i + 1] = B.off[2 * i] + l1;
+        memcpy(B.seq + B.off[2 * i + 1], M.seq + M.off[i], l2);
+        B.off[2 * i + 2] = B.off[2 * i + 1] + l2;
+    }
+    rc = debwt_pack_fasta_opts(ref, (int)threads, iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, seed, &pt, err, sizeof err);
+    if (rc) {
+        fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", ref, err);
+        goto done;
+    }
+    if (pt.n != fi.n || pt.nrec != fi.nrec) {
+        fprintf(stderr, "%s is not the text of %s: %llu symbols in %llu records, the index has %llu in %llu\n", ref, out,
+                (unsigned long long)pt.n, (unsigned long long)pt.nrec, (unsigned long long)fi.n, (unsigned long long)fi.nrec);
+        goto done;
+    }
+    rc = debwt_fm_attach_text(fm, NULL, pt.words, pt.sep);
+    if (rc) { fprintf(stderr, "%s is not the text of %s: %s\n", ref, out, debwt_fm_last_error(fm)); goto done; }
+    for (;;) {                                            /* grow to the exact op count on DEBWT_ERANGE */
+        free(cig);
+        cig = malloc(cap * 4);
+        if (!cig) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_map_pairs(fm, B.seq, B.off, np, opts, hits, info, coff, cig, cap);
+        if (rc == DEBWT_ERANGE && coff[nr] > cap) { cap = coff[nr]; continue; }
+        break;
+    }
+    if (!rc) rc = debwt_fm_record_starts(fm, starts, fi.nrec);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    starts[fi.nrec] = fi.n;
+    for (uint64_t i = 0; i < nr; i++) {
+        const debwt_fm_hit *h = &hits[i];
+        if (h->flags & DEBWT_FM_MAP_UNMAPPED) continue;
+        paf_line(i & 1 ? M.name[i / 2] : P.name[i / 2], B.off[i + 1] - B.off[i], h, starts, cig, coff[i], coff[i + 1]);
+        printf("\tpr:A:%c", h->flags & DEBWT_FM_MAP_PROPER ? 'P' : 'U');
+        if (h->flags & DEBWT_FM_MAP_PROPER)
+            printf("\ttl:i:%lld", (long long)(h->flags & DEBWT_FM_MAP_REVERSE ? -info[i / 2].tlen : info[i / 2].tlen));
+        if (h->flags & DEBWT_FM_MAP_RESCUED) printf("\trs:i:1");
+        putchar('\n');
+    }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    debwt_free_packed(&pt);
+    free(coff); free(cig); free(hits); free(info); free(starts);
+    debwt_fm_destroy(fm);
+    free(B.seq); free(B.off);
+    free_patterns(&P); free_patterns(&M);
     return ret;
 }
 
@@ -583,7 +680,10 @@ int main(int argc, char **argv) {
     debwt_fm_map_defaults(&mo);
     debwt_fm_chain_opts co;
     debwt_fm_chain_defaults(&co);
-    int iupac = 0, search = 0, chain = 0, gap_given = 0;
+    debwt_fm_pair_opts po;
+    debwt_fm_pair_defaults(&po);
+    const char *mate = NULL;
+    int iupac = 0, search = 0, chain = 0, gap_given = 0, insert_given = 0, no_rescue = 0;
     uint32_t flags = 0;
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
@@ -595,6 +695,11 @@ int main(int argc, char **argv) {
         if (mode >= 1 && mode <= 3 && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
         if ((mode == 1 || mode == 2) && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
         if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
+        if (mode == 4 && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
+        if (mode != 4 && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
+            fprintf(stderr, "%s: only with map\n", a);
+            return 1;
+        }
         if (i + 1 >= argc) { usage(); return 1; }
         const char *v = argv[++i];
         if (!strcmp(a, "-i")) out = v;
@@ -628,6 +733,19 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-gap: a length of at least 0\n"); return 1; }
             co.max_gap = (uint32_t)v64; gap_given = 1;
         }
+        else if (mode == 4 && !strcmp(a, "--mate")) mate = v;
+        else if (mode == 4 && !strcmp(a, "--insert")) {
+            uint64_t lo = 0, hi = 0;
+            char buf[48];
+            const char *comma = strchr(v, ',');
+            if (!comma || (size_t)(comma - v) >= sizeof buf) { fprintf(stderr, "--insert: LO,HI, two template lengths\n"); return 1; }
+            memcpy(buf, v, (size_t)(comma - v)); buf[comma - v] = 0;
+            if (parse_u64(buf, &lo) || parse_u64(comma + 1, &hi) || lo > hi || hi < 1 || hi > DEBWT_FM_INSERT_MAX) {
+                fprintf(stderr, "--insert: LO,HI with LO <= HI, HI in 1..%u\n", DEBWT_FM_INSERT_MAX);
+                return 1;
+            }
+            po.ins_lo = (uint32_t)lo; po.ins_hi = (uint32_t)hi; insert_given = 1;
+        }
         else if ((mode == 3 || mode == 4) && !strcmp(a, "--min-len")) {
             if (parse_u64(v, &min_len) || min_len < 1 || min_len > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
         }
@@ -638,7 +756,15 @@ int main(int argc, char **argv) {
     if (mode == 4) {
         if (!ref) { fprintf(stderr, "map: --ref INPUT.fa[.gz] (the text OUT is the BWT of) is required\n"); return 1; }
         if (gap_given && !chain) { fprintf(stderr, "--max-gap: only with --chain\n"); return 1; }
+        if (mate && chain) { fprintf(stderr, "--mate: not with --chain (pairs are mapped with the fixed band)\n"); return 1; }
+        if (insert_given && !mate) { fprintf(stderr, "--insert: only with --mate\n"); return 1; }
+        if (no_rescue && !mate) { fprintf(stderr, "--no-rescue: only with --mate\n"); return 1; }
         mo.min_len = (uint32_t)min_len;
+        if (mate) {
+            po.map = mo;
+            if (no_rescue) po.max_rescue = 0;
+            return cmd_map_pairs(out, ref, file, mate, threads, iupac, seed, (int)device, &po);
+        }
         return cmd_map(out, ref, file, threads, iupac, seed, (int)device, &mo, chain, co.max_gap);
     }
     if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);

@@ -138,6 +138,41 @@ class DebwtFmChainOpts(ctypes.Structure):
     _fields_ = [("map", DebwtFmMapOpts), ("max_gap", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class DebwtFmWindowJob(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_uint64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32),
+                ("wbeg", ctypes.c_uint64), ("wend", ctypes.c_uint64)]
+
+
+class DebwtFmPcand(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_int32), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("tbeg", ctypes.c_uint64), ("tend", ctypes.c_uint64)]
+
+
+class DebwtFmPairChoice(ctypes.Structure):
+    _fields_ = [("i1", ctypes.c_int32), ("i2", ctypes.c_int32), ("proper", ctypes.c_uint32), ("mapq1", ctypes.c_uint32),
+                ("mapq2", ctypes.c_uint32), ("sub1", ctypes.c_int32), ("sub2", ctypes.c_int32), ("pair_score", ctypes.c_int32),
+                ("pair_sub", ctypes.c_int32), ("tlen", ctypes.c_int64)]
+
+
+class DebwtFmPairOpts(ctypes.Structure):
+    _fields_ = [("map", DebwtFmMapOpts), ("ins_lo", ctypes.c_uint32), ("ins_hi", ctypes.c_uint32),
+                ("max_rescue", ctypes.c_uint32), ("unpaired_penalty", ctypes.c_int32)]
+
+
+class DebwtFmPairInfo(ctypes.Structure):
+    _fields_ = [("tlen", ctypes.c_int64), ("pair_score", ctypes.c_int32), ("pair_sub", ctypes.c_int32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class DebwtFmPairStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("pairs", "proper", "rescue_jobs", "rescued", "ins_lo", "ins_hi",
+                                                "estimate_pairs")] +
+                [(n, ctypes.c_float) for n in ("ms_candidates", "ms_rescue", "ms_select", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DebwtFmExtendStats(ctypes.Structure):
     _fields_ = ([(n, ctypes.c_uint64) for n in ("jobs", "batches", "launches", "cells", "wave_steps", "scratch_bytes")] +
                 [(n, ctypes.c_float) for n in ("ms_kernel", "ms_trace", "ms_wall")])
@@ -185,6 +220,8 @@ SYMBOLS = [
     "debwt_fm_attach_text", "debwt_fm_extend", "debwt_fm_extend_stats_get", "debwt_fm_cluster_seeds",
     "debwt_fm_map_defaults", "debwt_fm_map", "debwt_fm_map_stats_get",
     "debwt_fm_chain_seeds", "debwt_fm_extend_chain", "debwt_fm_chain_defaults", "debwt_fm_map_chained",
+    "debwt_fm_align_window", "debwt_fm_insert_bounds", "debwt_fm_pair_select", "debwt_fm_pair_defaults",
+    "debwt_fm_map_pairs", "debwt_fm_pair_stats_get",
 ]
 
 
@@ -420,6 +457,24 @@ def lib():
     L.debwt_fm_map_chained.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.POINTER(DebwtFmChainOpts),
                                        ctypes.POINTER(DebwtFmHit), u64p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint64,
                                        u64p, ctypes.POINTER(DebwtFmAnchor), ctypes.c_uint64]
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    L.debwt_fm_align_window.restype = ctypes.c_int
+    L.debwt_fm_align_window.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.POINTER(DebwtFmWindowJob),
+                                        ctypes.c_uint64, ctypes.POINTER(DebwtFmScoring), ctypes.POINTER(DebwtFmAln), u64p,
+                                        u32p, ctypes.c_uint64]
+    L.debwt_fm_insert_bounds.restype = ctypes.c_int
+    L.debwt_fm_insert_bounds.argtypes = [u64p, ctypes.c_uint64, u32p, u32p]
+    L.debwt_fm_pair_select.restype = ctypes.c_int
+    L.debwt_fm_pair_select.argtypes = [ctypes.POINTER(DebwtFmPcand), ctypes.c_uint32, ctypes.POINTER(DebwtFmPcand),
+                                       ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int32, ctypes.c_int32,
+                                       ctypes.POINTER(DebwtFmPairChoice)]
+    L.debwt_fm_pair_defaults.restype = None
+    L.debwt_fm_pair_defaults.argtypes = [ctypes.POINTER(DebwtFmPairOpts)]
+    L.debwt_fm_map_pairs.restype = ctypes.c_int
+    L.debwt_fm_map_pairs.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.POINTER(DebwtFmPairOpts),
+                                     ctypes.POINTER(DebwtFmHit), ctypes.POINTER(DebwtFmPairInfo), u64p, u32p, ctypes.c_uint64]
+    L.debwt_fm_pair_stats_get.restype = ctypes.c_int
+    L.debwt_fm_pair_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmPairStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

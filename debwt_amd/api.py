@@ -573,6 +573,91 @@ class FMIndex:
             break
         return MapResult(hits[:npat], coff, cg[:int(coff[npat])].copy(), aoff, an[:int(aoff[npat])].copy())
 
+    def align_window(self, patterns, jobs, scoring=(1, 4, 6, 1), cigar=True):
+        """Affine-gap local alignment of jobs against text windows, without a band (debwt_fm_align_window).  jobs: rows of
+        (pattern index, strand, record, wbeg, wend); the query -- the pattern (strand 0) or its reverse complement (strand
+        1), at most 4096 bases -- is aligned against the global text positions [wbeg, wend) (at most 16384) clipped to the
+        record.  Everything else is as extend() has it.  Returns an ExtendResult."""
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        jobs = [tuple(int(x) for x in j) for j in jobs]
+        nj = len(jobs)
+        ja = (_lib.DebwtFmWindowJob * max(nj, 1))()
+        for k, (p, s, r, b, e) in enumerate(jobs):
+            if min(p, s, r, b, e) < 0 or max(s, r) >= 2 ** 32 or max(p, b, e) >= 2 ** 64:
+                raise DebwtError(-1, "a job with a negative or oversized field")
+            ja[k].pattern, ja[k].strand, ja[k].record, ja[k].wbeg, ja[k].wend = p, s, r, b, e
+        sc = _lib.DebwtFmScoring(*[int(x) for x in scoring])
+        out = np.zeros(max(nj, 1), dtype=_ALN_DTYPE)
+        outp = out.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmAln))
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        if not cigar:
+            self._chk(self._L.debwt_fm_align_window(self._h, buf, _p64(offs), npat, ja, nj, ctypes.byref(sc), outp, None,
+                                                    None, 0))
+            return ExtendResult(out[:nj], None, None)
+        coff = np.zeros(nj + 1, dtype=np.uint64)
+        cap = 4 * nj + 16
+        while True:
+            cg = np.zeros(cap, dtype=np.uint32)
+            rc = self._L.debwt_fm_align_window(self._h, buf, _p64(offs), npat, ja, nj, ctypes.byref(sc), outp, _p64(coff),
+                                               cg.ctypes.data_as(u32p), cap)
+            if rc == -5 and int(coff[nj]) > cap:
+                cap = int(coff[nj])
+                continue
+            self._chk(rc)
+            break
+        return ExtendResult(out[:nj], coff, cg[:int(coff[nj])].copy())
+
+    def map_pairs(self, reads1, reads2, insert=None, max_rescue=4, unpaired_penalty=17, min_len=19, band=16, max_occ=64,
+                  max_cand=8, min_score=30, scoring=(1, 4, 6, 1), strands="both"):
+        """Paired-end reads to alignments (debwt_fm_map_pairs): the candidates of map() for every read, insert-size bounds
+        (insert=(lo, hi), or None to estimate them from the pairs that map uniquely), the rescue of a mate in the window its
+        partner's candidates leave it (align_window; max_rescue=0: none), and the choice of the pair.  reads1[p] and
+        reads2[p] are the mates of pair p.  Returns a MapResult over the 2 * npairs reads in the order mate 1, mate 2 of
+        pair 0, mate 1 of pair 1, ... (flags also MAP_PROPER, MAP_RESCUED); its .pairs holds tlen, pair_score and pair_sub
+        of every pair.  strands: pairs are mapped on both strands; "forward" is passed on and refused by the library."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        r1 = [reads1] if isinstance(reads1, (str, bytes, bytearray)) else list(reads1)
+        r2 = [reads2] if isinstance(reads2, (str, bytes, bytearray)) else list(reads2)
+        if len(r1) != len(r2):
+            raise ValueError("reads1 and reads2 must have the same number of reads")
+        buf, offs = _patterns([r for pr in zip(r1, r2) for r in pr])
+        npairs, npat = len(r1), 2 * len(r1)
+        po = _lib.DebwtFmPairOpts()
+        self._L.debwt_fm_pair_defaults(ctypes.byref(po))
+        o = po.map
+        o.min_len, o.band, o.max_occ, o.max_cand, o.min_score = int(min_len), int(band), int(max_occ), int(max_cand), int(min_score)
+        o.flags = MAP_FORWARD if strands == "forward" else 0
+        o.scoring = _lib.DebwtFmScoring(*[int(x) for x in scoring])
+        if insert is not None:
+            po.ins_lo, po.ins_hi = int(insert[0]), int(insert[1])
+        po.max_rescue, po.unpaired_penalty = int(max_rescue), int(unpaired_penalty)
+        hits = np.zeros(max(npat, 1), dtype=_HIT_DTYPE)
+        info = np.zeros(max(npairs, 1), dtype=_PAIR_DTYPE)
+        coff = np.zeros(npat + 1, dtype=np.uint64)
+        cap = 4 * npat + 16
+        while True:
+            cg = np.zeros(cap, dtype=np.uint32)
+            rc = self._L.debwt_fm_map_pairs(self._h, buf, _p64(offs), npairs, ctypes.byref(po),
+                                            hits.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmHit)),
+                                            info.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmPairInfo)), _p64(coff),
+                                            cg.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cap)
+            if rc == -5 and int(coff[npat]) > cap:
+                cap = int(coff[npat])
+                continue
+            self._chk(rc)
+            break
+        res = MapResult(hits[:npat], coff, cg[:int(coff[npat])].copy())
+        res.pairs = info[:npairs]
+        return res
+
+    def pair_stats(self):
+        """Counts, the insert bounds used and the stage times of the last map_pairs() (debwt_fm_pair_stats_get)."""
+        st = _lib.DebwtFmPairStats()
+        self._chk(self._L.debwt_fm_pair_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def map_stats(self):
         """Stage times and counts of the last map() or map_chained() (debwt_fm_map_stats_get)."""
         st = _lib.DebwtFmMapStats()
@@ -614,6 +699,7 @@ class FMIndex:
 
 SEARCH_BOTH_STRANDS, SEARCH_BEST_ONLY = 1, 2
 MAP_REVERSE, MAP_UNMAPPED, MAP_TOO_LONG = 1, 2, 4      # MapResult.flags
+MAP_PROPER, MAP_RESCUED = 8, 16                        # MapResult.flags of FMIndex.map_pairs
 MAP_FORWARD = 1                                        # option flag of debwt_fm_map
 _ALN_DTYPE = np.dtype([("score", np.int32), ("qbeg", np.uint32), ("qend", np.uint32), ("edits", np.uint32),
                        ("tbeg", np.uint64), ("tend", np.uint64)])
@@ -622,6 +708,8 @@ _HIT_DTYPE = np.dtype([("pattern", np.uint64), ("flags", np.uint32), ("record", 
                        ("score", np.int32), ("sub", np.int32), ("mapq", np.uint32), ("edits", np.uint32),
                        ("diag", np.int64)])
 _ANCHOR_DTYPE = np.dtype([("qbeg", np.uint32), ("reserved", np.uint32), ("diag", np.int64)])
+_PAIR_DTYPE = np.dtype([("tlen", np.int64), ("pair_score", np.int32), ("pair_sub", np.int32), ("reserved", np.uint32)],
+                       align=True)
 
 
 def cigar_string(ops):
@@ -663,6 +751,42 @@ def chain_seeds(seeds, band=16, max_gap=5000, max_chains=8):
              "anchors": [(int(an[x].qbeg), int(an[x].diag))
                          for x in range(int(ch[k].first_anchor), int(ch[k].first_anchor) + int(ch[k].n_anchors))]}
             for k in range(rc)]
+
+
+def insert_bounds(tlens):
+    """(lo, hi) insert-size bounds from observed template lengths on the host (debwt_fm_insert_bounds, no GPU): with
+    the quartiles q1, q3 of the sorted values and d = q3 - q1, lo = max(1, q1 - 3 d) and hi = min(16384, q3 + 3 d).
+    Fewer than 32 values raise."""
+    L = _lib.lib()
+    t = np.ascontiguousarray(tlens, dtype=np.uint64)
+    lo, hi = ctypes.c_uint32(0), ctypes.c_uint32(0)
+    rc = L.debwt_fm_insert_bounds(_p64(t) if len(t) else None, len(t), ctypes.byref(lo), ctypes.byref(hi))
+    if rc < 0:
+        raise DebwtError(rc)
+    return int(lo.value), int(hi.value)
+
+
+def pair_select(c1, c2, ins_lo, ins_hi, unpaired_penalty=17, min_score=30):
+    """The choice of one pair from the candidates of its mates on the host (debwt_fm_pair_select, no GPU).  c1, c2: rows
+    of (score, record, strand, tbeg, tend).  Returns a dict (i1, i2, proper, mapq1, mapq2, sub1, sub2, pair_score,
+    pair_sub, tlen); i1 / i2 = -1: the mate has no eligible candidate."""
+    L = _lib.lib()
+
+    def arr(c):
+        c = list(c)
+        a = (_lib.DebwtFmPcand * max(len(c), 1))()
+        for k, (sc, rec, st, tb, te) in enumerate(c):
+            a[k].score, a[k].record, a[k].strand, a[k].tbeg, a[k].tend = int(sc), int(rec), int(st), int(tb), int(te)
+        return a, len(c)
+
+    (a1, n1), (a2, n2) = arr(c1), arr(c2)
+    if min(int(ins_lo), int(ins_hi)) < 0:
+        raise DebwtError(-1, "negative insert bounds")
+    ch = _lib.DebwtFmPairChoice()
+    rc = L.debwt_fm_pair_select(a1, n1, a2, n2, int(ins_lo), int(ins_hi), int(unpaired_penalty), int(min_score), ctypes.byref(ch))
+    if rc < 0:
+        raise DebwtError(rc)
+    return {n: int(getattr(ch, n)) for n, _ in _lib.DebwtFmPairChoice._fields_}
 
 
 class ExtendResult:

@@ -31,6 +31,7 @@
 #include "fm_mem_kernels.h"
 #include "fm_extend_kernels.h"
 #include "fm_chain_kernels.h"
+#include "fm_window_kernels.h"
 
 namespace {
 
@@ -2844,6 +2845,7 @@ struct debwt_fm {
     DevBuf x_anchors;            // the anchors of one batch of chain jobs
     debwt_fm_extend_stats x_stats{};
     debwt_fm_map_stats map_stats{};
+    debwt_fm_pair_stats pair_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -4596,6 +4598,584 @@ extern "C" int debwt_fm_map_chained(debwt_fm *f, const char *patterns, const uin
     if (rc) return rc;
     if (!all_cig.empty()) memcpy(cigar, all_cig.data(), all_cig.size() * 4);
     if (anchor_offsets && !all_anchors.empty()) memcpy(hit_anchors, all_anchors.data(), all_anchors.size() * sizeof(debwt_fm_anchor));
+    return DEBWT_OK;
+}
+
+// ---- paired ends: alignment against a text window, insert bounds, pair selection, the pair mapper (fm_window_kernels.h) --
+// The batches, the two traceback passes and the statistics are those of fm_extend_run; a job's flag scratch is 64 bytes
+// per step of its wave, a wave step being one anti-diagonal of one strip of 64 window columns.
+
+namespace {
+
+// the device form of a window job; false: the window misses the record (score 0)
+bool fm_win_prepare(const debwt_fm *f, u64 m, const debwt_fm_window_job &jb, FmWinJob *d) {
+    const u64 rs = f->rec_starts[jb.record];
+    const u64 re = (jb.record + 1 < f->nrec ? f->rec_starts[jb.record + 1] : f->n) - 1;
+    const u64 lo = std::max<u64>(rs, jb.wbeg), hi = std::min<u64>(re, jb.wend);
+    if (lo >= hi) return false;
+    d->qoff = 0; d->flag_off = 0; d->tbase = lo;
+    d->m = (u32)m; d->strand = jb.strand;
+    d->ncol = (u32)(hi - lo); d->nstrips = (d->ncol + 63) / 64;
+    return true;
+}
+
+u64 fm_win_steps(const FmWinJob &d) {                     // steps of the job's wave over all strips
+    return (u64)(d.nstrips - 1) * (d.m + 63) + d.m + (d.ncol - 64 * (d.nstrips - 1)) - 1;
+}
+
+// jobs [0, njobs) -> out; with `trace` also ops per job (cig_n) and the ops of all jobs in job order (cig).  The
+// arguments were validated by the caller; statistics are added to f->x_stats.
+int fm_window_run(debwt_fm *f, const char *patterns, const uint64_t *offsets, const debwt_fm_window_job *jobs, u64 njobs,
+                  const debwt_fm_scoring &sc, bool trace, debwt_fm_aln *out, std::vector<u32> *cig_n, std::vector<u32> *cig) {
+    debwt_fm_extend_stats &st = f->x_stats;
+    st.jobs += njobs;
+    if (trace) { cig_n->assign(njobs, 0); cig->clear(); }
+    if (!njobs) return DEBWT_OK;
+    const u64 limit = fm_env_u64("DEBWT_FM_EXTEND_BYTES", FM_EXTEND_BYTES);
+    FmExtEvents ev;
+    HIPCHK(f, hipEventCreate(&ev.a));
+    HIPCHK(f, hipEventCreate(&ev.b));
+    std::vector<FmWinJob> dj;
+    std::vector<u64> src;                                // job index of every device job
+    std::vector<char> chars;
+    std::vector<u64> best;
+    std::vector<u32> cells, tr, ops;
+    std::vector<u64> coff;
+    for (u64 j0 = 0; j0 < njobs;) {
+        dj.clear(); src.clear(); chars.clear();
+        u64 fbytes = 0, j1 = j0, last_pat = ~0ull, last_off = 0, steps = 0;
+        u32 lds_job = 8;
+        for (; j1 < njobs; j1++) {
+            const debwt_fm_window_job &jb = jobs[j1];
+            const u64 m = offsets[jb.pattern + 1] - offsets[jb.pattern];
+            FmWinJob d;
+            if (!fm_win_prepare(f, m, jb, &d)) { out[j1] = debwt_fm_aln{}; continue; }
+            const u64 ns = fm_win_steps(d), fb = trace ? 64 * ns : 0;
+            const bool fresh = jb.pattern != last_pat;
+            if (!dj.empty() && (fbytes + fb > limit || dj.size() >= FM_EXTEND_JOBS ||
+                                (fresh && chars.size() + m > FM_BATCH_CHARS)))
+                break;
+            if (fresh) {
+                last_pat = jb.pattern; last_off = chars.size();
+                chars.insert(chars.end(), patterns + offsets[jb.pattern], patterns + offsets[jb.pattern] + m);
+            }
+            d.qoff = last_off; d.flag_off = fbytes;
+            fbytes += fb; steps += ns;
+            lds_job = std::max(lds_job, fm_win_lds(d.m, d.ncol));
+            dj.push_back(d); src.push_back(j1);
+        }
+        const u64 nd = dj.size();
+        if (!nd) { j0 = j1; continue; }
+        // the workgroup: as many waves (1..4), one job each, as the staged strings and hand-over buffers leave room for
+        const u32 jpb = std::max<u32>(1, std::min<u32>(4, FM_EXT_LDS_BUDGET / lds_job));
+        const u32 block = 64 * jpb, grid = (u32)((nd + jpb - 1) / jpb);
+        st.wave_steps += steps;
+        st.scratch_bytes = std::max<u64>(st.scratch_bytes, fbytes);
+        FM_ENSURE(f, f->q_chars, std::max<size_t>(chars.size(), 1));
+        FM_ENSURE(f, f->x_jobs, nd * sizeof(FmWinJob));
+        FM_ENSURE(f, f->x_best, nd * 8);
+        FM_ENSURE(f, f->x_cells, nd * 4);
+        if (trace) {
+            FM_ENSURE(f, f->x_flags, (size_t)std::max<u64>(fbytes, 1));
+            FM_ENSURE(f, f->x_tr, nd * 16);
+            FM_ENSURE(f, f->x_cigoff, (nd + 1) * 8);
+        }
+        HIPCHK(f, hipMemcpyAsync(f->q_chars.p, chars.data(), chars.size(), hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->x_jobs.p, dj.data(), nd * sizeof(FmWinJob), hipMemcpyHostToDevice, f->stream));
+        (void)hipEventRecord(ev.a, f->stream);
+        const size_t lds = (size_t)jpb * lds_job;
+        if (trace)
+            k_fm_window<true><<<grid, block, lds, f->stream>>>(f->text.as<u64>(), f->q_chars.as<u8>(), f->x_jobs.as<FmWinJob>(),
+                                                               (u32)nd, sc.match, sc.mismatch, sc.gap_open, sc.gap_extend,
+                                                               lds_job, f->x_flags.as<u8>(), f->x_best.as<u64>(),
+                                                               f->x_cells.as<u32>());
+        else
+            k_fm_window<false><<<grid, block, lds, f->stream>>>(f->text.as<u64>(), f->q_chars.as<u8>(), f->x_jobs.as<FmWinJob>(),
+                                                                (u32)nd, sc.match, sc.mismatch, sc.gap_open, sc.gap_extend,
+                                                                lds_job, f->x_flags.as<u8>(), f->x_best.as<u64>(),
+                                                                f->x_cells.as<u32>());
+        (void)hipEventRecord(ev.b, f->stream);
+        st.launches++;
+        best.resize(nd); cells.resize(nd);
+        HIPCHK(f, hipMemcpyAsync(best.data(), f->x_best.p, nd * 8, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(f, hipMemcpyAsync(cells.data(), f->x_cells.p, nd * 4, hipMemcpyDeviceToHost, f->stream));
+        if (trace) {
+            k_fm_window_trace<<<grid_for(nd, 256), 256, 0, f->stream>>>(f->x_jobs.as<FmWinJob>(), (u32)nd, f->x_flags.as<u8>(),
+                                                                        f->x_best.as<u64>(), nullptr, nullptr, f->x_tr.as<u32>());
+            st.launches++;
+            tr.resize(4 * nd);
+            HIPCHK(f, hipMemcpyAsync(tr.data(), f->x_tr.p, nd * 16, hipMemcpyDeviceToHost, f->stream));
+        }
+        int rc = fm_sync(f);
+        if (rc) return rc;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+        st.ms_kernel += ms;
+        for (u64 a = 0; a < nd; a++) st.cells += cells[a];
+        u64 total = 0;
+        if (trace) {
+            coff.resize(nd + 1);
+            coff[0] = 0;
+            for (u64 a = 0; a < nd; a++) coff[a + 1] = coff[a] + tr[4 * a + 3];
+            total = coff[nd];
+            ops.resize(total);
+            if (total) {
+                FM_ENSURE(f, f->x_cig, (size_t)total * 4);
+                HIPCHK(f, hipMemcpyAsync(f->x_cigoff.p, coff.data(), (nd + 1) * 8, hipMemcpyHostToDevice, f->stream));
+                (void)hipEventRecord(ev.a, f->stream);
+                k_fm_window_trace<<<grid_for(nd, 256), 256, 0, f->stream>>>(f->x_jobs.as<FmWinJob>(), (u32)nd, f->x_flags.as<u8>(),
+                                                                            f->x_best.as<u64>(), f->x_cigoff.as<u64>(),
+                                                                            f->x_cig.as<u32>(), f->x_tr.as<u32>());
+                (void)hipEventRecord(ev.b, f->stream);
+                st.launches++;
+                HIPCHK(f, hipMemcpyAsync(ops.data(), f->x_cig.p, total * 4, hipMemcpyDeviceToHost, f->stream));
+                if ((rc = fm_sync(f))) return rc;
+                (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+                st.ms_trace += ms;
+            }
+        }
+        for (u64 a = 0; a < nd; a++) {
+            debwt_fm_aln &o = out[src[a]];
+            o = debwt_fm_aln{};
+            const u64 key = best[a];
+            if (!(key >> 32)) continue;
+            const u32 i = 4095u - (u32)((key >> 14) & 0xFFFu), c = 16383u - (u32)(key & 0x3FFFu);
+            o.score = (int32_t)(key >> 32);
+            o.qend = i + 1;
+            o.tend = dj[a].tbase + c + 1;
+            if (trace) {
+                o.qbeg = tr[4 * a]; o.tbeg = dj[a].tbase + tr[4 * a + 1]; o.edits = tr[4 * a + 2];
+                (*cig_n)[src[a]] = tr[4 * a + 3];
+            }
+        }
+        if (trace) cig->insert(cig->end(), ops.begin(), ops.end());   // device jobs are in job order
+        st.batches++;
+        j0 = j1;
+    }
+    return DEBWT_OK;
+}
+
+// the checks of debwt_fm_align_window, then the run; x_stats are those of this pass
+int fm_window_call(debwt_fm *f, const char *patterns, const uint64_t *offsets, u64 npat, const debwt_fm_window_job *jobs,
+                   u64 njobs, const debwt_fm_scoring *sc, bool trace, debwt_fm_aln *out, std::vector<u32> *cig_n,
+                   std::vector<u32> *cig) {
+    const auto t0 = std::chrono::steady_clock::now();
+    f->x_stats = debwt_fm_extend_stats{};
+    int rc = fm_ext_check(f, sc, 0, "debwt_fm_align_window");
+    if (rc) return rc;
+    for (u64 i = 0; i < npat; i++)
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_align_window: offsets must not decrease"; return DEBWT_EINVAL; }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    for (u64 j = 0; j < njobs; j++) {
+        const debwt_fm_window_job &jb = jobs[j];
+        const std::string who = "debwt_fm_align_window: job " + std::to_string(j);
+        if (jb.pattern >= npat || jb.strand > 1 || jb.record >= f->nrec) {
+            f->err = who + " names a pattern, strand or record that does not exist";
+            return DEBWT_EINVAL;
+        }
+        const u64 m = offsets[jb.pattern + 1] - offsets[jb.pattern];
+        if (m < 1 || m > DEBWT_FM_WINDOW_MAX_QUERY) {
+            f->err = who + " has a pattern of " + std::to_string(m) + " bytes (1..4096)";
+            return DEBWT_EINVAL;
+        }
+        if (jb.wend < jb.wbeg || jb.wend - jb.wbeg > DEBWT_FM_WINDOW_MAX_COLUMNS) {
+            f->err = who + " has a window that ends before it begins or is wider than 16384";
+            return DEBWT_EINVAL;
+        }
+    }
+    HIPCHK(f, hipSetDevice(f->device));
+    rc = fm_window_run(f, patterns, offsets, jobs, njobs, *sc, trace, out, cig_n, cig);
+    if (rc) return rc;
+    f->x_stats.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+static_assert(DEBWT_FM_WINDOW_MAX_QUERY == FM_WIN_MAX_LEN && DEBWT_FM_WINDOW_MAX_COLUMNS == FM_WIN_MAX_COLS,
+              "the limits of the header are those of the kernel's key");
+
+extern "C" int debwt_fm_align_window(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                                     const debwt_fm_window_job *jobs, uint64_t njobs, const debwt_fm_scoring *sc,
+                                     debwt_fm_aln *out, uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity) {
+    if (!f || !sc || !offsets || (njobs && (!jobs || !out))) return DEBWT_EINVAL;
+    const bool trace = cigar_offsets != nullptr;
+    std::vector<u32> cig_n, cig;
+    const int rc = fm_window_call(f, patterns, offsets, npat, jobs, njobs, sc, trace, out, &cig_n, &cig);
+    if (rc) return rc;
+    if (!trace) return DEBWT_OK;
+    cigar_offsets[0] = 0;
+    for (u64 j = 0; j < njobs; j++) cigar_offsets[j + 1] = cigar_offsets[j] + cig_n[j];
+    if (capacity < cig.size() || (!cig.empty() && !cigar)) {
+        f->err = "debwt_fm_align_window: capacity below the CIGAR ops (cigar_offsets[njobs] = " + std::to_string(cig.size()) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (!cig.empty()) memcpy(cigar, cig.data(), cig.size() * 4);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_insert_bounds(const uint64_t *tlen, uint64_t n, uint32_t *lo, uint32_t *hi) {
+    if (!tlen || !lo || !hi || n < DEBWT_FM_INSERT_MIN_PAIRS) return DEBWT_EINVAL;
+    std::vector<u64> s(tlen, tlen + n);
+    std::sort(s.begin(), s.end());
+    const __int128 q1 = s[n / 4], q3 = s[3 * n / 4], d = q3 - q1;
+    const __int128 l = std::max<__int128>(1, q1 - 3 * d), h = std::min<__int128>(DEBWT_FM_INSERT_MAX, q3 + 3 * d);
+    *lo = (uint32_t)std::min<__int128>(l, 0xFFFFFFFFu);
+    *hi = (uint32_t)h;
+    return DEBWT_OK;
+}
+
+namespace {
+
+bool fm_pair_disjoint(const debwt_fm_pcand &a, const debwt_fm_pcand &b) { return a.tend <= b.tbeg || a.tbeg >= b.tend; }
+
+// a proper pair by the header's rule; T and the forward mate's tbeg for the caller
+bool fm_pair_proper(const debwt_fm_pcand &a, const debwt_fm_pcand &b, int32_t thr, u32 lo, u32 hi, u64 *T, u64 *tbf) {
+    if (a.score < thr || b.score < thr || a.record != b.record || a.strand > 1 || b.strand > 1 || a.strand == b.strand)
+        return false;
+    const debwt_fm_pcand &fw = a.strand ? b : a, &rv = a.strand ? a : b;
+    if (fw.tbeg > rv.tbeg || fw.tend > rv.tend) return false;
+    *T = rv.tend - fw.tbeg; *tbf = fw.tbeg;
+    return *T >= lo && *T <= hi;
+}
+
+// b(x): the eligible candidate of largest score, ties by smaller (strand, record, tbeg), then by smaller index
+int32_t fm_pair_single(const debwt_fm_pcand *c, u32 n, int32_t thr) {
+    int32_t b = -1;
+    for (u32 i = 0; i < n; i++) {
+        if (c[i].score < thr) continue;
+        if (b < 0 || c[i].score > c[b].score ||
+            (c[i].score == c[b].score && std::make_tuple(c[i].strand, c[i].record, c[i].tbeg) <
+                                             std::make_tuple(c[b].strand, c[b].record, c[b].tbeg)))
+            b = (int32_t)i;
+    }
+    return b;
+}
+
+int32_t fm_pair_sub(const debwt_fm_pcand *c, u32 n, int32_t w) {
+    int32_t sub = 0;
+    if (w < 0) return 0;
+    for (u32 k = 0; k < n; k++)
+        if ((int32_t)k != w && c[k].score > sub && fm_pair_disjoint(c[k], c[w])) sub = c[k].score;
+    return sub;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_pair_select(const debwt_fm_pcand *c1, uint32_t n1, const debwt_fm_pcand *c2, uint32_t n2,
+                                    uint32_t ins_lo, uint32_t ins_hi, int32_t unpaired_penalty, int32_t min_score,
+                                    debwt_fm_pair_choice *out) {
+    if (!out || (n1 && !c1) || (n2 && !c2) || ins_lo > ins_hi || n1 > 0x7FFFFFFFu || n2 > 0x7FFFFFFFu) return DEBWT_EINVAL;
+    for (u32 i = 0; i < n1; i++) if (c1[i].score > 0 && c1[i].tend <= c1[i].tbeg) return DEBWT_EINVAL;
+    for (u32 j = 0; j < n2; j++) if (c2[j].score > 0 && c2[j].tend <= c2[j].tbeg) return DEBWT_EINVAL;
+    const int32_t thr = std::max<int32_t>(1, min_score);
+    const int32_t b1 = fm_pair_single(c1, n1, thr), b2 = fm_pair_single(c2, n2, thr);
+    int32_t pi = -1, pj = -1;
+    int64_t P = 0;
+    u64 pT = 0, ptb = 0;
+    for (u32 i = 0; i < n1; i++)
+        for (u32 j = 0; j < n2; j++) {
+            u64 T, tb;
+            if (!fm_pair_proper(c1[i], c2[j], thr, ins_lo, ins_hi, &T, &tb)) continue;
+            const int64_t p = (int64_t)c1[i].score + c2[j].score;
+            if (pi < 0 || p > P || (p == P && std::make_tuple(c1[i].record, tb) < std::make_tuple(c1[pi].record, ptb))) {
+                pi = (int32_t)i; pj = (int32_t)j; P = p; pT = T; ptb = tb;
+            }
+        }
+    debwt_fm_pair_choice ch{};
+    const bool proper = pi >= 0 && P >= (int64_t)c1[b1].score + c2[b2].score - unpaired_penalty;
+    ch.i1 = proper ? pi : b1; ch.i2 = proper ? pj : b2;
+    ch.proper = proper ? 1u : 0u;
+    ch.sub1 = fm_pair_sub(c1, n1, ch.i1); ch.sub2 = fm_pair_sub(c2, n2, ch.i2);
+    int64_t q1 = 0, q2 = 0;
+    if (ch.i1 >= 0) q1 = 60 * (int64_t)(c1[ch.i1].score - ch.sub1) / c1[ch.i1].score;
+    if (ch.i2 >= 0) q2 = 60 * (int64_t)(c2[ch.i2].score - ch.sub2) / c2[ch.i2].score;
+    if (proper) {
+        int64_t psub = 0;
+        for (u32 i = 0; i < n1; i++)
+            for (u32 j = 0; j < n2; j++) {
+                u64 T, tb;
+                if (!fm_pair_proper(c1[i], c2[j], thr, ins_lo, ins_hi, &T, &tb)) continue;
+                if (!fm_pair_disjoint(c1[i], c1[pi]) && !fm_pair_disjoint(c2[j], c2[pj])) continue;
+                psub = std::max<int64_t>(psub, (int64_t)c1[i].score + c2[j].score);
+            }
+        ch.tlen = (int64_t)pT; ch.pair_score = (int32_t)P; ch.pair_sub = (int32_t)psub;
+        const int64_t qp = 60 * (P - psub) / P;
+        q1 = std::max(q1, qp); q2 = std::max(q2, qp);
+    }
+    ch.mapq1 = (u32)std::max<int64_t>(q1, 0); ch.mapq2 = (u32)std::max<int64_t>(q2, 0);
+    *out = ch;
+    return DEBWT_OK;
+}
+
+namespace {
+
+struct FmPairCand {
+    debwt_fm_aln a;
+    int64_t diag;
+    u32 record, strand, rescued, cig_n;
+    u64 cig_first;           // in the pool of CIGAR ops
+};
+
+// The stages of debwt_fm_map that the pair mapper shares with it -- MEMs, locate, cluster, extend -- over all reads, from
+// the same public pieces; every job's alignment is kept: those of read r are cands[first[r] .. first[r + 1]).
+int fm_pair_candidates(debwt_fm *f, const char *patterns, const uint64_t *offsets, u64 npat, const debwt_fm_map_opts &o,
+                       std::vector<FmPairCand> &cands, std::vector<u64> &first, std::vector<u32> &pool) {
+    std::vector<uint64_t> moff, ranges, loff, pos;
+    std::vector<u32> spans, cig_n, cig;
+    std::vector<u8> strands;
+    std::vector<debwt_fm_seed> seeds;
+    std::vector<debwt_fm_cand> cand(o.max_cand);
+    std::vector<debwt_fm_job> jobs;
+    std::vector<debwt_fm_aln> aln;
+    cands.clear(); pool.clear();
+    first.assign(npat + 1, 0);
+    int rc;
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 p1 = p0 + 1;
+        while (p1 < npat && p1 - p0 < (1ull << 18) && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS) p1++;
+        const u64 np = p1 - p0;
+        moff.assign(np + 1, 0);
+        u64 cap = std::max<u64>(spans.size() / 2, 4 * np + 16);
+        for (;;) {
+            spans.resize(2 * cap); ranges.resize(2 * cap); strands.resize(cap);
+            rc = debwt_fm_mems(f, patterns, offsets + p0, np, o.min_len, DEBWT_FM_BOTH_STRANDS, moff.data(), spans.data(),
+                               ranges.data(), strands.data(), cap);
+            if (rc == DEBWT_ERANGE && moff[np] > cap) { cap = moff[np]; continue; }
+            if (rc) return rc;
+            break;
+        }
+        const u64 nmem = moff[np];
+        loff.assign(nmem + 1, 0);
+        u64 nocc = 0;
+        for (u64 i = 0; i < nmem; i++) nocc += std::min<u64>(ranges[2 * i + 1] - ranges[2 * i], o.max_occ);
+        pos.resize(std::max<u64>(nocc, 1));
+        rc = debwt_fm_locate(f, ranges.data(), nmem, o.max_occ, loff.data(), pos.data(), pos.size());
+        if (rc) return rc;
+        jobs.clear();
+        std::vector<u64> job_first(np + 1, 0);
+        for (u64 r = 0; r < np; r++) {
+            job_first[r] = jobs.size();
+            const u64 m = offsets[p0 + r + 1] - offsets[p0 + r];
+            if (m < 1 || m > FM_EXT_MAX_LEN) continue;
+            seeds.clear();
+            for (u64 i = moff[r]; i < moff[r + 1]; i++) {
+                const u32 qb = strands[i] ? (u32)m - spans[2 * i + 1] : spans[2 * i];      // in Q
+                const u32 qe = strands[i] ? (u32)m - spans[2 * i] : spans[2 * i + 1];
+                for (u64 x = loff[i]; x < loff[i + 1]; x++) {
+                    const u64 tp = pos[x];
+                    const u64 rec = (u64)(std::upper_bound(f->rec_starts.begin(), f->rec_starts.end(), tp) - f->rec_starts.begin()) - 1;
+                    seeds.push_back(debwt_fm_seed{(int64_t)tp - (int64_t)qb, (u32)rec, strands[i], qb, qe});
+                }
+            }
+            if (seeds.empty()) continue;
+            const int nc = debwt_fm_cluster_seeds(seeds.data(), seeds.size(), o.band, o.max_cand, cand.data());
+            if (nc < 0) { f->err = "debwt_fm_map_pairs: a MEM with an empty span"; return DEBWT_EINTERNAL; }
+            for (int k = 0; k < nc; k++) jobs.push_back(debwt_fm_job{p0 + r, cand[k].diag, cand[k].record, cand[k].strand});
+        }
+        job_first[np] = jobs.size();
+        aln.resize(jobs.size());
+        HIPCHK(f, hipSetDevice(f->device));
+        rc = fm_extend_run(f, patterns, offsets, jobs.data(), jobs.size(), o.scoring, o.band, true, aln.data(), &cig_n, &cig);
+        if (rc) return rc;
+        u64 cf = pool.size();
+        pool.insert(pool.end(), cig.begin(), cig.end());
+        for (u64 r = 0; r < np; r++) {
+            first[p0 + r] = cands.size();
+            for (u64 j = job_first[r]; j < job_first[r + 1]; j++) {
+                cands.push_back(FmPairCand{aln[j], jobs[j].diag, jobs[j].record, jobs[j].strand, 0u, cig_n[j], cf});
+                cf += cig_n[j];
+            }
+        }
+        p0 = p1;
+    }
+    first[npat] = cands.size();
+    return DEBWT_OK;
+}
+
+debwt_fm_pcand fm_pair_pcand(const FmPairCand &c) {
+    return debwt_fm_pcand{c.a.score, c.record, c.strand, c.rescued, c.a.tbeg, c.a.tend};
+}
+
+}  // namespace
+
+extern "C" void debwt_fm_pair_defaults(debwt_fm_pair_opts *o) {
+    if (!o) return;
+    memset(o, 0, sizeof *o);
+    debwt_fm_map_defaults(&o->map);
+    o->max_rescue = 4; o->unpaired_penalty = 17;
+}
+
+extern "C" int debwt_fm_map_pairs(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npairs,
+                                  const debwt_fm_pair_opts *opts, debwt_fm_hit *hits, debwt_fm_pair_info *pairs,
+                                  uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity) {
+    if (!f || !offsets || !cigar_offsets || (npairs && (!hits || !pairs)) || npairs > (1ull << 62)) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    debwt_fm_pair_opts po;
+    debwt_fm_pair_defaults(&po);
+    if (opts) po = *opts;
+    const debwt_fm_map_opts &o = po.map;
+    const u64 npat = 2 * npairs;
+    f->pair_stats = debwt_fm_pair_stats{};
+    f->x_stats = debwt_fm_extend_stats{};
+    int rc = fm_ext_check(f, &o.scoring, o.band, "debwt_fm_map_pairs");
+    if (rc) return rc;
+    if (!o.min_len || !o.max_occ || !o.max_cand || o.max_cand > 4096 || o.flags) {
+        f->err = "debwt_fm_map_pairs: min_len, max_occ and max_cand must be positive (max_cand <= 4096), no flag set "
+                 "(pairs are mapped on both strands)";
+        return DEBWT_EINVAL;
+    }
+    if (po.ins_lo > po.ins_hi || po.ins_hi > DEBWT_FM_INSERT_MAX) {
+        f->err = "debwt_fm_map_pairs: insert bounds must be ascending and at most 16384";
+        return DEBWT_EINVAL;
+    }
+    for (u64 i = 0; i < npat; i++)
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_map_pairs: offsets must not decrease"; return DEBWT_EINVAL; }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    debwt_fm_pair_stats &ps = f->pair_stats;
+    ps.pairs = npairs;
+    const int32_t thr = std::max<int32_t>(1, o.min_score);
+
+    // 1. the candidates of every read
+    auto t = std::chrono::steady_clock::now();
+    std::vector<FmPairCand> base;
+    std::vector<u64> first;
+    std::vector<u32> pool;
+    rc = fm_pair_candidates(f, patterns, offsets, npat, o, base, first, pool);
+    if (rc) return rc;
+    std::vector<std::vector<debwt_fm_pcand>> pc(npat);     // what debwt_fm_pair_select reads, rescued ones appended
+    std::vector<std::vector<FmPairCand>> extra(npat);      // the rescued candidates of a read
+    for (u64 r = 0; r < npat; r++)
+        for (u64 k = first[r]; k < first[r + 1]; k++) pc[r].push_back(fm_pair_pcand(base[k]));
+    ps.ms_candidates = (float)fm_ms_since(t);
+
+    // 2. the insert bounds
+    u32 ins_lo = po.ins_lo, ins_hi = po.ins_hi;
+    if (!ins_lo && !ins_hi) {
+        std::vector<uint64_t> tl;
+        for (u64 p = 0; p < npairs; p++) {
+            const auto &a = pc[2 * p], &b = pc[2 * p + 1];
+            const int32_t b1 = fm_pair_single(a.data(), (u32)a.size(), thr), b2 = fm_pair_single(b.data(), (u32)b.size(), thr);
+            if (b1 < 0 || b2 < 0) continue;
+            const int32_t s1 = fm_pair_sub(a.data(), (u32)a.size(), b1), s2 = fm_pair_sub(b.data(), (u32)b.size(), b2);
+            if (60 * (int64_t)(a[b1].score - s1) / a[b1].score < 20 || 60 * (int64_t)(b[b2].score - s2) / b[b2].score < 20) continue;
+            u64 T, tb;
+            if (fm_pair_proper(a[b1], b[b2], thr, 0, DEBWT_FM_INSERT_MAX, &T, &tb)) tl.push_back(T);
+        }
+        ps.estimate_pairs = tl.size();
+        if (debwt_fm_insert_bounds(tl.data(), tl.size(), &ins_lo, &ins_hi)) {
+            f->err = "debwt_fm_map_pairs: only " + std::to_string(tl.size()) + " pairs map uniquely and face each other, " +
+                     std::to_string(DEBWT_FM_INSERT_MIN_PAIRS) + " are needed to estimate the insert size: give explicit insert bounds (ins_lo, ins_hi)";
+            return DEBWT_EINVAL;
+        }
+    }
+    ps.ins_lo = ins_lo; ps.ins_hi = ins_hi;
+
+    // 3. rescue: a window next to a candidate whose partner has no candidate that pairs with it
+    t = std::chrono::steady_clock::now();
+    if (po.max_rescue) {
+        std::vector<debwt_fm_window_job> wj;
+        std::vector<u32> ord;
+        for (u64 r = 0; r < npat; r++) {
+            const u64 y = r ^ 1ull, my = offsets[y + 1] - offsets[y];
+            if (my < 1 || my > DEBWT_FM_WINDOW_MAX_QUERY) continue;
+            const auto &cx = pc[r], &cy = pc[y];
+            ord.clear();
+            for (u32 k = 0; k < cx.size(); k++) if (cx[k].score >= thr) ord.push_back(k);
+            std::sort(ord.begin(), ord.end(), [&](u32 a, u32 b) {
+                if (cx[a].score != cx[b].score) return cx[a].score > cx[b].score;
+                return std::make_tuple(cx[a].strand, cx[a].record, cx[a].tbeg, a) < std::make_tuple(cx[b].strand, cx[b].record, cx[b].tbeg, b);
+            });
+            if (ord.size() > po.max_rescue) ord.resize(po.max_rescue);
+            const size_t w0 = wj.size();
+            for (u32 k : ord) {
+                const debwt_fm_pcand &c = cx[k];
+                bool paired = false;
+                for (const debwt_fm_pcand &d : cy) {
+                    u64 T, tb;
+                    if (fm_pair_proper(c, d, thr, ins_lo, ins_hi, &T, &tb)) { paired = true; break; }
+                }
+                if (paired) continue;
+                debwt_fm_window_job jb{y, c.record, 1u - c.strand, 0, 0};
+                if (c.strand == 0) { jb.wbeg = c.tbeg; jb.wend = c.tbeg + ins_hi; }
+                else { jb.wbeg = c.tend > ins_hi ? c.tend - ins_hi : 0; jb.wend = c.tend; }
+                bool dup = false;
+                for (size_t x = w0; x < wj.size() && !dup; x++)
+                    dup = wj[x].record == jb.record && wj[x].strand == jb.strand && wj[x].wbeg == jb.wbeg && wj[x].wend == jb.wend;
+                if (!dup) wj.push_back(jb);
+            }
+        }
+        ps.rescue_jobs = wj.size();
+        if (!wj.empty()) {
+            std::vector<debwt_fm_aln> wa(wj.size());
+            std::vector<u32> cig_n, cig;
+            rc = fm_window_call(f, patterns, offsets, npat, wj.data(), wj.size(), &o.scoring, true, wa.data(), &cig_n, &cig);
+            if (rc) return rc;
+            u64 cf = pool.size();
+            pool.insert(pool.end(), cig.begin(), cig.end());
+            for (size_t x = 0; x < wj.size(); cf += cig_n[x], x++) {
+                const debwt_fm_aln &a = wa[x];
+                if (a.score < thr) continue;
+                const u64 y = wj[x].pattern;
+                bool known = false;
+                for (const debwt_fm_pcand &d : pc[y])
+                    if (d.score > 0 && d.strand == wj[x].strand && d.tbeg == a.tbeg && d.tend == a.tend) { known = true; break; }
+                if (known) continue;
+                FmPairCand c{a, (int64_t)a.tbeg - (int64_t)a.qbeg, wj[x].record, wj[x].strand, 1u, cig_n[x], cf};
+                extra[y].push_back(c);
+                pc[y].push_back(fm_pair_pcand(c));
+            }
+        }
+    }
+    ps.ms_rescue = (float)fm_ms_since(t);
+
+    // 4. the choice of every pair
+    t = std::chrono::steady_clock::now();
+    std::vector<u32> all_cig;
+    cigar_offsets[0] = 0;
+    for (u64 p = 0; p < npairs; p++) {
+        debwt_fm_pair_choice ch;
+        rc = debwt_fm_pair_select(pc[2 * p].data(), (u32)pc[2 * p].size(), pc[2 * p + 1].data(), (u32)pc[2 * p + 1].size(),
+                                  ins_lo, ins_hi, po.unpaired_penalty, o.min_score, &ch);
+        if (rc) { f->err = "debwt_fm_map_pairs: a candidate with an empty text interval"; return DEBWT_EINTERNAL; }
+        pairs[p] = debwt_fm_pair_info{ch.tlen, ch.pair_score, ch.pair_sub, 0u};
+        ps.proper += ch.proper;
+        for (u32 x = 0; x < 2; x++) {
+            const u64 r = 2 * p + x, m = offsets[r + 1] - offsets[r];
+            const int32_t w = x ? ch.i2 : ch.i1;
+            debwt_fm_hit &h = hits[r];
+            memset(&h, 0, sizeof h);
+            h.pattern = r;
+            h.flags = DEBWT_FM_MAP_UNMAPPED | (m > FM_EXT_MAX_LEN ? DEBWT_FM_MAP_TOO_LONG : 0u);
+            cigar_offsets[r + 1] = cigar_offsets[r];
+            if (w < 0) continue;
+            const u64 nbase = first[r + 1] - first[r];
+            const FmPairCand &c = (u64)w < nbase ? base[first[r] + w] : extra[r][w - nbase];
+            const debwt_fm_aln &a = c.a;
+            h.flags = (c.strand ? DEBWT_FM_MAP_REVERSE : 0u) | (ch.proper ? DEBWT_FM_MAP_PROPER : 0u) |
+                      (c.rescued ? DEBWT_FM_MAP_RESCUED : 0u);
+            h.record = c.record; h.offset = a.tbeg - f->rec_starts[c.record];
+            h.qbeg = a.qbeg; h.qend = a.qend; h.tbeg = a.tbeg; h.tend = a.tend;
+            h.score = a.score; h.sub = x ? ch.sub2 : ch.sub1; h.mapq = x ? ch.mapq2 : ch.mapq1; h.edits = a.edits;
+            h.diag = c.diag;
+            all_cig.insert(all_cig.end(), pool.begin() + c.cig_first, pool.begin() + c.cig_first + c.cig_n);
+            cigar_offsets[r + 1] = all_cig.size();
+            ps.rescued += c.rescued;
+        }
+    }
+    ps.ms_select = (float)fm_ms_since(t);
+    ps.ms_wall = (float)fm_ms_since(t0);
+    if (capacity < all_cig.size() || (!all_cig.empty() && !cigar)) {
+        f->err = "debwt_fm_map_pairs: capacity below the CIGAR ops (cigar_offsets[2 npairs] = " + std::to_string(all_cig.size()) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (!all_cig.empty()) memcpy(cigar, all_cig.data(), all_cig.size() * 4);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_pair_stats_get(const debwt_fm *f, debwt_fm_pair_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->pair_stats;
     return DEBWT_OK;
 }
 

@@ -749,6 +749,120 @@ int debwt_fm_map_chained(debwt_fm *fm, const char *patterns, const uint64_t *off
                          const debwt_fm_chain_opts *opts, debwt_fm_hit *hits,
                          uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity,
                          uint64_t *anchor_offsets, debwt_fm_anchor *hit_anchors, uint64_t anchor_capacity);
+
+/* ---- paired-end reads: alignment against a text window, insert bounds, pair selection, the pair mapper
+ * (fm_window_kernels.h) ----------------------------------------------------------------------------------------------
+ * Affine-gap local alignment of jobs against text windows.  Everything is as debwt_fm_extend documents it -- Q and the
+ * strand handling, the recurrence for E, F, H and the score, the scoring limits, out[] and the BAM-coded CIGAR, the
+ * DEBWT_ERANGE protocol and the score-only mode with cigar_offsets NULL, the rule for the end cell (largest H, then the
+ * smallest query index, then the smallest text position), the traceback tie rule and the independence from batching --
+ * except the set of allowed cells.  With [rs, re) the bases of `record`, cell (i, t) is allowed iff 0 <= i < m and
+ * max(rs, wbeg) <= t < min(re, wend), wbeg and wend being global text positions.  There is no band.  A window that misses
+ * the record gives score 0 (empty CIGAR, coordinates 0); it is not an error.
+ * DEBWT_EINVAL: m outside 1..DEBWT_FM_WINDOW_MAX_QUERY, wend < wbeg, wend - wbeg > DEBWT_FM_WINDOW_MAX_COLUMNS, pattern >=
+ * npat, strand > 1, record >= nrec, a scoring value out of range.  DEBWT_ESTATE without an attached text.
+ * Device scratch with a traceback: 64 flag bytes per step of the job's wave; a window of L columns has ceil(L / 64)
+ * strips and a strip of c columns m + c - 1 steps, so a job takes at most 64 x ceil(L / 64) x (m + 63) bytes.  Batches
+ * are cut at DEBWT_FM_EXTEND_BYTES of it, as in debwt_fm_extend; a job above that goes alone.
+ * debwt_fm_extend_stats_get reports the last window pass too; a wave step is then one anti-diagonal of one strip of 64
+ * columns, so cells / (64 x wave_steps) is the share of busy lanes. */
+#define DEBWT_FM_WINDOW_MAX_QUERY   4096u    /* longest query of a window job */
+#define DEBWT_FM_WINDOW_MAX_COLUMNS 16384u   /* widest window, wend - wbeg */
+typedef struct {
+    uint64_t pattern;
+    uint32_t record, strand;
+    uint64_t wbeg, wend;
+} debwt_fm_window_job;
+int debwt_fm_align_window(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                          const debwt_fm_window_job *jobs, uint64_t njobs, const debwt_fm_scoring *scoring,
+                          debwt_fm_aln *out, uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity);
+
+/* Insert-size bounds from observed template lengths (host only, no GPU).  On a sorted copy s of tlen[0 .. n):
+ * q1 = s[n / 4], q3 = s[3 n / 4], d = q3 - q1; *lo = max(1, q1 - 3 d) in signed arithmetic, *hi = min(16384, q3 + 3 d).
+ * DEBWT_EINVAL for n < DEBWT_FM_INSERT_MIN_PAIRS.  The quartile rule and the 32 are common practice, not measurements. */
+#define DEBWT_FM_INSERT_MIN_PAIRS 32u
+#define DEBWT_FM_INSERT_MAX       16384u
+int debwt_fm_insert_bounds(const uint64_t *tlen, uint64_t n, uint32_t *lo, uint32_t *hi);
+
+/* The choice of one pair from the candidate alignments of its two mates (host only, no GPU).  c1[0 .. n1), c2[0 .. n2):
+ * score, record, strand and the global text interval [tbeg, tend) of each candidate; flags are not read.
+ * Eligible.    A candidate is eligible when score >= max(1, min_score).
+ * Single best. b(x) is mate x's eligible candidate of largest score, ties by smaller (strand, record, tbeg), then by
+ *              smaller index; -1 when there is none.
+ * Proper pair. (i, j) is a proper pair when both are eligible, the record is the same, the strands differ, and, with f
+ *              the strand-0 one and r the strand-1 one, tbeg_f <= tbeg_r, tend_f <= tend_r and
+ *              ins_lo <= T = tend_r - tbeg_f <= ins_hi.
+ * Pair score.  P = score_i + score_j.  The best proper pair is the one with the largest P, ties by smaller
+ *              (record, tbeg_f, i, j).
+ * Choice.      The best proper pair is chosen iff one exists and P >= score(b1) + score(b2) - unpaired_penalty.  Then
+ *              i1 = i, i2 = j, proper = 1, tlen = T and pair_score = P.
+ * Otherwise.   i1 = b1, i2 = b2, proper = 0 and tlen = pair_score = pair_sub = 0.
+ * pair_sub.    The largest P' of a proper pair (i', j') whose i' interval does not intersect the chosen i1's, or whose
+ *              j' interval does not intersect the chosen i2's; 0 when there is none.
+ * sub_x.       The largest score > 0 of another candidate of mate x, eligible or not, whose interval does not intersect
+ *              the chosen one's (the rule of debwt_fm_map); 0 when there is none or mate x has no choice.
+ * mapq_x.      single_x = 60 (s - sub_x) / s in integers, s the chosen score (0 without a choice).  For a proper pair
+ *              mapq_x = max(single_x, 60 (P - pair_sub) / P).
+ * DEBWT_EINVAL for ins_lo > ins_hi or a candidate with tend <= tbeg and score > 0. */
+typedef struct {
+    int32_t score;
+    uint32_t record, strand, flags;
+    uint64_t tbeg, tend;
+} debwt_fm_pcand;
+typedef struct {
+    int32_t i1, i2;
+    uint32_t proper, mapq1, mapq2;
+    int32_t sub1, sub2, pair_score, pair_sub;
+    int64_t tlen;
+} debwt_fm_pair_choice;
+int debwt_fm_pair_select(const debwt_fm_pcand *c1, uint32_t n1, const debwt_fm_pcand *c2, uint32_t n2,
+                         uint32_t ins_lo, uint32_t ins_hi, int32_t unpaired_penalty, int32_t min_score,
+                         debwt_fm_pair_choice *out);
+
+/* Paired-end reads to alignments.  Patterns 2p and 2p + 1 are the mates of pair p; hits and cigar_offsets have 2 npairs
+ * (+ 1) entries with the meanings debwt_fm_map gives them.  DEBWT_FM_MAP_FORWARD in map.flags is DEBWT_EINVAL.
+ * 1. Candidates.  The stages MEMs, locate, cluster, extend of debwt_fm_map over all reads, keeping every job's alignment
+ *    and CIGAR.  All batches finish before stage 2, so no result depends on the internal batching.
+ * 2. Insert bounds.  With ins_lo = ins_hi = 0 they are estimated: the pairs whose two single bests have a single mapq >=
+ *    20, share a record, have opposite strands and the forward-before-reverse geometry of debwt_fm_pair_select with
+ *    T <= 16384 give their T, in pair order, to debwt_fm_insert_bounds.  Fewer than 32 such pairs: DEBWT_EINVAL, and
+ *    debwt_fm_last_error asks for explicit bounds.
+ * 3. Rescue (skipped for max_rescue = 0).  For each mate x and each of its max_rescue best eligible candidates c, in
+ *    the single-best order: when the other mate y has no eligible candidate that forms a proper pair with c, and y has at
+ *    most DEBWT_FM_WINDOW_MAX_QUERY bases, one window job aligns y on strand 1 - strand(c) in record(c), in the window
+ *    [tbeg_c, tbeg_c + ins_hi) for strand(c) = 0, else [max(0, tend_c - ins_hi), tend_c).  Identical jobs are issued
+ *    once; all jobs of the call go through debwt_fm_align_window with tracebacks.  A result with score >= min_score that
+ *    is not identical (strand, tbeg, tend) to an existing candidate of y joins y's candidates, marked rescued.
+ * 4. Selection.  debwt_fm_pair_select per pair; the hits are filled as debwt_fm_map fills them, sub and mapq being the
+ *    choice's.  A rescued winner has diag = tbeg - qbeg and DEBWT_FM_MAP_RESCUED; DEBWT_FM_MAP_PROPER is set on both
+ *    mates of a proper pair.  A mate without a choice is unmapped, under the rules of debwt_fm_map.
+ * pairs[p]: tlen (T of a proper pair, else 0), pair_score and pair_sub of the choice. */
+#define DEBWT_FM_MAP_PROPER  8u    /* hit flag */
+#define DEBWT_FM_MAP_RESCUED 16u   /* hit flag */
+typedef struct {
+    debwt_fm_map_opts map;
+    uint32_t ins_lo, ins_hi;      /* 0, 0: estimated from the reads */
+    uint32_t max_rescue;          /* candidates of a mate that may start a rescue of its partner (4) */
+    int32_t unpaired_penalty;     /* 17, BWA-MEM's */
+} debwt_fm_pair_opts;
+typedef struct {
+    int64_t tlen;
+    int32_t pair_score, pair_sub;
+    uint32_t reserved;
+} debwt_fm_pair_info;
+void debwt_fm_pair_defaults(debwt_fm_pair_opts *o);
+/* opts NULL: the defaults */
+int debwt_fm_map_pairs(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npairs,
+                       const debwt_fm_pair_opts *opts, debwt_fm_hit *hits, debwt_fm_pair_info *pairs,
+                       uint64_t *cigar_offsets, uint32_t *cigar, uint64_t capacity);
+/* the last debwt_fm_map_pairs: pairs, proper pairs, window jobs of the rescue, rescued alignments that won, the insert
+ * bounds used, the pairs the estimate used (0 with explicit bounds), and host wall milliseconds of the candidates,
+ * the rescue, the selection and the whole call */
+typedef struct {
+    uint64_t pairs, proper, rescue_jobs, rescued, ins_lo, ins_hi, estimate_pairs;
+    float ms_candidates, ms_rescue, ms_select, ms_wall;
+} debwt_fm_pair_stats;
+int debwt_fm_pair_stats_get(const debwt_fm *fm, debwt_fm_pair_stats *out);
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
