@@ -6,6 +6,7 @@
  *   deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq
+ *   deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self] READS.fa|.fq
  *   deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]
  *                      [--max-occ N] [--min-score S] [--chain [--max-gap G]]
  *                      [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq
@@ -27,6 +28,14 @@
  * with --both-strands those of its reverse complement: one line per MEM, name, strand (+ or -), qbeg, qend (0-based, end
  * exclusive, in the read's own coordinates on both strands), occurrences and record:offset ascending.  --max-hits M lists
  * the first M occurrences in suffix order (the count column stays the full count).  Reads without MEMs print nothing.
+ *
+ * overlaps prints the suffix-prefix overlaps of every read with the records of OUT (debwt_fm_overlaps): one line per
+ * (record, length) of at least L bases (default 20) such that the record begins with the read's last `length` bases --
+ * name, strand (+ or -), record, length and flags: C when the whole record is the overlap, W when the whole read is, CW,
+ * or "." -- ordered by (strand, length descending, record).  --both-strands adds the overlaps of the read's reverse
+ * complement (strand -: the record begins with the reverse complement of the read's first `length` bases); --longest
+ * keeps the longest overlap per read, strand and record; --no-self, for querying the indexed file itself, drops read
+ * number i's overlap with record i over its whole length.  It needs OUT, OUT.#, OUT.$ and OUT.sa only.
  *
  * map aligns every read (debwt_fm_map: MEM seeds of at least L bases, at most N occurrences of each, clustered by diagonal,
  * banded affine-gap extension with half-width W, 0..63; a plain heuristic, not BWA-MEM's).  The index holds no text, so
@@ -66,6 +75,7 @@ static void usage(void) {
             "       deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq\n"
+            "       deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self] READS.fa|.fq\n"
             "       deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]\n"
             "                          [--max-occ N] [--min-score S] [--chain [--max-gap G]]\n"
             "                          [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq\n"
@@ -75,6 +85,9 @@ static void usage(void) {
             "name<TAB>total<TAB>record:offset:strand:mismatches,... (locate);\n"
             "mems prints name<TAB>strand<TAB>qbeg<TAB>qend<TAB>count<TAB>record:offset,... per maximal exact match of at\n"
             "least L bases (default 19);\n"
+            "overlaps prints name<TAB>strand<TAB>record<TAB>length<TAB>flags per record that begins with the last `length`\n"
+            "(at least L, default 20) bases of the read; flags C (the whole record), W (the whole read), CW or .; --longest\n"
+            "keeps the longest overlap per read, strand and record, --no-self drops read i's whole-length overlap with record i;\n"
             "map prints one PAF line per mapped read (AS:i: score, NM:i: edits, cg:Z: CIGAR); --ref is the FASTA that OUT\n"
             "is the BWT of; --chain chains the seeds of a read across diagonals and aligns along the chain (stretches of\n"
             "at most G bases between two seeds, default 5000); --mate maps paired ends, read i of READS2 being the mate of\n"
@@ -504,6 +517,42 @@ done:
     return ret;
 }
 
+static int cmd_overlaps(const char *out, const char *pfile, int device, uint32_t min_overlap, uint32_t flags, int no_self) {
+    struct patterns P;
+    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    int ret = 1, rc;
+    uint64_t cap = 4 * P.n + 16, *hoff = malloc((P.n + 1) * 8);
+    debwt_fm_overlap *hits = NULL;
+    if (!hoff) { fprintf(stderr, "out of memory\n"); goto done; }
+    for (;;) {                                            /* grow to the exact hit count on DEBWT_ERANGE */
+        free(hits);
+        hits = malloc(cap * sizeof *hits);
+        if (!hits) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_overlaps(fm, P.seq, P.off, P.n, min_overlap, flags, hoff, hits, cap);
+        if (rc == DEBWT_ERANGE && hoff[P.n] > cap) { cap = hoff[P.n]; continue; }
+        break;
+    }
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    for (uint64_t i = 0; i < P.n; i++) {
+        const uint64_t m = P.off[i + 1] - P.off[i];
+        for (uint64_t h = hoff[i]; h < hoff[i + 1]; h++) {
+            const debwt_fm_overlap *o = hits + h;
+            if (no_self && !o->strand && o->record == i && o->length == m) continue;
+            printf("%s\t%c\t%u\t%u\t%s\n", P.name[i], o->strand ? '-' : '+', o->record, o->length,
+                   (o->flags & 3u) == 3u ? "CW" : (o->flags & DEBWT_FM_OVERLAP_CONTAINS) ? "C" :
+                   (o->flags & DEBWT_FM_OVERLAP_WHOLE) ? "W" : ".");
+        }
+    }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(hoff); free(hits);
+    debwt_fm_destroy(fm);
+    free_patterns(&P);
+    return ret;
+}
+
 /* ---- map ------------------------------------------------------------------------------------------------------------- */
 
 /* the PAF columns and the tags AS, NM, cg of a mapped read, without the line's end */
@@ -672,10 +721,10 @@ int main(int argc, char **argv) {
     if (argc < 2) { usage(); return 1; }
     const char *cmd = argv[1];
     int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 :
-               !strcmp(cmd, "map") ? 4 : -1;
+               !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : -1;
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
-    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, v64 = 0;
+    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, min_overlap = 20, v64 = 0;
     debwt_fm_map_opts mo;
     debwt_fm_map_defaults(&mo);
     debwt_fm_chain_opts co;
@@ -683,7 +732,7 @@ int main(int argc, char **argv) {
     debwt_fm_pair_opts po;
     debwt_fm_pair_defaults(&po);
     const char *mate = NULL;
-    int iupac = 0, search = 0, chain = 0, gap_given = 0, insert_given = 0, no_rescue = 0;
+    int iupac = 0, search = 0, chain = 0, gap_given = 0, insert_given = 0, no_rescue = 0, no_self = 0;
     uint32_t flags = 0;
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
@@ -692,8 +741,10 @@ int main(int argc, char **argv) {
             file = a;
             continue;
         }
-        if (mode >= 1 && mode <= 3 && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
+        if (((mode >= 1 && mode <= 3) || mode == 5) && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
         if ((mode == 1 || mode == 2) && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
+        if (mode == 5 && !strcmp(a, "--longest")) { flags |= DEBWT_FM_OVERLAP_LONGEST; continue; }
+        if (mode == 5 && !strcmp(a, "--no-self")) { no_self = 1; continue; }
         if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mode == 4 && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
         if (mode != 4 && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
@@ -749,6 +800,9 @@ int main(int argc, char **argv) {
         else if ((mode == 3 || mode == 4) && !strcmp(a, "--min-len")) {
             if (parse_u64(v, &min_len) || min_len < 1 || min_len > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
         }
+        else if (mode == 5 && !strcmp(a, "--min-overlap")) {
+            if (parse_u64(v, &min_overlap) || min_overlap < 1 || min_overlap > 0xFFFFFFFFull) { fprintf(stderr, "--min-overlap: a length of at least 1\n"); return 1; }
+        }
         else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
@@ -768,6 +822,7 @@ int main(int argc, char **argv) {
         return cmd_map(out, ref, file, threads, iupac, seed, (int)device, &mo, chain, co.max_gap);
     }
     if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
+    if (mode == 5) return cmd_overlaps(out, file, (int)device, (uint32_t)min_overlap, flags, no_self);
     if (mode == 3) return cmd_mems(out, file, (int)device, max_hits, (uint32_t)min_len, flags);
     if (search) return cmd_search(out, file, (int)device, mode == 2, max_hits, (uint32_t)K, flags);
     return cmd_query(out, file, (int)device, mode == 2, max_hits);

@@ -84,6 +84,19 @@ class DebwtFmMemsStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmOverlapsStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("patterns", "batches", "launches", "runs", "hits", "steps", "line_reads",
+                                                 "wave_steps", "scratch_bytes")] +
+                [("ms_kernel", ctypes.c_float), ("ms_wall", ctypes.c_float)])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DebwtFmOverlap(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("record", "length", "strand", "flags")]
+
+
 class DebwtFmJob(ctypes.Structure):
     _fields_ = [("pattern", ctypes.c_uint64), ("diag", ctypes.c_int64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32)]
 
@@ -222,6 +235,7 @@ SYMBOLS = [
     "debwt_fm_chain_seeds", "debwt_fm_extend_chain", "debwt_fm_chain_defaults", "debwt_fm_map_chained",
     "debwt_fm_align_window", "debwt_fm_insert_bounds", "debwt_fm_pair_select", "debwt_fm_pair_defaults",
     "debwt_fm_map_pairs", "debwt_fm_pair_stats_get",
+    "debwt_fm_overlaps", "debwt_fm_overlaps_stats_get", "debwt_fm_overlap_longest",
 ]
 
 
@@ -424,6 +438,13 @@ def lib():
                                 ctypes.POINTER(ctypes.c_uint32), u64p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint64]
     L.debwt_fm_mems_stats_get.restype = ctypes.c_int
     L.debwt_fm_mems_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmMemsStats)]
+    L.debwt_fm_overlaps.restype = ctypes.c_int
+    L.debwt_fm_overlaps.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p,
+                                    ctypes.POINTER(DebwtFmOverlap), ctypes.c_uint64]
+    L.debwt_fm_overlaps_stats_get.restype = ctypes.c_int
+    L.debwt_fm_overlaps_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmOverlapsStats)]
+    L.debwt_fm_overlap_longest.restype = ctypes.c_int
+    L.debwt_fm_overlap_longest.argtypes = [ctypes.POINTER(DebwtFmOverlap), u64p, ctypes.c_uint64, u64p]
     L.debwt_fm_attach_text.restype = ctypes.c_int
     L.debwt_fm_attach_text.argtypes = [vp, vp, u64p, u64p]
     L.debwt_fm_extend.restype = ctypes.c_int

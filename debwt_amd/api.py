@@ -413,6 +413,37 @@ class FMIndex:
         self._chk(self._L.debwt_fm_mems_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def overlaps(self, patterns, min_overlap=20, strands="forward", longest=False):
+        """Suffix-prefix overlaps (debwt_fm_overlaps): for each pattern every (record, length) with length >= min_overlap
+        whose record begins with the pattern's last `length` bases, the pattern's own record and containments included.
+        strands "both" adds the overlaps of the reverse complement (strand 1: the record begins with the reverse
+        complement of the pattern's FIRST `length` bases).  longest: per (pattern, strand, record) only the largest
+        length.  No attached text is needed.  Returns an OverlapResult."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        flags = (SEARCH_BOTH_STRANDS if strands == "both" else 0) | (OVERLAP_LONGEST if longest else 0)
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        hoff = np.zeros(npat + 1, dtype=np.uint64)
+        cap = 4 * npat + 16                                   # first estimate; grown to the exact count on DEBWT_ERANGE
+        while True:
+            hits = np.zeros(cap, dtype=_OVERLAP_DTYPE)
+            rc = self._L.debwt_fm_overlaps(self._h, buf, _p64(offs), npat, int(min_overlap), flags, _p64(hoff),
+                                           hits.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmOverlap)), cap)
+            if rc == -5 and int(hoff[npat]) > cap:
+                cap = int(hoff[npat])
+                continue
+            self._chk(rc)
+            break
+        return OverlapResult(self, hoff, hits[:int(hoff[npat])].copy())
+
+    def overlaps_stats(self):
+        """What the last overlaps call did (debwt_fm_overlaps_stats_get): batches, runs, hits, rank steps and lines, wave
+        steps, scratch bytes, ms."""
+        st = _lib.DebwtFmOverlapsStats()
+        self._chk(self._L.debwt_fm_overlaps_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def attach_text(self, source=None, words=None, sep=None):
         """Give the index its text (debwt_fm_attach_text; n / 4 bytes of HBM), which extend() and map() read.  source: the
         DeBWT context the index was made from (device-to-device copy), or None with the host text words / sep as
@@ -701,6 +732,9 @@ SEARCH_BOTH_STRANDS, SEARCH_BEST_ONLY = 1, 2
 MAP_REVERSE, MAP_UNMAPPED, MAP_TOO_LONG = 1, 2, 4      # MapResult.flags
 MAP_PROPER, MAP_RESCUED = 8, 16                        # MapResult.flags of FMIndex.map_pairs
 MAP_FORWARD = 1                                        # option flag of debwt_fm_map
+OVERLAP_LONGEST = 2                                    # option flag of debwt_fm_overlaps
+OVERLAP_CONTAINS, OVERLAP_WHOLE = 1, 2                 # OverlapResult hit flags
+_OVERLAP_DTYPE = np.dtype([("record", np.uint32), ("length", np.uint32), ("strand", np.uint32), ("flags", np.uint32)])
 _ALN_DTYPE = np.dtype([("score", np.int32), ("qbeg", np.uint32), ("qend", np.uint32), ("edits", np.uint32),
                        ("tbeg", np.uint64), ("tend", np.uint64)])
 _HIT_DTYPE = np.dtype([("pattern", np.uint64), ("flags", np.uint32), ("record", np.uint32), ("offset", np.uint64),
@@ -730,6 +764,23 @@ def cluster_seeds(seeds, band=16, max_cand=8):
     if rc < 0:
         raise DebwtError(rc)
     return [{n: int(getattr(out[k], n)) for n, _ in _lib.DebwtFmCand._fields_} for k in range(rc)]
+
+
+def overlap_longest(hits, offsets):
+    """The reduction of overlaps(longest=True) on the host (debwt_fm_overlap_longest, no GPU): hits (structured array of
+    record, length, strand, flags) in the order of OverlapResult, pattern i's in offsets[i] .. offsets[i + 1]; per
+    (pattern, strand, record) the longest stays.  Returns (hits, offsets) of the reduced list; input that is not in that
+    order raises DebwtError (DEBWT_EINVAL)."""
+    h = np.array(hits, dtype=_OVERLAP_DTYPE, copy=True)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    if len(offs) < 1 or int(offs[-1]) > len(h):
+        raise ValueError("offsets do not fit the hits")
+    out = np.zeros(len(offs), dtype=np.uint64)
+    rc = _lib.lib().debwt_fm_overlap_longest(h.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmOverlap)), _p64(offs), len(offs) - 1,
+                                             _p64(out))
+    if rc:
+        raise DebwtError(rc)
+    return h[int(out[0]):int(out[-1])].copy(), out - out[0]
 
 
 def chain_seeds(seeds, band=16, max_gap=5000, max_chains=8):
@@ -903,6 +954,26 @@ class MemResult:
             self.index._chk(self.index._L.debwt_fm_locate(self.index._h, _p64(r), nm, int(max_per_mem or 0), _p64(offs),
                                                           _p64(pos), len(pos)))
         return [pos[int(offs[i]):int(offs[i + 1])] for i in range(nm)]
+
+
+class OverlapResult:
+    """Overlaps of FMIndex.overlaps: pattern i's hits are offsets[i] .. offsets[i + 1], ordered by (strand, length
+    descending, record).  all_hits: structured array with record, length, strand (0 forward, 1 reverse complement) and
+    flags (OVERLAP_CONTAINS: the record is as long as the overlap; OVERLAP_WHOLE: the pattern is)."""
+
+    def __init__(self, index, offsets, hits):
+        self.index, self.offsets, self.all_hits = index, offsets, hits
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def hits(self, i):
+        """structured array (record, length, strand, flags) of pattern i"""
+        return self.all_hits[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+    def count(self):
+        """hits per pattern (np.uint64)"""
+        return self.offsets[1:] - self.offsets[:-1]
 
 
 class MultiDeBWT:

@@ -32,6 +32,7 @@
 #include "fm_extend_kernels.h"
 #include "fm_chain_kernels.h"
 #include "fm_window_kernels.h"
+#include "fm_overlap_kernels.h"
 
 namespace {
 
@@ -2846,6 +2847,10 @@ struct debwt_fm {
     debwt_fm_extend_stats x_stats{};
     debwt_fm_map_stats map_stats{};
     debwt_fm_pair_stats pair_stats{};
+    DevBuf o_table;              // overlaps: record and length per entry of srows, made by the first debwt_fm_overlaps
+    bool has_otable = false;
+    DevBuf o_slot, o_runs, o_nruns, o_nhits, o_rbase, o_hbase, o_cruns, o_rout, o_hits;   // overlap scratch of one batch
+    debwt_fm_overlaps_stats o_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -3116,7 +3121,8 @@ extern "C" int debwt_fm_info_get(const debwt_fm *f, debwt_fm_info *out) {
     if (!f || !out) return DEBWT_EINVAL;
     memset(out, 0, sizeof *out);
     out->n = f->n; out->nrec = f->nrec; out->sa_sample = f->s; out->samples = f->nsamp;
-    out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap + (f->has_text ? f->text.cap : 0);
+    out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap + (f->has_text ? f->text.cap : 0) +
+                        (f->has_otable ? f->o_table.cap : 0);
     out->ms_rank = f->ms_rank; out->ms_samples = f->ms_samples;
     for (int q = 0; q < 4; q++) out->census[q] = f->census[q];
     return DEBWT_OK;
@@ -3563,6 +3569,304 @@ extern "C" int debwt_fm_mems(debwt_fm *f, const char *patterns, const uint64_t *
 extern "C" int debwt_fm_mems_stats_get(const debwt_fm *f, debwt_fm_mems_stats *out) {
     if (!f || !out) return DEBWT_EINVAL;
     *out = f->m_stats;
+    return DEBWT_OK;
+}
+
+// ---- suffix-prefix overlaps (fm_overlap_kernels.h) ------------------------------------------------------------------
+// A batch of patterns [p0, p1) runs as np x strands items with max(0, m - min_overlap + 1) run slots each (one per depth,
+// so no atomics and no overflow).  The walk's run and hit counts come back; the host lays runs and hits out by (pattern,
+// strand), k_fm_overlap_compact moves the runs there deepest first, and k_fm_overlap_expand writes the hits at most
+// DEBWT_FM_OVERLAP_HITS at a launch, straight into the caller's array.  One run is one (pattern, strand, length) group in
+// row order; the host sorts every group of two or more by record on up to 16 threads.
+
+namespace {
+
+constexpr u64 FM_OVL_SLOTS = 1ull << 24;               // worst-case run slots per batch (16 bytes each)
+constexpr u64 FM_OVL_HITS = 1ull << 24;                // hits per expansion launch (16 bytes each)
+
+static_assert(sizeof(debwt_fm_overlap) == sizeof(uint4), "k_fm_overlap_expand writes debwt_fm_overlap as one uint4");
+
+// the record table: for every entry of srows the record that starts at that row, and its length
+int fm_overlap_table(debwt_fm *f) {
+    if (f->has_otable) return DEBWT_OK;
+    const u64 nrec = f->nrec, n = f->n;
+    if (nrec >> 32) { f->err = "debwt_fm_overlaps: 2^32 records or more"; return DEBWT_EINVAL; }
+    std::vector<u64> sr(nrec), pos(nrec - 1);
+    HIPCHK(f, hipMemcpyAsync(sr.data(), f->V.srows, nrec * 8, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    if (nrec > 1 && (rc = fm_locate_runs(f, {f->V.C[4]}, {nrec - 1}, pos.data()))) return rc;   // LF of the j-th '#' row
+    const std::vector<u64> &rs = f->rec_starts;
+    std::vector<FmOvlRec> tab(nrec);
+    u64 jh = 0, dollars = 0;
+    for (u64 k = 0; k < nrec; k++) {
+        u64 rec = 0;
+        if (sr[k] == f->dollar_row) dollars++;
+        else if (jh < nrec - 1) {
+            const u64 p = pos[jh++] + 1;
+            rec = (u64)(std::lower_bound(rs.begin(), rs.end(), p) - rs.begin());
+            if (rec == 0 || rec >= nrec || rs[rec] != p) {
+                f->err = "debwt_fm_overlaps: a '#' row does not lead to a record start"; return DEBWT_EINTERNAL;
+            }
+        } else dollars = 2;                                    // more '#' rows than records: reported below
+        const u64 len = (rec + 1 < nrec ? rs[rec + 1] - 1 : n - 1) - rs[rec];
+        tab[k] = FmOvlRec{(u32)rec, (u32)std::min<u64>(len, 0xFFFFFFFFull)};
+    }
+    if (dollars != 1 || jh != nrec - 1) { f->err = "debwt_fm_overlaps: the separator rows are inconsistent"; return DEBWT_EINTERNAL; }
+    FM_ENSURE(f, f->o_table, (size_t)nrec * sizeof(FmOvlRec));
+    HIPCHK(f, hipMemcpyAsync(f->o_table.p, tab.data(), nrec * sizeof(FmOvlRec), hipMemcpyHostToDevice, f->stream));
+    if ((rc = fm_sync(f))) return rc;                          // tab is host memory
+    f->has_otable = true;
+    return DEBWT_OK;
+}
+
+struct FmOvlBatch {
+    u64 p0 = 0, np = 0, nit = 0, nruns = 0, nhits = 0;
+    std::vector<u64> slot, rbase, hbase, per;              // per: hits per pattern of the batch
+};
+
+// the walk of one batch: fills b (run and hit layout in (pattern, strand) order) and the counters
+int fm_overlaps_walk(debwt_fm *f, const char *patterns, const uint64_t *offsets, u64 p0, u64 p1, u32 min_overlap, u64 nstr,
+                     hipEvent_t e0, hipEvent_t e1, FmOvlBatch *b) {
+    debwt_fm_overlaps_stats &st = f->o_stats;
+    const u64 np = p1 - p0, base = offsets[p0], bytes = offsets[p1] - base, nit = np * nstr;
+    b->p0 = p0; b->np = np; b->nit = nit;
+    b->slot.resize(nit + 1);
+    b->slot[0] = 0;
+    for (u64 g = 0; g < nit; g++) {
+        const u64 j = p0 + (g < np ? g : g - np), m = offsets[j + 1] - offsets[j];
+        b->slot[g + 1] = b->slot[g] + (m >= min_overlap ? m - min_overlap + 1 : 0);
+    }
+    const u64 ns = b->slot[nit];
+    FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
+    FM_ENSURE(f, f->q_off, (size_t)(np + 1) * 8);
+    FM_ENSURE(f, f->o_slot, (size_t)(nit + 1) * 8);
+    FM_ENSURE(f, f->o_nruns, (size_t)nit * 4);
+    FM_ENSURE(f, f->o_nhits, (size_t)nit * 8);
+    FM_ENSURE(f, f->o_runs, (size_t)std::max<u64>(ns, 1) * sizeof(FmOvlRun));
+    FM_ENSURE(f, f->s_ctr, 64);
+    if (bytes) HIPCHK(f, hipMemcpyAsync(f->q_chars.p, patterns + base, bytes, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->q_off.p, offsets + p0, (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->o_slot.p, b->slot.data(), (nit + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(f->s_ctr.p, 0, 32, f->stream));
+    (void)hipEventRecord(e0, f->stream);
+    k_fm_overlap_walk<<<grid_for(nit, 256), 256, 0, f->stream>>>(f->V, f->q_chars.as<u8>(), f->q_off.as<u64>(), base, np, nit,
+                                                                 min_overlap, f->o_slot.as<u64>(), f->o_runs.as<FmOvlRun>(),
+                                                                 f->o_nruns.as<u32>(), f->o_nhits.as<u64>(), f->s_ctr.as<u64>());
+    (void)hipEventRecord(e1, f->stream);
+    std::vector<u32> nr(nit);
+    std::vector<u64> nh(nit);
+    u64 h[4];
+    HIPCHK(f, hipMemcpyAsync(nr.data(), f->o_nruns.p, nit * 4, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(nh.data(), f->o_nhits.p, nit * 8, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(h, f->s_ctr.p, 32, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    st.ms_kernel += ms; st.launches++;
+    st.steps += h[0]; st.line_reads += h[1]; st.wave_steps += h[2];
+    b->rbase.resize(nit); b->hbase.resize(nit); b->per.assign(np, 0);
+    u64 tr = 0, th = 0;
+    for (u64 j = 0; j < np; j++)
+        for (u64 sd = 0; sd < nstr; sd++) {
+            const u64 g = sd * np + j;
+            if (nr[g] > b->slot[g + 1] - b->slot[g]) { f->err = "debwt_fm_overlaps: an item wrote more runs than its slots"; return DEBWT_EINTERNAL; }
+            b->rbase[g] = tr; b->hbase[g] = th;
+            tr += nr[g]; th += nh[g]; b->per[j] += nh[g];
+        }
+    b->nruns = tr; b->nhits = th;
+    st.runs += tr;
+    st.scratch_bytes = std::max<u64>(st.scratch_bytes, ns * sizeof(FmOvlRun) + nit * 36 + tr * 24);
+    return DEBWT_OK;
+}
+
+// the hits of a walked batch into dst (b.nhits of them), in the documented order
+int fm_overlaps_expand(debwt_fm *f, const FmOvlBatch &b, u64 limit, hipEvent_t e0, hipEvent_t e1, debwt_fm_overlap *dst) {
+    debwt_fm_overlaps_stats &st = f->o_stats;
+    if (!b.nhits) return DEBWT_OK;
+    const u64 chunk = std::min(b.nhits, limit);
+    FM_ENSURE(f, f->o_rbase, (size_t)b.nit * 8);
+    FM_ENSURE(f, f->o_hbase, (size_t)b.nit * 8);
+    FM_ENSURE(f, f->o_cruns, (size_t)b.nruns * sizeof(FmOvlRun));
+    FM_ENSURE(f, f->o_rout, (size_t)b.nruns * 8);
+    FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
+    st.scratch_bytes = std::max<u64>(st.scratch_bytes, b.slot[b.nit] * sizeof(FmOvlRun) + b.nit * 36 + b.nruns * 24 + chunk * 16);
+    HIPCHK(f, hipMemcpyAsync(f->o_rbase.p, b.rbase.data(), b.nit * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->o_hbase.p, b.hbase.data(), b.nit * 8, hipMemcpyHostToDevice, f->stream));
+    (void)hipEventRecord(e0, f->stream);
+    k_fm_overlap_compact<<<grid_for(b.nit, 256), 256, 0, f->stream>>>(f->q_off.as<u64>(), f->o_slot.as<u64>(), f->o_nruns.as<u32>(),
+                                                                      f->o_rbase.as<u64>(), f->o_hbase.as<u64>(), b.np, b.nit,
+                                                                      f->o_runs.as<FmOvlRun>(), f->o_cruns.as<FmOvlRun>(),
+                                                                      f->o_rout.as<u64>());
+    st.launches++;
+    for (u64 g0 = 0; g0 < b.nhits; g0 += chunk) {
+        const u64 cnt = std::min(b.nhits - g0, chunk);
+        if (g0) (void)hipEventRecord(e0, f->stream);
+        k_fm_overlap_expand<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_cruns.as<FmOvlRun>(), f->o_rout.as<u64>(), b.nruns,
+                                                                       f->o_table.as<FmOvlRec>(), g0, cnt, f->o_hits.as<uint4>());
+        (void)hipEventRecord(e1, f->stream);
+        HIPCHK(f, hipMemcpyAsync(dst + g0, f->o_hits.p, cnt * sizeof(uint4), hipMemcpyDeviceToHost, f->stream));
+        int rc = fm_sync(f);                                   // the next launch reuses o_hits
+        if (rc) return rc;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        st.ms_kernel += ms; st.launches++;
+    }
+    // record order inside every (pattern, strand, length) group
+    std::vector<u64> start(b.np + 1, 0);
+    for (u64 j = 0; j < b.np; j++) start[j + 1] = start[j] + b.per[j];
+    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), b.nhits / 65536 + 1}));
+    auto work = [&](unsigned t) {
+        for (u64 j = t; j < b.np; j += nt)
+            for (u64 a = start[j]; a < start[j + 1];) {
+                u64 e = a + 1;
+                while (e < start[j + 1] && dst[e].strand == dst[a].strand && dst[e].length == dst[a].length) e++;
+                if (e - a > 1)
+                    std::sort(dst + a, dst + e, [](const debwt_fm_overlap &x, const debwt_fm_overlap &y) { return x.record < y.record; });
+                a = e;
+            }
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto &x : th) x.join();
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_overlap_longest(debwt_fm_overlap *hits, const uint64_t *offsets_in, uint64_t npat, uint64_t *offsets_out) {
+    if (!offsets_in || !offsets_out || (npat && offsets_in[npat] > offsets_in[0] && !hits)) return DEBWT_EINVAL;
+    for (u64 i = 0; i < npat; i++) {                           // the whole input is checked before anything moves
+        if (offsets_in[i + 1] < offsets_in[i]) return DEBWT_EINVAL;
+        for (u64 h = offsets_in[i]; h < offsets_in[i + 1]; h++) {
+            const debwt_fm_overlap &x = hits[h];
+            if (x.strand > 1) return DEBWT_EINVAL;
+            if (h == offsets_in[i]) continue;
+            const debwt_fm_overlap &w = hits[h - 1];
+            if (x.strand != w.strand ? x.strand < w.strand
+                                     : x.length != w.length ? x.length > w.length : x.record <= w.record) return DEBWT_EINVAL;
+        }
+    }
+    u64 out = npat ? offsets_in[0] : 0;
+    std::vector<std::pair<u32, u64>> by;                   // (record, hit) of one pattern and strand
+    std::vector<u8> keep;
+    for (u64 i = 0; i < npat; i++) {
+        const u64 a = offsets_in[i], e = offsets_in[i + 1];
+        offsets_out[i] = out;
+        for (u64 s = a; s < e;) {
+            u64 t = s + 1;
+            while (t < e && hits[t].strand == hits[s].strand) t++;
+            if (t - s <= 64) {                                 // the usual case: against the hits kept so far, which lie
+                const u64 o0 = out;                            // at or before h and hold every record's first hit
+                for (u64 h = s; h < t; h++) {
+                    u64 g = o0;
+                    while (g < out && hits[g].record != hits[h].record) g++;
+                    if (g == out) hits[out++] = hits[h];
+                }
+                s = t;
+                continue;
+            }
+            by.clear();
+            for (u64 h = s; h < t; h++) by.emplace_back(hits[h].record, h);
+            std::sort(by.begin(), by.end());                 // per record the earliest hit first: its largest length
+            keep.assign(t - s, 0);
+            for (size_t k = 0; k < by.size(); k++)
+                if (!k || by[k].first != by[k - 1].first) keep[by[k].second - s] = 1;
+            for (u64 h = s; h < t; h++)
+                if (keep[h - s]) hits[out++] = hits[h];
+            s = t;
+        }
+    }
+    offsets_out[npat] = out;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_overlaps(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                                 uint32_t min_overlap, uint32_t flags, uint64_t *hit_offsets, debwt_fm_overlap *hits,
+                                 uint64_t capacity) {
+    if (!f || !offsets || !hit_offsets) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->o_stats = debwt_fm_overlaps_stats{};
+    if (!min_overlap) { f->err = "debwt_fm_overlaps: min_overlap must be at least 1"; return DEBWT_EINVAL; }
+    if (flags & ~(DEBWT_FM_BOTH_STRANDS | DEBWT_FM_OVERLAP_LONGEST)) { f->err = "debwt_fm_overlaps: unknown flags"; return DEBWT_EINVAL; }
+    u64 maxlen = 0;
+    for (u64 i = 0; i < npat; i++) {
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_overlaps: offsets must not decrease"; return DEBWT_EINVAL; }
+        if ((offsets[i + 1] - offsets[i]) >> 32) { f->err = "debwt_fm_overlaps: a pattern of 2^32 bytes or more"; return DEBWT_EINVAL; }
+        maxlen = std::max<u64>(maxlen, offsets[i + 1] - offsets[i]);
+    }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    hit_offsets[0] = 0;
+    if (!npat) return DEBWT_OK;
+    HIPCHK(f, hipSetDevice(f->device));
+    int rc = fm_overlap_table(f);
+    if (rc) return rc;
+    const u64 nstr = (flags & DEBWT_FM_BOTH_STRANDS) ? 2 : 1;
+    const bool longest = (flags & DEBWT_FM_OVERLAP_LONGEST) != 0;
+    const u64 slots = fm_env_u64("DEBWT_FM_OVERLAP_SLOTS", FM_OVL_SLOTS);
+    const u64 limit = fm_env_u64("DEBWT_FM_OVERLAP_HITS", FM_OVL_HITS);
+    debwt_fm_overlaps_stats &st = f->o_stats;
+    st.patterns = npat;
+    hipEvent_t e0, e1;
+    HIPCHK(f, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
+    auto worst = [&](u64 i) {
+        const u64 m = offsets[i + 1] - offsets[i];
+        return nstr * (m >= min_overlap ? m - min_overlap + 1 : 0);
+    };
+    FmOvlBatch b;
+    std::vector<debwt_fm_overlap> tmp;                     // DEBWT_FM_OVERLAP_LONGEST: a batch's hits before the reduction
+    std::vector<uint64_t> loc;
+    bool fits = true;                                      // false once the hits so far exceed the capacity: count only
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 p1 = p0 + 1, ws = worst(p0);                  // at least one pattern, however long
+        while (p1 < npat && p1 - p0 < FM_BATCH_PATTERNS && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS &&
+               ws + worst(p1) <= slots)
+            ws += worst(p1++);
+        if ((rc = fm_overlaps_walk(f, patterns, offsets, p0, p1, min_overlap, nstr, e0, e1, &b))) return rc;
+        const u64 at = hit_offsets[p0];
+        if (longest) {
+            tmp.resize(b.nhits);
+            if ((rc = fm_overlaps_expand(f, b, limit, e0, e1, tmp.data()))) return rc;
+            loc.assign(b.np + 1, 0);
+            for (u64 j = 0; j < b.np; j++) loc[j + 1] = loc[j] + b.per[j];
+            if ((rc = debwt_fm_overlap_longest(tmp.data(), loc.data(), b.np, loc.data()))) {
+                f->err = "debwt_fm_overlaps: a batch's hits are not in order"; return DEBWT_EINTERNAL;
+            }
+            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = at + loc[j + 1];
+            fits = fits && hits && at + loc[b.np] <= capacity;
+            if (fits && loc[b.np]) memcpy(hits + at, tmp.data(), loc[b.np] * sizeof(debwt_fm_overlap));
+        } else {
+            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = hit_offsets[p0 + j] + b.per[j];
+            fits = fits && (hits || !b.nhits) && at + b.nhits <= capacity;
+            if (fits && (rc = fm_overlaps_expand(f, b, limit, e0, e1, hits + at))) return rc;
+        }
+        st.batches++;
+        p0 = p1;
+    }
+    const u64 total = hit_offsets[npat];
+    st.hits = total;
+    if (!fits || capacity < total) {
+        f->err = "debwt_fm_overlaps: capacity below the hits (hit_offsets[npat] = " + std::to_string(total) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (maxlen == 0xFFFFFFFFull)                           // the table's lengths stop at 2^32 - 1: such overlaps from the starts
+        for (u64 h = 0; h < total; h++)
+            if (hits[h].length == 0xFFFFFFFFu) {
+                const u64 r = hits[h].record;
+                const u64 len = (r + 1 < f->nrec ? f->rec_starts[r + 1] - 1 : f->n - 1) - f->rec_starts[r];
+                hits[h].flags = (hits[h].flags & ~DEBWT_FM_OVERLAP_CONTAINS) | (len == 0xFFFFFFFFull ? DEBWT_FM_OVERLAP_CONTAINS : 0u);
+            }
+    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_overlaps_stats_get(const debwt_fm *f, debwt_fm_overlaps_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->o_stats;
     return DEBWT_OK;
 }
 
@@ -5186,7 +5490,8 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
     for (DevBuf *b : {&f->idx, &f->rowlists, &f->sa, &f->q_chars, &f->q_off, &f->q_out, &f->q_runs, &f->s_hits, &f->s_ctr,
                       &f->s_plist, &f->m_slot, &f->m_cnt, &f->m_obase, &f->m_spans, &f->m_ranges, &f->m_cspans,
                       &f->m_cranges, &f->text, &f->x_jobs, &f->x_best, &f->x_cells, &f->x_flags, &f->x_tr, &f->x_cigoff,
-                      &f->x_cig, &f->x_anchors})
+                      &f->x_cig, &f->x_anchors, &f->o_table, &f->o_slot, &f->o_runs, &f->o_nruns, &f->o_nhits, &f->o_rbase,
+                      &f->o_hbase, &f->o_cruns, &f->o_rout, &f->o_hits})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -541,9 +541,65 @@ typedef struct {
 } debwt_fm_mems_stats;
 int debwt_fm_mems_stats_get(const debwt_fm *fm, debwt_fm_mems_stats *out);
 
+/* ---- suffix-prefix overlaps of patterns against the records (fm_overlap_kernels.h) --------------------------------
+ * For every pattern, the records whose beginning equals its end.  Q is the pattern as given (strand 0) or, with
+ * DEBWT_FM_BOTH_STRANDS, also its reverse complement (strand 1; complementing as in debwt_fm_mems: A<->T, C<->G, other
+ * characters stay non-bases).  With m = |Q| and S_j the string of record j, (Q, j, L) is an overlap iff
+ *   min_overlap <= L <= min(m, |S_j|),  Q[m-L .. m) == S_j[0 .. L) with A/C/G/T in either case,  and all of Q[m-L .. m)
+ *   are bases.
+ * A character outside ACGTacgt at Q[p] therefore limits L to m - 1 - p, and one at Q[m-1] gives no overlap.  EVERY overlap
+ * is reported: the overlap of a record of the collection with itself (L = m = |S_j|), containments, and several lengths
+ * with one record (periodic reads).  Exact overlaps only.
+ * A hit is (record j, length L, strand, flags): DEBWT_FM_OVERLAP_CONTAINS when L == |S_j| (the record is a suffix of Q),
+ * DEBWT_FM_OVERLAP_WHOLE when L == m (Q is a prefix of the record).
+ * Strand 1, read carefully: a strand-1 hit says that the last L bases of revcomp(P) start record j, that is, record j
+ * begins with the reverse complement of P's FIRST L bases.  On a collection that holds reads of one strand only this
+ * finds head-to-head overlaps; tail-to-tail ones (a read's end against the reverse complement of another read's end) need
+ * the reverse complements in the collection (or an index of the reversed text) and are not found here.
+ * hit_offsets (npat + 1): pattern i's hits are [hit_offsets[i], hit_offsets[i+1]), ascending by (strand, length
+ * DESCENDING, record ascending): an order the strings alone determine, whatever order the BWT gives equal suffixes.
+ * An empty pattern has 0 hits, as has one shorter than min_overlap; pattern length below 2^32 bytes; fewer than 2^32
+ * records.  DEBWT_ERANGE when capacity < hit_offsets[npat], hit_offsets written first (the protocol of debwt_fm_locate).
+ * DEBWT_EINVAL for min_overlap 0, flags other than DEBWT_FM_BOTH_STRANDS | DEBWT_FM_OVERLAP_LONGEST, decreasing offsets
+ * and a pattern of 2^32 bytes or more.  No attached text is needed: an index from debwt_fm_open answers as one from
+ * debwt_fm_create.
+ * DEBWT_FM_OVERLAP_LONGEST keeps per (pattern, strand, record) only the largest L: a subsequence of the full result, bit
+ * for bit what debwt_fm_overlap_longest makes of it (capacity then counts the kept hits).
+ * The first call makes the record table (for every separator row the record that starts there and its length, 8 bytes
+ * per record, from a locate of the '#' suffixes: DEBWT_EINTERNAL if one does not land on a record start) and keeps it
+ * with the index: it is counted in debwt_fm_info.device_bytes from then on.
+ * Batches are cut inside the library at 64 MB of pattern bytes, 2^20 patterns and DEBWT_FM_OVERLAP_SLOTS (environment,
+ * read per call; default 2^24) worst-case run slots, max(0, m - min_overlap + 1) per pattern and strand; a pattern with
+ * more goes alone.  Hits are expanded at most DEBWT_FM_OVERLAP_HITS (default 2^24) at a launch, from counts that are
+ * exact after the walk, so there is no worst-case hit buffer; the result depends on neither limit.  Device scratch: 16
+ * bytes per slot, 24 per run found, 16 per hit of one launch, 36 per pattern and strand and the pattern bytes, each with
+ * up to 25 % slack: at most about 0.8 GB at the defaults (more only for a single pattern beyond the slot limit). */
+#define DEBWT_FM_OVERLAP_LONGEST  2u   /* option flag, beside DEBWT_FM_BOTH_STRANDS (1u) */
+#define DEBWT_FM_OVERLAP_CONTAINS 1u   /* hit flag: length == length of `record` (the record is a suffix of Q) */
+#define DEBWT_FM_OVERLAP_WHOLE    2u   /* hit flag: length == |Q| (Q is a prefix of the record) */
+typedef struct { uint32_t record, length, strand, flags; } debwt_fm_overlap;
+int debwt_fm_overlaps(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                      uint32_t min_overlap, uint32_t flags,
+                      uint64_t *hit_offsets, debwt_fm_overlap *hits, uint64_t capacity);
+/* what the last debwt_fm_overlaps did: patterns, batches, kernel launches (walk, compaction, expansions), runs (one per
+ * pattern, strand and length with at least one record), hits (hit_offsets[npat]), rank steps (one fm_occ2 each), rank
+ * lines read, wave steps (64 x the longest lane per wave: steps / wave_steps is the share of lanes busy), the largest
+ * scratch of a batch, kernel time (events; walk + compaction + expansion) and host wall time */
+typedef struct {
+    uint64_t patterns, batches, launches, runs, hits, steps, line_reads, wave_steps, scratch_bytes;
+    float ms_kernel, ms_wall;
+} debwt_fm_overlaps_stats;
+int debwt_fm_overlaps_stats_get(const debwt_fm *fm, debwt_fm_overlaps_stats *out);
+/* The reduction of DEBWT_FM_OVERLAP_LONGEST on the host (no GPU): hits in the order above, pattern i's in [offsets_in[i],
+ * offsets_in[i+1]); per (pattern, strand, record) the first (longest) hit stays.  Compacts `hits` in place from
+ * offsets_in[0] and writes the new offsets (npat + 1; offsets_out may be offsets_in).  DEBWT_EINVAL, with nothing moved,
+ * when the input is not in that order (decreasing offsets, a strand above 1, strands descending, lengths ascending inside
+ * a strand, records not strictly ascending inside a length). */
+int debwt_fm_overlap_longest(debwt_fm_overlap *hits, const uint64_t *offsets_in, uint64_t npat, uint64_t *offsets_out);
+
 /* ---- gapped extension of seeds and a read mapper (fm_extend_kernels.h) -------------------------------------------
  * An index holds no text; the two entry points below read the text next to a seed, so it is attached first (n / 4 bytes
- * of HBM, counted in debwt_fm_info.device_bytes).  Without it they answer DEBWT_ESTATE; count, locate, search and mems
+ * of HBM, counted in debwt_fm_info.device_bytes, as is the record table of debwt_fm_overlaps once made).  Without it they answer DEBWT_ESTATE; count, locate, search and mems
  * never need it.
  *   ctx given: device-to-device copy of the context's loaded text (same n and nrec, else DEBWT_EINVAL); packed / sep are
  *              ignored.  The path after debwt_fm_create.
