@@ -6,7 +6,8 @@
  *   deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq
- *   deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self] READS.fa|.fq
+ *   deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self]
+ *                      [--max-mismatches K [--max-error-permille R]] READS.fa|.fq
  *   deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]
  *                      [--max-occ N] [--min-score S] [--chain [--max-gap G]]
  *                      [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq
@@ -36,6 +37,11 @@
  * complement (strand -: the record begins with the reverse complement of the read's first `length` bases); --longest
  * keeps the longest overlap per read, strand and record; --no-self, for querying the indexed file itself, drops read
  * number i's overlap with record i over its whole length.  It needs OUT, OUT.#, OUT.$ and OUT.sa only.
+ * --max-mismatches K (0..4) goes through debwt_fm_overlaps_mm instead: the record's first `length` bases may differ from
+ * the read's last `length` in up to K columns (a letter outside ACGTacgt is a mismatch), and with --max-error-permille R
+ * (0..1000, only with --max-mismatches) in at most R / 1000 of the columns; every line then gets a sixth column, the
+ * mismatches of that overlap (also with K = 0).  Without --max-mismatches the output is what it was.  Reads hold at most
+ * 1024 bases there.
  *
  * map aligns every read (debwt_fm_map: MEM seeds of at least L bases, at most N occurrences of each, clustered by diagonal,
  * banded affine-gap extension with half-width W, 0..63; a plain heuristic, not BWA-MEM's).  The index holds no text, so
@@ -75,7 +81,8 @@ static void usage(void) {
             "       deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq\n"
-            "       deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self] READS.fa|.fq\n"
+            "       deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self]\n"
+            "                          [--max-mismatches K [--max-error-permille R]] READS.fa|.fq\n"
             "       deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]\n"
             "                          [--max-occ N] [--min-score S] [--chain [--max-gap G]]\n"
             "                          [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq\n"
@@ -88,6 +95,8 @@ static void usage(void) {
             "overlaps prints name<TAB>strand<TAB>record<TAB>length<TAB>flags per record that begins with the last `length`\n"
             "(at least L, default 20) bases of the read; flags C (the whole record), W (the whole read), CW or .; --longest\n"
             "keeps the longest overlap per read, strand and record, --no-self drops read i's whole-length overlap with record i;\n"
+            "--max-mismatches K (0..4) admits K mismatching columns in an overlap, --max-error-permille R (0..1000) at most\n"
+            "R / 1000 of its columns, and a sixth column gives every overlap's mismatches;\n"
             "map prints one PAF line per mapped read (AS:i: score, NM:i: edits, cg:Z: CIGAR); --ref is the FASTA that OUT\n"
             "is the BWT of; --chain chains the seeds of a read across diagonals and aligns along the chain (stretches of\n"
             "at most G bases between two seeds, default 5000); --mate maps paired ends, read i of READS2 being the mate of\n"
@@ -517,7 +526,9 @@ done:
     return ret;
 }
 
-static int cmd_overlaps(const char *out, const char *pfile, int device, uint32_t min_overlap, uint32_t flags, int no_self) {
+/* mm: --max-mismatches was given (the call with a mismatch budget and the sixth column) */
+static int cmd_overlaps(const char *out, const char *pfile, int device, uint32_t min_overlap, uint32_t flags, int no_self,
+                        int mm, uint32_t K, uint32_t permille) {
     struct patterns P;
     if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
@@ -530,7 +541,8 @@ static int cmd_overlaps(const char *out, const char *pfile, int device, uint32_t
         free(hits);
         hits = malloc(cap * sizeof *hits);
         if (!hits) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = debwt_fm_overlaps(fm, P.seq, P.off, P.n, min_overlap, flags, hoff, hits, cap);
+        rc = mm ? debwt_fm_overlaps_mm(fm, P.seq, P.off, P.n, min_overlap, K, permille, flags, hoff, hits, cap)
+                : debwt_fm_overlaps(fm, P.seq, P.off, P.n, min_overlap, flags, hoff, hits, cap);
         if (rc == DEBWT_ERANGE && hoff[P.n] > cap) { cap = hoff[P.n]; continue; }
         break;
     }
@@ -540,9 +552,11 @@ static int cmd_overlaps(const char *out, const char *pfile, int device, uint32_t
         for (uint64_t h = hoff[i]; h < hoff[i + 1]; h++) {
             const debwt_fm_overlap *o = hits + h;
             if (no_self && !o->strand && o->record == i && o->length == m) continue;
-            printf("%s\t%c\t%u\t%u\t%s\n", P.name[i], o->strand ? '-' : '+', o->record, o->length,
+            printf("%s\t%c\t%u\t%u\t%s", P.name[i], o->strand ? '-' : '+', o->record, o->length,
                    (o->flags & 3u) == 3u ? "CW" : (o->flags & DEBWT_FM_OVERLAP_CONTAINS) ? "C" :
                    (o->flags & DEBWT_FM_OVERLAP_WHOLE) ? "W" : ".");
+            if (mm) printf("\t%u", DEBWT_FM_OVERLAP_MM(o->flags));
+            putchar('\n');
         }
     }
     ret = fflush(stdout) ? 1 : 0;
@@ -725,6 +739,8 @@ int main(int argc, char **argv) {
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
     uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, min_overlap = 20, v64 = 0;
+    uint64_t ovl_k = 0, ovl_permille = 0;
+    int ovl_mm = 0, permille_given = 0;
     debwt_fm_map_opts mo;
     debwt_fm_map_defaults(&mo);
     debwt_fm_chain_opts co;
@@ -803,6 +819,14 @@ int main(int argc, char **argv) {
         else if (mode == 5 && !strcmp(a, "--min-overlap")) {
             if (parse_u64(v, &min_overlap) || min_overlap < 1 || min_overlap > 0xFFFFFFFFull) { fprintf(stderr, "--min-overlap: a length of at least 1\n"); return 1; }
         }
+        else if (mode == 5 && !strcmp(a, "--max-mismatches")) {
+            if (parse_u64(v, &ovl_k) || ovl_k > 4) { fprintf(stderr, "--max-mismatches: a count in 0..4\n"); return 1; }
+            ovl_mm = 1;
+        }
+        else if (mode == 5 && !strcmp(a, "--max-error-permille")) {
+            if (parse_u64(v, &ovl_permille) || ovl_permille > 1000) { fprintf(stderr, "--max-error-permille: a rate in 0..1000\n"); return 1; }
+            permille_given = 1;
+        }
         else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
@@ -822,7 +846,11 @@ int main(int argc, char **argv) {
         return cmd_map(out, ref, file, threads, iupac, seed, (int)device, &mo, chain, co.max_gap);
     }
     if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
-    if (mode == 5) return cmd_overlaps(out, file, (int)device, (uint32_t)min_overlap, flags, no_self);
+    if (mode == 5) {
+        if (permille_given && !ovl_mm) { fprintf(stderr, "--max-error-permille: only with --max-mismatches\n"); usage(); return 1; }
+        return cmd_overlaps(out, file, (int)device, (uint32_t)min_overlap, flags, no_self, ovl_mm, (uint32_t)ovl_k,
+                            (uint32_t)ovl_permille);
+    }
     if (mode == 3) return cmd_mems(out, file, (int)device, max_hits, (uint32_t)min_len, flags);
     if (search) return cmd_search(out, file, (int)device, mode == 2, max_hits, (uint32_t)K, flags);
     return cmd_query(out, file, (int)device, mode == 2, max_hits);

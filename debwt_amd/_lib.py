@@ -93,6 +93,17 @@ class DebwtFmOverlapsStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmOverlapsMmStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("patterns", "batches", "launches", "retries", "runs", "hits", "steps",
+                                                 "line_reads", "wave_steps", "scratch_bytes")] +
+                [("items", ctypes.c_uint64 * 5), ("ms_kernel", ctypes.c_float), ("ms_wall", ctypes.c_float)])
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["items"] = [int(x) for x in self.items]
+        return d
+
+
 class DebwtFmOverlap(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("record", "length", "strand", "flags")]
 
@@ -236,6 +247,7 @@ SYMBOLS = [
     "debwt_fm_align_window", "debwt_fm_insert_bounds", "debwt_fm_pair_select", "debwt_fm_pair_defaults",
     "debwt_fm_map_pairs", "debwt_fm_pair_stats_get",
     "debwt_fm_overlaps", "debwt_fm_overlaps_stats_get", "debwt_fm_overlap_longest",
+    "debwt_fm_overlaps_mm", "debwt_fm_overlaps_mm_stats_get",
 ]
 
 
@@ -443,6 +455,11 @@ def lib():
                                     ctypes.POINTER(DebwtFmOverlap), ctypes.c_uint64]
     L.debwt_fm_overlaps_stats_get.restype = ctypes.c_int
     L.debwt_fm_overlaps_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmOverlapsStats)]
+    L.debwt_fm_overlaps_mm.restype = ctypes.c_int
+    L.debwt_fm_overlaps_mm.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.c_uint32, u64p, ctypes.POINTER(DebwtFmOverlap), ctypes.c_uint64]
+    L.debwt_fm_overlaps_mm_stats_get.restype = ctypes.c_int
+    L.debwt_fm_overlaps_mm_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmOverlapsMmStats)]
     L.debwt_fm_overlap_longest.restype = ctypes.c_int
     L.debwt_fm_overlap_longest.argtypes = [ctypes.POINTER(DebwtFmOverlap), u64p, ctypes.c_uint64, u64p]
     L.debwt_fm_attach_text.restype = ctypes.c_int

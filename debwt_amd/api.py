@@ -444,6 +444,38 @@ class FMIndex:
         self._chk(self._L.debwt_fm_overlaps_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def overlaps_mm(self, patterns, min_overlap=20, mismatches=1, error_permille=0, strands="forward", longest=False):
+        """Suffix-prefix overlaps with substitutions (debwt_fm_overlaps_mm): every (record, length) with length >=
+        min_overlap whose first `length` bases differ from the pattern's last `length` in at most `mismatches` (0..4)
+        columns and, with error_permille R > 0, in at most R / 1000 of them; a character outside ACGTacgt is a mismatch.
+        Patterns hold at most 1024 bytes.  strands and longest as in overlaps(); the order is that of overlaps(), and
+        mismatches=0 gives its result.  Returns an OverlapResult whose mismatches() are the counts per hit."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        flags = (SEARCH_BOTH_STRANDS if strands == "both" else 0) | (OVERLAP_LONGEST if longest else 0)
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        hoff = np.zeros(npat + 1, dtype=np.uint64)
+        cap = 4 * npat + 16                                   # first estimate; grown to the exact count on DEBWT_ERANGE
+        while True:
+            hits = np.zeros(cap, dtype=_OVERLAP_DTYPE)
+            rc = self._L.debwt_fm_overlaps_mm(self._h, buf, _p64(offs), npat, int(min_overlap), int(mismatches),
+                                              int(error_permille), flags, _p64(hoff),
+                                              hits.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmOverlap)), cap)
+            if rc == -5 and int(hoff[npat]) > cap:
+                cap = int(hoff[npat])
+                continue
+            self._chk(rc)
+            break
+        return OverlapResult(self, hoff, hits[:int(hoff[npat])].copy())
+
+    def overlaps_mm_stats(self):
+        """What the last overlaps_mm call did (debwt_fm_overlaps_mm_stats_get): batches, launches and re-run launches, runs,
+        hits, work items per mismatch level, rank steps and lines, wave steps, scratch bytes, ms."""
+        st = _lib.DebwtFmOverlapsMmStats()
+        self._chk(self._L.debwt_fm_overlaps_mm_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def attach_text(self, source=None, words=None, sep=None):
         """Give the index its text (debwt_fm_attach_text; n / 4 bytes of HBM), which extend() and map() read.  source: the
         DeBWT context the index was made from (device-to-device copy), or None with the host text words / sep as
@@ -959,7 +991,8 @@ class MemResult:
 class OverlapResult:
     """Overlaps of FMIndex.overlaps: pattern i's hits are offsets[i] .. offsets[i + 1], ordered by (strand, length
     descending, record).  all_hits: structured array with record, length, strand (0 forward, 1 reverse complement) and
-    flags (OVERLAP_CONTAINS: the record is as long as the overlap; OVERLAP_WHOLE: the pattern is)."""
+    flags (OVERLAP_CONTAINS: the record is as long as the overlap; OVERLAP_WHOLE: the pattern is; from overlaps_mm also the
+    hit's mismatches in bits 8-15, see mismatches())."""
 
     def __init__(self, index, offsets, hits):
         self.index, self.offsets, self.all_hits = index, offsets, hits
@@ -974,6 +1007,10 @@ class OverlapResult:
     def count(self):
         """hits per pattern (np.uint64)"""
         return self.offsets[1:] - self.offsets[:-1]
+
+    def mismatches(self):
+        """mismatches per hit (np.uint8, flags bits 8-15): zeros for a result of FMIndex.overlaps"""
+        return ((self.all_hits["flags"] >> 8) & 0xFF).astype(np.uint8)
 
 
 class MultiDeBWT:

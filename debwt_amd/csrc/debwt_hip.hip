@@ -33,6 +33,7 @@
 #include "fm_chain_kernels.h"
 #include "fm_window_kernels.h"
 #include "fm_overlap_kernels.h"
+#include "fm_overlap_mm_kernels.h"
 
 namespace {
 
@@ -2851,6 +2852,7 @@ struct debwt_fm {
     bool has_otable = false;
     DevBuf o_slot, o_runs, o_nruns, o_nhits, o_rbase, o_hbase, o_cruns, o_rout, o_hits;   // overlap scratch of one batch
     debwt_fm_overlaps_stats o_stats{};
+    debwt_fm_overlaps_mm_stats om_stats{};   // overlaps with mismatches: scratch is s_items, s_hits (runs), o_cruns, o_rout, o_hits
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -3867,6 +3869,270 @@ extern "C" int debwt_fm_overlaps(debwt_fm *f, const char *patterns, const uint64
 extern "C" int debwt_fm_overlaps_stats_get(const debwt_fm *f, debwt_fm_overlaps_stats *out) {
     if (!f || !out) return DEBWT_EINVAL;
     *out = f->o_stats;
+    return DEBWT_OK;
+}
+
+// ---- suffix-prefix overlaps with mismatches (fm_overlap_mm_kernels.h) -----------------------------------------------
+// The levels of a batch are drained depth first as in debwt_fm_search: a chunk of level L writes its children into level
+// L + 1's buffer, which is drained before the next chunk of L, and its runs into the run buffer, which comes back to the
+// host after every chunk.  One item asks for at most 4 * 1024 children and 1024 + 1 runs, and the buffers hold at least
+// that, so every chunk finishes.  The host orders the batch's runs by (pattern, strand, length descending, first entry),
+// which gives the exact hit counts, uploads them with their first hit numbers, and k_fm_overlap_mm_expand writes the hits
+// at most DEBWT_FM_OVERLAP_HITS at a launch straight into the caller's array.  A (pattern, strand, length) group may be
+// made of several runs (one per work item); the host sorts every group of two or more hits by record.
+
+namespace {
+
+constexpr u64 FM_OVL_MM_ITEMS = 1ull << 23;            // entries per buffer: 24 bytes an item, 16 a run
+
+struct FmOvlMmRun {
+    debwt_fm *f;
+    const u8 *chars; const u64 *off; u64 base, np;
+    u32 kmax, min_overlap, permille;
+    u64 cap;                                             // entries per buffer (children and runs)
+    u64 hint[FM_SEARCH_MAX_K + 1];
+    hipEvent_t e0, e1;
+    std::vector<uint4> *runs;                            // (batch-local pattern, first entry, entries, d | level << 16 | strand << 24)
+};
+
+int fm_overlap_mm_drain(FmOvlMmRun &r, u32 level, u64 count) {
+    debwt_fm *f = r.f;
+    debwt_fm_overlaps_mm_stats &st = f->om_stats;
+    const u64 *in = level ? f->s_items[level].as<u64>() : nullptr;
+    u64 *out = level < r.kmax ? f->s_items[level + 1].as<u64>() : nullptr;
+    u64 *ctr = f->s_ctr.as<u64>();
+    for (u64 a = 0; a < count;) {
+        const u64 c = std::min(count - a, r.hint[level]);
+        HIPCHK(f, hipMemsetAsync(ctr, 0, 40, f->stream));
+        (void)hipEventRecord(r.e0, f->stream);
+        k_fm_overlap_mm<<<grid_for(c, 256), 256, 0, f->stream>>>(f->V, r.chars, r.off, r.base, r.np, in, a, c, level, r.kmax,
+                                                                 r.min_overlap, r.permille, out, out ? r.cap : 0,
+                                                                 f->s_hits.as<uint4>(), r.cap, ctr);
+        (void)hipEventRecord(r.e1, f->stream);
+        u64 h[5];
+        HIPCHK(f, hipMemcpyAsync(h, ctr, 40, hipMemcpyDeviceToHost, f->stream));
+        int rc = fm_sync(f);
+        if (rc) return rc;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, r.e0, r.e1);
+        st.ms_kernel += ms; st.launches++;
+        if (h[0] > r.cap || h[1] > r.cap) {                 // overflow: nothing of this chunk is kept
+            if (c == 1) { f->err = "debwt_fm_overlaps_mm: one item overflowed the buffers"; return DEBWT_EINTERNAL; }
+            const double fit = std::min((double)r.cap / (double)std::max<u64>(h[0], 1), (double)r.cap / (double)std::max<u64>(h[1], 1));
+            r.hint[level] = std::max<u64>(1, std::min<u64>(c / 2, (u64)((double)c * fit * 0.9)));
+            st.retries++;
+            continue;
+        }
+        if (h[1]) {
+            const size_t at = r.runs->size();
+            r.runs->resize(at + h[1]);
+            HIPCHK(f, hipMemcpyAsync(r.runs->data() + at, f->s_hits.p, h[1] * sizeof(uint4), hipMemcpyDeviceToHost, f->stream));
+            if ((rc = fm_sync(f))) return rc;
+        }
+        st.items[level] += c; st.steps += h[2]; st.line_reads += h[3]; st.wave_steps += h[4];
+        if (h[0] < r.cap / 4 && h[1] < r.cap / 4 && r.hint[level] < (1ull << 40)) r.hint[level] *= 2;
+        a += c;
+        if (h[0] && (rc = fm_overlap_mm_drain(r, level + 1, h[0]))) return rc;
+    }
+    return DEBWT_OK;
+}
+
+struct FmOvlMmBatch {
+    u64 p0 = 0, np = 0, nruns = 0, nhits = 0;
+    std::vector<uint4> raw;                                // runs as the levels wrote them
+    std::vector<FmOvlRun> cruns;                           // ordered, in k_fm_overlap_mm_expand's layout
+    std::vector<u64> rout, per;                            // first hit number per run; hits per pattern of the batch
+};
+
+// the levels of one batch, then its runs in order: fills b
+int fm_overlaps_mm_walk(debwt_fm *f, const char *patterns, const uint64_t *offsets, u64 p0, u64 p1, u64 nstr, FmOvlMmRun &r,
+                        FmOvlMmBatch *b) {
+    debwt_fm_overlaps_mm_stats &st = f->om_stats;
+    const u64 np = p1 - p0, base = offsets[p0], bytes = offsets[p1] - base;
+    b->p0 = p0; b->np = np;
+    b->raw.clear();
+    FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
+    FM_ENSURE(f, f->q_off, (size_t)(np + 1) * 8);
+    if (bytes) HIPCHK(f, hipMemcpyAsync(f->q_chars.p, patterns + base, bytes, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->q_off.p, offsets + p0, (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    r.chars = f->q_chars.as<u8>(); r.off = f->q_off.as<u64>(); r.base = base; r.np = np; r.runs = &b->raw;
+    int rc = fm_overlap_mm_drain(r, 0, np * nstr);
+    if (rc) return rc;
+    const u64 nr = b->raw.size();
+    // bucket by pattern, then (strand, length descending, first entry) inside each pattern, on up to 16 host threads
+    std::vector<u64> start(np + 1, 0);
+    for (u64 k = 0; k < nr; k++) {
+        if (b->raw[k].x >= np) { f->err = "debwt_fm_overlaps_mm: a run names a pattern outside its batch"; return DEBWT_EINTERNAL; }
+        start[b->raw[k].x + 1]++;
+    }
+    for (u64 j = 0; j < np; j++) start[j + 1] += start[j];
+    b->cruns.resize(nr); b->rout.resize(nr); b->per.assign(np, 0);
+    {
+        std::vector<u64> at(start.begin(), start.end() - 1);
+        for (u64 k = 0; k < nr; k++) b->cruns[at[b->raw[k].x]++] = b->raw[k];
+    }
+    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), nr / 65536 + 1}));
+    auto work = [&](unsigned t) {
+        for (u64 j = t; j < np; j += nt) {
+            const u32 m = (u32)(offsets[p0 + j + 1] - offsets[p0 + j]);
+            FmOvlRun *a = b->cruns.data() + start[j], *e = b->cruns.data() + start[j + 1];
+            std::sort(a, e, [](const FmOvlRun &x, const FmOvlRun &y) {
+                const u32 sx = x.w >> 24, sy = y.w >> 24, dx = x.w & 0xFFFFu, dy = y.w & 0xFFFFu;
+                return sx != sy ? sx < sy : dx != dy ? dx > dy : x.y < y.y;
+            });
+            u64 h = 0;
+            for (FmOvlRun *x = a; x < e; x++) {              // to the expansion's layout
+                const u32 d = x->w & 0xFFFFu, lv = (x->w >> 16) & 0xFFu, sd = x->w >> 24;
+                h += x->z;
+                *x = make_uint4(d, x->y, x->z, sd | (d == m ? 2u : 0u) | (lv << 8));
+            }
+            b->per[j] = h;
+        }
+    };
+    {
+        std::vector<std::thread> th;
+        for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
+        work(0);
+        for (auto &x : th) x.join();
+    }
+    u64 h = 0;
+    for (u64 k = 0; k < nr; k++) { b->rout[k] = h; h += b->cruns[k].z; }
+    b->nruns = nr; b->nhits = h;
+    st.runs += nr;
+    return DEBWT_OK;
+}
+
+// the hits of a walked batch into dst (b.nhits of them), in the documented order
+int fm_overlaps_mm_expand(debwt_fm *f, const FmOvlMmBatch &b, u64 limit, u64 fixed, hipEvent_t e0, hipEvent_t e1, debwt_fm_overlap *dst) {
+    debwt_fm_overlaps_mm_stats &st = f->om_stats;
+    if (!b.nhits) return DEBWT_OK;
+    const u64 chunk = std::min(b.nhits, limit);
+    FM_ENSURE(f, f->o_cruns, (size_t)b.nruns * sizeof(FmOvlRun));
+    FM_ENSURE(f, f->o_rout, (size_t)b.nruns * 8);
+    FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
+    st.scratch_bytes = std::max<u64>(st.scratch_bytes, fixed + b.nruns * 24 + chunk * 16);
+    HIPCHK(f, hipMemcpyAsync(f->o_cruns.p, b.cruns.data(), b.nruns * sizeof(FmOvlRun), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->o_rout.p, b.rout.data(), b.nruns * 8, hipMemcpyHostToDevice, f->stream));
+    for (u64 g0 = 0; g0 < b.nhits; g0 += chunk) {
+        const u64 cnt = std::min(b.nhits - g0, chunk);
+        (void)hipEventRecord(e0, f->stream);
+        k_fm_overlap_mm_expand<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_cruns.as<FmOvlRun>(), f->o_rout.as<u64>(), b.nruns,
+                                                                          f->o_table.as<FmOvlRec>(), g0, cnt, f->o_hits.as<uint4>());
+        (void)hipEventRecord(e1, f->stream);
+        HIPCHK(f, hipMemcpyAsync(dst + g0, f->o_hits.p, cnt * sizeof(uint4), hipMemcpyDeviceToHost, f->stream));
+        int rc = fm_sync(f);                                   // the next launch reuses o_hits
+        if (rc) return rc;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        st.ms_kernel += ms; st.launches++;
+    }
+    // record order inside every (pattern, strand, length) group, whatever runs it is made of
+    std::vector<u64> start(b.np + 1, 0);
+    for (u64 j = 0; j < b.np; j++) start[j + 1] = start[j] + b.per[j];
+    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), b.nhits / 65536 + 1}));
+    auto work = [&](unsigned t) {
+        for (u64 j = t; j < b.np; j += nt)
+            for (u64 a = start[j]; a < start[j + 1];) {
+                u64 e = a + 1;
+                while (e < start[j + 1] && dst[e].strand == dst[a].strand && dst[e].length == dst[a].length) e++;
+                if (e - a > 1)
+                    std::sort(dst + a, dst + e, [](const debwt_fm_overlap &x, const debwt_fm_overlap &y) { return x.record < y.record; });
+                a = e;
+            }
+    };
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
+    work(0);
+    for (auto &x : th) x.join();
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_overlaps_mm(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                                    uint32_t min_overlap, uint32_t max_mismatches, uint32_t max_error_permille, uint32_t flags,
+                                    uint64_t *hit_offsets, debwt_fm_overlap *hits, uint64_t capacity) {
+    if (!f || !offsets || !hit_offsets) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->om_stats = debwt_fm_overlaps_mm_stats{};
+    if (!min_overlap) { f->err = "debwt_fm_overlaps_mm: min_overlap must be at least 1"; return DEBWT_EINVAL; }
+    if (max_mismatches > FM_SEARCH_MAX_K) { f->err = "debwt_fm_overlaps_mm: max_mismatches must be 0..4"; return DEBWT_EINVAL; }
+    if (max_error_permille > 1000) { f->err = "debwt_fm_overlaps_mm: max_error_permille must be 0..1000"; return DEBWT_EINVAL; }
+    if (flags & ~(DEBWT_FM_BOTH_STRANDS | DEBWT_FM_OVERLAP_LONGEST)) { f->err = "debwt_fm_overlaps_mm: unknown flags"; return DEBWT_EINVAL; }
+    if (npat >> 31) { f->err = "debwt_fm_overlaps_mm: too many patterns"; return DEBWT_EINVAL; }
+    for (u64 i = 0; i < npat; i++) {
+        if (offsets[i + 1] < offsets[i]) { f->err = "debwt_fm_overlaps_mm: offsets must not decrease"; return DEBWT_EINVAL; }
+        if (offsets[i + 1] - offsets[i] > FM_SEARCH_MAX_LEN) {
+            f->err = "debwt_fm_overlaps_mm: a pattern is longer than " + std::to_string(FM_SEARCH_MAX_LEN) + " bytes";
+            return DEBWT_EINVAL;
+        }
+    }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    hit_offsets[0] = 0;
+    if (!npat) return DEBWT_OK;
+    HIPCHK(f, hipSetDevice(f->device));
+    int rc = fm_overlap_table(f);
+    if (rc) return rc;
+    const u64 nstr = (flags & DEBWT_FM_BOTH_STRANDS) ? 2 : 1;
+    const bool longest = (flags & DEBWT_FM_OVERLAP_LONGEST) != 0;
+    // per buffer at least what one item can ask for (4 children per step, 1024 steps; a run per step and one on arrival)
+    const u64 cap = std::max<u64>(fm_env_u64("DEBWT_FM_OVERLAP_ITEMS", FM_OVL_MM_ITEMS), 4 * FM_SEARCH_MAX_LEN + 64);
+    const u64 batch = std::min<u64>(fm_env_u64("DEBWT_FM_OVERLAP_BATCH", FM_BATCH_PATTERNS), FM_BATCH_PATTERNS);
+    const u64 limit = fm_env_u64("DEBWT_FM_OVERLAP_HITS", FM_OVL_HITS);
+    for (u32 l = 1; l <= max_mismatches; l++) if ((rc = fm_search_buf(f, f->s_items[l], (size_t)cap * 24))) return rc;
+    if ((rc = fm_search_buf(f, f->s_hits, (size_t)cap * sizeof(uint4)))) return rc;
+    if ((rc = fm_search_buf(f, f->s_ctr, 64))) return rc;
+    debwt_fm_overlaps_mm_stats &st = f->om_stats;
+    st.patterns = npat;
+    const u64 fixed = (u64)max_mismatches * cap * 24 + cap * sizeof(uint4);   // the level and run buffers this call may fill
+    st.scratch_bytes = fixed;
+    FmOvlMmRun r{};
+    r.f = f; r.kmax = max_mismatches; r.min_overlap = min_overlap; r.permille = max_error_permille; r.cap = cap;
+    for (u32 l = 0; l <= FM_SEARCH_MAX_K; l++) r.hint[l] = ~0ull;
+    HIPCHK(f, hipEventCreate(&r.e0));
+    if (hipEventCreate(&r.e1) != hipSuccess) { (void)hipEventDestroy(r.e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{r.e0, r.e1};
+    FmOvlMmBatch b;
+    std::vector<debwt_fm_overlap> tmp;                     // DEBWT_FM_OVERLAP_LONGEST: a batch's hits before the reduction
+    std::vector<uint64_t> loc;
+    bool fits = true;                                      // false once the hits so far exceed the capacity: count only
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 p1 = p0 + 1;
+        while (p1 < npat && p1 - p0 < batch && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS) p1++;
+        if ((rc = fm_overlaps_mm_walk(f, patterns, offsets, p0, p1, nstr, r, &b))) return rc;
+        const u64 at = hit_offsets[p0];
+        if (longest) {
+            tmp.resize(b.nhits);
+            if ((rc = fm_overlaps_mm_expand(f, b, limit, fixed, r.e0, r.e1, tmp.data()))) return rc;
+            loc.assign(b.np + 1, 0);
+            for (u64 j = 0; j < b.np; j++) loc[j + 1] = loc[j] + b.per[j];
+            if ((rc = debwt_fm_overlap_longest(tmp.data(), loc.data(), b.np, loc.data()))) {
+                f->err = "debwt_fm_overlaps_mm: a batch's hits are not in order"; return DEBWT_EINTERNAL;
+            }
+            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = at + loc[j + 1];
+            fits = fits && hits && at + loc[b.np] <= capacity;
+            if (fits && loc[b.np]) memcpy(hits + at, tmp.data(), loc[b.np] * sizeof(debwt_fm_overlap));
+        } else {
+            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = hit_offsets[p0 + j] + b.per[j];
+            fits = fits && (hits || !b.nhits) && at + b.nhits <= capacity;
+            if (fits && (rc = fm_overlaps_mm_expand(f, b, limit, fixed, r.e0, r.e1, hits + at))) return rc;
+        }
+        st.batches++;
+        p0 = p1;
+    }
+    const u64 total = hit_offsets[npat];
+    st.hits = total;
+    if (!fits || capacity < total) {
+        f->err = "debwt_fm_overlaps_mm: capacity below the hits (hit_offsets[npat] = " + std::to_string(total) + ")";
+        return DEBWT_ERANGE;
+    }
+    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_overlaps_mm_stats_get(const debwt_fm *f, debwt_fm_overlaps_mm_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->om_stats;
     return DEBWT_OK;
 }
 

@@ -549,7 +549,7 @@ int debwt_fm_mems_stats_get(const debwt_fm *fm, debwt_fm_mems_stats *out);
  *   are bases.
  * A character outside ACGTacgt at Q[p] therefore limits L to m - 1 - p, and one at Q[m-1] gives no overlap.  EVERY overlap
  * is reported: the overlap of a record of the collection with itself (L = m = |S_j|), containments, and several lengths
- * with one record (periodic reads).  Exact overlaps only.
+ * with one record (periodic reads).  Exact overlaps only; debwt_fm_overlaps_mm below takes a mismatch budget.
  * A hit is (record j, length L, strand, flags): DEBWT_FM_OVERLAP_CONTAINS when L == |S_j| (the record is a suffix of Q),
  * DEBWT_FM_OVERLAP_WHOLE when L == m (Q is a prefix of the record).
  * Strand 1, read carefully: a strand-1 hit says that the last L bases of revcomp(P) start record j, that is, record j
@@ -596,6 +596,45 @@ int debwt_fm_overlaps_stats_get(const debwt_fm *fm, debwt_fm_overlaps_stats *out
  * when the input is not in that order (decreasing offsets, a strand above 1, strands descending, lengths ascending inside
  * a strand, records not strictly ascending inside a length). */
 int debwt_fm_overlap_longest(debwt_fm_overlap *hits, const uint64_t *offsets_in, uint64_t npat, uint64_t *offsets_out);
+
+/* ---- suffix-prefix overlaps with up to K mismatches (fm_overlap_mm_kernels.h) --------------------------------------
+ * Q, strand, m and S_j as in debwt_fm_overlaps.  For min_overlap <= L <= min(m, |S_j|) let mm(Q, j, L) be the number of
+ * columns c in [0, L) where Q[m-L+c] does not equal S_j[c] (A/C/G/T in either case; a character of Q outside ACGTacgt
+ * equals no base: one mismatch whatever the record holds, the rule of debwt_fm_search).  (Q, j, L) is a hit iff
+ *   mm <= max_mismatches  and  (max_error_permille == 0  or  1000 * mm <= max_error_permille * L).
+ * Every hit is reported once: self overlaps, containments and several lengths of one record all appear, and a record can
+ * appear at a length with mm > 0 next to a longer or shorter length with another mm.
+ * A hit is the debwt_fm_overlap of debwt_fm_overlaps: flags bits 0-1 are DEBWT_FM_OVERLAP_CONTAINS / DEBWT_FM_OVERLAP_WHOLE,
+ * bits 8-15 hold mm (DEBWT_FM_OVERLAP_MM).  The order per pattern is that of debwt_fm_overlaps, (strand, length DESCENDING,
+ * record ascending); mm takes no part in it, and as a (record, length, strand) occurs once the order is total and
+ * debwt_fm_overlap_longest accepts the list as it is.  DEBWT_FM_BOTH_STRANDS and DEBWT_FM_OVERLAP_LONGEST as there:
+ * LONGEST keeps the largest L per (pattern, strand, record) whatever its mm, bit for bit what debwt_fm_overlap_longest
+ * makes of the full list.  With max_mismatches 0 the result is that of debwt_fm_overlaps with the same arguments,
+ * hit_offsets and every byte of hits.
+ * max_mismatches 0..4, max_error_permille 0..1000 (0: no rate limit), a pattern of at most 1024 bytes, fewer than 2^31
+ * patterns; otherwise, and for min_overlap 0, unknown flags and decreasing offsets, DEBWT_EINVAL with the reason in
+ * debwt_fm_last_error.  An empty pattern, or one shorter than min_overlap, has 0 hits.  DEBWT_ERANGE as debwt_fm_overlaps:
+ * hit_offsets is written first, the remaining batches are only counted.  No attached text is needed.
+ * Batches are cut at 64 MB of pattern bytes and DEBWT_FM_OVERLAP_BATCH patterns (environment, read per call; default and
+ * cap 2^20).  Device scratch is capped as in debwt_fm_search: one buffer of DEBWT_FM_OVERLAP_ITEMS (environment, read per
+ * call; default 2^23, raised to at least 4 * 1024 + 64 so that a chunk of one item always fits) items of 24 bytes per
+ * level 1..K and one of as many runs of 16 bytes, 0.94 GB at K = 4 and the default; beside them, as in
+ * debwt_fm_overlaps, 24 bytes per run found in one batch, 16 per hit of one launch (at most DEBWT_FM_OVERLAP_HITS,
+ * default 2^24) and the pattern bytes, each with up to 25 % slack.  The result depends on none of the limits. */
+#define DEBWT_FM_OVERLAP_MM(flags) (((flags) >> 8) & 0xFFu)   /* mismatches of a hit of debwt_fm_overlaps_mm */
+int debwt_fm_overlaps_mm(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                         uint32_t min_overlap, uint32_t max_mismatches, uint32_t max_error_permille, uint32_t flags,
+                         uint64_t *hit_offsets, debwt_fm_overlap *hits, uint64_t capacity);
+/* what the last debwt_fm_overlaps_mm did: patterns, batches, kernel launches (levels and expansions), the level launches
+ * re-run in smaller chunks after a buffer overflowed, runs (one per work item and length with at least one record), hits
+ * (hit_offsets[npat]), rank steps (one fm_occ4 each), rank lines read, wave steps (64 x the longest lane per wave), the
+ * scratch this call may fill, work items per mismatch level, kernel time (events) and host wall time */
+typedef struct {
+    uint64_t patterns, batches, launches, retries, runs, hits, steps, line_reads, wave_steps, scratch_bytes;
+    uint64_t items[5];          /* work items per mismatch level, as debwt_fm_search_stats */
+    float ms_kernel, ms_wall;
+} debwt_fm_overlaps_mm_stats;
+int debwt_fm_overlaps_mm_stats_get(const debwt_fm *fm, debwt_fm_overlaps_mm_stats *out);
 
 /* ---- gapped extension of seeds and a read mapper (fm_extend_kernels.h) -------------------------------------------
  * An index holds no text; the two entry points below read the text next to a seed, so it is attached first (n / 4 bytes
