@@ -233,11 +233,12 @@ class DeBWT:
         self._chk(self._L.debwt_kmer_count_sorted(self._h, _p64(km), _p64(ct), d.value, ctypes.byref(d)))
         return km[:d.value], ct[:d.value]
 
-    def radix_sort_device(self, keys_ptr, tmp_ptr, count, key_bits=64, want_ms=False):
-        """Sort `count` u64 keys resident in HBM (raw device pointers, e.g. torch tensor .data_ptr())."""
+    def radix_sort_device(self, keys_ptr, tmp_ptr, count, key_bits=64, want_ms=False, key_lo=0, key_hi=0):
+        """Sort `count` u64 keys resident in HBM (raw device pointers, e.g. torch tensor .data_ptr()).
+        key_lo, key_hi: bounds the caller vouches for, every key in [key_lo, key_hi) (key_hi = 0: no upper bound)."""
         ms = ctypes.c_float()
-        self._chk(self._L.debwt_radix_sort_u64(self._h, ctypes.c_void_p(keys_ptr), ctypes.c_void_p(tmp_ptr), count,
-                                               key_bits, ctypes.byref(ms) if want_ms else None))
+        self._chk(self._L.debwt_radix_sort_u64_range(self._h, ctypes.c_void_p(keys_ptr), ctypes.c_void_p(tmp_ptr), count,
+                                                     key_bits, int(key_lo), int(key_hi), ctypes.byref(ms) if want_ms else None))
         return ms.value
 
     def bwt_device_ptr(self):

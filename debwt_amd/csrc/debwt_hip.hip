@@ -65,7 +65,7 @@ struct debwt_ctx {
     // device buffers
     DevBuf rs_rle, text, sepbits, sep, keysA, keysB, rs_counts, cp_counts, dk, dstart, mchar, head_keys, facts, facts_tmp,
         red, red_q, mi_j0, mi_freq, bstart, cursor, blue, spkey, sprow, spchr, branch, pflag, spsym, spn, bwt,
-        hmask, hash_rows, dollar, large_q, large_k0, large_en, rowsym, momask, mimask, rbits, rs_over, rs_skew, mi_list, htab, fact_work, facts_all, shard_hist, dest_tab, qbounds, qcursor, qlist, qwave;
+        hmask, hash_rows, dollar, large_q, large_k0, large_en, rowsym, momask, mimask, rbits, rs_over, rs_skew, rs_pair, mi_list, htab, fact_work, facts_all, shard_hist, dest_tab, qbounds, qcursor, qlist, qwave;
     DevBuf brbits;              // the special branches as a bitmap over the text positions (collections of many records)
     DevBuf blue_done;           // one byte per multi-in block: finished by k_blue_classify
     bool branch_bitmap = false;
@@ -284,25 +284,31 @@ RadixWorkspace radix_ws(debwt_ctx *c) {
     ws.h_over = c->h_over;
     ws.over_cap = c->rs_over.cap >= 48 ? (u32)std::min<size_t>((c->rs_over.cap - 32) / 16, 0xFFFFFFFFu) : 0;
     ws.skew_list = c->rs_skew.as<u32>();
+    ws.pair = c->rs_pair.as<u32>();                          // grown by whoever sorts enough keys to gain from it
+    ws.pair_cap = c->rs_pair.cap;
     return ws;
 }
 
 // main: the key sort of a range (kernels named for the profile, keys possibly read off the text); otherwise one of
 // the small auxiliary sorts.  Pass events are recorded when `record_passes`.
 int sort_keys(debwt_ctx *c, u64 *a, u64 *b, u64 count, int key_bits, u64 **result, bool record_passes,
-              const TextKeySrc *text = nullptr, bool main_sort = false, RleSink *sink = nullptr) {
+              const TextKeySrc *text = nullptr, bool main_sort = false, RleSink *sink = nullptr, const u64 *key_range = nullptr) {
     ENSURE(c, c->rs_over, radix_over_bytes(count));      // one list entry per 4096-key tile can be oversize
+    // the joint counts of the last two array passes of a key range (no bytes unless the range's top byte is narrow)
+    const u64 text_range[2] = {text ? text->key_lo : 0ull, text ? text->key_hi : 0ull};
+    if (!key_range && text) key_range = text_range;
+    ENSURE(c, c->rs_pair, radix_pair_bytes_u64(count, key_bits, key_range));
     RadixWorkspace ws = radix_ws(c);
     hipError_t e = hipSuccess;
     const bool main = main_sort || record_passes;
     const int net = (c->cfg.reserved & 32768) ? 32 : 0;     // bit 15: the bucket finish prefers the 4096-key network (tests)
     if (record_passes) {
         *result = radix_sort_u64(c->stream, a, b, count, key_bits, ws, c->cfg.sort_algo | net, &c->ev_pass[0][0], 16,
-                                 &c->n_pass_events, &e, text, sink);
+                                 &c->n_pass_events, &e, text, sink, key_range);
         c->st.radix_pass_keys = count;
     } else {
         *result = radix_sort_u64(c->stream, a, b, count, key_bits, ws, c->cfg.sort_algo | net | (main ? 0 : 16), nullptr, 0,
-                                 nullptr, &e, text, sink);
+                                 nullptr, &e, text, sink, key_range);
     }
     if (e != hipSuccess) { c->err = std::string("radix sort: ") + hipGetErrorString(e); return DEBWT_EDEVICE; }
     return DEBWT_OK;
@@ -318,7 +324,7 @@ static std::vector<DevBuf *> all_buffers(debwt_ctx *c) {
             &c->dstart, &c->mchar, &c->head_keys, &c->facts, &c->facts_tmp, &c->red, &c->red_q,
             &c->mi_j0, &c->mi_freq, &c->bstart, &c->cursor, &c->blue, &c->spkey, &c->sprow, &c->spchr,
             &c->branch, &c->pflag, &c->spsym, &c->spn, &c->bwt, &c->hmask, &c->hash_rows, &c->dollar,
-            &c->large_q, &c->large_k0, &c->large_en, &c->rowsym, &c->momask, &c->mimask, &c->rbits, &c->rs_over, &c->rs_skew,
+            &c->large_q, &c->large_k0, &c->large_en, &c->rowsym, &c->momask, &c->mimask, &c->rbits, &c->rs_over, &c->rs_skew, &c->rs_pair,
             &c->mi_list, &c->htab, &c->fact_work, &c->facts_all, &c->shard_hist, &c->dest_tab, &c->qbounds, &c->qcursor,
             &c->sx, &c->sppos, &c->sprec, &c->tail_d, &c->brbits,
             &c->blk_j0, &c->blk_freq, &c->blk_start, &c->facts_acc, &c->large_tmp, &c->blue_tmp, &c->sub_start, &c->sub_j0,
@@ -836,6 +842,12 @@ static int sort_begin(debwt_ctx *c) {
     ENSURE(c, c->keysB, maxM * 8 + 64);
     ENSURE(c, c->rs_skew, (maxM / 2048 + 2) * 4);
     ENSURE(c, c->rs_rle, radix_rle_ws_bytes(maxM));
+    size_t pair_bytes = 0;                                // the joint counts of every range fit what the widest one needs
+    for (auto &r : c->ranges) {
+        const u64 range[2] = {r.key_lo, r.key_hi};
+        pair_bytes = std::max(pair_bytes, radix_pair_bytes_u64(r.M, 2 * c->cfg.k, range));
+    }
+    ENSURE(c, c->rs_pair, pair_bytes);
     ENSURE(c, c->dk, maxM * 8 + 64);
     ENSURE(c, c->dstart, maxM * 4 + 64);
     ENSURE(c, c->pflag, maxM + 64);                      // classification byte per distinct key of a range
@@ -909,9 +921,10 @@ static int sort_range(debwt_ctx *c, size_t i, u64 *imported) {
                  // the sorted keys can be asked for (debwt_fetch_array) after the sort stage of a one-range build driven
                  // stage by stage on one GPU, and by nobody else: every other build keeps the encoding only (tune bit 23: keeps both -- A/B)
                  (P > 1 || c->exchange || c->whole_build || c->shard_world > 1) && !(c->cfg.reserved & 8388608), false};
+    const u64 key_range[2] = {r.key_lo, r.key_hi};        // imported keys are the range's too
     if (imported && r.M < 2) c->sk = c->sort_a;
     else if ((rc = sort_keys(c, c->sort_a, c->sort_b, r.M, 2 * c->cfg.k, &c->sk, i == 0, imported ? nullptr : &ts, true,
-                             (c->cfg.reserved & 256) ? nullptr : &sink))) return rc;
+                             (c->cfg.reserved & 256) ? nullptr : &sink, key_range))) return rc;
     if (P == 1 && !c->exchange) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     if (!sink.done) {
         RleF f{c->sk, c->dk.as<u64>(), c->dstart.as<u32>(), c->mchar.as<u8>() + r.Mbase};
@@ -1381,6 +1394,7 @@ extern "C" int debwt_sp_generate(debwt_ctx *c) {
             bool stripped = false;                                                     // (the last pass strips when it writes to `reg`)
             if (span) {
                 ENSURE(c, c->rs_over, radix_over_bytes(r.B));
+                ENSURE(c, c->rs_pair, radix_pair_bytes(r.B, qshift, std::min(64, qshift + span), true, nullptr));
                 u64 *tmp = c->keysA.as<u64>();
                 if (c->keysA.cap < r.B * 8 + 64) { ENSURE(c, c->blue_tmp, r.B * 8 + 64); tmp = c->blue_tmp.as<u64>(); }
                 hipError_t e = hipSuccess;
@@ -1398,6 +1412,7 @@ extern "C" int debwt_sp_generate(debwt_ctx *c) {
         if (c->keysA.cap >= c->B * 8) tmp = c->keysA.as<u64>();
         else { ENSURE(c, c->blue_tmp, c->B * 8 + 64); tmp = c->blue_tmp.as<u64>(); }
         ENSURE(c, c->rs_over, radix_over_bytes(c->B));
+        ENSURE(c, c->rs_pair, radix_pair_bytes(c->B, qshift, 64, true, nullptr));
         hipError_t e = hipSuccess;
         bool stripped = false;                                   // (the last pass strips when it writes to `blue`)
         u64 *third = c->keysB.cap >= c->B * 8 + 64 && c->keysB.as<u64>() != tmp ? c->keysB.as<u64>() : nullptr;
@@ -2333,6 +2348,7 @@ extern "C" int debwt_shard_blue_place(debwt_ctx *c, uint64_t *d_entries, uint64_
     // bit 5.)
     if (count >= 2 && count < 0xFFFFFFF0ull - (1ull << 20) && !(c->cfg.reserved & 32)) {
         ENSURE(c, c->rs_over, radix_over_bytes(count));
+        ENSURE(c, c->rs_pair, radix_pair_bytes(count, qshift, 64, true, nullptr));
         // the passes of debwt_sp_generate's entry sort: bits spread evenly, the strip folded into the stores of the last one,
         // which writes `blue`; an even number of passes takes its first hop through a free key buffer
         {
@@ -2577,16 +2593,44 @@ extern "C" int debwt_kmer_count_sorted(debwt_ctx *c, uint64_t *kmers, uint64_t *
 
 extern "C" int debwt_radix_sort_u64(debwt_ctx *c, uint64_t *d_keys, uint64_t *d_tmp, uint64_t count, int key_bits,
                                     float *ms_per_pass) {
+    return debwt_radix_sort_u64_range(c, d_keys, d_tmp, count, key_bits, 0, 0, ms_per_pass);
+}
+
+extern "C" uint64_t debwt_radix_pair_passes(void) { return radix_pair_passes(); }
+
+// keys outside [lo, hi] (a derived pass sizes the runs of its digits by the bounds: such a key would be stored outside its run)
+__global__ void k_keys_outside(const u64 *__restrict__ keys, u64 n, u64 lo, u64 hi, u32 *__restrict__ flag) {
+    bool bad = false;
+    for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) bad |= keys[i] < lo || keys[i] > hi;
+    if (bad) *flag = 1u;
+}
+
+extern "C" int debwt_radix_sort_u64_range(debwt_ctx *c, uint64_t *d_keys, uint64_t *d_tmp, uint64_t count, int key_bits,
+                                          uint64_t key_lo, uint64_t key_hi, float *ms_per_pass) {
     if (!c || !d_keys || !d_tmp || key_bits < 1 || key_bits > 64) return DEBWT_EINVAL;
+    if (key_hi && key_hi <= key_lo) return DEBWT_EINVAL;
     if (count >= 0xFFFFFFF0ull) return DEBWT_ERANGE;
     HIPCHK(c, hipSetDevice(c->cfg.device));
     ENSURE(c, c->rs_skew, (count / 2048 + 2) * 4);
     ENSURE(c, c->rs_over, radix_over_bytes(count));
+    const u64 range[2] = {key_lo, key_hi};
+    const u64 *rg = key_lo || key_hi ? range : nullptr;
+    if (rg) {
+        const u64 top = key_bits >= 64 ? ~0ull : (1ull << key_bits) - 1ull;
+        u32 outside = 0;
+        HIPCHK(c, hipMemsetAsync(c->rs_over.p, 0, 4, c->stream));
+        k_keys_outside<<<(u32)std::min<u64>(2048, (count + 255) / 256), 256, 0, c->stream>>>((const u64 *)d_keys, count, key_lo, key_hi ? key_hi - 1 : top,
+                                                                                            c->rs_over.as<u32>());
+        HIPCHK(c, hipMemcpyAsync(&outside, c->rs_over.p, 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (outside) { c->err = "a key lies outside [key_lo, key_hi)"; return DEBWT_EINVAL; }
+    }
+    ENSURE(c, c->rs_pair, radix_pair_bytes_u64(count, key_bits, rg));
     RadixWorkspace ws = radix_ws(c);
     hipError_t e = hipSuccess;
     int np = 0;
     u64 *res = radix_sort_u64(c->stream, (u64 *)d_keys, (u64 *)d_tmp, count, key_bits, ws, c->cfg.sort_algo,
-                              ms_per_pass ? &c->ev_pass[0][0] : nullptr, 16, &np, &e);
+                              ms_per_pass ? &c->ev_pass[0][0] : nullptr, 16, &np, &e, nullptr, nullptr, rg);
     if (e != hipSuccess) { c->err = hipGetErrorString(e); return DEBWT_EDEVICE; }
     if (res != (u64 *)d_keys)
         HIPCHK(c, hipMemcpyAsync(d_keys, res, count * 8, hipMemcpyDeviceToDevice, c->stream));

@@ -24,7 +24,19 @@ struct RadixWorkspace {
     u32 *h_over;        // pinned host word for the count
     u32 over_cap;       // entries the list holds (radix_over_bytes sizes it for one entry per 4096-key tile)
     u32 *skew_list;     // hybrid path: one byte per 4096-key tile, set when a 1024-key wave tile did not fit
+    u32 *pair;          // pair counts (optional): the chunk table of a derived pass, then the joint counts J of the pass before it
+    size_t pair_cap;    // bytes behind `pair`; a pair of passes whose J does not fit runs a count pass each, as without it
 };
+
+// Bytes of RadixWorkspace::pair that let rs_lsd drop the count pass of every second array pass (see rs_hist_pair_kernel):
+// for the stable passes over the bits [lo_bit, hi_bit) of n keys, `aux` as in radix_sort_bits (else 8 bits per pass).
+// range (optional): {lo, hi}, every key lies in [lo, hi) (hi = 0: no upper bound); the key sort needs it, an auxiliary
+// sort takes the bounds of a digit from its width.  0: no pair of passes qualifies.
+size_t radix_pair_bytes(u64 n, int lo_bit, int hi_bit, bool aux, const u64 *range);
+// the same for radix_sort_u64(n keys, key_bits) with any algo
+size_t radix_pair_bytes_u64(u64 n, int key_bits, const u64 *range);
+// passes this process has launched with derived chunk histograms (tests: which form a sort took)
+u64 radix_pair_passes();
 
 // Optional key source for the FIRST pass: node keys (node << 2 | pred) computed on the fly from the 2-bit text,
 // one per position whose K-window holds no separator -- the key array is then never written out unsorted.
@@ -94,6 +106,8 @@ bool radix_sort_bits_into(hipStream_t stream, u64 *a, u64 *dst, u64 *third, u64 
 // in registers and writes the row symbols key & 3, and the run-length encoding of the sorted keys -- distinct keys,
 // first row of each (row = index in sorted order) -- follows tile by tile without a counting pass over the keys.
 // `done` tells the caller whether that happened; if not, it encodes the returned keys itself.
+// key_range (optional): {lo, hi}, every key lies in [lo, hi) (hi = 0: no upper bound) -- with `text` its key_lo / key_hi
+// say the same; the last array pass then takes its chunk histograms from the pass before it (RadixWorkspace::pair).
 struct RleSink {
     u64 *dk; u32 *dstart; u8 *mchar;   // out: distinct keys, their first rows, one symbol per row
     void *ws;                          // radix_rle_ws_bytes(n) bytes of device scratch
@@ -109,4 +123,4 @@ struct RleSink {
 size_t radix_rle_ws_bytes(u64 n);
 u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, const RadixWorkspace &ws,
                     int algo, hipEvent_t *pass_events, int max_pairs, int *npairs, hipError_t *err,
-                    const TextKeySrc *text = nullptr, RleSink *sink = nullptr);
+                    const TextKeySrc *text = nullptr, RleSink *sink = nullptr, const u64 *key_range = nullptr);

@@ -10,6 +10,7 @@
 #include "radix_sort.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
 #include <utility>
 #include <cstdio>
@@ -184,6 +185,118 @@ __global__ __launch_bounds__(RS_BLOCK) void rs_hist_kernel(const u64 *__restrict
     }
     __syncthreads();
     counts[(u64)threadIdx.x * nchunks + blockIdx.x] = h[threadIdx.x];
+}
+
+// ---- pair counts: the chunk histograms of pass p+1 out of the read of pass p ---------------------------------------
+// A stable pass p writes its output digit-major and chunk-minor: the keys of (digit d, chunk c) -- a UNIT -- form one
+// contiguous run, and the runs follow each other in the order of the counts table.  When digit p+1 takes few values
+// (the top byte inside a key range, a 6- or 7-bit digit of an auxiliary sort), the count kernel of pass p counts the
+// cells J[d][v] (v = digit p+1 minus its smallest value) instead of h[d]; pass p+1 takes chunks that are whole units,
+// and its chunk histograms are sums of rows of J: it needs no read of the keys.
+//
+// rs_hist_pair_kernel: rs_hist_kernel<0, AUX> with the joint count in dynamic LDS (rows * nv words).  Writes
+// J[(d * nchunks + c) * nv + v] and counts[d * nchunks + c] = sum over v.
+#define RS_PAIR_LDS_MAX 65536u
+#define RS_PAIR_UNROLL 4               // 16-byte loads in flight per lane: the joint count leaves room for 2-4 workgroups per CU
+template <int AUX>
+__global__ __launch_bounds__(RS_BLOCK) void rs_hist_pair_kernel(const u64 *__restrict__ keys, u64 n, u64 chunk, RsDigit dg, RsDigit dn,
+                                                                 u32 vbase, u32 nv, u32 rows, u32 *__restrict__ counts,
+                                                                 u32 *__restrict__ J, u32 nchunks) {
+    extern __shared__ u32 hj[];
+    const u32 cells = rows * nv;
+    for (u32 i = threadIdx.x; i < cells; i += RS_BLOCK) hj[i] = 0;
+    __syncthreads();
+    const u64 beg = (u64)blockIdx.x * chunk;
+    const u64 end = beg + chunk < n ? beg + chunk : n;
+    // (a key outside the bounds the caller gave would index outside the table: it is counted in the last column instead;
+    // the callers vouch for the bounds -- a key range cut from the text, a checked array -- since the derived pass has no
+    // room for a key whose digit was not counted)
+    auto cell = [&](u64 k) {
+        const u32 v = rs_digit<!AUX>(dn, k) - vbase;
+        return rs_digit<!AUX>(dg, k) * nv + (v < nv ? v : nv - 1u);
+    };
+    auto add2 = [&](const ulonglong2 &v) {
+        const u32 c0 = cell(v.x), c1 = cell(v.y);
+        if (AUX) {                                            // one cell for the whole wave: one lane adds (see rs_hist_kernel)
+            const u32 f = (u32)__builtin_amdgcn_readfirstlane((int)c0);
+            if (__ballot(c0 != f || c1 != f) == 0ull) {
+                const u64 act = __ballot(1);
+                if ((threadIdx.x & 63u) == (u32)__ffsll((long long)act) - 1u) atomicAdd(&hj[f], 2u * (u32)__popcll(act));
+                return;
+            }
+        }
+        atomicAdd(&hj[c0], 1u);
+        atomicAdd(&hj[c1], 1u);
+    };
+    // chunk is a multiple of RS_TILE, so beg is 16-byte aligned: two keys per lane per load
+    u64 i = beg + 2ull * threadIdx.x;
+    for (; i + 2ull * RS_BLOCK * (RS_PAIR_UNROLL - 1) + 1 < end; i += 2ull * RS_BLOCK * RS_PAIR_UNROLL) {
+        ulonglong2 v[RS_PAIR_UNROLL];
+#pragma unroll
+        for (int j = 0; j < RS_PAIR_UNROLL; j++) v[j] = *reinterpret_cast<const ulonglong2 *>(keys + i + 2ull * RS_BLOCK * j);
+#pragma unroll
+        for (int j = 0; j < RS_PAIR_UNROLL; j++) add2(v[j]);
+    }
+    for (; i < end; i += 2ull * RS_BLOCK) {
+        if (i + 1 < end) add2(*reinterpret_cast<const ulonglong2 *>(keys + i));
+        else atomicAdd(&hj[cell(keys[i])], 1u);
+    }
+    __syncthreads();
+    for (u32 j = threadIdx.x; j < cells; j += RS_BLOCK) {
+        const u32 d = j / nv, v = j - d * nv;
+        J[((u64)d * nchunks + blockIdx.x) * nv + v] = hj[j];
+    }
+    u32 s = 0;
+    if (threadIdx.x < rows)
+        for (u32 v = 0; v < nv; v++) s += hj[threadIdx.x * nv + v];
+    counts[(u64)threadIdx.x * nchunks + blockIdx.x] = s;
+}
+
+// Chunks of pass p+1: boundary k is the first unit that starts at or after k * chunk (bisection over the unit starts
+// digit_base[d] + offsets[d][c], which pass p has scanned; they ascend in the order of the table).  Units that start at
+// the same key are empty except the last of them: the chunk before the boundary ends in front of them, the chunk behind
+// it begins at the last, so that no chunk sums the rows of a stretch of empty units at its ends.
+// tab: [0, nb) first key of chunk k (tab[nchunks] = n), [nb, 2 nb) first unit of chunk k, [2 nb, 3 nb) the unit behind
+// chunk k - 1; nb = nchunks + 1.
+__global__ void rs_pair_bounds_kernel(const u32 *__restrict__ offsets, const u32 *__restrict__ digit_base, u32 nchunks_p, u32 rows,
+                                      u64 n, u64 chunk, u32 nchunks, u32 *__restrict__ tab) {
+    const u32 k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > nchunks) return;
+    const u32 U = rows * nchunks_p, nb = nchunks + 1;
+    auto start = [&](u32 u) { return (u64)digit_base[u / nchunks_p] + offsets[u]; };
+    auto first_at = [&](u64 t) {                             // first unit with start >= t, U if none
+        u32 lo = 0, hi = U;
+        while (lo < hi) { const u32 mid = lo + ((hi - lo) >> 1); if (start(mid) >= t) hi = mid; else lo = mid + 1; }
+        return lo;
+    };
+    const u32 f = first_at((u64)k * chunk);
+    if (f == U) { tab[k] = (u32)n; tab[nb + k] = U; tab[2 * nb + k] = U; return; }
+    const u64 s = start(f);
+    tab[k] = (u32)s;
+    tab[nb + k] = first_at(s + 1) - 1u;
+    tab[2 * nb + k] = f;
+}
+
+// Chunk histograms of pass p+1: workgroup k sums the rows of J over the units of chunk k (consecutive rows) and writes
+// them at the real digit value, row v + vbase; every other row is zero.
+__global__ __launch_bounds__(RS_RADIX) void rs_pair_derive_kernel(const u32 *__restrict__ J, const u32 *__restrict__ tab, u32 nv,
+                                                                   u32 vbase, u32 *__restrict__ counts, u32 nchunks) {
+    __shared__ u32 acc[RS_RADIX];
+    acc[threadIdx.x] = 0;
+    __syncthreads();
+    const u32 nb = nchunks + 1;
+    const u64 b = (u64)tab[nb + blockIdx.x] * nv, e = (u64)tab[2 * nb + blockIdx.x + 1] * nv;
+    u32 v = threadIdx.x % nv;                                // b is a multiple of nv
+    const u32 step = RS_RADIX % nv;
+    for (u64 i = b + threadIdx.x; i < e; i += RS_RADIX) {
+        const u32 x = J[i];
+        if (x) atomicAdd(&acc[v], x);
+        v += step;
+        if (v >= nv) v -= nv;
+    }
+    __syncthreads();
+    const u32 r = threadIdx.x - vbase;
+    counts[(u64)threadIdx.x * nchunks + blockIdx.x] = r < nv ? acc[r] : 0u;
 }
 
 // first-pass histograms of several key ranges in one scan of the text (see radix_sort.h)
@@ -622,7 +735,8 @@ __device__ __forceinline__ void rs_flush_body(ScShared &sh, const RsDigit &dg, u
 template <int SRC, int AUX, int HI>
 __global__ __launch_bounds__(SC_NT) __attribute__((amdgpu_waves_per_eu(RS_WAVES_EU, RS_WAVES_EU)))
 void rs_scatter_kernel(const u64 *__restrict__ in, TextKeySrc ts, u64 *__restrict__ out, u64 n, u64 chunk, RsDigit dg,
-                       const u32 *__restrict__ offsets, const u32 *__restrict__ digit_base, u32 nchunks) {
+                       const u32 *__restrict__ offsets, const u32 *__restrict__ digit_base, u32 nchunks,
+                       const u32 *__restrict__ chunk_tab = nullptr) {
     constexpr int DG = AUX ? 0 : (HI ? 2 : 1);
     __shared__ ScShared sh;
     __shared__ u64 stext[SRC ? RS_STEXT : 1], ssep[SRC ? RS_SSEP : 1];
@@ -634,6 +748,9 @@ void rs_scatter_kernel(const u64 *__restrict__ in, TextKeySrc ts, u64 *__restric
     const u32 oalign = (u32)(reinterpret_cast<uintptr_t>(out) >> 3) & (SC_LINE - 1u);   // lines are 128-byte aligned addresses
     u64 beg = (u64)blockIdx.x * chunk;
     u64 end = beg + chunk < n ? beg + chunk : n;
+    // a pass whose chunk histograms were derived (rs_pair_derive_kernel) takes the keys [tab[c], tab[c + 1]) of its chunk
+    // from the table of rs_pair_bounds_kernel: whole units of the pass before, any start (the tile loads are 8-byte loads)
+    if (SRC == 0 && chunk_tab) { beg = chunk_tab[blockIdx.x]; end = chunk_tab[blockIdx.x + 1]; }
     TextStage st{stext, ssep, 0, 0};
     rs_clear_rank_state(sh);
     lds_barrier();
@@ -2043,9 +2160,75 @@ static void rs_plan(u64 n, u32 *nchunks, u64 *chunk) {
 
 size_t radix_over_bytes(u64 max_keys) { return 16 + (size_t)(max_keys / RL_H + 2) * 16 + 16; }
 
+// bits of the pass that has `left` bits in front of it (auxiliary sorts spread their bits evenly, see rs_lsd)
+static int rs_pass_bits(bool aux, int left) {
+    const int passes_left = (left + 7) / 8;
+    return aux ? (left + passes_left - 1) / passes_left : (left < 8 ? left : 8);
+}
+
+// ---- pair counts (rs_hist_pair_kernel): which pairs of passes qualify and what they need ----------------------------
+#define RS_PAIR_TAB_WORDS ((3u * (RS_MAXCHUNKS + 1u) + 63u) / 64u * 64u)     // the chunk table in front of J
+struct PairPlan { u32 rows, nv, vbase; };                                   // nv = 0: the pass behind counts for itself
+// {lo, hi} with hi exclusive and 0 for none -> the smallest and the largest key
+static const u64 *rs_range_incl(const u64 *range, int hi_bit, u64 (&incl)[2]) {
+    if (!range) return nullptr;
+    incl[0] = range[0];
+    incl[1] = range[1] ? range[1] - 1 : (hi_bit >= 64 ? ~0ull : (1ull << hi_bit) - 1ull);
+    return incl[0] <= incl[1] ? incl : nullptr;
+}
+// The pass of `bits` bits at `shift` and the pass behind it, of stable passes up to hi_bit.  An auxiliary sort knows the
+// values of the next digit from its width; the key sort knows them for the top digit of a key range [incl[0], incl[1]].
+static PairPlan rs_pair_plan(bool aux, int shift, int bits, int hi_bit, const u64 *incl, u64 n) {
+    const PairPlan none{0, 0, 0};
+    const int nshift = shift + bits, left = hi_bit - nshift;
+    if (left <= 0 || n < 2 || n >= 0xFFFFFFF0ull) return none;            // (the chunk table holds 32-bit key positions)
+    const int nbits = rs_pass_bits(aux, left);
+    u32 vlo = 0, vhi = (1u << nbits) - 1u;
+    if (!aux) {
+        if (!incl || nbits < left) return none;
+        if (hi_bit < 64 && (incl[0] >> hi_bit) != (incl[1] >> hi_bit)) return none;
+        vlo = (u32)(incl[0] >> nshift) & vhi;
+        vhi = (u32)(incl[1] >> nshift) & vhi;
+        if (vhi < vlo) return none;
+    }
+    const u32 nv = vhi - vlo + 1u, rows = 1u << bits;
+    if ((size_t)rows * nv * sizeof(u32) > RS_PAIR_LDS_MAX) return none;
+    return PairPlan{rows, nv, vlo};
+}
+static size_t rs_pair_need(const PairPlan &pp, u32 nchunks) {
+    return ((size_t)RS_PAIR_TAB_WORDS + (size_t)pp.rows * nchunks * pp.nv) * sizeof(u32);
+}
+
+size_t radix_pair_bytes(u64 n, int lo_bit, int hi_bit, bool aux, const u64 *range) {
+    u64 incl[2];
+    const u64 *rg = rs_range_incl(range, hi_bit, incl);
+    u32 nchunks; u64 chunk;
+    rs_plan(n, &nchunks, &chunk);
+    size_t need = 0;
+    bool derived = false;
+    for (int shift = lo_bit, bits = 0; shift < hi_bit; shift += bits) {
+        bits = rs_pass_bits(aux, hi_bit - shift);
+        if (derived) { derived = false; continue; }
+        const PairPlan pp = rs_pair_plan(aux, shift, bits, hi_bit, rg, n);
+        if (pp.nv) { need = std::max(need, rs_pair_need(pp, nchunks)); derived = true; }
+    }
+    return need;
+}
+
+size_t radix_pair_bytes_u64(u64 n, int key_bits, const u64 *range) {
+    if (key_bits > 64) key_bits = 64;
+    if (key_bits < 1) return 0;
+    return std::max(radix_pair_bytes(n, radix_first_shift(n, key_bits, 3), key_bits, false, range),
+                    radix_pair_bytes(n, 0, key_bits, false, range));
+}
+
+static std::atomic<u64> rs_pair_launched{0};
+u64 radix_pair_passes() { return rs_pair_launched.load(std::memory_order_relaxed); }
+
 static u64 *rs_lsd(hipStream_t stream, u64 *a, u64 *b, u64 n, int lo_bit, int hi_bit, const RadixWorkspace &ws,
                    hipEvent_t *pass_events, int max_pairs, int *npairs, const TextKeySrc *text = nullptr,
-                   bool aux = false, int strip_last = 0, u64 *third = nullptr, u64 *final_dst = nullptr) {
+                   bool aux = false, int strip_last = 0, u64 *third = nullptr, u64 *final_dst = nullptr,
+                   const u64 *key_range = nullptr) {
     // stable LSD passes over bits [lo_bit, hi_bit), 8 bits per pass starting at lo_bit.  With `text` the first
     // pass reads node keys from the text (its index space is the ts->n positions) and writes them to `a`.
     // third (auxiliary sorts of an odd number of passes >= 3): a second scratch buffer, so that the LAST pass writes into `a`
@@ -2058,12 +2241,26 @@ static u64 *rs_lsd(hipStream_t stream, u64 *a, u64 *b, u64 n, int lo_bit, int hi
     const int npasses = (hi_bit - lo_bit + 7) / 8;
     if (final_dst) dst = (npasses - 1) % 2 == 0 ? final_dst : third;
     TextKeySrc none{};
+    // Pair counts: a pass whose next digit takes few values counts both digits in its one read of the keys, and the pass
+    // behind it derives its chunk histograms and takes its chunks from a table (rs_hist_pair_kernel ff.).  A derived pass
+    // cannot derive the next one, so pairs are (counted, derived): the last two array passes of a key range, passes (0, 1)
+    // and (2, 3) of an auxiliary sort.  DEBWT_HIST_EVERY_PASS=1: a count pass in front of every pass, as before (A/B, tests).
+    const bool pairs = ws.pair && !getenv("DEBWT_HIST_EVERY_PASS");
+    u64 incl[2];
+    const u64 *rg = rs_range_incl(key_range, hi_bit, incl);
+    u32 *const pair_tab = ws.pair, *const pair_J = ws.pair ? ws.pair + RS_PAIR_TAB_WORDS : nullptr;
+    bool derived = false;                  // the counts and the chunk table of this pass came out of the pass before
+    static const bool lds_set = [] {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&rs_hist_pair_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_PAIR_LDS_MAX);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&rs_hist_pair_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)RS_PAIR_LDS_MAX);
+        return true;
+    }();
+    (void)lds_set;
     // (auxiliary sorts spread their bits evenly over the passes -- 29 bits of block id: 8 + 7 + 7 + 7, not 8 + 8 + 8 + 5: the
     // histogram of a 5-bit digit adds 128 keys a wave to 32 counters and took 9.2 ms for 3.9 G blue entries where the 8-bit
     // passes before it took 4.1)
     for (int shift = lo_bit, bits = 0; shift < hi_bit; shift += bits, p++) {
-        const int left = hi_bit - shift, passes_left = (left + 7) / 8;
-        bits = aux ? (left + passes_left - 1) / passes_left : (left < 8 ? left : 8);
+        bits = rs_pass_bits(aux, hi_bit - shift);
         RsDigit dg{};
         dg.shift = shift; dg.mask = (1u << bits) - 1u;
         const bool from_text = text && p == 0;
@@ -2094,18 +2291,39 @@ static u64 *rs_lsd(hipStream_t stream, u64 *a, u64 *b, u64 n, int lo_bit, int hi
             continue;
         }
         bool ev = pass_events && ev_idx < max_pairs;
-        if (aux) rs_hist_kernel<0, 1><<<nchunks, RS_BLOCK, 0, stream>>>(src, none, n, chunk, dg, ws.counts, nchunks);
+        PairPlan pp{0, 0, 0};
+        if (pairs && !derived) {
+            pp = rs_pair_plan(aux, shift, bits, hi_bit, rg, n);
+            if (pp.nv && rs_pair_need(pp, nchunks) > ws.pair_cap) pp.nv = 0;
+        }
+        const u32 *ctab = derived ? pair_tab : nullptr;
+        if (derived) {
+            // counted by the pass before
+        } else if (pp.nv) {
+            RsDigit dn{};
+            dn.shift = shift + bits; dn.mask = (1u << rs_pass_bits(aux, hi_bit - dn.shift)) - 1u;
+            const size_t lds = (size_t)pp.rows * pp.nv * sizeof(u32);
+            if (aux) rs_hist_pair_kernel<1><<<nchunks, RS_BLOCK, lds, stream>>>(src, n, chunk, dg, dn, pp.vbase, pp.nv, pp.rows, ws.counts, pair_J, nchunks);
+            else rs_hist_pair_kernel<0><<<nchunks, RS_BLOCK, lds, stream>>>(src, n, chunk, dg, dn, pp.vbase, pp.nv, pp.rows, ws.counts, pair_J, nchunks);
+        } else if (aux) rs_hist_kernel<0, 1><<<nchunks, RS_BLOCK, 0, stream>>>(src, none, n, chunk, dg, ws.counts, nchunks);
         else rs_hist_kernel<0, 0><<<nchunks, RS_BLOCK, 0, stream>>>(src, none, n, chunk, dg, ws.counts, nchunks);
         rs_scan_digit_kernel<<<RS_RADIX, 1024, 0, stream>>>(ws.counts, nchunks, digit_tot);
         rs_scan_tot_kernel<<<1, RS_RADIX, 0, stream>>>(digit_tot);
         if (ev) (void)hipEventRecord(pass_events[2 * ev_idx], stream);
         if (aux && strip_last && shift + bits >= hi_bit) {
             dg.out_strip = strip_last;
-            rs_scatter_kernel<0, 2, 0><<<nchunks, SC_NT, 0, stream>>>(src, none, dst, n, chunk, dg, ws.counts, digit_tot, nchunks);
-        } else if (aux) rs_scatter_kernel<0, 1, 0><<<nchunks, SC_NT, 0, stream>>>(src, none, dst, n, chunk, dg, ws.counts, digit_tot, nchunks);
-        else if (shift >= 32) rs_scatter_kernel<0, 0, 1><<<nchunks, SC_NT, 0, stream>>>(src, none, dst, n, chunk, dg, ws.counts, digit_tot, nchunks);
-        else rs_scatter_kernel<0, 0, 0><<<nchunks, SC_NT, 0, stream>>>(src, none, dst, n, chunk, dg, ws.counts, digit_tot, nchunks);
+            rs_scatter_kernel<0, 2, 0><<<nchunks, SC_NT, 0, stream>>>(src, none, dst, n, chunk, dg, ws.counts, digit_tot, nchunks, ctab);
+        } else if (aux) rs_scatter_kernel<0, 1, 0><<<nchunks, SC_NT, 0, stream>>>(src, none, dst, n, chunk, dg, ws.counts, digit_tot, nchunks, ctab);
+        else if (shift >= 32) rs_scatter_kernel<0, 0, 1><<<nchunks, SC_NT, 0, stream>>>(src, none, dst, n, chunk, dg, ws.counts, digit_tot, nchunks, ctab);
+        else rs_scatter_kernel<0, 0, 0><<<nchunks, SC_NT, 0, stream>>>(src, none, dst, n, chunk, dg, ws.counts, digit_tot, nchunks, ctab);
         if (ev) { (void)hipEventRecord(pass_events[2 * ev_idx + 1], stream); ev_idx++; if (npairs) *npairs = ev_idx; }
+        derived = pp.nv != 0;
+        if (derived) {
+            // the offsets of this pass are the starts of the next pass's units: its chunks, then its counts into ws.counts
+            rs_pair_bounds_kernel<<<(nchunks + 1 + 255) / 256, 256, 0, stream>>>(ws.counts, digit_tot, nchunks, pp.rows, n, chunk, nchunks, pair_tab);
+            rs_pair_derive_kernel<<<nchunks, RS_RADIX, 0, stream>>>(pair_J, pair_tab, pp.nv, pp.vbase, ws.counts, nchunks);
+            rs_pair_launched.fetch_add(1, std::memory_order_relaxed);
+        }
         if (final_dst) { src = dst; dst = (npasses - (p + 2)) % 2 == 0 ? final_dst : (src == a ? third : a); }
         else if (third) { src = dst; dst = p + 2 == npasses ? a : (src == b ? third : b); }
         else { u64 *t = src; src = dst; dst = t; }
@@ -2174,7 +2392,7 @@ bool radix_sort_bits_into(hipStream_t stream, u64 *a, u64 *dst, u64 *third, u64 
 
 u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, const RadixWorkspace &ws, int algo,
                     hipEvent_t *pass_events, int max_pairs, int *npairs, hipError_t *err, const TextKeySrc *text,
-                    RleSink *sink) {
+                    RleSink *sink, const u64 *key_range) {
     *err = hipSuccess;
     if (sink) { sink->done = false; sink->n_over = 0; }
     if (npairs) *npairs = 0;
@@ -2184,16 +2402,18 @@ u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, con
     algo &= 15;
     if (key_bits > 64) key_bits = 64;
     if (!text && (n < 2 || key_bits <= 0)) return a;
+    const u64 text_range[2] = {text ? text->key_lo : 0ull, text ? text->key_hi : 0ull};
+    if (!key_range && text) key_range = text_range;
     // hybrid: T top digits in HBM so that a bucket holds at most RS_BUCKET_TARGET keys on average, the rest in registers
     int T = 0;
     while ((n >> (8 * T)) > RS_BUCKET_TARGET && T < 4) T++;
     if (algo != 3 || T == 0 || key_bits - 8 * T < 1 || !ws.over || !ws.h_over) {
-        u64 *r = rs_lsd(stream, a, b, n, 0, key_bits, ws, pass_events, max_pairs, npairs, text, aux);
+        u64 *r = rs_lsd(stream, a, b, n, 0, key_bits, ws, pass_events, max_pairs, npairs, text, aux, 0, nullptr, nullptr, key_range);
         *err = hipGetLastError();
         return r;
     }
     const int pshift = key_bits - 8 * T;
-    u64 *src = rs_lsd(stream, a, b, n, pshift, key_bits, ws, pass_events, max_pairs, npairs, text, aux);
+    u64 *src = rs_lsd(stream, a, b, n, pshift, key_bits, ws, pass_events, max_pairs, npairs, text, aux, 0, nullptr, nullptr, key_range);
     u64 *other = src == a ? b : a;
     (void)hipMemsetAsync(ws.over, 0, 16, stream);
     u32 ntiles = (u32)((n + RL_H - 1) / RL_H), nwtiles = (u32)((n + RLW_H - 1) / RLW_H);
@@ -2270,7 +2490,7 @@ u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, con
             }
         }
         if (whole) {
-            src = rs_lsd(stream, src, other, n, 0, key_bits, ws, nullptr, 0, nullptr);
+            src = rs_lsd(stream, src, other, n, 0, key_bits, ws, nullptr, 0, nullptr, nullptr, false, 0, nullptr, nullptr, key_range);
             staging_lost = true;                                   // both key buffers were overwritten
         } else {
             u64 *const free_buf = sink ? sink->dk : other;            // sink: `other` holds staged distinct keys

@@ -417,6 +417,14 @@ int debwt_kmer_count_sorted(debwt_ctx *ctx, uint64_t *kmers, uint64_t *counts, u
  * ms_per_pass (optional) receives the mean device time of one scatter pass. */
 int debwt_radix_sort_u64(debwt_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint64_t count, int key_bits,
                          float *ms_per_pass);
+/* The same for keys the caller knows to lie in [key_lo, key_hi) (key_hi = 0: no upper bound), as the keys of one key
+ * range of a build do: when the top byte of such keys takes few values, the last pass takes its chunk histograms from
+ * the count kernel of the pass before it.  DEBWT_EINVAL when a key lies outside the bounds (nothing is sorted then). */
+int debwt_radix_sort_u64_range(debwt_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint64_t count, int key_bits,
+                               uint64_t key_lo, uint64_t key_hi, float *ms_per_pass);
+/* Passes this process has run that took their chunk histograms from the pass before them (tests and A/B runs: which form
+ * a sort took; DEBWT_HIST_EVERY_PASS=1 in the environment keeps it from counting up). */
+uint64_t debwt_radix_pair_passes(void);
 
 /* Host-only: checksums of the special-region tables (`collect`'s specialSA / specialBwt / specialBranch / head / tail
  * tables, src/collect#$.c:118-157,348-602) that debwt_kmer_sort_rle builds on host threads for the loaded text layout;
