@@ -8,9 +8,10 @@
  *   deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq
  *   deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self]
  *                      [--max-mismatches K [--max-error-permille R]] READS.fa|.fq
- *   deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]
+ *   deBWT-query map    -i OUT [--ref INPUT.fa[.gz] [-t T] [--iupac SEED]] [--device D] [--min-len L] [--band W]
  *                      [--max-occ N] [--min-score S] [--chain [--max-gap G]]
  *                      [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq
+ *   deBWT-query extract -i OUT [--device D] --all | REGIONS.txt
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -44,9 +45,10 @@
  * 1024 bases there.
  *
  * map aligns every read (debwt_fm_map: MEM seeds of at least L bases, at most N occurrences of each, clustered by diagonal,
- * banded affine-gap extension with half-width W, 0..63; a plain heuristic, not BWA-MEM's).  The index holds no text, so
- * --ref names the input again; it is packed as index packs it (same -t, same --iupac SEED) and refused when it is not
- * the text of OUT.  One PAF line per mapped read: name, length, query start and end (on the read's own strand), strand,
+ * banded affine-gap extension with half-width W, 0..63; a plain heuristic, not BWA-MEM's).  The index holds no text:
+ * without --ref it is restored on the GPU from OUT, OUT.#, OUT.$ and OUT.sa alone (debwt_fm_restore_text; a note on
+ * stderr says so); with --ref the input is named again, packed as index packs it (same -t, same --iupac SEED) and
+ * refused when it is not the text of OUT.  Both give the same PAF.  One PAF line per mapped read: name, length, query start and end (on the read's own strand), strand,
  * record number, record length, target start and end, matching bases, alignment columns, mapping quality, then AS:i:
  * (score), NM:i: (mismatches + gap bases) and cg:Z: (CIGAR along the text).  Reads that are not mapped print nothing.
  * --chain maps with debwt_fm_map_chained instead: the seeds of a read are chained across diagonals (steps of at most W,
@@ -59,6 +61,13 @@
  * every pair, mapped mates only, with three more tags: pr:A:P on both mates of a proper pair and pr:A:U otherwise, tl:i:
  * (the template length, positive on the forward mate and negative on the reverse one; proper pairs only) and rs:i:1 on a
  * mate that was placed by the rescue.
+ *
+ * extract gives the indexed sequence back as FASTA (debwt_fm_extract); it needs OUT, OUT.#, OUT.$ and OUT.sa only.  --all
+ * writes every record, header >J (the 0-based record number the other subcommands print), the sequence on one line, in
+ * upper case (the index holds four codes: neither the case nor the IUPAC letters nor the names of the input).
+ * REGIONS.txt holds one region per line, J (a whole record) or J:BEG-END (0-based, end exclusive: the coordinates locate
+ * prints); the header is the region as given.  A malformed line or a region outside its record: exit status 1 with a
+ * message naming the line, and nothing on stdout.  The output is produced in batches of about 64 MB.
  *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
@@ -83,9 +92,10 @@ static void usage(void) {
             "       deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq\n"
             "       deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self]\n"
             "                          [--max-mismatches K [--max-error-permille R]] READS.fa|.fq\n"
-            "       deBWT-query map    -i OUT --ref INPUT.fa[.gz] [-t T] [--iupac SEED] [--device D] [--min-len L] [--band W]\n"
+            "       deBWT-query map    -i OUT [--ref INPUT.fa[.gz] [-t T] [--iupac SEED]] [--device D] [--min-len L] [--band W]\n"
             "                          [--max-occ N] [--min-score S] [--chain [--max-gap G]]\n"
             "                          [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq\n"
+            "       deBWT-query extract -i OUT [--device D] --all | REGIONS.txt\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
@@ -98,10 +108,12 @@ static void usage(void) {
             "--max-mismatches K (0..4) admits K mismatching columns in an overlap, --max-error-permille R (0..1000) at most\n"
             "R / 1000 of its columns, and a sixth column gives every overlap's mismatches;\n"
             "map prints one PAF line per mapped read (AS:i: score, NM:i: edits, cg:Z: CIGAR); --ref is the FASTA that OUT\n"
-            "is the BWT of; --chain chains the seeds of a read across diagonals and aligns along the chain (stretches of\n"
+            "is the BWT of, without it the text is restored from the index; --chain chains the seeds of a read across diagonals and aligns along the chain (stretches of\n"
             "at most G bases between two seeds, default 5000); --mate maps paired ends, read i of READS2 being the mate of\n"
             "read i of READS (tags pr:A:P|U, tl:i: template length, rs:i:1 rescued mate), --insert LO,HI bounds the template\n"
-            "length instead of estimating it, --no-rescue leaves a mate without a seed unmapped\n");
+            "length instead of estimating it, --no-rescue leaves a mate without a seed unmapped;\n"
+            "extract writes FASTA from the index alone: --all every record under the header >J (its 0-based number), or\n"
+            "the regions of REGIONS.txt, one per line, J or J:BEG-END (0-based, end exclusive), under the region as given\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -261,9 +273,9 @@ static int push_record(struct patterns *p, const char *header) {
 
 /* FASTA (sequence over several lines) or FASTQ (4 lines per record), told apart by the first character */
 static int read_patterns(const char *path, struct patterns *p) {
+    memset(p, 0, sizeof *p);                                /* callers free it whatever comes back */
     FILE *f = fopen(path, "r");
     if (!f) { fprintf(stderr, "cannot open %s\n", path); return -1; }
-    memset(p, 0, sizeof *p);
     char *line = NULL;
     size_t lcap = 0;
     ssize_t l;
@@ -587,6 +599,32 @@ static void paf_line(const char *name, uint64_t m, const debwt_fm_hit *h, const 
     for (uint64_t k = c0; k < c1; k++) printf("%u%c", cig[k] >> 4, "MID"[cig[k] & 3]);
 }
 
+/* the text the mappers read: --ref packed as index packs it and checked against the index, or, without --ref, restored
+ * from the index itself */
+static int map_text(debwt_fm *fm, const char *out, const char *ref, uint64_t threads, int iupac, uint64_t seed,
+                    const debwt_fm_info *fi, debwt_packed_text *pt) {
+    char err[256] = "";
+    int rc;
+    if (!ref) {
+        rc = debwt_fm_restore_text(fm);
+        if (rc) fprintf(stderr, "%s.sa does not restore the text of %s: %s\n", out, out, debwt_fm_last_error(fm));
+        return rc ? -1 : 0;
+    }
+    rc = debwt_pack_fasta_opts(ref, (int)threads, iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, seed, pt, err, sizeof err);
+    if (rc) {
+        fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", ref, err);
+        return -1;
+    }
+    if (pt->n != fi->n || pt->nrec != fi->nrec) {
+        fprintf(stderr, "%s is not the text of %s: %llu symbols in %llu records, the index has %llu in %llu\n", ref, out,
+                (unsigned long long)pt->n, (unsigned long long)pt->nrec, (unsigned long long)fi->n, (unsigned long long)fi->nrec);
+        return -1;
+    }
+    rc = debwt_fm_attach_text(fm, NULL, pt->words, pt->sep);
+    if (rc) { fprintf(stderr, "%s is not the text of %s: %s\n", ref, out, debwt_fm_last_error(fm)); return -1; }
+    return 0;
+}
+
 static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t threads, int iupac, uint64_t seed, int device,
                    const debwt_fm_map_opts *opts, int chain, uint32_t max_gap) {
     struct patterns P;
@@ -595,7 +633,6 @@ static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t
     if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1, rc;
     debwt_packed_text pt;
-    char err[256] = "";
     memset(&pt, 0, sizeof pt);
     uint64_t cap = 4 * P.n + 16, *coff = malloc((P.n + 1) * 8), *starts = NULL;
     uint32_t *cig = NULL;
@@ -604,18 +641,7 @@ static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t
     debwt_fm_info_get(fm, &fi);
     starts = malloc((fi.nrec + 1) * 8);
     if (!coff || !hits || !starts) { fprintf(stderr, "out of memory\n"); goto done; }
-    rc = debwt_pack_fasta_opts(ref, (int)threads, iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, seed, &pt, err, sizeof err);
-    if (rc) {
-        fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", ref, err);
-        goto done;
-    }
-    if (pt.n != fi.n || pt.nrec != fi.nrec) {
-        fprintf(stderr, "%s is not the text of %s: %llu symbols in %llu records, the index has %llu in %llu\n", ref, out,
-                (unsigned long long)pt.n, (unsigned long long)pt.nrec, (unsigned long long)fi.n, (unsigned long long)fi.nrec);
-        goto done;
-    }
-    rc = debwt_fm_attach_text(fm, NULL, pt.words, pt.sep);
-    if (rc) { fprintf(stderr, "%s is not the text of %s: %s\n", ref, out, debwt_fm_last_error(fm)); goto done; }
+    if (map_text(fm, out, ref, threads, iupac, seed, &fi, &pt)) goto done;
     for (;;) {                                            /* grow to the exact op count on DEBWT_ERANGE */
         free(cig);
         cig = malloc(cap * 4);
@@ -668,7 +694,6 @@ static int cmd_map_pairs(const char *out, const char *ref, const char *pfile, co
     if (open_index(out, device, &fm)) { free_patterns(&P); free_patterns(&M); return 1; }
     int ret = 1, rc;
     debwt_packed_text pt;
-    char err[256] = "";
     memset(&pt, 0, sizeof pt);
     uint64_t cap = 4 * nr + 16, *coff = malloc((nr + 1) * 8), *starts = NULL;
     uint32_t *cig = NULL;
@@ -688,18 +713,7 @@ static int cmd_map_pairs(const char *out, const char *ref, const char *pfile, co
         memcpy(B.seq + B.off[2 * i + 1], M.seq + M.off[i], l2);
         B.off[2 * i + 2] = B.off[2 * i + 1] + l2;
     }
-    rc = debwt_pack_fasta_opts(ref, (int)threads, iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, seed, &pt, err, sizeof err);
-    if (rc) {
-        fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", ref, err);
-        goto done;
-    }
-    if (pt.n != fi.n || pt.nrec != fi.nrec) {
-        fprintf(stderr, "%s is not the text of %s: %llu symbols in %llu records, the index has %llu in %llu\n", ref, out,
-                (unsigned long long)pt.n, (unsigned long long)pt.nrec, (unsigned long long)fi.n, (unsigned long long)fi.nrec);
-        goto done;
-    }
-    rc = debwt_fm_attach_text(fm, NULL, pt.words, pt.sep);
-    if (rc) { fprintf(stderr, "%s is not the text of %s: %s\n", ref, out, debwt_fm_last_error(fm)); goto done; }
+    if (map_text(fm, out, ref, threads, iupac, seed, &fi, &pt)) goto done;
     for (;;) {                                            /* grow to the exact op count on DEBWT_ERANGE */
         free(cig);
         cig = malloc(cap * 4);
@@ -731,11 +745,131 @@ done:
     return ret;
 }
 
+/* ---- extract ---------------------------------------------------------------------------------------------------------- */
+
+#define EXTRACT_BATCH_BYTES (64ull << 20)
+#define EXTRACT_BATCH_JOBS (1ull << 16)
+
+struct regions { debwt_fm_extract_job *job; char **name; uint64_t n, cap; };
+
+static int push_region(struct regions *R, const char *name, uint64_t rec, uint64_t beg, uint64_t len) {
+    if (R->n == R->cap) {
+        uint64_t nc = R->cap ? 2 * R->cap : 1024;
+        debwt_fm_extract_job *j = realloc(R->job, nc * sizeof *j);
+        if (!j) return -1;
+        R->job = j;
+        char **nm = realloc(R->name, nc * sizeof *nm);
+        if (!nm) return -1;
+        R->name = nm; R->cap = nc;
+    }
+    R->name[R->n] = NULL;
+    if (name && !(R->name[R->n] = strdup(name))) return -1;
+    R->job[R->n].record = (uint32_t)rec; R->job[R->n].reserved = 0; R->job[R->n].offset = beg; R->job[R->n].length = len;
+    R->n++;
+    return 0;
+}
+
+/* J or J:BEG-END into (rec, beg, end); whole: no interval was given */
+static int parse_region(const char *s, uint64_t *rec, uint64_t *beg, uint64_t *end, int *whole) {
+    char buf[64];
+    const char *colon = strchr(s, ':');
+    *whole = !colon;
+    if (!colon) return parse_u64(s, rec);
+    const char *dash = strchr(colon + 1, '-');
+    if (!dash || (size_t)(colon - s) >= sizeof buf || (size_t)(dash - colon - 1) >= sizeof buf) return -1;
+    memcpy(buf, s, (size_t)(colon - s)); buf[colon - s] = 0;
+    if (parse_u64(buf, rec)) return -1;
+    memcpy(buf, colon + 1, (size_t)(dash - colon - 1)); buf[dash - colon - 1] = 0;
+    if (parse_u64(buf, beg) || parse_u64(dash + 1, end)) return -1;
+    return 0;
+}
+
+static int cmd_extract(const char *out, const char *rfile, int device) {
+    debwt_fm *fm = NULL;
+    struct regions R;
+    memset(&R, 0, sizeof R);
+    int ret = 1, rc = 0;
+    uint64_t *starts = NULL, *off = NULL;
+    char *bases = NULL, *line = NULL;
+    FILE *f = NULL;
+    if (rfile && !(f = fopen(rfile, "r"))) { fprintf(stderr, "cannot open %s\n", rfile); return 1; }
+    if (open_index(out, device, &fm)) { if (f) fclose(f); return 1; }
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    starts = malloc((fi.nrec + 1) * 8);
+    if (!starts) { fprintf(stderr, "out of memory\n"); goto done; }
+    rc = debwt_fm_record_starts(fm, starts, fi.nrec);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    starts[fi.nrec] = fi.n;                               /* record r holds starts[r + 1] - 1 - starts[r] bases */
+    if (fi.nrec >> 32) { fprintf(stderr, "extract: 2^32 records or more\n"); goto done; }
+    if (f) {
+        size_t lcap = 0;
+        ssize_t l;
+        uint64_t lineno = 0;
+        while ((l = getline(&line, &lcap, f)) >= 0) {
+            lineno++;
+            while (l > 0 && (line[l - 1] == '\n' || line[l - 1] == '\r' || line[l - 1] == ' ' || line[l - 1] == '\t')) line[--l] = 0;
+            if (!l) continue;
+            uint64_t rec = 0, beg = 0, end = 0;
+            int whole = 0;
+            if (parse_region(line, &rec, &beg, &end, &whole)) {
+                fprintf(stderr, "%s:%llu: '%s' is not a region (J or J:BEG-END)\n", rfile, (unsigned long long)lineno, line);
+                goto done;
+            }
+            const uint64_t len = rec < fi.nrec ? starts[rec + 1] - 1 - starts[rec] : 0;
+            if (whole) end = len;
+            if (rec >= fi.nrec || beg > end || end > len) {
+                fprintf(stderr, "%s:%llu: region '%s' lies outside its record (%llu records; record %llu holds %llu bases)\n", rfile,
+                        (unsigned long long)lineno, line, (unsigned long long)fi.nrec, (unsigned long long)rec, (unsigned long long)len);
+                goto done;
+            }
+            if (push_region(&R, line, rec, beg, end - beg)) { fprintf(stderr, "out of memory\n"); goto done; }
+        }
+    }
+    /* --all: the records are the jobs, made batch by batch; REGIONS: the jobs read above */
+    const uint64_t njobs = f ? R.n : fi.nrec;
+    off = malloc((EXTRACT_BATCH_JOBS + 1) * 8);
+    debwt_fm_extract_job *jb = f ? NULL : malloc(EXTRACT_BATCH_JOBS * sizeof *jb);
+    uint64_t bcap = 0;
+    if (!off || (!f && !jb)) { fprintf(stderr, "out of memory\n"); free(jb); goto done; }
+    for (uint64_t j0 = 0; j0 < njobs && !rc;) {
+        uint64_t j1 = j0, bytes = 0;
+        while (j1 < njobs && j1 - j0 < EXTRACT_BATCH_JOBS) {  /* at least one job, however long */
+            const uint64_t l = f ? R.job[j1].length : starts[j1 + 1] - 1 - starts[j1];
+            if (j1 > j0 && bytes + l > EXTRACT_BATCH_BYTES) break;
+            if (!f) { jb[j1 - j0].record = (uint32_t)j1; jb[j1 - j0].reserved = 0; jb[j1 - j0].offset = 0; jb[j1 - j0].length = l; }
+            bytes += l; j1++;
+        }
+        if (bytes > bcap) {
+            free(bases);
+            bases = malloc(bytes);
+            bcap = bases ? bytes : 0;
+            if (!bases) { fprintf(stderr, "out of memory\n"); rc = DEBWT_ENOMEM; break; }
+        }
+        rc = debwt_fm_extract(fm, f ? R.job + j0 : jb, j1 - j0, off, bases, bcap);
+        if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); break; }
+        for (uint64_t j = j0; j < j1; j++) {
+            if (f) printf(">%s\n", R.name[j]); else printf(">%llu\n", (unsigned long long)j);
+            fwrite(bases + off[j - j0], 1, off[j - j0 + 1] - off[j - j0], stdout);
+            putchar('\n');
+        }
+        j0 = j1;
+    }
+    free(jb);
+    if (!rc) ret = fflush(stdout) ? 1 : 0;
+done:
+    if (f) fclose(f);
+    for (uint64_t i = 0; i < R.n; i++) free(R.name[i]);
+    free(R.name); free(R.job); free(starts); free(off); free(bases); free(line);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { usage(); return 1; }
     const char *cmd = argv[1];
     int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 :
-               !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : -1;
+               !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 : -1;
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
     uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, min_overlap = 20, v64 = 0;
@@ -748,7 +882,7 @@ int main(int argc, char **argv) {
     debwt_fm_pair_opts po;
     debwt_fm_pair_defaults(&po);
     const char *mate = NULL;
-    int iupac = 0, search = 0, chain = 0, gap_given = 0, insert_given = 0, no_rescue = 0, no_self = 0;
+    int iupac = 0, search = 0, chain = 0, gap_given = 0, insert_given = 0, no_rescue = 0, no_self = 0, all = 0;
     uint32_t flags = 0;
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
@@ -761,6 +895,7 @@ int main(int argc, char **argv) {
         if ((mode == 1 || mode == 2) && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
         if (mode == 5 && !strcmp(a, "--longest")) { flags |= DEBWT_FM_OVERLAP_LONGEST; continue; }
         if (mode == 5 && !strcmp(a, "--no-self")) { no_self = 1; continue; }
+        if (mode == 6 && !strcmp(a, "--all")) { all = 1; continue; }
         if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mode == 4 && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
         if (mode != 4 && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
@@ -830,9 +965,13 @@ int main(int argc, char **argv) {
         else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
+    if (mode == 6) {
+        if (!out || (all != 0) == (file != NULL)) { usage(); return 1; }
+        return cmd_extract(out, file, (int)device);
+    }
     if (!out || !file) { usage(); return 1; }
     if (mode == 4) {
-        if (!ref) { fprintf(stderr, "map: --ref INPUT.fa[.gz] (the text OUT is the BWT of) is required\n"); return 1; }
+        if (!ref) fprintf(stderr, "map: no --ref INPUT.fa[.gz]: the text is restored from %s.sa and the BWT\n", out);
         if (gap_given && !chain) { fprintf(stderr, "--max-gap: only with --chain\n"); return 1; }
         if (mate && chain) { fprintf(stderr, "--mate: not with --chain (pairs are mapped with the fixed band)\n"); return 1; }
         if (insert_given && !mate) { fprintf(stderr, "--insert: only with --mate\n"); return 1; }

@@ -104,6 +104,20 @@ class DebwtFmOverlapsMmStats(ctypes.Structure):
         return d
 
 
+class DebwtFmExtractStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("jobs", "batches", "launches", "segments", "bases", "steps", "wave_steps",
+                                                 "line_reads", "anchor_bytes")] +
+                [(n, ctypes.c_float) for n in ("ms_anchors", "ms_kernel", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class DebwtFmExtractJob(ctypes.Structure):
+    _fields_ = [("record", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("offset", ctypes.c_uint64),
+                ("length", ctypes.c_uint64)]
+
+
 class DebwtFmOverlap(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("record", "length", "strand", "flags")]
 
@@ -248,6 +262,7 @@ SYMBOLS = [
     "debwt_fm_map_pairs", "debwt_fm_pair_stats_get",
     "debwt_fm_overlaps", "debwt_fm_overlaps_stats_get", "debwt_fm_overlap_longest",
     "debwt_fm_overlaps_mm", "debwt_fm_overlaps_mm_stats_get",
+    "debwt_fm_extract", "debwt_fm_extract_stats_get", "debwt_fm_restore_text", "debwt_fm_text_fetch",
 ]
 
 
@@ -518,6 +533,14 @@ def lib():
                                      ctypes.POINTER(DebwtFmHit), ctypes.POINTER(DebwtFmPairInfo), u64p, u32p, ctypes.c_uint64]
     L.debwt_fm_pair_stats_get.restype = ctypes.c_int
     L.debwt_fm_pair_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmPairStats)]
+    L.debwt_fm_extract.restype = ctypes.c_int
+    L.debwt_fm_extract.argtypes = [vp, ctypes.POINTER(DebwtFmExtractJob), ctypes.c_uint64, u64p, ctypes.c_char_p, ctypes.c_uint64]
+    L.debwt_fm_extract_stats_get.restype = ctypes.c_int
+    L.debwt_fm_extract_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmExtractStats)]
+    L.debwt_fm_restore_text.restype = ctypes.c_int
+    L.debwt_fm_restore_text.argtypes = [vp]
+    L.debwt_fm_text_fetch.restype = ctypes.c_int
+    L.debwt_fm_text_fetch.argtypes = [vp, u64p, ctypes.c_uint64, u64p]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

@@ -492,6 +492,49 @@ class FMIndex:
             raise DebwtError(-1, "the text has another number of records or fewer words than the index's n asks for")
         self._chk(self._L.debwt_fm_attach_text(self._h, None, _p64(words), _p64(sep)))
 
+    def restore_text(self):
+        """Rebuild the 2-bit text from the index alone and attach it (debwt_fm_restore_text): attach_text() without a
+        source, for an index opened from its files.  Returns at once when a text is attached; raises DEBWT_EINVAL, with no
+        text attached, when the samples are not those of the rows."""
+        self._chk(self._L.debwt_fm_restore_text(self._h))
+
+    def text(self):
+        """The attached text on the host (debwt_fm_text_fetch): (words, sep) as pack_records() returns them, ((n + 63) >> 5)
+        + 2 words and the nrec separator positions -- DeBWT.load_packed(words, n, sep) takes them."""
+        words = np.zeros(((self.n + 63) >> 5) + 2, dtype=np.uint64)
+        sep = np.zeros(self.nrec, dtype=np.uint64)
+        self._chk(self._L.debwt_fm_text_fetch(self._h, _p64(words), len(words), _p64(sep)))
+        return words, sep
+
+    def extract(self, jobs):
+        """Record text from the index alone (debwt_fm_extract).  jobs: (record, offset, length) or (record,) for a whole
+        record; a length past the record's end is clipped.  Returns a list of bytes, upper-case ACGT."""
+        jobs = [tuple(int(x) for x in j) for j in jobs]
+        nj = len(jobs)
+        ja = (_lib.DebwtFmExtractJob * max(nj, 1))()
+        for k, j in enumerate(jobs):
+            rec, off, length = j if len(j) == 3 else (j[0], 0, 2 ** 64 - 1)
+            if not (0 <= rec < 2 ** 32 and 0 <= off < 2 ** 64 and 0 <= length < 2 ** 64):
+                raise DebwtError(-1, "a job with a negative or oversized field")
+            ja[k].record, ja[k].reserved, ja[k].offset, ja[k].length = rec, 0, off, length
+        offs = np.zeros(nj + 1, dtype=np.uint64)
+        rc = self._L.debwt_fm_extract(self._h, ja, nj, _p64(offs), None, 0)      # the lengths first
+        if rc != -5:
+            self._chk(rc)
+        total = int(offs[nj])
+        buf = ctypes.create_string_buffer(max(total, 1))
+        if total:
+            self._chk(self._L.debwt_fm_extract(self._h, ja, nj, _p64(offs), buf, total))
+        raw = buf.raw
+        return [raw[int(offs[k]):int(offs[k + 1])] for k in range(nj)]
+
+    def extract_stats(self):
+        """What the last extract() or restore_text() did (debwt_fm_extract_stats_get): jobs, batches, segments, bases, LF
+        steps and wave steps, the anchors' bytes and the ms to build them, kernel and wall ms."""
+        st = _lib.DebwtFmExtractStats()
+        self._chk(self._L.debwt_fm_extract_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def extend(self, patterns, jobs, scoring=(1, 4, 6, 1), band=16, cigar=True):
         """Banded affine-gap local alignment of jobs (debwt_fm_extend).  jobs: rows of (pattern index, strand, diag, record),
         diag = text position - query position, the query being the pattern (strand 0) or its reverse complement (strand 1).

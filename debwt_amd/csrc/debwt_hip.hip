@@ -34,6 +34,7 @@
 #include "fm_window_kernels.h"
 #include "fm_overlap_kernels.h"
 #include "fm_overlap_mm_kernels.h"
+#include "fm_extract_kernels.h"
 
 namespace {
 
@@ -2897,6 +2898,12 @@ struct debwt_fm {
     DevBuf o_slot, o_runs, o_nruns, o_nhits, o_rbase, o_hbase, o_cruns, o_rout, o_hits;   // overlap scratch of one batch
     debwt_fm_overlaps_stats o_stats{};
     debwt_fm_overlaps_mm_stats om_stats{};   // overlaps with mismatches: scratch is s_items, s_hits (runs), o_cruns, o_rout, o_hits
+    DevBuf anchors;              // extract: sample numbers ordered by position, made by the first extract or restore
+    bool has_anchors = false;
+    u64 na = 0;                  // anchors: the samples and the free ends (0, '$' row), (n - 1, n - 1) where not sampled
+    float ms_anchors = 0.f;
+    DevBuf e_jobs, e_seg, e_out, e_ctr, e_sep;   // extract scratch of one batch; counters; separator positions of a restore
+    debwt_fm_extract_stats e_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -3168,7 +3175,7 @@ extern "C" int debwt_fm_info_get(const debwt_fm *f, debwt_fm_info *out) {
     memset(out, 0, sizeof *out);
     out->n = f->n; out->nrec = f->nrec; out->sa_sample = f->s; out->samples = f->nsamp;
     out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap + (f->has_text ? f->text.cap : 0) +
-                        (f->has_otable ? f->o_table.cap : 0);
+                        (f->has_otable ? f->o_table.cap : 0) + (f->has_anchors ? f->anchors.cap : 0);
     out->ms_rank = f->ms_rank; out->ms_samples = f->ms_samples;
     for (int q = 0; q < 4; q++) out->census[q] = f->census[q];
     return DEBWT_OK;
@@ -5793,6 +5800,251 @@ extern "C" int debwt_fm_pair_stats_get(const debwt_fm *f, debwt_fm_pair_stats *o
     return DEBWT_OK;
 }
 
+// ---- extract and text restore (fm_extract_kernels.h) ----------------------------------------------------------------
+// The anchors are made by the first call that needs them and stay with the index.  An extract batch is planned on the
+// device (per job the anchor gaps that meet it), laid out by a prefix sum on the host and walked one gap per item, so a
+// job of 10^6 bases is 10^6 / s items, not one lane's walk.  A restore walks every gap once into the packed text.
+
+namespace {
+
+constexpr u64 FM_EXTRACT_BYTES = 256ull << 20;         // output bytes of one extract batch
+constexpr u64 FM_EXTRACT_JOBS = 1ull << 22;            // jobs of one extract batch
+
+FmAnchors fm_anchors_of(const debwt_fm *f) {
+    return FmAnchors{f->anchors.as<u64>(), f->sa.as<u64>(), f->na, f->nsamp, f->sh};
+}
+
+int fm_anchors_build(debwt_fm *f) {
+    if (f->has_anchors) return DEBWT_OK;
+    const u64 n = f->n, nsamp = f->nsamp;
+    const u64 nwords = (n + 63) >> 6, nchunks = (nwords + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;
+    FmTmp bits, wpre, csum;
+    HIPCHK(f, hipMalloc(&bits.p, (size_t)nwords * 8));
+    HIPCHK(f, hipMalloc(&wpre.p, (size_t)nwords * 4));
+    HIPCHK(f, hipMalloc(&csum.p, (size_t)nchunks * 8));
+    FM_ENSURE(f, f->e_ctr, 64);
+    u64 *ctr = f->e_ctr.as<u64>(), *d_bits = reinterpret_cast<u64 *>(bits.p);
+    HIPCHK(f, hipMemsetAsync(d_bits, 0, (size_t)nwords * 8, f->stream));
+    HIPCHK(f, hipMemsetAsync(ctr, 0, 64, f->stream));
+    hipEvent_t e0, e1;
+    HIPCHK(f, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
+    (void)hipEventRecord(e0, f->stream);
+    k_fm_anc_mark<<<grid_for(nsamp, 256), 256, 0, f->stream>>>(f->sa.as<u64>(), nsamp, n, d_bits, ctr);
+    k_fm_anc_free<<<1, 64, 0, f->stream>>>(n, d_bits, ctr);
+    u64 h[8];
+    HIPCHK(f, hipMemcpyAsync(h, ctr, 64, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    if (h[FM_EX_A_RANGE] || h[FM_EX_A_DUP]) {
+        f->err = "the samples are not a suffix array of the rows: " + std::to_string(h[FM_EX_A_RANGE]) +
+                 " are no text position, " + std::to_string(h[FM_EX_A_DUP]) + " repeat another sample's position";
+        return DEBWT_EINVAL;
+    }
+    const u64 na = nsamp + h[FM_EX_A_FIRST] + h[FM_EX_A_LAST];
+    FM_ENSURE(f, f->anchors, (size_t)na * 8);
+    HIPCHK(f, hipMemsetAsync(f->anchors.p, 0xFF, (size_t)na * 8, f->stream));
+    k_fm_anc_count<<<(u32)nchunks, FM_EX_CHUNK_WORDS, 0, f->stream>>>(d_bits, nwords, reinterpret_cast<u32 *>(wpre.p),
+                                                                     reinterpret_cast<u64 *>(csum.p));
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(reinterpret_cast<u64 *>(csum.p), nchunks, ctr + FM_EX_A_TOTAL);
+    k_fm_anc_scatter<<<grid_for(nsamp + 2, 256), 256, 0, f->stream>>>(f->sa.as<u64>(), nsamp, n, d_bits,
+                                                                     reinterpret_cast<const u32 *>(wpre.p),
+                                                                     reinterpret_cast<const u64 *>(csum.p), ctr, na,
+                                                                     f->anchors.as<u64>());
+    (void)hipEventRecord(e1, f->stream);
+    HIPCHK(f, hipMemcpyAsync(h, ctr, 64, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    if (h[FM_EX_A_TOTAL] != na) { f->err = "anchors: the rank over the sampled positions is inconsistent"; return DEBWT_EINTERNAL; }
+    (void)hipEventElapsedTime(&f->ms_anchors, e0, e1);
+    f->na = na;
+    f->has_anchors = true;
+    return DEBWT_OK;
+}
+
+// one walk over nitems items; the counters come back in h[0..7] and are added to the stats
+template <class E>
+int fm_extract_walk(debwt_fm *f, const E &em, u64 nitems, bool pad, u64 h[8]) {
+    debwt_fm_extract_stats &st = f->e_stats;
+    u64 *ctr = f->e_ctr.as<u64>();
+    hipEvent_t e0, e1;
+    HIPCHK(f, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
+    // a run per wave long enough that the drain of its last items is a small part of it, short enough for several
+    // waves per SIMD slot of the device
+    const u32 chunk = (u32)std::min<u64>(std::max<u64>(nitems / 16384, 128), 4096);
+    const u64 waves = (nitems + chunk - 1) / chunk;
+    HIPCHK(f, hipMemsetAsync(ctr, 0, 64, f->stream));
+    (void)hipEventRecord(e0, f->stream);
+    k_fm_extract_walk<E><<<grid_for(waves * 64, 256), 256, 0, f->stream>>>(f->V, fm_anchors_of(f), em, nitems, chunk, ctr);
+    if (pad) k_fm_extract_pad<<<1, 64, 0, f->stream>>>(f->text.as<u64>(), f->n);
+    (void)hipEventRecord(e1, f->stream);
+    HIPCHK(f, hipMemcpyAsync(h, ctr, 64, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    st.ms_kernel += ms; st.launches += pad ? 2 : 1; st.segments += nitems;
+    st.steps += h[FM_EX_W_STEPS]; st.line_reads += h[FM_EX_W_STEPS]; st.wave_steps += h[FM_EX_W_WAVE];
+    return DEBWT_OK;
+}
+
+int fm_extract_begin(debwt_fm *f) {
+    f->e_stats = debwt_fm_extract_stats{};
+    HIPCHK(f, hipSetDevice(f->device));
+    const bool had = f->has_anchors;
+    int rc = fm_anchors_build(f);
+    if (rc) return rc;
+    f->e_stats.anchor_bytes = f->anchors.cap;
+    f->e_stats.ms_anchors = had ? 0.f : f->ms_anchors;
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_extract(debwt_fm *f, const debwt_fm_extract_job *jobs, uint64_t njobs, uint64_t *out_offsets,
+                                char *bases, uint64_t capacity) {
+    if (!f || !out_offsets || (njobs && !jobs)) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->e_stats = debwt_fm_extract_stats{};
+    const u64 n = f->n, nrec = f->nrec;
+    const std::vector<u64> &rs = f->rec_starts;
+    out_offsets[0] = 0;
+    for (u64 j = 0; j < njobs; j++) {
+        const debwt_fm_extract_job &q = jobs[j];
+        if (q.reserved) { f->err = "debwt_fm_extract: job " + std::to_string(j) + " has a non-zero reserved field"; return DEBWT_EINVAL; }
+        if (q.record >= nrec) { f->err = "debwt_fm_extract: job " + std::to_string(j) + " names record " + std::to_string(q.record) + " of " + std::to_string(nrec); return DEBWT_EINVAL; }
+        const u64 len = (q.record + 1 < nrec ? rs[q.record + 1] : n) - 1 - rs[q.record];
+        if (q.offset > len) { f->err = "debwt_fm_extract: job " + std::to_string(j) + " begins at " + std::to_string(q.offset) + " in a record of " + std::to_string(len) + " bases"; return DEBWT_EINVAL; }
+        out_offsets[j + 1] = out_offsets[j] + std::min<u64>(q.length, len - q.offset);
+    }
+    const u64 total = out_offsets[njobs];
+    f->e_stats.jobs = njobs; f->e_stats.bases = total;
+    if (capacity < total || (total && !bases)) {
+        f->err = "debwt_fm_extract: capacity below the bases asked for (out_offsets[njobs] = " + std::to_string(total) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (!total) return DEBWT_OK;
+    int rc = fm_extract_begin(f);
+    if (rc) return rc;
+    f->e_stats.jobs = njobs; f->e_stats.bases = total;
+    const u64 limit = fm_env_u64("DEBWT_FM_EXTRACT_BYTES", FM_EXTRACT_BYTES);
+    std::vector<FmExJob> hj;
+    std::vector<u64> seg;
+    for (u64 j0 = 0; j0 < njobs;) {
+        u64 j1 = j0 + 1;                                       // at least one job, however long
+        while (j1 < njobs && j1 - j0 < FM_EXTRACT_JOBS && out_offsets[j1 + 1] - out_offsets[j0] <= limit) j1++;
+        const u64 nb = j1 - j0, bytes = out_offsets[j1] - out_offsets[j0];
+        if (!bytes) { j0 = j1; continue; }
+        hj.resize(nb); seg.resize(nb + 1);
+        for (u64 j = 0; j < nb; j++) {
+            const debwt_fm_extract_job &q = jobs[j0 + j];
+            const u64 a = rs[q.record] + q.offset;
+            hj[j] = FmExJob{a, a + (out_offsets[j0 + j + 1] - out_offsets[j0 + j]), out_offsets[j0 + j] - out_offsets[j0], 0};
+        }
+        FM_ENSURE(f, f->e_jobs, (size_t)nb * sizeof(FmExJob));
+        FM_ENSURE(f, f->e_seg, (size_t)(nb + 1) * 8);
+        FM_ENSURE(f, f->e_out, (size_t)bytes);
+        HIPCHK(f, hipMemcpyAsync(f->e_jobs.p, hj.data(), nb * sizeof(FmExJob), hipMemcpyHostToDevice, f->stream));
+        k_fm_extract_plan<<<grid_for(nb, 256), 256, 0, f->stream>>>(f->V, fm_anchors_of(f), f->e_jobs.as<FmExJob>(), nb,
+                                                                    f->e_seg.as<u64>());
+        HIPCHK(f, hipMemcpyAsync(seg.data(), f->e_seg.p, nb * 8, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+        f->e_stats.launches++;
+        u64 run = 0;
+        for (u64 j = 0; j < nb; j++) { const u64 c = seg[j]; seg[j] = run; run += c; }
+        seg[nb] = run;
+        HIPCHK(f, hipMemcpyAsync(f->e_seg.p, seg.data(), (nb + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        u64 h[8];
+        const FmExAscii em{f->e_jobs.as<FmExJob>(), f->e_seg.as<u64>(), nb, f->e_out.as<u8>()};
+        if ((rc = fm_extract_walk(f, em, run, false, h))) return rc;
+        if (h[FM_EX_W_CHAIN] || h[FM_EX_W_BAD]) {
+            f->err = "debwt_fm_extract: the samples are not those of the rows (" + std::to_string(h[FM_EX_W_CHAIN]) +
+                     " walks missed the row of their anchor, " + std::to_string(h[FM_EX_W_BAD]) + " left their record)";
+            return DEBWT_EINVAL;
+        }
+        HIPCHK(f, hipMemcpyAsync(bases + out_offsets[j0], f->e_out.p, bytes, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+        f->e_stats.batches++;
+        j0 = j1;
+    }
+    f->e_stats.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_extract_stats_get(const debwt_fm *f, debwt_fm_extract_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->e_stats;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_restore_text(debwt_fm *f) {
+    if (!f) return DEBWT_EINVAL;
+    if (f->has_text) return DEBWT_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc = fm_extract_begin(f);
+    if (rc) return rc;
+    debwt_fm_extract_stats &st = f->e_stats;
+    const u64 n = f->n, nrec = f->nrec;
+    const size_t tw = (size_t)((n + 63) >> 5) + 2;
+    FM_ENSURE(f, f->text, tw * 8);
+    FM_ENSURE(f, f->e_sep, (size_t)nrec * 8);
+    FM_ENSURE(f, f->s_ctr, 64);
+    HIPCHK(f, hipMemsetAsync(f->text.p, 0, tw * 8, f->stream));
+    u64 h[8];
+    const FmExPacked em{f->text.as<u64>(), f->e_sep.as<u64>(), nrec};
+    if ((rc = fm_extract_walk(f, em, f->na - 1, true, h))) return rc;
+    st.bases = n; st.batches = 1;
+    if (h[FM_EX_W_CHAIN] || h[FM_EX_W_BAD] || h[FM_EX_W_STEPS] != n - 1 || h[FM_EX_W_SEPS] != nrec - 1) {
+        f->err = "debwt_fm_restore_text: the samples are not those of the rows (" + std::to_string(h[FM_EX_W_CHAIN]) +
+                 " segments missed the row of their lower anchor or the '$' at the text's start, " +
+                 std::to_string(h[FM_EX_W_BAD]) + " were refused, " + std::to_string(h[FM_EX_W_SEPS]) + " separators met, " +
+                 std::to_string(nrec - 1) + " expected)";
+        return DEBWT_EINVAL;
+    }
+    std::vector<u64> sp(nrec - 1);
+    if (nrec > 1) {
+        HIPCHK(f, hipMemcpyAsync(sp.data(), f->e_sep.p, (nrec - 1) * 8, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+        std::sort(sp.begin(), sp.end());
+    }
+    for (u64 r = 0; r + 1 < nrec; r++)
+        if (sp[r] != f->rec_starts[r + 1] - 1) {               // a '$' met inside the text carries bit 63: never equal
+            f->err = "debwt_fm_restore_text: separator " + std::to_string(r) + " was met at " + std::to_string(sp[r] & ~(1ull << 63)) +
+                     ", the index has it at " + std::to_string(f->rec_starts[r + 1] - 1);
+            return DEBWT_EINVAL;
+        }
+    HIPCHK(f, hipMemsetAsync(f->s_ctr.p, 0, 8, f->stream));
+    k_fm_text_check<<<grid_for(f->nsamp, 256), 256, 0, f->stream>>>(f->V, f->sa.as<u64>(), f->nsamp, f->sh, f->text.as<u64>(),
+                                                                   f->s_ctr.as<u64>());
+    u64 bad = 0;
+    HIPCHK(f, hipMemcpyAsync(&bad, f->s_ctr.p, 8, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    st.launches++;
+    if (bad) {
+        f->err = "debwt_fm_restore_text: the restored text fails the check of debwt_fm_attach_text (" + std::to_string(bad) +
+                 " of " + std::to_string(f->nsamp) + " sampled rows)";
+        return DEBWT_EINVAL;
+    }
+    f->has_text = true;
+    st.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_text_fetch(debwt_fm *f, uint64_t *packed, uint64_t capacity_words, uint64_t *sep) {
+    if (!f || !packed || !sep) return DEBWT_EINVAL;
+    if (!f->has_text) { f->err = "debwt_fm_text_fetch: no text attached (debwt_fm_attach_text, debwt_fm_restore_text)"; return DEBWT_ESTATE; }
+    const u64 n = f->n, nrec = f->nrec, tw = ((n + 63) >> 5) + 2;
+    if (capacity_words < tw) { f->err = "debwt_fm_text_fetch: capacity below ((n + 63) >> 5) + 2 = " + std::to_string(tw) + " words"; return DEBWT_ERANGE; }
+    HIPCHK(f, hipSetDevice(f->device));
+    HIPCHK(f, hipMemcpyAsync(packed, f->text.p, (size_t)tw * 8, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    for (u64 r = 0; r < nrec; r++) sep[r] = (r + 1 < nrec ? f->rec_starts[r + 1] : n) - 1;
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
@@ -5801,7 +6053,8 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
                       &f->s_plist, &f->m_slot, &f->m_cnt, &f->m_obase, &f->m_spans, &f->m_ranges, &f->m_cspans,
                       &f->m_cranges, &f->text, &f->x_jobs, &f->x_best, &f->x_cells, &f->x_flags, &f->x_tr, &f->x_cigoff,
                       &f->x_cig, &f->x_anchors, &f->o_table, &f->o_slot, &f->o_runs, &f->o_nruns, &f->o_nhits, &f->o_rbase,
-                      &f->o_hbase, &f->o_cruns, &f->o_rout, &f->o_hits})
+                      &f->o_hbase, &f->o_cruns, &f->o_rout, &f->o_hits, &f->anchors, &f->e_jobs, &f->e_seg, &f->e_out, &f->e_ctr,
+                      &f->e_sep})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -654,7 +654,8 @@ int debwt_fm_overlaps_mm_stats_get(const debwt_fm *fm, debwt_fm_overlaps_mm_stat
  *              The path after debwt_fm_open; a host gets them from debwt_pack_fasta.
  * The text must be the index's text: the separators must be the record starts - 1 (and n - 1), and for every sample i
  * with p = sa[i] > 0 the 2-bit code of row i * sa_sample must be the text's code at p - 1 (checked on the device);
- * otherwise DEBWT_EINVAL with the reason in debwt_fm_last_error, and no text is attached. */
+ * otherwise DEBWT_EINVAL with the reason in debwt_fm_last_error, and no text is attached.  debwt_fm_restore_text (below)
+ * attaches the same text without a source, from the index alone. */
 int debwt_fm_attach_text(debwt_fm *fm, debwt_ctx *ctx, const uint64_t *packed, const uint64_t *sep);
 
 /* Banded affine-gap local alignment of jobs.  A job aligns the query string Q (length m, 1..65535) of pattern `pattern`
@@ -966,6 +967,55 @@ typedef struct {
     float ms_candidates, ms_rescue, ms_select, ms_wall;
 } debwt_fm_pair_stats;
 int debwt_fm_pair_stats_get(const debwt_fm *fm, debwt_fm_pair_stats *out);
+/* ---- extract: record text and the whole text from the index alone (fm_extract_kernels.h) --------------------------
+ * The third query of an FM-index.  Both calls below need the rows, the separator rows and the samples only: an index
+ * from debwt_fm_open answers exactly as one from debwt_fm_create.
+ * Anchors.  The first call of either kind orders the samples by text position on the device (8 bytes per sample: a
+ * permutation of sample numbers; position and row follow from it) and keeps the list with the index: it is counted in
+ * debwt_fm_info.device_bytes from then on, as the record table of debwt_fm_overlaps is.  It is built from a bitmap of
+ * the sampled positions and a rank over it (n / 8 + n / 16 bytes while it is built, released afterwards), so it has no
+ * capacity below the index's own.  The samples are checked on the way: every position < n, all distinct; otherwise
+ * DEBWT_EINVAL with the reason in debwt_fm_last_error, and no anchors are kept.
+ * Every walk takes a number of LF steps fixed by two checked positions: samples that are not the rows' can give wrong
+ * letters or DEBWT_EINVAL, never an endless walk or a store outside the output.
+ *
+ * debwt_fm_extract.  Job j yields S_record[offset, min(offset + length, |S_record|)) as upper-case ACGT: length
+ * UINT64_MAX means "to the end"; offset == |S_record| and length == 0 are legal and yield nothing.  DEBWT_EINVAL for
+ * record >= nrec, offset > |S_record| or reserved != 0.  out_offsets (njobs + 1) are the prefix sums of the lengths and
+ * are written first; DEBWT_ERANGE when capacity < out_offsets[njobs] (the protocol of debwt_fm_locate).  bases
+ * [out_offsets[j], out_offsets[j + 1]) is job j's text; no terminator is written.  A walk that misses the row of its
+ * anchor or meets a separator inside a record is DEBWT_EINVAL (the samples are not those of the rows).
+ * Batches are cut inside the library at DEBWT_FM_EXTRACT_BYTES output bytes (environment, read per call; default 256 MiB)
+ * and 2^22 jobs; a job above the limit goes alone.  A job is cut into one walk per gap between sampled positions, so a
+ * long job is as parallel as many short ones.  The result depends on neither the limit nor on sa_sample.  Device
+ * scratch: the bytes of one batch, 40 bytes per job of it, each with up to 25 % slack. */
+typedef struct { uint32_t record, reserved; uint64_t offset, length; } debwt_fm_extract_job;
+int debwt_fm_extract(debwt_fm *fm, const debwt_fm_extract_job *jobs, uint64_t njobs,
+                     uint64_t *out_offsets, char *bases, uint64_t capacity);
+/* what the last debwt_fm_extract or debwt_fm_restore_text did: jobs (0 for a restore), batches, kernel launches (plan and
+ * walk per batch; walk, padding and text check for a restore), segments (walks between two anchors), bases (n for a
+ * restore), LF steps (one v_lf each), wave steps (64 x the loop iterations per wave: steps / wave_steps is the share of
+ * lanes busy), rank lines read, the bytes of the anchors, the time to build them (events; 0 when they existed), walk
+ * time (events) and host wall time */
+typedef struct {
+    uint64_t jobs, batches, launches, segments, bases, steps, wave_steps, line_reads, anchor_bytes;
+    float ms_anchors, ms_kernel, ms_wall;
+} debwt_fm_extract_stats;
+int debwt_fm_extract_stats_get(const debwt_fm *fm, debwt_fm_extract_stats *out);
+/* debwt_fm_attach_text without a source: the 2-bit text is rebuilt in HBM from the index alone and attached.  DEBWT_OK at
+ * once when a text is attached already.  Afterwards the text is counted in debwt_fm_info.device_bytes and every call
+ * that wants a text works.  A text is attached only if every segment between two anchors arrives on the row of its
+ * lower anchor (the chain condition of the verifier's walk), the first segment ends on the '$' symbol, the positions
+ * at which '#' was met are exactly the record starts - 1 with '$' met nowhere but before position 0, and the check of
+ * debwt_fm_attach_text finds nothing; otherwise DEBWT_EINVAL with the reason in debwt_fm_last_error, and no text is
+ * attached.  debwt_fm_extract_stats_get describes it, with jobs = 0 and bases = n. */
+int debwt_fm_restore_text(debwt_fm *fm);
+/* The attached text to the host, however it was attached: packed receives ((n + 63) >> 5) + 2 words in the format
+ * debwt_load_text takes (32 'T' behind position n - 1, zeros behind), sep the nrec separator positions -- enough to
+ * load a context and build again with another k.  DEBWT_ESTATE without a text, DEBWT_ERANGE when capacity_words is
+ * below the word count. */
+int debwt_fm_text_fetch(debwt_fm *fm, uint64_t *packed, uint64_t capacity_words, uint64_t *sep);
+
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
