@@ -241,6 +241,11 @@ class DeBWT:
                                                      key_bits, int(key_lo), int(key_hi), ctypes.byref(ms) if want_ms else None))
         return ms.value
 
+    def radix_bucket_passes(self):
+        """Sorts of this process whose lowest prefix digit was split bucket by bucket in LDS (debwt_radix_bucket_passes;
+        DEBWT_BUCKET_PASS=0 / 1 in the environment switch that form off / on everywhere)."""
+        return int(self._L.debwt_radix_bucket_passes())
+
     def bwt_device_ptr(self):
         p = ctypes.c_void_p()
         self._chk(self._L.debwt_bwt_device_ptr(self._h, ctypes.byref(p)))

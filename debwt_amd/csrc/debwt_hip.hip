@@ -84,7 +84,8 @@ struct debwt_ctx {
     // the node instances exceed range_cap: "bucket streaming" for texts whose keys do not fit HBM at once).
     // D, Rmo and the buffers keysA/keysB/dk/dstart/pflag/mi_*/bstart/facts belong to the range being processed;
     // Q, B, nlarge and blk_*/facts_acc/large_q/mchar/sprow cover the whole context with 64-bit offsets.
-    struct KeyRange { u64 key_lo, key_hi, M, Mbase, Q, qbase, B, Bbase, s0, s1, l0, nl; };   // l0, nl: its blocks above the LDS capacity in large_q
+    struct KeyRange { u64 key_lo, key_hi, M, Mbase, Q, qbase, B, Bbase, s0, s1, l0, nl;      // l0, nl: its blocks above the LDS capacity in large_q
+                      bool heavy = false, heavy_known = false; };   // heavy: long 12-mer bins, no bucket pass (heavy_ranges)
     std::vector<KeyRange> ranges;
     u64 range_cap = 0;          // 0: from the free HBM at the first build (plan_ranges)
     u64 Mctx = 0;               // node instances of this context (sum over its ranges)
@@ -293,23 +294,24 @@ RadixWorkspace radix_ws(debwt_ctx *c) {
 // main: the key sort of a range (kernels named for the profile, keys possibly read off the text); otherwise one of
 // the small auxiliary sorts.  Pass events are recorded when `record_passes`.
 int sort_keys(debwt_ctx *c, u64 *a, u64 *b, u64 count, int key_bits, u64 **result, bool record_passes,
-              const TextKeySrc *text = nullptr, bool main_sort = false, RleSink *sink = nullptr, const u64 *key_range = nullptr) {
+              const TextKeySrc *text = nullptr, bool main_sort = false, RleSink *sink = nullptr, const u64 *key_range = nullptr,
+              bool heavy = false) {
     ENSURE(c, c->rs_over, radix_over_bytes(count));      // one list entry per 4096-key tile can be oversize
     // the joint counts of the last two array passes of a key range (no bytes unless the range's top byte is narrow)
     const u64 text_range[2] = {text ? text->key_lo : 0ull, text ? text->key_hi : 0ull};
     if (!key_range && text) key_range = text_range;
-    ENSURE(c, c->rs_pair, radix_pair_bytes_u64(count, key_bits, key_range));
+    ENSURE(c, c->rs_pair, radix_pair_bytes_u64(count, key_bits, key_range, heavy));
     RadixWorkspace ws = radix_ws(c);
     hipError_t e = hipSuccess;
     const bool main = main_sort || record_passes;
     const int net = (c->cfg.reserved & 32768) ? 32 : 0;     // bit 15: the bucket finish prefers the 4096-key network (tests)
     if (record_passes) {
         *result = radix_sort_u64(c->stream, a, b, count, key_bits, ws, c->cfg.sort_algo | net, &c->ev_pass[0][0], 16,
-                                 &c->n_pass_events, &e, text, sink, key_range);
+                                 &c->n_pass_events, &e, text, sink, key_range, heavy);
         c->st.radix_pass_keys = count;
     } else {
         *result = radix_sort_u64(c->stream, a, b, count, key_bits, ws, c->cfg.sort_algo | net | (main ? 0 : 16), nullptr, 0,
-                                 nullptr, &e, text, sink, key_range);
+                                 nullptr, &e, text, sink, key_range, heavy);
     }
     if (e != hipSuccess) { c->err = std::string("radix sort: ") + hipGetErrorString(e); return DEBWT_EDEVICE; }
     return DEBWT_OK;
@@ -829,6 +831,71 @@ static int special_device_build(debwt_ctx *c, bool release_arena = true) {
     return DEBWT_OK;
 }
 
+// how the key sort of a range divides its key bits (what sort_range's radix_sort_u64 will decide)
+static RadixSplit range_split(const debwt_ctx *c, const debwt_ctx::KeyRange &r) {
+    const u64 range[2] = {r.key_lo, r.key_hi};
+    return radix_split(r.M, 2 * c->cfg.k, c->cfg.sort_algo, range, r.heavy);
+}
+
+// Sampled census of the 12-mer prefixes (the top 24 key bits) of the text's nodes: one position in HEAVY_STRIDE (a prime:
+// no beat with tandem repeats) adds to one of 2^24 counters; k_heavy_bins then sums, per 12-bit bin of the range planner,
+// the counters above `limit` samples and keeps the largest.  The bucket pass gives a 12-mer bin to ONE workgroup, which
+// takes a bin above RS_BUCKET_HEAVY keys in two reads of global memory at a few per cent of the rate of the rest.
+#define HEAVY_STRIDE 251u
+__global__ __launch_bounds__(256) void k_prefix24_sample(const u64 *__restrict__ text, const u64 *__restrict__ sepbits, u64 n, int K,
+                                                         u32 *__restrict__ bins) {
+    const u64 kmask = K >= 64 ? ~0ull : (1ull << K) - 1ull;
+    for (u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x; j * HEAVY_STRIDE + (u64)K <= n; j += (u64)gridDim.x * blockDim.x) {
+        const u64 pos = j * HEAVY_STRIDE;
+        if (sep_window(sepbits, pos) & kmask) continue;               // no node starts here
+        atomicAdd(&bins[(u32)(text_window(text, pos) >> 40)], 1u);
+    }
+}
+__global__ __launch_bounds__(256) void k_heavy_bins(const u32 *__restrict__ bins, u32 limit, u64 *__restrict__ sum, u32 *__restrict__ top) {
+    for (u32 b = blockIdx.x * blockDim.x + threadIdx.x; b < (1u << 24); b += gridDim.x * blockDim.x) {
+        const u32 v = bins[b];
+        if (v > limit) { atomicAdd(&sum[b >> 12], (u64)v); atomicMax(&top[b >> 12], v); }
+    }
+}
+
+// Which key ranges leave the bucket pass alone (KeyRange::heavy): those where more than 1/64 of the keys sit in 12-mer bins
+// above RS_BUCKET_HEAVY keys, or one bin holds four times that (distribution R: Alu-like 12-mers with 10^7 instances).
+// Only ranges that would take the bucket pass are asked, once per plan; the counters borrow key buffer B.
+static int heavy_ranges(debwt_ctx *c) {
+    const int kb = 2 * c->cfg.k;
+    bool ask = false;
+    for (auto &r : c->ranges) {
+        const u64 range[2] = {r.key_lo, r.key_hi};
+        if (!r.heavy_known && radix_split(r.M, kb, c->cfg.sort_algo, range, false).bucket) ask = true;
+    }
+    const size_t need = ((size_t)4 << 24) + SHARD_BINS * 12;
+    if (!ask || c->K < 12 || kb < 24 || c->keysB.cap < need || c->n < (u64)c->K) return DEBWT_OK;
+    u32 *bins = c->keysB.as<u32>();
+    u64 *d_sum = reinterpret_cast<u64 *>(bins + (1u << 24));
+    u32 *d_top = reinterpret_cast<u32 *>(d_sum + SHARD_BINS);
+    HIPCHK(c, hipMemsetAsync(bins, 0, need, c->stream));
+    k_prefix24_sample<<<4096, 256, 0, c->stream>>>(c->text.as<u64>(), c->sepbits.as<u64>(), c->n, c->K, bins);
+    k_heavy_bins<<<4096, 256, 0, c->stream>>>(bins, RS_BUCKET_HEAVY / HEAVY_STRIDE, d_sum, d_top);
+    std::vector<u64> sum(SHARD_BINS);
+    std::vector<u32> top(SHARD_BINS);
+    HIPCHK(c, hipMemcpyAsync(sum.data(), d_sum, SHARD_BINS * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(top.data(), d_top, SHARD_BINS * 4, hipMemcpyDeviceToHost, c->stream));
+    int rc = sync_check(c);
+    if (rc) return rc;
+    for (auto &r : c->ranges) {
+        const u32 lo = (u32)(r.key_lo >> (kb - 12)), hi = r.key_hi ? (u32)(r.key_hi >> (kb - 12)) : SHARD_BINS;
+        u64 in_heavy = 0, largest = 0;
+        for (u32 b = lo; b < hi; b++) { in_heavy += sum[b] * HEAVY_STRIDE; largest = std::max<u64>(largest, (u64)top[b] * HEAVY_STRIDE); }
+        r.heavy = in_heavy > r.M / 64 || largest > 4ull * RS_BUCKET_HEAVY;
+        r.heavy_known = true;
+        if (getenv("DEBWT_TRACE_SORT"))
+            fprintf(stderr, "key range [%u, %u) of %llu keys: ~%llu in 12-mer bins above %u keys, the largest ~%llu: %s\n", lo, hi,
+                    (unsigned long long)r.M, (unsigned long long)in_heavy, (unsigned)RS_BUCKET_HEAVY, (unsigned long long)largest,
+                    r.heavy ? "four HBM passes" : "bucket pass");
+    }
+    return DEBWT_OK;
+}
+
 // plans the ranges, sizes the range workspace, starts the host special-region module
 static int sort_begin(debwt_ctx *c) {
     const u64 n = c->n;
@@ -843,10 +910,11 @@ static int sort_begin(debwt_ctx *c) {
     ENSURE(c, c->keysB, maxM * 8 + 64);
     ENSURE(c, c->rs_skew, (maxM / 2048 + 2) * 4);
     ENSURE(c, c->rs_rle, radix_rle_ws_bytes(maxM));
+    if ((rc = heavy_ranges(c))) return rc;
     size_t pair_bytes = 0;                                // the joint counts of every range fit what the widest one needs
     for (auto &r : c->ranges) {
         const u64 range[2] = {r.key_lo, r.key_hi};
-        pair_bytes = std::max(pair_bytes, radix_pair_bytes_u64(r.M, 2 * c->cfg.k, range));
+        pair_bytes = std::max(pair_bytes, radix_pair_bytes_u64(r.M, 2 * c->cfg.k, range, r.heavy));
     }
     ENSURE(c, c->rs_pair, pair_bytes);
     ENSURE(c, c->dk, maxM * 8 + 64);
@@ -855,7 +923,7 @@ static int sort_begin(debwt_ctx *c) {
     ENSURE(c, c->mchar, c->Mctx + 64);
     c->reclaim_ok = false;
     c->Q = c->B = c->nlarge = 0; c->nfacts_acc = 0; c->n1024 = 0; c->n512 = 0; c->Dsum = 0;
-    c->st.sort_unfit_stretches = c->st.sort_unfit_network = c->st.sort_over_stretches = 0;
+    c->st.sort_unfit_stretches = c->st.sort_unfit_network = c->st.sort_over_stretches = c->st.sort_bucket_passes = 0;
     const size_t P = c->ranges.size();
     HIPCHK(c, hipEventRecord(c->ev[0], c->stream));
     // the keys (node << 2 | pred) are read off the text inside the first radix pass: no unsorted key array
@@ -880,7 +948,7 @@ static int sort_begin(debwt_ctx *c) {
     // lane per text word, radix_text_hist_ranges); a single range of a long text takes the same kernel -- it is twice
     // as fast as the histogram pass of the sort itself (a shard of 8 reads the whole text for its one range)
     c->shared_hist = P <= RS_MAX_RANGES && !c->exchange &&
-                     (P > 1 || (P == 1 && n >= (1ull << 26) && radix_first_shift(c->ranges[0].M, 2 * c->cfg.k, c->cfg.sort_algo) > 0));
+                     (P > 1 || (P == 1 && n >= (1ull << 26) && range_split(c, c->ranges[0]).hbm_shift > 0));
     if (c->shared_hist) {
         const int kb = 2 * c->cfg.k;
         std::vector<u8> rob(SHARD_BINS, 0xFF);
@@ -889,7 +957,7 @@ static int sort_begin(debwt_ctx *c) {
             const u32 lo = (u32)(c->ranges[i].key_lo >> (kb - 12));
             const u32 hi = c->ranges[i].key_hi ? (u32)(c->ranges[i].key_hi >> (kb - 12)) : SHARD_BINS;
             for (u32 b = lo; b < hi; b++) rob[b] = (u8)i;
-            shifts[i] = radix_first_shift(c->ranges[i].M, kb, c->cfg.sort_algo);
+            shifts[i] = range_split(c, c->ranges[i]).hbm_shift;
         }
         ENSURE(c, c->dest_tab, SHARD_BINS);
         ENSURE(c, c->range_hist, P * radix_text_hist_stride() * sizeof(u32));
@@ -925,7 +993,8 @@ static int sort_range(debwt_ctx *c, size_t i, u64 *imported) {
     const u64 key_range[2] = {r.key_lo, r.key_hi};        // imported keys are the range's too
     if (imported && r.M < 2) c->sk = c->sort_a;
     else if ((rc = sort_keys(c, c->sort_a, c->sort_b, r.M, 2 * c->cfg.k, &c->sk, i == 0, imported ? nullptr : &ts, true,
-                             (c->cfg.reserved & 256) ? nullptr : &sink, key_range))) return rc;
+                             (c->cfg.reserved & 256) ? nullptr : &sink, key_range, r.heavy))) return rc;
+    else if (range_split(c, r).bucket) c->st.sort_bucket_passes++;
     if (P == 1 && !c->exchange) HIPCHK(c, hipEventRecord(c->ev[2], c->stream));
     if (!sink.done) {
         RleF f{c->sk, c->dk.as<u64>(), c->dstart.as<u32>(), c->mchar.as<u8>() + r.Mbase};
@@ -2598,6 +2667,7 @@ extern "C" int debwt_radix_sort_u64(debwt_ctx *c, uint64_t *d_keys, uint64_t *d_
 }
 
 extern "C" uint64_t debwt_radix_pair_passes(void) { return radix_pair_passes(); }
+extern "C" uint64_t debwt_radix_bucket_passes(void) { return radix_bucket_passes(); }
 
 // keys outside [lo, hi] (a derived pass sizes the runs of its digits by the bounds: such a key would be stored outside its run)
 __global__ void k_keys_outside(const u64 *__restrict__ keys, u64 n, u64 lo, u64 hi, u32 *__restrict__ flag) {

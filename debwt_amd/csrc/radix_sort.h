@@ -34,9 +34,27 @@ struct RadixWorkspace {
 // sort takes the bounds of a digit from its width.  0: no pair of passes qualifies.
 size_t radix_pair_bytes(u64 n, int lo_bit, int hi_bit, bool aux, const u64 *range);
 // the same for radix_sort_u64(n keys, key_bits) with any algo
-size_t radix_pair_bytes_u64(u64 n, int key_bits, const u64 *range);
+size_t radix_pair_bytes_u64(u64 n, int key_bits, const u64 *range, bool heavy = false);
 // passes this process has launched with derived chunk histograms (tests: which form a sort took)
 u64 radix_pair_passes();
+
+// How radix_sort_u64(n keys, key_bits, algo) divides the key bits -- the ONE place that decides it (the sort itself, the
+// first-pass histograms of the key ranges and the pair-count workspace all ask here):
+//   hybrid  the top T digits by passes, the bits below pshift by the bucket finish in LDS; else every digit by LSD passes
+//   bucket  the lowest of the T digits (bits pshift .. pshift + 7) is not an HBM pass: once the digits above it are in
+//           order the keys are a sequence of contiguous buckets, and rs_bucket_digit_kernel splits each in LDS
+//   hbm_shift  the bit the HBM passes start at, which is the digit the first pass buckets by: pshift, with `bucket` pshift + 8
+// range / heavy are the facts of a key range: range = {lo, hi} when every key lies in [lo, hi) (hi = 0: no upper bound),
+// heavy = a notable share of its keys sits in buckets too long for one workgroup (the caller's estimate).
+// By default the bucket pass serves the key ranges of four HBM digits that are not heavy.  DEBWT_BUCKET_PASS=0: never;
+// DEBWT_BUCKET_PASS=1: every hybrid sort, and every sort gets at least two prefix digits, so that small inputs reach it.
+struct RadixSplit { bool hybrid, bucket; int T, pshift, hbm_shift; };
+RadixSplit radix_split(u64 n, int key_bits, int algo, const u64 *range, bool heavy);
+// launches of rs_bucket_digit_kernel by this process (tests: which form a sort took)
+u64 radix_bucket_passes();
+// a bucket above this many keys is split by ONE workgroup in two reads of global memory at a fraction of the rate of the
+// rest: what a caller's estimate of `heavy` counts
+#define RS_BUCKET_HEAVY (1u << 20)
 
 // Optional key source for the FIRST pass: node keys (node << 2 | pred) computed on the fly from the 2-bit text,
 // one per position whose K-window holds no separator -- the key array is then never written out unsorted.
@@ -58,8 +76,6 @@ struct TextKeySrc {
 // shift[r].  counts: RS_MAX_RANGES-or-fewer blocks of radix_text_hist_stride() words, range r's histograms in block r.
 #define RS_MAX_RANGES 16
 size_t radix_text_hist_stride();
-// bit position of the digit the first pass of radix_sort_u64(n keys, key_bits, algo) buckets by
-int radix_first_shift(u64 n, int key_bits, int algo);
 hipError_t radix_text_hist_ranges(hipStream_t stream, const TextKeySrc &text, const u8 *range_of_bin, int key_bits,
                                   const int *shift, int nranges, u32 *counts);
 
@@ -108,6 +124,7 @@ bool radix_sort_bits_into(hipStream_t stream, u64 *a, u64 *dst, u64 *third, u64 
 // `done` tells the caller whether that happened; if not, it encodes the returned keys itself.
 // key_range (optional): {lo, hi}, every key lies in [lo, hi) (hi = 0: no upper bound) -- with `text` its key_lo / key_hi
 // say the same; the last array pass then takes its chunk histograms from the pass before it (RadixWorkspace::pair).
+// heavy: see radix_split.
 struct RleSink {
     u64 *dk; u32 *dstart; u8 *mchar;   // out: distinct keys, their first rows, one symbol per row
     void *ws;                          // radix_rle_ws_bytes(n) bytes of device scratch
@@ -123,4 +140,5 @@ struct RleSink {
 size_t radix_rle_ws_bytes(u64 n);
 u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, const RadixWorkspace &ws,
                     int algo, hipEvent_t *pass_events, int max_pairs, int *npairs, hipError_t *err,
-                    const TextKeySrc *text = nullptr, RleSink *sink = nullptr, const u64 *key_range = nullptr);
+                    const TextKeySrc *text = nullptr, RleSink *sink = nullptr, const u64 *key_range = nullptr,
+                    bool heavy = false);

@@ -2133,6 +2133,138 @@ __global__ void rs_over_ends(const u64 *__restrict__ keys, const u64 *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------------
+// bucket pass: the lowest prefix digit of keys that are in the order of the digits above it already
+//
+// The keys come as a sequence of buckets (equal key >> bshift), each contiguous.  Splitting one bucket by the 8 bits at
+// dshift is a counting sort that fits in LDS: it needs no chunk histograms, no scans over HBM and no write fronts -- the
+// bucket is read once, ranked in LDS and written once over the same index range of the other key buffer.  The order
+// inside a digit is free (the bucket finish sorts those keys by the whole key), so ranks come from returning LDS adds.
+// Raster: tile j owns the buckets that START in [j * RB_H, (j + 1) * RB_H).  A workgroup loads a window of up to RB_CAP
+// keys from where it stands (16 loads in flight per lane), finishes every bucket that ends inside the window and loads
+// the next window from the start of the bucket the window cut; the stretch in front of the tile's first boundary is the
+// tile before's and only measured.  A bucket that fills a whole window takes two reads: counted from global memory up to
+// its end (bisection), then read again and every key stored straight to bucket start + base[digit] + rank.
+#define RB_NT 256
+#define RB_KPT 16
+#define RB_CAP (RB_NT * RB_KPT)        // keys of a window: 32 KB of LDS and 126 VGPRs, four workgroups (16 waves) per CU.  Measured per
+                                       // 4.29 G keys of pan10x3G (12-mer bins of ~1,800 keys): 14.5 ms; 512 threads and windows of
+                                       // 8192 keys took 19.1 ms -- every bucket costs four barriers and a look at all 16 keys of a
+                                       // lane, and two workgroups per CU leave the loads of a window uncovered
+#define RB_H (4 * RB_CAP)              // tile stride: a workgroup walks its tile window by window, each starting where the last
+                                       // whole bucket of the one before ended -- only the cut bucket (and the stretch in front of
+                                       // the tile) is read twice; tiles of half a window read every key twice (22.1 ms with
+                                       // windows of 8192 keys, as long as the count and the scatter pass they replace)
+#define RB_UNROLL 4                    // loads in flight per lane in the two reads of a long bucket
+
+// exclusive scan of the 256 digit counters in place (one wave, four counters a lane)
+__device__ __forceinline__ void rb_scan_counts(u32 *cnt) {
+    const u32 lane = threadIdx.x;
+    const u32 c0 = cnt[4 * lane], c1 = cnt[4 * lane + 1], c2 = cnt[4 * lane + 2], c3 = cnt[4 * lane + 3];
+    const u32 tot = c0 + c1 + c2 + c3, ex = wave_scan_incl(tot) - tot;
+    cnt[4 * lane] = ex; cnt[4 * lane + 1] = ex + c0; cnt[4 * lane + 2] = ex + c0 + c1; cnt[4 * lane + 3] = ex + c0 + c1 + c2;
+}
+
+__global__ __launch_bounds__(RB_NT) void rs_bucket_digit_kernel(const u64 *__restrict__ src, u64 *__restrict__ dst, u64 n,
+                                                                int bshift, int dshift) {
+    __shared__ u64 buf[RB_CAP];
+    __shared__ u32 cnt[RS_RADIX];
+    __shared__ u64 s_p;
+    __shared__ u32 s_len[2];
+    const u32 tid = threadIdx.x;
+    const u64 x0 = (u64)blockIdx.x * RB_H, x1 = x0 + RB_H;
+    if (x0 >= n) return;
+    bool skip = x0 > 0;                   // the stretch in front of the first boundary belongs to the tile before
+    const u64 p_before = skip ? src[x0 - 1] >> bshift : 0ull;
+    u64 s = x0;
+    u32 it = 0;
+    while (s < n && s < x1) {
+        const u32 wlen = (u32)(n - s < (u64)RB_CAP ? n - s : (u64)RB_CAP);
+        u64 k[RB_KPT];
+#pragma unroll
+        for (int r = 0; r < RB_KPT; r++) { const u32 i = r * RB_NT + tid; k[r] = i < wlen ? src[s + i] : 0ull; }
+        u32 off = 0;
+        for (;;) {
+            it ^= 1u;                     // two slots for the length: a wave may still read the last one when the next is zeroed
+            if (skip) { if (tid == 0) s_p = p_before; }
+            else {
+#pragma unroll
+                for (int r = 0; r < RB_KPT; r++) if (r * RB_NT + tid == off) s_p = k[r] >> bshift;
+            }
+            if (tid < RS_RADIX) cnt[tid] = 0;
+            if (tid == 0) s_len[it] = 0;
+            lds_barrier();
+            const u64 p = s_p;
+            u32 rank[RB_KPT], inb = 0;
+#pragma unroll
+            for (int r = 0; r < RB_KPT; r++) {
+                const u32 i = r * RB_NT + tid;
+                rank[r] = 0;
+                if (i >= off && i < wlen && (k[r] >> bshift) == p) {
+                    inb |= 1u << r;
+                    if (!skip) rank[r] = atomicAdd(&cnt[(u32)(k[r] >> dshift) & (RS_RADIX - 1u)], 1u);
+                }
+            }
+            {
+                const u32 w = wave_scan_incl((u32)__popc(inb));
+                if ((tid & 63u) == 63u && w) atomicAdd(&s_len[it], w);
+            }
+            lds_barrier();
+            const u32 len = s_len[it];
+            if (off + len == wlen && s + wlen < n) {
+                // the bucket may go on behind the window: read it from its start, or, when it fills the window, take the two reads
+                if (off > 0) { s += off; break; }
+                u64 lo = s + wlen, hi = n;
+                while (lo < hi) { const u64 mid = (lo + hi) >> 1; if ((src[mid] >> bshift) <= p) lo = mid + 1; else hi = mid; }
+                const u64 e = lo;
+                if (!skip) {
+                    lds_barrier();
+                    if (tid < RS_RADIX) cnt[tid] = 0;
+                    lds_barrier();
+                    for (u64 i0 = s; i0 < e; i0 += (u64)RB_UNROLL * RB_NT) {
+                        u64 v[RB_UNROLL];
+#pragma unroll
+                        for (int j = 0; j < RB_UNROLL; j++) { const u64 i = i0 + (u64)j * RB_NT + tid; v[j] = i < e ? src[i] : 0ull; }
+#pragma unroll
+                        for (int j = 0; j < RB_UNROLL; j++)
+                            if (i0 + (u64)j * RB_NT + tid < e) atomicAdd(&cnt[(u32)(v[j] >> dshift) & (RS_RADIX - 1u)], 1u);
+                    }
+                    lds_barrier();
+                    if (tid < 64) rb_scan_counts(cnt);
+                    lds_barrier();
+                    for (u64 i0 = s; i0 < e; i0 += (u64)RB_UNROLL * RB_NT) {
+                        u64 v[RB_UNROLL];
+#pragma unroll
+                        for (int j = 0; j < RB_UNROLL; j++) { const u64 i = i0 + (u64)j * RB_NT + tid; v[j] = i < e ? src[i] : 0ull; }
+#pragma unroll
+                        for (int j = 0; j < RB_UNROLL; j++)
+                            if (i0 + (u64)j * RB_NT + tid < e) {
+                                const u32 pos = atomicAdd(&cnt[(u32)(v[j] >> dshift) & (RS_RADIX - 1u)], 1u);
+                                dst[s + pos] = v[j];
+                            }
+                    }
+                    lds_barrier();
+                }
+                skip = false;
+                s = e;
+                break;
+            }
+            if (!skip) {
+                if (tid < 64) rb_scan_counts(cnt);
+                lds_barrier();
+#pragma unroll
+                for (int r = 0; r < RB_KPT; r++)
+                    if (inb >> r & 1u) buf[cnt[(u32)(k[r] >> dshift) & (RS_RADIX - 1u)] + rank[r]] = k[r];
+                lds_barrier();
+                for (u32 i = tid; i < len; i += RB_NT) dst[s + off + i] = buf[i];
+            }
+            skip = false;
+            off += len;
+            if (off >= wlen || s + off >= x1) { s += off; break; }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------
 
 size_t radix_workspace_bytes(u64 max_keys) {
     (void)max_keys;
@@ -2215,10 +2347,10 @@ size_t radix_pair_bytes(u64 n, int lo_bit, int hi_bit, bool aux, const u64 *rang
     return need;
 }
 
-size_t radix_pair_bytes_u64(u64 n, int key_bits, const u64 *range) {
+size_t radix_pair_bytes_u64(u64 n, int key_bits, const u64 *range, bool heavy) {
     if (key_bits > 64) key_bits = 64;
     if (key_bits < 1) return 0;
-    return std::max(radix_pair_bytes(n, radix_first_shift(n, key_bits, 3), key_bits, false, range),
+    return std::max(radix_pair_bytes(n, radix_split(n, key_bits, 3, range, heavy).hbm_shift, key_bits, false, range),
                     radix_pair_bytes(n, 0, key_bits, false, range));
 }
 
@@ -2333,14 +2465,32 @@ static u64 *rs_lsd(hipStream_t stream, u64 *a, u64 *b, u64 n, int lo_bit, int hi
 
 size_t radix_text_hist_stride() { return (size_t)RS_RADIX * RS_MAXCHUNKS; }
 
-int radix_first_shift(u64 n, int key_bits, int algo) {
+static int rs_bucket_mode() {          // DEBWT_BUCKET_PASS: 0 = never, 1 = wherever it can run, unset (-1) = the default rule
+    const char *e = getenv("DEBWT_BUCKET_PASS");
+    return !e || !*e ? -1 : (atoi(e) != 0 ? 1 : 0);
+}
+
+RadixSplit radix_split(u64 n, int key_bits, int algo, const u64 *range, bool heavy) {
     algo &= 15;
     if (key_bits > 64) key_bits = 64;
+    const int mode = rs_bucket_mode();
+    // T top digits in HBM so that a bucket holds at most RS_BUCKET_TARGET keys on average, the rest in registers
     int T = 0;
     while ((n >> (8 * T)) > RS_BUCKET_TARGET && T < 4) T++;
-    if (algo != 3 || T == 0 || key_bits - 8 * T < 1) return 0;
-    return key_bits - 8 * T;
+    if (mode == 1 && T < 2) T = 2;
+    RadixSplit sp{false, false, 0, 0, 0};
+    if (algo != 3 || T == 0 || key_bits - 8 * T < 1) return sp;
+    sp.hybrid = true;
+    sp.T = T;
+    sp.pshift = key_bits - 8 * T;
+    const bool ranged = range && (range[0] || range[1]);
+    sp.bucket = mode == 1 ? T >= 2 : (mode != 0 && T == 4 && ranged && !heavy);
+    sp.hbm_shift = sp.bucket ? sp.pshift + 8 : sp.pshift;
+    return sp;
 }
+
+static std::atomic<u64> rs_bucket_launched{0};
+u64 radix_bucket_passes() { return rs_bucket_launched.load(std::memory_order_relaxed); }
 
 hipError_t radix_text_hist_ranges(hipStream_t stream, const TextKeySrc &text, const u8 *range_of_bin, int key_bits,
                                   const int *shift, int nranges, u32 *counts) {
@@ -2392,7 +2542,7 @@ bool radix_sort_bits_into(hipStream_t stream, u64 *a, u64 *dst, u64 *third, u64 
 
 u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, const RadixWorkspace &ws, int algo,
                     hipEvent_t *pass_events, int max_pairs, int *npairs, hipError_t *err, const TextKeySrc *text,
-                    RleSink *sink, const u64 *key_range) {
+                    RleSink *sink, const u64 *key_range, bool heavy) {
     *err = hipSuccess;
     if (sink) { sink->done = false; sink->n_over = 0; }
     if (npairs) *npairs = 0;
@@ -2401,20 +2551,26 @@ u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, con
     (void)net_only;
     algo &= 15;
     if (key_bits > 64) key_bits = 64;
-    if (!text && (n < 2 || key_bits <= 0)) return a;
+    // (DEBWT_BUCKET_PASS=1 takes a single key through the passes too: tests reach the bucket pass at every size)
+    if (!text && (n < (rs_bucket_mode() == 1 ? 1u : 2u) || key_bits <= 0)) return a;
     const u64 text_range[2] = {text ? text->key_lo : 0ull, text ? text->key_hi : 0ull};
     if (!key_range && text) key_range = text_range;
-    // hybrid: T top digits in HBM so that a bucket holds at most RS_BUCKET_TARGET keys on average, the rest in registers
-    int T = 0;
-    while ((n >> (8 * T)) > RS_BUCKET_TARGET && T < 4) T++;
-    if (algo != 3 || T == 0 || key_bits - 8 * T < 1 || !ws.over || !ws.h_over) {
+    const RadixSplit sp = radix_split(n, key_bits, algo, key_range, heavy);
+    if (!sp.hybrid || !ws.over || !ws.h_over) {
         u64 *r = rs_lsd(stream, a, b, n, 0, key_bits, ws, pass_events, max_pairs, npairs, text, aux, 0, nullptr, nullptr, key_range);
         *err = hipGetLastError();
         return r;
     }
-    const int pshift = key_bits - 8 * T;
-    u64 *src = rs_lsd(stream, a, b, n, pshift, key_bits, ws, pass_events, max_pairs, npairs, text, aux, 0, nullptr, nullptr, key_range);
+    const int pshift = sp.pshift;
+    u64 *src = rs_lsd(stream, a, b, n, sp.hbm_shift, key_bits, ws, pass_events, max_pairs, npairs, text, aux, 0, nullptr, nullptr, key_range);
     u64 *other = src == a ? b : a;
+    if (sp.bucket && n > 0) {
+        // the lowest prefix digit bucket by bucket in LDS, into the other key buffer (same buffer parity as the pass it replaces)
+        const u32 nbt = (u32)((n + RB_H - 1) / RB_H);
+        rs_bucket_digit_kernel<<<nbt, RB_NT, 0, stream>>>(src, other, n, sp.hbm_shift, pshift);
+        rs_bucket_launched.fetch_add(1, std::memory_order_relaxed);
+        u64 *t = src; src = other; other = t;
+    }
     (void)hipMemsetAsync(ws.over, 0, 16, stream);
     u32 ntiles = (u32)((n + RL_H - 1) / RL_H), nwtiles = (u32)((n + RLW_H - 1) / RLW_H);
     u8 *mark = reinterpret_cast<u8 *>(ws.skew_list);          // one byte per 4096-key tile

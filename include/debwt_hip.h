@@ -69,6 +69,8 @@ typedef struct {
     /* bucket finish of the key sort (all key ranges of the last run): stretches above a wave tile (1024 keys), those of
      * them the classifying kernel left to the 4096-key network, stretches above 4096 keys (all-HBM passes) */
     uint64_t sort_unfit_stretches, sort_unfit_network, sort_over_stretches;
+    /* key ranges of the last run whose lowest prefix digit was split bucket by bucket in LDS instead of by an HBM pass */
+    uint64_t sort_bucket_passes;
 } debwt_stats;
 
 int debwt_create(const debwt_config *cfg, debwt_ctx **out);
@@ -425,6 +427,11 @@ int debwt_radix_sort_u64_range(debwt_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp
 /* Passes this process has run that took their chunk histograms from the pass before them (tests and A/B runs: which form
  * a sort took; DEBWT_HIST_EVERY_PASS=1 in the environment keeps it from counting up). */
 uint64_t debwt_radix_pair_passes(void);
+/* Sorts this process has run whose lowest prefix digit was split bucket by bucket in LDS (one streaming pass) instead of by
+ * a count and a scatter pass in HBM.  By default that is the key ranges of four prefix digits; DEBWT_BUCKET_PASS=0 in the
+ * environment restores the HBM pass everywhere, DEBWT_BUCKET_PASS=1 takes the bucket pass in every sort with a bucket
+ * finish and gives every sort at least two prefix digits (tests: small inputs reach it). */
+uint64_t debwt_radix_bucket_passes(void);
 
 /* Host-only: checksums of the special-region tables (`collect`'s specialSA / specialBwt / specialBranch / head / tail
  * tables, src/collect#$.c:118-157,348-602) that debwt_kmer_sort_rle builds on host threads for the loaded text layout;
