@@ -12,6 +12,8 @@
  *                      [--max-occ N] [--min-score S] [--chain [--max-gap G]]
  *                      [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq
  *   deBWT-query extract -i OUT [--device D] --all | REGIONS.txt
+ *   deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq
+ *   deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -69,6 +71,16 @@
  * prints); the header is the region as given.  A malformed line or a region outside its record: exit status 1 with a
  * message naming the line, and nothing on stdout.  The output is produced in batches of about 64 MB.
  *
+ * kmers prints the count of every K-mer along every read (debwt_fm_kmer_counts): one line per read, name, TAB, the counts
+ * of the K-mers at positions 0, 1, .. joined by commas, or * when the read is shorter than K.  A K-mer with a letter
+ * outside ACGTacgt counts 0; --both-strands adds the occurrences of the reverse complement.
+ *
+ * correct removes substitution errors from the reads with the K-mer counts of the indexed collection (debwt_fm_correct;
+ * a K-mer is weak below T occurrences, default 3, at most R rounds, 1..16, default 4, both strands unless --forward) and
+ * writes them as FASTA to stdout, the names unchanged, one line per sequence; a fixed base is in upper case, every other
+ * letter as it came.  --report FILE writes a TSV of name, status (short, clean, fixed or weak), fixes, weak_before and
+ * weak_after; stderr gets one summary line.  Both need OUT, OUT.#, OUT.$ and OUT.sa only, and -k is required.
+ *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
  * that does not match OUT, OUT.# and OUT.$ is refused.
@@ -96,6 +108,8 @@ static void usage(void) {
             "                          [--max-occ N] [--min-score S] [--chain [--max-gap G]]\n"
             "                          [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq\n"
             "       deBWT-query extract -i OUT [--device D] --all | REGIONS.txt\n"
+            "       deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq\n"
+            "       deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
@@ -113,7 +127,11 @@ static void usage(void) {
             "read i of READS (tags pr:A:P|U, tl:i: template length, rs:i:1 rescued mate), --insert LO,HI bounds the template\n"
             "length instead of estimating it, --no-rescue leaves a mate without a seed unmapped;\n"
             "extract writes FASTA from the index alone: --all every record under the header >J (its 0-based number), or\n"
-            "the regions of REGIONS.txt, one per line, J or J:BEG-END (0-based, end exclusive), under the region as given\n");
+            "the regions of REGIONS.txt, one per line, J or J:BEG-END (0-based, end exclusive), under the region as given;\n"
+            "kmers prints name<TAB>c0,c1,.. per read, the occurrences of its K-mers (* for a read shorter than K);\n"
+            "correct writes the reads as FASTA with the substitution errors fixed that their K-mer counts single out (weak below\n"
+            "T occurrences, default 3; at most R rounds, default 4; both strands unless --forward); --report FILE gets\n"
+            "name<TAB>status<TAB>fixes<TAB>weak_before<TAB>weak_after, stderr one summary line\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -865,11 +883,84 @@ done:
     return ret;
 }
 
+/* ---- kmers / correct -------------------------------------------------------------------------------------------------- */
+
+static int cmd_kmers(const char *out, const char *pfile, int device, uint32_t k, uint32_t flags) {
+    struct patterns P;
+    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    int ret = 1;
+    uint64_t total = 0, *coff = malloc((P.n + 1) * 8);
+    for (uint64_t i = 0; i < P.n; i++) {
+        uint64_t m = P.off[i + 1] - P.off[i];
+        total += m >= k ? m - k + 1 : 0;
+    }
+    uint32_t *cnt = malloc((total ? total : 1) * 4);
+    if (!coff || !cnt) { fprintf(stderr, "out of memory\n"); goto done; }
+    int rc = debwt_fm_kmer_counts(fm, P.seq, P.off, P.n, k, flags, coff, cnt, total);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    for (uint64_t i = 0; i < P.n; i++) {
+        printf("%s\t", P.name[i]);
+        if (coff[i + 1] == coff[i]) putchar('*');
+        for (uint64_t j = coff[i]; j < coff[i + 1]; j++) printf("%s%u", j > coff[i] ? "," : "", cnt[j]);
+        putchar('\n');
+    }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(coff); free(cnt);
+    free_patterns(&P);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
+static int cmd_correct(const char *out, const char *pfile, int device, const debwt_fm_correct_opts *o, const char *report) {
+    struct patterns P;
+    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    int ret = 1;
+    char *fixed = malloc(P.len ? P.len : 1);
+    debwt_fm_correct_info *info = malloc((P.n ? P.n : 1) * sizeof *info);
+    FILE *rf = NULL;
+    if (!fixed || !info) { fprintf(stderr, "out of memory\n"); goto done; }
+    int rc = debwt_fm_correct(fm, P.seq, P.off, P.n, o, fixed, info);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    if (report && !(rf = fopen(report, "w"))) { fprintf(stderr, "cannot write %s\n", report); goto done; }
+    for (uint64_t i = 0; i < P.n; i++) {
+        printf(">%s\n", P.name[i]);
+        fwrite(fixed + P.off[i], 1, P.off[i + 1] - P.off[i], stdout);
+        putchar('\n');
+        if (rf) {
+            const uint32_t f = info[i].flags;
+            fprintf(rf, "%s\t%s\t%u\t%u\t%u\n", P.name[i],
+                    f & DEBWT_FM_CORRECT_SHORT ? "short" : f & DEBWT_FM_CORRECT_CLEAN ? "clean" : f & DEBWT_FM_CORRECT_FIXED ? "fixed" : "weak",
+                    info[i].fixes, info[i].weak_before, info[i].weak_after);
+        }
+    }
+    if (rf && fclose(rf)) { rf = NULL; fprintf(stderr, "cannot write %s\n", report); goto done; }
+    rf = NULL;
+    debwt_fm_correct_stats st;
+    debwt_fm_correct_stats_get(fm, &st);
+    fprintf(stderr, "correct: %llu reads, %llu short, %llu clean, %llu fixed, %llu weak; %llu fixes in %llu rounds, k = %u, %.1f ms\n",
+            (unsigned long long)P.n, (unsigned long long)st.reads_short, (unsigned long long)st.reads_clean,
+            (unsigned long long)st.reads_fixed, (unsigned long long)st.reads_weak, (unsigned long long)st.fixes,
+            (unsigned long long)st.rounds, o->k, st.kmers.ms_wall);
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    if (rf) fclose(rf);
+    free(fixed); free(info);
+    free_patterns(&P);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { usage(); return 1; }
     const char *cmd = argv[1];
     int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 :
-               !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 : -1;
+               !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
+               !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : -1;
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
     uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, min_overlap = 20, v64 = 0;
@@ -884,6 +975,10 @@ int main(int argc, char **argv) {
     const char *mate = NULL;
     int iupac = 0, search = 0, chain = 0, gap_given = 0, insert_given = 0, no_rescue = 0, no_self = 0, all = 0;
     uint32_t flags = 0;
+    debwt_fm_correct_opts ko;
+    debwt_fm_correct_defaults(&ko);
+    const char *report = NULL;
+    int k_given = 0;
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
         if (a[0] != '-' || !a[1]) {
@@ -891,11 +986,12 @@ int main(int argc, char **argv) {
             file = a;
             continue;
         }
-        if (((mode >= 1 && mode <= 3) || mode == 5) && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
+        if (((mode >= 1 && mode <= 3) || mode == 5 || mode == 7) && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
         if ((mode == 1 || mode == 2) && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
         if (mode == 5 && !strcmp(a, "--longest")) { flags |= DEBWT_FM_OVERLAP_LONGEST; continue; }
         if (mode == 5 && !strcmp(a, "--no-self")) { no_self = 1; continue; }
         if (mode == 6 && !strcmp(a, "--all")) { all = 1; continue; }
+        if (mode == 8 && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
         if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mode == 4 && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
         if (mode != 4 && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
@@ -962,6 +1058,19 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &ovl_permille) || ovl_permille > 1000) { fprintf(stderr, "--max-error-permille: a rate in 0..1000\n"); return 1; }
             permille_given = 1;
         }
+        else if ((mode == 7 || mode == 8) && !strcmp(a, "-k")) {
+            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "-k: a k-mer length of at least 1\n"); return 1; }
+            ko.k = (uint32_t)v64; k_given = 1;
+        }
+        else if (mode == 8 && !strcmp(a, "--min-count")) {
+            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-count: a count of at least 1\n"); return 1; }
+            ko.min_count = (uint32_t)v64;
+        }
+        else if (mode == 8 && !strcmp(a, "--rounds")) {
+            if (parse_u64(v, &v64) || v64 < 1 || v64 > DEBWT_FM_CORRECT_MAX_ROUNDS) { fprintf(stderr, "--rounds: a number in 1..%d\n", DEBWT_FM_CORRECT_MAX_ROUNDS); return 1; }
+            ko.max_rounds = (uint32_t)v64;
+        }
+        else if (mode == 8 && !strcmp(a, "--report")) report = v;
         else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
@@ -985,6 +1094,11 @@ int main(int argc, char **argv) {
         return cmd_map(out, ref, file, threads, iupac, seed, (int)device, &mo, chain, co.max_gap);
     }
     if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
+    if (mode == 7 || mode == 8) {
+        if (!k_given) { fprintf(stderr, "%s: -k K is required\n", cmd); usage(); return 1; }
+        if (mode == 7) return cmd_kmers(out, file, (int)device, ko.k, flags);
+        return cmd_correct(out, file, (int)device, &ko, report);
+    }
     if (mode == 5) {
         if (permille_given && !ovl_mm) { fprintf(stderr, "--max-error-permille: only with --max-mismatches\n"); usage(); return 1; }
         return cmd_overlaps(out, file, (int)device, (uint32_t)min_overlap, flags, no_self, ovl_mm, (uint32_t)ovl_k,

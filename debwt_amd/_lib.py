@@ -113,6 +113,45 @@ class DebwtFmExtractStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmKmerStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("patterns", "batches", "launches", "kmers", "steps", "line_reads", "wave_steps",
+                                                 "table_starts", "scratch_bytes")] +
+                [("table_q", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] +
+                [(n, ctypes.c_float) for n in ("ms_table", "ms_kernel", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
+CORRECT_MAX_ROUNDS = 16
+
+
+class DebwtFmCorrectStats(ctypes.Structure):
+    _fields_ = ([("kmers", DebwtFmKmerStats)] +
+                [(n, ctypes.c_uint64) for n in ("rounds", "trials", "fixes", "reads_short", "reads_clean", "reads_fixed",
+                                                 "reads_weak")] +
+                [("active", ctypes.c_uint64 * CORRECT_MAX_ROUNDS), ("ms_round", ctypes.c_float * CORRECT_MAX_ROUNDS)])
+
+    def as_dict(self):
+        d = self.kmers.as_dict()
+        d.update({n: getattr(self, n) for n, _ in self._fields_[1:8]})
+        d["active"] = [int(x) for x in self.active]
+        d["ms_round"] = [float(x) for x in self.ms_round]
+        return d
+
+
+class DebwtFmTrial(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("run_a", "run_b", "pos", "window", "kind")]
+
+
+class DebwtFmCorrectOpts(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("k", "min_count", "max_rounds", "flags")]
+
+
+class DebwtFmCorrectInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("flags", "fixes", "weak_before", "weak_after")]
+
+
 class DebwtFmExtractJob(ctypes.Structure):
     _fields_ = [("record", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("offset", ctypes.c_uint64),
                 ("length", ctypes.c_uint64)]
@@ -263,6 +302,8 @@ SYMBOLS = [
     "debwt_fm_overlaps", "debwt_fm_overlaps_stats_get", "debwt_fm_overlap_longest",
     "debwt_fm_overlaps_mm", "debwt_fm_overlaps_mm_stats_get",
     "debwt_fm_extract", "debwt_fm_extract_stats_get", "debwt_fm_restore_text", "debwt_fm_text_fetch",
+    "debwt_fm_kmer_counts", "debwt_fm_kmer_stats_get", "debwt_fm_weak_trials", "debwt_fm_correct_defaults",
+    "debwt_fm_correct", "debwt_fm_correct_stats_get",
 ]
 
 
@@ -543,6 +584,21 @@ def lib():
     L.debwt_fm_restore_text.argtypes = [vp]
     L.debwt_fm_text_fetch.restype = ctypes.c_int
     L.debwt_fm_text_fetch.argtypes = [vp, u64p, ctypes.c_uint64, u64p]
+    L.debwt_fm_kmer_counts.restype = ctypes.c_int
+    L.debwt_fm_kmer_counts.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, u64p, u32p,
+                                       ctypes.c_uint64]
+    L.debwt_fm_kmer_stats_get.restype = ctypes.c_int
+    L.debwt_fm_kmer_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmKmerStats)]
+    L.debwt_fm_weak_trials.restype = ctypes.c_int
+    L.debwt_fm_weak_trials.argtypes = [u32p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(DebwtFmTrial),
+                                       ctypes.c_uint64]
+    L.debwt_fm_correct_defaults.restype = None
+    L.debwt_fm_correct_defaults.argtypes = [ctypes.POINTER(DebwtFmCorrectOpts)]
+    L.debwt_fm_correct.restype = ctypes.c_int
+    L.debwt_fm_correct.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, ctypes.POINTER(DebwtFmCorrectOpts), vp,
+                                   ctypes.POINTER(DebwtFmCorrectInfo)]
+    L.debwt_fm_correct_stats_get.restype = ctypes.c_int
+    L.debwt_fm_correct_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmCorrectStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

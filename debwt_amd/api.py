@@ -482,6 +482,56 @@ class FMIndex:
         self._chk(self._L.debwt_fm_overlaps_mm_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def kmer_counts(self, patterns, k, strands="forward"):
+        """The count of every k-mer along every pattern (debwt_fm_kmer_counts): occurrences inside one record, 0 for a
+        k-mer with a character outside ACGTacgt; strands "both" adds the occurrences of the reverse complement (a k-mer
+        that is its own reverse complement counts twice).  Counts are uint32, clamped at 2^32 - 1.  A pattern shorter than
+        k has no k-mers.  No attached text is needed.  Returns a KmerResult."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        flags = SEARCH_BOTH_STRANDS if strands == "both" else 0
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        k = int(k)
+        coff = np.zeros(npat + 1, dtype=np.uint64)
+        cap = int(np.maximum(np.diff(offs.astype(np.int64)) - (k - 1), 0).sum()) if k > 0 else 0
+        counts = np.zeros(max(cap, 1), dtype=np.uint32)
+        self._chk(self._L.debwt_fm_kmer_counts(self._h, buf, _p64(offs), npat, k, flags, _p64(coff),
+                                               counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cap))
+        return KmerResult(coff, counts[:int(coff[npat])])
+
+    def kmer_stats(self):
+        """What the last kmer_counts call did (debwt_fm_kmer_stats_get): batches, k-mers, rank steps and lines, wave
+        steps, walks started from the prefix table, its q and build time, scratch bytes, ms."""
+        st = _lib.DebwtFmKmerStats()
+        self._chk(self._L.debwt_fm_kmer_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
+    def correct(self, patterns, k, min_count=3, rounds=4, strands="both"):
+        """k-mer read correction on the device (debwt_fm_correct): per read and round, a run of weak k-mers (count below
+        min_count) that has the signature of one substitution is fixed when exactly one other base makes the k-mer next
+        to the solid ones solid.  Bytes that are not fixed stay as given.  Returns (reads, info): the reads as a list of
+        bytes and a structured array of flags (CORRECT_SHORT / CLEAN / FIXED / WEAK), fixes, weak_before, weak_after."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        buf, offs = _patterns(patterns)
+        npat = len(offs) - 1
+        opts = _lib.DebwtFmCorrectOpts(k=int(k), min_count=int(min_count), max_rounds=int(rounds),
+                                       flags=SEARCH_BOTH_STRANDS if strands == "both" else 0)
+        out = ctypes.create_string_buffer(max(len(buf), 1))
+        info = np.zeros(max(npat, 1), dtype=_CORRECT_DTYPE)
+        self._chk(self._L.debwt_fm_correct(self._h, buf, _p64(offs), npat, ctypes.byref(opts), out,
+                                           info.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmCorrectInfo))))
+        raw = out.raw
+        return [raw[int(offs[i]):int(offs[i + 1])] for i in range(npat)], info[:npat]
+
+    def correct_stats(self):
+        """What the last correct call did (debwt_fm_correct_stats_get): the counters of kmer_stats over all its kernels,
+        rounds, reads that got a fix and ms per round, trials, fixes and reads per flag."""
+        st = _lib.DebwtFmCorrectStats()
+        self._chk(self._L.debwt_fm_correct_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def attach_text(self, source=None, words=None, sep=None):
         """Give the index its text (debwt_fm_attach_text; n / 4 bytes of HBM), which extend() and map() read.  source: the
         DeBWT context the index was made from (device-to-device copy), or None with the host text words / sep as
@@ -815,6 +865,10 @@ MAP_PROPER, MAP_RESCUED = 8, 16                        # MapResult.flags of FMIn
 MAP_FORWARD = 1                                        # option flag of debwt_fm_map
 OVERLAP_LONGEST = 2                                    # option flag of debwt_fm_overlaps
 OVERLAP_CONTAINS, OVERLAP_WHOLE = 1, 2                 # OverlapResult hit flags
+CORRECT_SHORT, CORRECT_CLEAN, CORRECT_FIXED, CORRECT_WEAK = 1, 2, 4, 8   # flags of FMIndex.correct's info
+_CORRECT_DTYPE = np.dtype([("flags", np.uint32), ("fixes", np.uint32), ("weak_before", np.uint32), ("weak_after", np.uint32)])
+_TRIAL_DTYPE = np.dtype([("run_a", np.uint32), ("run_b", np.uint32), ("pos", np.uint32), ("window", np.uint32),
+                         ("kind", np.uint32)])
 _OVERLAP_DTYPE = np.dtype([("record", np.uint32), ("length", np.uint32), ("strand", np.uint32), ("flags", np.uint32)])
 _ALN_DTYPE = np.dtype([("score", np.int32), ("qbeg", np.uint32), ("qend", np.uint32), ("edits", np.uint32),
                        ("tbeg", np.uint64), ("tend", np.uint64)])
@@ -845,6 +899,23 @@ def cluster_seeds(seeds, band=16, max_cand=8):
     if rc < 0:
         raise DebwtError(rc)
     return [{n: int(getattr(out[k], n)) for n, _ in _lib.DebwtFmCand._fields_} for k in range(rc)]
+
+
+def weak_trials(counts, k, min_count):
+    """Weak runs and trials of one read's k-mer counts on the host (debwt_fm_weak_trials, no GPU): a structured array of
+    (run_a, run_b, pos, window, kind) with kind 0 = left, 1 = right, runs ascending, left first."""
+    c = np.ascontiguousarray(counts, dtype=np.uint32)
+    L = _lib.lib()
+    p = c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if len(c) else None
+    n = L.debwt_fm_weak_trials(p, len(c), int(k), int(min_count), None, 0)
+    if n < 0:
+        raise DebwtError(n)
+    out = np.zeros(n, dtype=_TRIAL_DTYPE)
+    if n:
+        rc = L.debwt_fm_weak_trials(p, len(c), int(k), int(min_count), out.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmTrial)), n)
+        if rc != n:
+            raise DebwtError(rc if rc < 0 else -6)
+    return out
 
 
 def overlap_longest(hits, offsets):
@@ -1035,6 +1106,20 @@ class MemResult:
             self.index._chk(self.index._L.debwt_fm_locate(self.index._h, _p64(r), nm, int(max_per_mem or 0), _p64(offs),
                                                           _p64(pos), len(pos)))
         return [pos[int(offs[i]):int(offs[i + 1])] for i in range(nm)]
+
+
+class KmerResult:
+    """k-mer counts of FMIndex.kmer_counts: offsets (npat + 1 prefix sums of max(0, m - k + 1)) and counts (uint32);
+    profile(i): the counts along pattern i."""
+
+    def __init__(self, offsets, counts):
+        self.offsets, self.counts = offsets, counts
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def profile(self, i):
+        return self.counts[int(self.offsets[i]):int(self.offsets[i + 1])]
 
 
 class OverlapResult:

@@ -35,6 +35,7 @@
 #include "fm_overlap_kernels.h"
 #include "fm_overlap_mm_kernels.h"
 #include "fm_extract_kernels.h"
+#include "fm_kmer_kernels.h"
 
 namespace {
 
@@ -2974,6 +2975,12 @@ struct debwt_fm {
     float ms_anchors = 0.f;
     DevBuf e_jobs, e_seg, e_out, e_ctr, e_sep;   // extract scratch of one batch; counters; separator positions of a restore
     debwt_fm_extract_stats e_stats{};
+    DevBuf k_table;              // k-mers: [lo, hi) of every q-mer, made by the first call that needs it (k_q: its q)
+    bool has_ktable = false;
+    u32 k_q = 0;
+    DevBuf k_coff, k_counts, k_ctr, k_active, k_info, k_ntr, k_trials, k_trun, k_res;   // k-mer and correction scratch of one batch
+    debwt_fm_kmer_stats k_stats{};
+    debwt_fm_correct_stats c_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -3245,7 +3252,8 @@ extern "C" int debwt_fm_info_get(const debwt_fm *f, debwt_fm_info *out) {
     memset(out, 0, sizeof *out);
     out->n = f->n; out->nrec = f->nrec; out->sa_sample = f->s; out->samples = f->nsamp;
     out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap + (f->has_text ? f->text.cap : 0) +
-                        (f->has_otable ? f->o_table.cap : 0) + (f->has_anchors ? f->anchors.cap : 0);
+                        (f->has_otable ? f->o_table.cap : 0) + (f->has_anchors ? f->anchors.cap : 0) +
+                        (f->has_ktable ? f->k_table.cap : 0);
     out->ms_rank = f->ms_rank; out->ms_samples = f->ms_samples;
     for (int q = 0; q < 4; q++) out->census[q] = f->census[q];
     return DEBWT_OK;
@@ -6115,6 +6123,304 @@ extern "C" int debwt_fm_text_fetch(debwt_fm *f, uint64_t *packed, uint64_t capac
     return DEBWT_OK;
 }
 
+// ---- k-mer counts along reads and read correction (fm_kmer_kernels.h) ------------------------------------------------
+// A batch of patterns [p0, p1) runs as one lane per (position, strand); the positions of the batch are numbered by the
+// prefix sums of the reads' k-mer numbers, which the kernels search for the read of a lane.  The prefix table is made by
+// the first call that wants it and kept.  The correction keeps a batch's reads in q_chars over all its rounds: profile,
+// trials, evaluation and fixes are kernels, and per round only the number of reads that got a fix comes back.
+
+namespace {
+
+constexpr u64 FM_KMER_ITEMS = 1ull << 24;              // k-mer positions per batch
+constexpr u32 FM_KMER_TABLE_Q = 12;                    // default q of the prefix table
+
+int fm_kmer_env_q(debwt_fm *f, u32 *q) {
+    *q = FM_KMER_TABLE_Q;
+    const char *e = getenv("DEBWT_FM_KMER_TABLE_Q");
+    if (!e || !*e) return DEBWT_OK;
+    char *end = nullptr;
+    const u64 v = strtoull(e, &end, 10);
+    if (*end || v > FM_KMER_MAX_Q) { f->err = "DEBWT_FM_KMER_TABLE_Q must be 0..12"; return DEBWT_EINVAL; }
+    *q = (u32)v;
+    return DEBWT_OK;
+}
+
+// the table of q-mers in f->k_table (q >= 1): kept when it is there, otherwise built level by level (st->ms_table)
+int fm_kmer_table(debwt_fm *f, u32 q, debwt_fm_kmer_stats *st) {
+    st->table_q = q;
+    if (!q || (f->has_ktable && f->k_q == q)) return DEBWT_OK;
+    const size_t bytes = (size_t)16 << (2 * q);
+    f->has_ktable = false;
+    if (f->k_table.cap != bytes) {                            // exactly the table: it is reported in device_bytes
+        HIPCHK(f, hipStreamSynchronize(f->stream));
+        if (f->k_table.p) { (void)hipFree(f->k_table.p); f->k_table.p = nullptr; f->k_table.cap = 0; }
+        HIPCHK(f, hipMalloc(&f->k_table.p, bytes));
+        f->k_table.cap = bytes;
+    }
+    hipEvent_t e0, e1;
+    HIPCHK(f, hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
+    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
+    const u64 root[2] = {0, f->n};
+    HIPCHK(f, hipMemcpyAsync(f->k_table.p, root, 16, hipMemcpyHostToDevice, f->stream));
+    (void)hipEventRecord(e0, f->stream);
+    for (u32 l = 1; l <= q; l++) {
+        const u64 prev = 1ull << (2 * (l - 1));
+        k_fm_kmer_table_level<<<grid_for(prev, 256), 256, 0, f->stream>>>(f->V, f->k_table.as<u64>(), prev);
+        st->launches++;
+    }
+    (void)hipEventRecord(e1, f->stream);
+    int rc = fm_sync(f);                                       // root is host memory
+    if (rc) return rc;
+    (void)hipEventElapsedTime(&st->ms_table, e0, e1);
+    f->has_ktable = true;
+    f->k_q = q;
+    return DEBWT_OK;
+}
+
+struct FmKmerCall {                                     // what kmer_counts and correct share
+    u32 k = 0, nstr = 1, q = 0;
+    u64 limit = 0;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    ~FmKmerCall() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
+inline u64 fm_kmer_nk(const uint64_t *offsets, u64 i, u32 k) {
+    const u64 m = offsets[i + 1] - offsets[i];
+    return m >= k ? m - k + 1 : 0;
+}
+
+int fm_kmer_begin(debwt_fm *f, const char *what, const char *patterns, const uint64_t *offsets, u64 npat, u32 k, u32 flags,
+                  u64 max_len, FmKmerCall *c, debwt_fm_kmer_stats *st) {
+    if (!k) { f->err = std::string(what) + ": k must be at least 1"; return DEBWT_EINVAL; }
+    if (flags & ~DEBWT_FM_BOTH_STRANDS) { f->err = std::string(what) + ": unknown flags"; return DEBWT_EINVAL; }
+    for (u64 i = 0; i < npat; i++) {
+        if (offsets[i + 1] < offsets[i]) { f->err = std::string(what) + ": offsets must not decrease"; return DEBWT_EINVAL; }
+        if (offsets[i + 1] - offsets[i] >= max_len) { f->err = std::string(what) + ": a pattern is too long"; return DEBWT_EINVAL; }
+    }
+    if (npat && offsets[npat] > offsets[0] && !patterns) return DEBWT_EINVAL;
+    int rc = fm_kmer_env_q(f, &c->q);
+    if (rc) return rc;
+    if (k < c->q) c->q = 0;                                    // every k-mer walks from [0, n): the call needs no table
+    c->k = k;
+    c->nstr = (flags & DEBWT_FM_BOTH_STRANDS) ? 2 : 1;
+    c->limit = fm_env_u64("DEBWT_FM_KMER_ITEMS", FM_KMER_ITEMS);
+    st->patterns = npat;
+    if (!npat) return DEBWT_OK;
+    HIPCHK(f, hipSetDevice(f->device));
+    HIPCHK(f, hipEventCreate(&c->e0));
+    HIPCHK(f, hipEventCreate(&c->e1));
+    if ((rc = fm_kmer_table(f, c->q, st))) return rc;
+    FM_ENSURE(f, f->k_ctr, FM_KM_NCTR * 8);
+    HIPCHK(f, hipMemsetAsync(f->k_ctr.p, 0, FM_KM_NCTR * 8, f->stream));
+    return DEBWT_OK;
+}
+
+// end of the batch that begins at p0: at least one pattern, however long
+u64 fm_kmer_cut(const uint64_t *offsets, u64 npat, u64 p0, const FmKmerCall &c, u64 *items) {
+    u64 p1 = p0 + 1, it = fm_kmer_nk(offsets, p0, c.k);
+    while (p1 < npat && p1 - p0 < FM_BATCH_PATTERNS && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS &&
+           it + fm_kmer_nk(offsets, p1, c.k) <= c.limit)
+        it += fm_kmer_nk(offsets, p1++, c.k);
+    *items = it;
+    return p1;
+}
+
+// the batch's bytes, offsets and position numbers to q_chars, q_off and k_coff
+int fm_kmer_upload(debwt_fm *f, const char *patterns, const uint64_t *offsets, u64 p0, u64 p1, u32 k, u64 items) {
+    const u64 np = p1 - p0, base = offsets[p0], bytes = offsets[p1] - base;
+    std::vector<u64> coff(np + 1);
+    coff[0] = 0;
+    for (u64 i = 0; i < np; i++) coff[i + 1] = coff[i] + fm_kmer_nk(offsets, p0 + i, k);
+    FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
+    FM_ENSURE(f, f->q_off, (size_t)(np + 1) * 8);
+    FM_ENSURE(f, f->k_coff, (size_t)(np + 1) * 8);
+    FM_ENSURE(f, f->k_counts, (size_t)std::max<u64>(items, 1) * 4);
+    if (bytes) HIPCHK(f, hipMemcpyAsync(f->q_chars.p, patterns + base, bytes, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->q_off.p, offsets + p0, (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->k_coff.p, coff.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    return fm_sync(f);                                         // coff is host memory
+}
+
+void fm_kmer_profile_launch(debwt_fm *f, const FmKmerCall &c, u64 base, u64 np, u64 items, const u8 *active,
+                            debwt_fm_kmer_stats *st) {
+    k_fm_kmer_profile<<<grid_for(items * c.nstr, 256), 256, 0, f->stream>>>(
+        f->V, c.q ? f->k_table.as<u64>() : nullptr, c.q, f->q_chars.as<u8>(), f->q_off.as<u64>(), base, f->k_coff.as<u64>(), np,
+        items, c.k, c.nstr, active, f->k_counts.as<u32>(), f->k_ctr.as<u64>());
+    st->launches++;
+}
+
+int fm_kmer_end(debwt_fm *f, debwt_fm_kmer_stats *st, u64 h[FM_KM_NCTR]) {
+    HIPCHK(f, hipMemcpyAsync(h, f->k_ctr.p, FM_KM_NCTR * 8, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    st->steps = h[FM_KM_STEPS]; st->line_reads = h[FM_KM_READS]; st->wave_steps = h[FM_KM_WSTEPS];
+    st->table_starts = h[FM_KM_TSTART]; st->kmers = h[FM_KM_KMERS];
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_kmer_counts(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat, uint32_t k,
+                                    uint32_t flags, uint64_t *count_offsets, uint32_t *counts, uint64_t capacity) {
+    if (!f || !offsets || !count_offsets) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->k_stats = debwt_fm_kmer_stats{};
+    debwt_fm_kmer_stats &st = f->k_stats;
+    FmKmerCall c;
+    int rc = fm_kmer_begin(f, "debwt_fm_kmer_counts", patterns, offsets, npat, k, flags, 1ull << 32, &c, &st);
+    if (rc) return rc;
+    count_offsets[0] = 0;
+    for (u64 i = 0; i < npat; i++) count_offsets[i + 1] = count_offsets[i] + fm_kmer_nk(offsets, i, k);
+    const u64 total = count_offsets[npat];
+    if (capacity < total || (total && !counts)) {
+        f->err = "debwt_fm_kmer_counts: capacity below the k-mers (count_offsets[npat] = " + std::to_string(total) + ")";
+        return DEBWT_ERANGE;
+    }
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 items;
+        const u64 p1 = fm_kmer_cut(offsets, npat, p0, c, &items);
+        if (items) {
+            const u64 np = p1 - p0;
+            if ((rc = fm_kmer_upload(f, patterns, offsets, p0, p1, k, items))) return rc;
+            st.scratch_bytes = std::max<u64>(st.scratch_bytes, (offsets[p1] - offsets[p0]) + (np + 1) * 16 + items * 4);
+            (void)hipEventRecord(c.e0, f->stream);
+            fm_kmer_profile_launch(f, c, offsets[p0], np, items, nullptr, &st);
+            (void)hipEventRecord(c.e1, f->stream);
+            HIPCHK(f, hipMemcpyAsync(counts + count_offsets[p0], f->k_counts.p, items * 4, hipMemcpyDeviceToHost, f->stream));
+            if ((rc = fm_sync(f))) return rc;                  // the next batch reuses the scratch
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, c.e0, c.e1);
+            st.ms_kernel += ms;
+        }
+        st.batches++;
+        p0 = p1;
+    }
+    u64 h[FM_KM_NCTR];
+    if (npat && (rc = fm_kmer_end(f, &st, h))) return rc;
+    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_kmer_stats_get(const debwt_fm *f, debwt_fm_kmer_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->k_stats;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_weak_trials(const uint32_t *counts, uint64_t nk, uint32_t k, uint32_t min_count, debwt_fm_trial *out,
+                                    uint64_t capacity) {
+    if (!k || !min_count || nk + k > (1ull << 31) || (nk && !counts) || (capacity && !out)) return DEBWT_EINVAL;
+    u64 n = 0;
+    fm_weak_trials(counts, (u32)nk, k, min_count, [&](u32 a, u32 b, u32 pos, u32 window, u32 kind) {
+        if (n < capacity) out[n] = debwt_fm_trial{a, b, pos, window, kind};
+        n++;
+    });
+    return (int)n;
+}
+
+extern "C" void debwt_fm_correct_defaults(debwt_fm_correct_opts *o) {
+    if (!o) return;
+    o->k = 0; o->min_count = 3; o->max_rounds = 4; o->flags = DEBWT_FM_BOTH_STRANDS;
+}
+
+extern "C" int debwt_fm_correct(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                                const debwt_fm_correct_opts *opts, char *out, debwt_fm_correct_info *info) {
+    if (!f || !offsets || !opts || (npat && !info)) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->c_stats = debwt_fm_correct_stats{};
+    debwt_fm_correct_stats &cs = f->c_stats;
+    debwt_fm_kmer_stats &st = cs.kmers;
+    const u32 k = opts->k, min_count = opts->min_count, rounds = opts->max_rounds;
+    if (!min_count) { f->err = "debwt_fm_correct: min_count must be at least 1"; return DEBWT_EINVAL; }
+    if (rounds < 1 || rounds > DEBWT_FM_CORRECT_MAX_ROUNDS) { f->err = "debwt_fm_correct: max_rounds must be 1..16"; return DEBWT_EINVAL; }
+    FmKmerCall c;
+    int rc = fm_kmer_begin(f, "debwt_fm_correct", patterns, offsets, npat, k, opts->flags, 1ull << 31, &c, &st);
+    if (rc) return rc;
+    if (npat && offsets[npat] > offsets[0] && !out) return DEBWT_EINVAL;
+    std::vector<u8> act;
+    for (u64 p0 = 0; p0 < npat;) {
+        u64 items;
+        const u64 p1 = fm_kmer_cut(offsets, npat, p0, c, &items);
+        const u64 np = p1 - p0, base = offsets[p0], bytes = offsets[p1] - base, nslots = items + np;
+        debwt_fm_correct_info *inf = info + p0;
+        memset(inf, 0, np * sizeof *inf);
+        if (!items) {                                          // short reads only: copied
+            if (bytes) memcpy(out + base, patterns + base, bytes);
+        } else {
+            if ((rc = fm_kmer_upload(f, patterns, offsets, p0, p1, k, items))) return rc;
+            FM_ENSURE(f, f->k_active, (size_t)np);
+            FM_ENSURE(f, f->k_info, (size_t)np * 16);
+            FM_ENSURE(f, f->k_ntr, (size_t)np * 4);
+            FM_ENSURE(f, f->k_trials, (size_t)nslots * 8);
+            FM_ENSURE(f, f->k_trun, (size_t)nslots * 4);
+            FM_ENSURE(f, f->k_res, (size_t)nslots);
+            st.scratch_bytes = std::max<u64>(st.scratch_bytes, bytes + (np + 1) * 16 + items * 4 + np * 21 + nslots * 13);
+            act.resize(np);
+            for (u64 i = 0; i < np; i++) act[i] = fm_kmer_nk(offsets, p0 + i, k) ? 1 : 0;
+            HIPCHK(f, hipMemcpyAsync(f->k_active.p, act.data(), np, hipMemcpyHostToDevice, f->stream));
+            HIPCHK(f, hipMemsetAsync(f->k_info.p, 0, np * 16, f->stream));
+            u8 *d_act = f->k_active.as<u8>();
+            u64 *ctr = f->k_ctr.as<u64>();
+            for (u32 r = 0; r <= rounds; r++) {
+                const bool last = r == rounds;                 // after the last round: the profile of weak_after alone
+                (void)hipEventRecord(c.e0, f->stream);
+                fm_kmer_profile_launch(f, c, base, np, items, d_act, &st);
+                k_fm_correct_trials<<<grid_for(np, 256), 256, 0, f->stream>>>(
+                    f->k_coff.as<u64>(), np, k, min_count, f->k_counts.as<u32>(), d_act, r == 0, last, f->k_trials.as<u32>(),
+                    f->k_trun.as<u32>(), f->k_ntr.as<u32>(), f->k_info.as<u32>(), ctr);
+                st.launches++;
+                u64 got = 0;
+                if (!last) {
+                    HIPCHK(f, hipMemsetAsync(ctr + FM_KM_ACTIVE, 0, 8, f->stream));
+                    k_fm_correct_eval<<<grid_for(nslots * 4 * c.nstr, 256), 256, 0, f->stream>>>(
+                        f->V, c.q ? f->k_table.as<u64>() : nullptr, c.q, f->q_chars.as<u8>(), f->q_off.as<u64>(), base,
+                        f->k_coff.as<u64>(), np, nslots, k, c.nstr, min_count, d_act, f->k_trials.as<u32>(),
+                        f->k_ntr.as<u32>(), f->k_res.as<u8>(), ctr);
+                    k_fm_correct_apply<<<grid_for(np, 256), 256, 0, f->stream>>>(
+                        f->q_chars.as<u8>(), f->q_off.as<u64>(), base, f->k_coff.as<u64>(), np, f->k_trials.as<u32>(),
+                        f->k_trun.as<u32>(), f->k_ntr.as<u32>(), f->k_res.as<u8>(), d_act, f->k_info.as<u32>(), ctr);
+                    st.launches += 2;
+                    HIPCHK(f, hipMemcpyAsync(&got, ctr + FM_KM_ACTIVE, 8, hipMemcpyDeviceToHost, f->stream));
+                }
+                (void)hipEventRecord(c.e1, f->stream);
+                if ((rc = fm_sync(f))) return rc;
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, c.e0, c.e1);
+                st.ms_kernel += ms;
+                if (last) { cs.ms_round[rounds - 1] += ms; break; }
+                cs.ms_round[r] += ms;
+                cs.active[r] += got;
+                cs.rounds = std::max<u64>(cs.rounds, r + 1);
+                if (!got) break;
+            }
+            if (bytes) HIPCHK(f, hipMemcpyAsync(out + base, f->q_chars.p, bytes, hipMemcpyDeviceToHost, f->stream));
+            HIPCHK(f, hipMemcpyAsync(inf, f->k_info.p, np * 16, hipMemcpyDeviceToHost, f->stream));
+            if ((rc = fm_sync(f))) return rc;                  // the next batch reuses the scratch
+        }
+        for (u64 i = 0; i < np; i++) {
+            debwt_fm_correct_info &x = inf[i];
+            if (!fm_kmer_nk(offsets, p0 + i, k)) { x = debwt_fm_correct_info{DEBWT_FM_CORRECT_SHORT, 0, 0, 0}; cs.reads_short++; }
+            else if (!x.weak_before) { x.flags = DEBWT_FM_CORRECT_CLEAN; cs.reads_clean++; }
+            else if (!x.weak_after) { x.flags = DEBWT_FM_CORRECT_FIXED; cs.reads_fixed++; }
+            else { x.flags = DEBWT_FM_CORRECT_WEAK; cs.reads_weak++; }
+        }
+        st.batches++;
+        p0 = p1;
+    }
+    u64 h[FM_KM_NCTR] = {};
+    if (npat && (rc = fm_kmer_end(f, &st, h))) return rc;
+    cs.trials = h[FM_KM_TRIALS]; cs.fixes = h[FM_KM_FIXES];
+    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_correct_stats_get(const debwt_fm *f, debwt_fm_correct_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->c_stats;
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
@@ -6124,7 +6430,8 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
                       &f->m_cranges, &f->text, &f->x_jobs, &f->x_best, &f->x_cells, &f->x_flags, &f->x_tr, &f->x_cigoff,
                       &f->x_cig, &f->x_anchors, &f->o_table, &f->o_slot, &f->o_runs, &f->o_nruns, &f->o_nhits, &f->o_rbase,
                       &f->o_hbase, &f->o_cruns, &f->o_rout, &f->o_hits, &f->anchors, &f->e_jobs, &f->e_seg, &f->e_out, &f->e_ctr,
-                      &f->e_sep})
+                      &f->e_sep, &f->k_table, &f->k_coff, &f->k_counts, &f->k_ctr, &f->k_active, &f->k_info, &f->k_ntr,
+                      &f->k_trials, &f->k_trun, &f->k_res})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

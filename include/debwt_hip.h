@@ -1022,6 +1022,93 @@ int debwt_fm_restore_text(debwt_fm *fm);
  * load a context and build again with another k.  DEBWT_ESTATE without a text, DEBWT_ERANGE when capacity_words is
  * below the word count. */
 int debwt_fm_text_fetch(debwt_fm *fm, uint64_t *packed, uint64_t capacity_words, uint64_t *sep);
+/* ---- k-mer counts along reads and k-mer read correction (fm_kmer_kernels.h) ----------------------------------------
+ * Characters: A/C/G/T in either case are bases, every other byte is a non-base.  For a string W of k bytes, occ W is 0
+ * when W holds a non-base and otherwise what debwt_fm_count reports for it, hi - lo: the occurrences inside one record.
+ * cnt W = occ W, and with DEBWT_FM_BOTH_STRANDS cnt W = occ W + occ revcomp W (A<->T, C<->G): a k-mer that equals its
+ * own reverse complement is therefore counted TWICE.  None of the calls below needs an attached text: an index from
+ * debwt_fm_open answers as one from debwt_fm_create.
+ *
+ * debwt_fm_kmer_counts.  Pattern i of m bytes has nk = max(0, m - k + 1) k-mers.  count_offsets (npat + 1) are the prefix
+ * sums of nk and are written first; DEBWT_ERANGE when capacity < count_offsets[npat] (the protocol of debwt_fm_locate).
+ * counts[count_offsets[i] + j] = min(cnt of P_i[j .. j + k), 2^32 - 1).  DEBWT_EINVAL for k = 0, flags other than
+ * DEBWT_FM_BOTH_STRANDS, decreasing offsets and a pattern of 2^32 bytes or more.
+ * Batches are cut inside the library at 64 MB of pattern bytes and DEBWT_FM_KMER_ITEMS k-mer positions (environment, read
+ * per call; default 2^24; a pattern with more goes alone); the result depends on neither.  Device scratch of a batch, each
+ * with up to 25 % slack: the pattern bytes, 16 bytes per pattern and 4 per position (64 MiB at the default); the
+ * correction adds 13 bytes per position and 34 per pattern (about 300 MiB in all at the default).
+ *
+ * The prefix table.  For every q-mer w the table holds the [lo, hi) that debwt_fm_count gives for w: 2 u64 per entry,
+ * 16 * 4^q bytes, the first character the most significant digit.  It is made on the device, level by level, by the
+ * first call that needs it (q > 0 and k >= q; a call with k < q uses none and reports table_q 0), and kept with the index like the record table of debwt_fm_overlaps: from then on it is
+ * counted in debwt_fm_info.device_bytes.  A k-mer with k >= q starts from the entry of its last q characters and walks
+ * the remaining k - q; a k-mer with k < q walks from [0, n).  q is DEBWT_FM_KMER_TABLE_Q (environment, read per call;
+ * 0..12, default 12: 268 MB; 0 = no table, anything else DEBWT_EINVAL); a kept table of another q is replaced.  No result
+ * depends on q. */
+int debwt_fm_kmer_counts(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat, uint32_t k,
+                         uint32_t flags, uint64_t *count_offsets, uint32_t *counts, uint64_t capacity);
+/* what the last debwt_fm_kmer_counts did (and, inside debwt_fm_correct_stats, the last debwt_fm_correct): patterns,
+ * batches, kernel launches (the table's levels included), k-mers counted (positions; for a correction also the
+ * substituted k-mers of the trials), rank steps (one fm_occ2 each), rank lines read, wave steps (64 x the longest lane
+ * per wave: steps / wave_steps is the share of lanes busy, the rest idle behind k-mers that died), the walks started
+ * from a table entry (per k-mer and strand), the largest scratch of a batch, the table's q (0: none used), the time to
+ * build the table (events; 0 when it existed), kernel time (events) and host wall time */
+typedef struct {
+    uint64_t patterns, batches, launches, kmers, steps, line_reads, wave_steps, table_starts, scratch_bytes;
+    uint32_t table_q, reserved;
+    float ms_table, ms_kernel, ms_wall;
+} debwt_fm_kmer_stats;
+int debwt_fm_kmer_stats_get(const debwt_fm *fm, debwt_fm_kmer_stats *out);
+/* Weak runs and trials of one read, on the host (no GPU).  counts are the nk counts of its k-mers.  k-mer j is weak iff
+ * counts[j] < min_count; a run [a, b] is a maximal interval of weak k-mers, len = b - a + 1.  Each run yields up to two
+ * trials (pos, window), the left one first:
+ *   left  (kind 0) when a > 0 and (len >= k or b == nk - 1):       pos = a + k - 1, window = a;
+ *   right (kind 1) when b < nk - 1 and (len >= k or a == 0):       pos = b,         window = b.
+ * This is the signature of one substitution at pos: every k-mer over pos is weak, and window is the weak k-mer next to a
+ * solid one.  A run that covers the whole read has no trial, and interior runs shorter than k are left alone.
+ * Trials are written runs ascending; the call returns the number of trials of the read and writes the first `capacity`
+ * of them (out may be NULL when capacity is 0), so a return above capacity names the capacity to come back with.
+ * DEBWT_EINVAL for k = 0, min_count = 0 and nk + k above 2^31. */
+typedef struct { uint32_t run_a, run_b, pos, window, kind; } debwt_fm_trial;
+int debwt_fm_weak_trials(const uint32_t *counts, uint64_t nk, uint32_t k, uint32_t min_count, debwt_fm_trial *out,
+                         uint64_t capacity);
+/* Read correction from the k-mer spectrum of the indexed collection.  out has the layout of patterns and the same
+ * offsets.  Per read R of m >= k bytes, at most max_rounds times:
+ *   1. cnt of all nk k-mers of the current R; if none is weak (cnt < min_count), stop;
+ *   2. the trials of debwt_fm_weak_trials; per run they are evaluated in order, left first;
+ *   3. a trial (pos, window) tests every x of A, C, G, T other than upper R[pos] (all four when R[pos] is a non-base):
+ *      W_x is R[window .. window + k) with position pos replaced by x, and x is a candidate iff cnt W_x >= min_count;
+ *   4. the trial succeeds iff there is exactly one candidate; a run's fix is that of its first successful trial;
+ *   5. if no run has a fix, stop; otherwise all fixes are applied, R[pos] := x in upper case.
+ * The fixes of one round fall on distinct positions.  Bytes that are not fixed stay as given, case included.
+ * info[i] = {flags, fixes, weak_before, weak_after}; weak_after is counted on the output read, and exactly one flag is
+ * set: DEBWT_FM_CORRECT_SHORT (m < k: the read is copied, the other fields are 0), DEBWT_FM_CORRECT_CLEAN (weak_before ==
+ * 0), DEBWT_FM_CORRECT_FIXED (weak_before > 0, weak_after == 0), DEBWT_FM_CORRECT_WEAK (weak_after > 0).
+ * Every count, the resolution and the write into the read bytes run on the device; between rounds only the number of
+ * reads that got a fix reaches the host.  Batches as debwt_fm_kmer_counts; the result depends on neither limit nor on q.
+ * DEBWT_EINVAL for k = 0, min_count = 0, max_rounds outside 1..16, flags other than DEBWT_FM_BOTH_STRANDS, decreasing
+ * offsets and a pattern of 2^31 bytes or more. */
+#define DEBWT_FM_CORRECT_SHORT 1u
+#define DEBWT_FM_CORRECT_CLEAN 2u
+#define DEBWT_FM_CORRECT_FIXED 4u
+#define DEBWT_FM_CORRECT_WEAK  8u
+#define DEBWT_FM_CORRECT_MAX_ROUNDS 16
+typedef struct { uint32_t k, min_count, max_rounds, flags; } debwt_fm_correct_opts;
+typedef struct { uint32_t flags, fixes, weak_before, weak_after; } debwt_fm_correct_info;
+/* min_count 3, max_rounds 4, both strands; k is set to 0: it has no default */
+void debwt_fm_correct_defaults(debwt_fm_correct_opts *opts);
+int debwt_fm_correct(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                     const debwt_fm_correct_opts *opts, char *out, debwt_fm_correct_info *info);
+/* what the last debwt_fm_correct did: the counters above over all its kernels, the largest number of rounds a batch
+ * ran, per round the reads that got a fix (they stay active) and the time of its kernels (events), trials evaluated,
+ * fixes applied, and the reads per flag */
+typedef struct {
+    debwt_fm_kmer_stats kmers;
+    uint64_t rounds, trials, fixes, reads_short, reads_clean, reads_fixed, reads_weak;
+    uint64_t active[DEBWT_FM_CORRECT_MAX_ROUNDS];
+    float ms_round[DEBWT_FM_CORRECT_MAX_ROUNDS];
+} debwt_fm_correct_stats;
+int debwt_fm_correct_stats_get(const debwt_fm *fm, debwt_fm_correct_stats *out);
 
 void debwt_fm_destroy(debwt_fm *fm);
 
