@@ -280,7 +280,7 @@ SYMBOLS = [
     "debwt_create", "debwt_destroy", "debwt_strerror", "debwt_last_error", "debwt_load_text",
     "debwt_load_ascii", "debwt_kmer_sort_rle", "debwt_classify", "debwt_sp_generate", "debwt_blue_sort",
     "debwt_bwt_assemble", "debwt_build", "debwt_fetch_bwt", "debwt_bwt_device_ptr", "debwt_get_stats",
-    "debwt_fetch_array", "debwt_kmer_count_sorted", "debwt_radix_sort_u64", "debwt_radix_sort_u64_range", "debwt_radix_pair_passes", "debwt_radix_bucket_passes", "debwt_verify_inverse",
+    "debwt_fetch_array", "debwt_kmer_count_sorted", "debwt_radix_sort_u64", "debwt_radix_sort_u64_range", "debwt_radix_pair_passes", "debwt_radix_bucket_passes", "debwt_radix_low_finishes", "debwt_verify_inverse",
     "debwt_shard_begin", "debwt_shard_histogram", "debwt_shard_set_range", "debwt_shard_classify_local",
     "debwt_shard_facts_export", "debwt_shard_classify_global", "debwt_shard_info", "debwt_shard_fetch",
     "debwt_shard_partition_keys", "debwt_shard_plan", "debwt_shard_ranges", "debwt_shard_sort_begin",
@@ -367,6 +367,8 @@ def lib():
     L.debwt_radix_pair_passes.argtypes = []
     L.debwt_radix_bucket_passes.restype = ctypes.c_uint64
     L.debwt_radix_bucket_passes.argtypes = []
+    L.debwt_radix_low_finishes.restype = ctypes.c_uint64
+    L.debwt_radix_low_finishes.argtypes = []
     L.debwt_radix_sort_u64_range.restype = ctypes.c_int
     L.debwt_radix_sort_u64_range.argtypes = [vp, vp, vp, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64,
                                              ctypes.POINTER(ctypes.c_float)]

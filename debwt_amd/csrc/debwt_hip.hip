@@ -2669,6 +2669,7 @@ extern "C" int debwt_radix_sort_u64(debwt_ctx *c, uint64_t *d_keys, uint64_t *d_
 
 extern "C" uint64_t debwt_radix_pair_passes(void) { return radix_pair_passes(); }
 extern "C" uint64_t debwt_radix_bucket_passes(void) { return radix_bucket_passes(); }
+extern "C" uint64_t debwt_radix_low_finishes(void) { return radix_low_finishes(); }
 
 // keys outside [lo, hi] (a derived pass sizes the runs of its digits by the bounds: such a key would be stored outside its run)
 __global__ void k_keys_outside(const u64 *__restrict__ keys, u64 n, u64 lo, u64 hi, u32 *__restrict__ flag) {

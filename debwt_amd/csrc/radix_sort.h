@@ -52,6 +52,8 @@ struct RadixSplit { bool hybrid, bucket; int T, pshift, hbm_shift; };
 RadixSplit radix_split(u64 n, int key_bits, int algo, const u64 *range, bool heavy);
 // launches of rs_bucket_digit_kernel by this process (tests: which form a sort took)
 u64 radix_bucket_passes();
+// sorts of this process whose bucket finish took its low-word form (tests: which form a sort took)
+u64 radix_low_finishes();
 // a bucket above this many keys is split by ONE workgroup in two reads of global memory at a fraction of the rate of the
 // rest: what a caller's estimate of `heavy` counts
 #define RS_BUCKET_HEAVY (1u << 20)

@@ -1161,10 +1161,21 @@ __device__ __forceinline__ void rl_cex(u64 &a, u64 &b, bool up) {      // (a,b) 
     a = lo; b = hi;
 }
 
+// The same ascending comparator for two slots of a tile that is ordered by its high words already (slot a before slot
+// b): a > b only where the high words are equal, so the low words alone change place -- two selects instead of four.
+__device__ __forceinline__ void rl_cex_low(u64 &a, u64 &b) {
+    // (through the wave's mask: the compiler otherwise proves that either select may take a < b or a > b and compares twice)
+    const bool sw = __builtin_amdgcn_inverse_ballot_w64(__builtin_amdgcn_ballot_w64(a > b));
+    const u32 al = (u32)a, bl = (u32)b;
+    a = (a & 0xffffffff00000000ull) | (sw ? bl : al);
+    b = (b & 0xffffffff00000000ull) | (sw ? al : bl);
+}
+
 // the 16 keys of a lane ascending: a 60-comparator network in 10 layers (the best known for 16 inputs; checked on all
-// 2^16 zero-one inputs) instead of the bitonic sorter's 80
+// 2^16 zero-one inputs) instead of the bitonic sorter's 80.  LOW: the keys are ordered by their high words (rl_cex_low).
+template <bool LOW = false>
 __device__ __forceinline__ void rl_sort16(u64 (&k)[16]) {
-#define RL_CE(a, b) rl_cex(k[a], k[b], true)
+#define RL_CE(a, b) do { if (LOW) rl_cex_low(k[a], k[b]); else rl_cex(k[a], k[b], true); } while (0)
     RL_CE(0, 13); RL_CE(1, 12); RL_CE(2, 15); RL_CE(3, 14); RL_CE(4, 8); RL_CE(5, 6); RL_CE(7, 11); RL_CE(9, 10);
     RL_CE(0, 5); RL_CE(1, 7); RL_CE(2, 9); RL_CE(3, 4); RL_CE(6, 13); RL_CE(8, 14); RL_CE(10, 15); RL_CE(11, 12);
     RL_CE(0, 1); RL_CE(2, 3); RL_CE(4, 5); RL_CE(6, 8); RL_CE(7, 9); RL_CE(10, 11); RL_CE(12, 13); RL_CE(14, 15);
@@ -1233,6 +1244,129 @@ __device__ __forceinline__ void rl_network(u64 (&k)[16], u64 *A, const u32 tid, 
     }
 }
 
+#ifndef RLW_DPP
+#define RLW_DPP 1                      // neighbour exchange of the low-word rounds: 0 = __shfl (ds_bpermute), 1 = DPP in the even
+#endif                                 // rounds (lane ^ 1 is one quad_perm move), 2 = DPP in the odd rounds too (lane +- 1 is two
+                                       // wave shifts and a select per word).  rs_local_count_kernel per launch of 4.29 G keys, the
+                                       // three forms in one session: 14.90 / 14.57 / 14.69 ms (profiles/r19_finish_low_words.txt)
+
+// value of `v` in the partner lane of a merge-split round: lane ^ 1 in the even rounds, lane + 1 for the odd lanes and
+// lane - 1 for the even ones in the odd rounds (lanes 0 and 63 have no partner there and keep `old`)
+template <bool ODD>
+__device__ __forceinline__ u32 rlw_partner(const u32 old, const u32 v, const u32 lane) {
+    if (RLW_DPP > (ODD ? 1 : 0)) {
+        if (!ODD) return (u32)__builtin_amdgcn_update_dpp((int)old, (int)v, 0xB1, 0xf, 0xf, false);     // quad_perm:[1,0,3,2]
+        const u32 up = (u32)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x130, 0xf, 0xf, false);      // wave_shl:1 = lane + 1
+        const u32 dn = (u32)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138, 0xf, 0xf, false);      // wave_shr:1 = lane - 1
+        return (lane & 1u) ? up : dn;
+    }
+    const int p = ODD ? ((lane & 1u) ? (int)lane + 1 : (int)lane - 1) : (int)(lane ^ 1u);
+    return (u32)__shfl((int)v, p < 0 || p > 63 ? (int)lane : p, 64);
+}
+
+// One merge-split round of a wave tile in its low-word form.  pt: the partner lane's keys, last slot first.  Their high
+// words never move, so they were fetched once per parity and stay; a round fetches the low words into the same registers
+// (the 64-bit compare finds its operand in place) and selects low words only.
+template <bool ODD>
+__device__ __forceinline__ void rlw_round_low(u64 (&k)[16], u64 (&pt)[16], const u32 lane) {
+    constexpr int KPT = 16;
+    const bool lower = ((lane ^ (ODD ? 1u : 0u)) & 1u) == 0;
+    const bool active = !ODD || (lane > 0 && lane < 63);
+#pragma unroll
+    for (int r = 0; r < KPT; r++) pt[r] = (pt[r] & 0xffffffff00000000ull) | rlw_partner<ODD>((u32)pt[r], (u32)k[KPT - 1 - r], lane);
+    if (active) {
+#pragma unroll
+        for (int r = 0; r < KPT; r++) {
+            const bool pless = pt[r] < k[r];
+            k[r] = (k[r] & 0xffffffff00000000ull) | ((lower == pless) ? (u32)pt[r] : (u32)k[r]);
+        }
+#pragma unroll
+        for (int lj = 3; lj >= 0; lj--) {
+            const int jj = 1 << lj;
+#pragma unroll
+            for (int r = 0; r < KPT; r++)
+                if ((r & jj) == 0) rl_cex_low(k[r], k[r | jj]);
+        }
+    }
+}
+
+// every lane boundary of a wave tile in order (whole keys)
+__device__ __forceinline__ bool rlw_in_order(const u64 (&k)[16], const u32 lane) {
+    const u64 nxt = __shfl_down(k[0], 1, 64);
+    const bool ok = lane == 63 || k[15] <= nxt;
+    return __ballot(!ok) == 0ull;
+}
+
+// The first try at a wave tile (1024 keys, 16 per lane, blocked layout): a network sized for what the data looks like
+// here.  The keys arrive ordered by bucket and a bucket holds ~16 keys, so after sorting every lane's 16 keys a key is at
+// most a few lanes from its place.  Rounds of merge-splits between neighbouring lanes (even pairs, then odd pairs: a
+// block odd-even transposition sort, ~18 operations per key and round instead of the full network's ~270) run until a
+// ballot finds every lane boundary in order -- runs of equal keys (repeat families) are in order from the start.  False:
+// not sorted after RL_MAX_ROUNDS rounds, the caller takes the full bitonic network.
+// LOW (the buckets are cut at bit 32 or below, so the tile arrives ordered by its high words): slot a before slot b has
+// hi(a) <= hi(b) on entry and after every exchange, because an exchange happens only between keys with a > b, that is
+// with equal high words (the padding ~0 keeps it).  So the high word of every slot is final from the start: comparisons
+// stay on whole keys (one 64-bit compare), the exchanges select low words only, and a round fetches the partner lane's low
+// words only -- in the even rounds by a DPP move of the VALU, not through the LDS crossbar (RLW_DPP).
+template <bool LOW>
+__device__ __forceinline__ bool rlw_rounds(u64 (&k)[16], const u32 lane) {
+    constexpr int KPT = 16;
+    bool sorted = false;
+    rl_sort16<LOW>(k);
+    if (LOW) {
+        sorted = rlw_in_order(k, lane);
+        if (!sorted) {
+            u64 pt[2][KPT];
+#pragma unroll
+            for (int r = 0; r < KPT; r++) {
+                pt[0][r] = (u64)rlw_partner<false>(0u, (u32)(k[KPT - 1 - r] >> 32), lane) << 32;
+                pt[1][r] = (u64)rlw_partner<true>(0u, (u32)(k[KPT - 1 - r] >> 32), lane) << 32;
+            }
+            for (int round = 0; round < RL_MAX_ROUNDS; round += 2) {      // the same rounds and checks, two per trip
+                rlw_round_low<false>(k, pt[0], lane);
+                if (rlw_in_order(k, lane)) { sorted = true; break; }
+                if (round + 1 < RL_MAX_ROUNDS) {
+                    rlw_round_low<true>(k, pt[1], lane);
+                    if (rlw_in_order(k, lane)) { sorted = true; break; }
+                }
+            }
+        }
+        return sorted;
+    }
+    for (int round = 0; round < RL_MAX_ROUNDS; round++) {
+        const u64 nxt = __shfl_down(k[0], 1, 64);
+        const bool ok = lane == 63 || k[KPT - 1] <= nxt;
+        if (__ballot(!ok) == 0ull) { sorted = true; break; }
+        // partner lane of this round; lanes without one (0 and 63 in odd rounds) keep their keys
+        const bool odd = round & 1;
+        const bool lower = ((lane ^ (u32)odd) & 1u) == 0;
+        const int partner = lower ? (int)lane + 1 : (int)lane - 1;
+        const bool active = partner >= 0 && partner < 64;
+        const int src = active ? partner : (int)lane;
+        u64 t[KPT];
+#pragma unroll
+        for (int r = 0; r < KPT; r++) t[r] = __shfl(k[KPT - 1 - r], src, 64);
+        if (active) {
+            // merge-split: the lower lane keeps the 16 smallest of the 32, the upper lane the 16 largest
+#pragma unroll
+            for (int r = 0; r < KPT; r++) {
+                const bool pless = t[r] < k[r];
+                k[r] = (lower == pless) ? t[r] : k[r];
+            }
+            // each half is bitonic now: four in-lane merge steps sort it ascending
+#pragma unroll
+            for (int lj = 3; lj >= 0; lj--) {
+                const int jj = 1 << lj;
+#pragma unroll
+                for (int r = 0; r < KPT; r++)
+                    if ((r & jj) == 0) rl_cex(k[r], k[r | jj], true);
+            }
+        }
+    }
+    if (!sorted) sorted = rlw_in_order(k, lane);
+    return sorted;
+}
+
 // keys are ordered by their top (key_bits - pshift) bits.  Tile j = [B(j*H), B((j+1)*H)) with B(x) the first
 // bucket boundary >= x, so tiles are disjoint and bucket-aligned, and hold <= CAP keys unless a bucket overshoots
 // a tile start by more than CAP - H.  A tile is finished by NT threads: a bitonic network over CAP = 16*NT keys
@@ -1242,7 +1376,8 @@ __device__ __forceinline__ void rl_network(u64 (&k)[16], u64 *A, const u32 tid, 
 //   NT = 64  (first, over all tiles): a tile that does not fit marks the 4096-key tiles that cover it;
 //   NT = 256 (second, marked tiles only; sorting an already sorted stretch again is harmless): a tile that
 //             does not fit is queued for the HBM path.
-template <int NT>
+//   LOW (NT = 64 only): the buckets are cut at bit 32 or below, the rounds take their low-word form (rlw_rounds).
+template <int NT, bool LOW = false>
 __global__ __launch_bounds__(NT) void rs_local_kernel(u64 *__restrict__ keys, u64 n, int pshift,
                                                        u32 *__restrict__ over, u32 over_cap, u8 *__restrict__ mark) {
     constexpr int KPT = 16;
@@ -1301,51 +1436,10 @@ __global__ __launch_bounds__(NT) void rs_local_kernel(u64 *__restrict__ keys, u6
         if (NT == 64 ? (__ballot(bad != 0) == 0ull) : !__syncthreads_or((int)bad)) return;
     }
     __syncthreads();
-    // Wave tiles first try a network sized for what the data looks like here: the keys arrive ordered by bucket and a
-    // bucket holds ~16 keys, so after sorting every lane's 16 keys a key is at most a few lanes from its place.
-    // Rounds of merge-splits between neighbouring lanes (even pairs, then odd pairs: a block odd-even transposition
-    // sort, ~18 operations per key and round instead of the full network's ~270) run until a ballot finds every lane
-    // boundary in order -- runs of equal keys (repeat families) are in order from the start.  Anything that is not
-    // sorted after RL_MAX_ROUNDS rounds goes through the full bitonic network below.
+    // wave tiles first try the rounds of merge-splits between neighbouring lanes (rlw_rounds); anything that is not
+    // sorted after RL_MAX_ROUNDS rounds goes through the full bitonic network below
     bool sorted = false;
-    if (NT == 64) {
-        rl_sort16(k);
-        for (int round = 0; round < RL_MAX_ROUNDS; round++) {
-            u64 nxt = __shfl_down(k[0], 1, 64);
-            bool ok = tid == 63 || k[KPT - 1] <= nxt;
-            if (__ballot(!ok) == 0ull) { sorted = true; break; }
-            // partner lane of this round; lanes without one (0 and 63 in odd rounds) keep their keys
-            const bool odd = round & 1;
-            const bool lower = ((tid ^ (u32)odd) & 1u) == 0;
-            const int partner = lower ? (int)tid + 1 : (int)tid - 1;
-            const bool active = partner >= 0 && partner < 64;
-            const int src = active ? partner : (int)tid;
-            u64 t[KPT];
-#pragma unroll
-            for (int r = 0; r < KPT; r++) t[r] = __shfl(k[KPT - 1 - r], src, 64);
-            if (active) {
-                // merge-split: the lower lane keeps the 16 smallest of the 32, the upper lane the 16 largest
-#pragma unroll
-                for (int r = 0; r < KPT; r++) {
-                    bool pless = t[r] < k[r];
-                    k[r] = (lower == pless) ? t[r] : k[r];
-                }
-                // each half is bitonic now: four in-lane merge steps sort it ascending
-#pragma unroll
-                for (int lj = 3; lj >= 0; lj--) {
-                    const int jj = 1 << lj;
-#pragma unroll
-                    for (int r = 0; r < KPT; r++)
-                        if ((r & jj) == 0) rl_cex(k[r], k[r | jj], true);
-                }
-            }
-        }
-        if (!sorted) {
-            u64 nxt = __shfl_down(k[0], 1, 64);
-            bool ok = tid == 63 || k[KPT - 1] <= nxt;
-            sorted = __ballot(!ok) == 0ull;
-        }
-    }
+    if (NT == 64) sorted = rlw_rounds<LOW>(k, tid);
     if (!sorted) {
         // a workgroup tile of at most half the capacity: the network over the lower half of the threads only
         if (NT == 256 && cnt <= CAP / 2) rl_network<LOGN - 1>(k, A, tid, tid < NT / 2);
@@ -1369,7 +1463,8 @@ __global__ __launch_bounds__(NT) void rs_local_kernel(u64 *__restrict__ keys, u6
 //   rs_tile_emit / rs_unfit_rle<1>  distinct keys and their first rows, tile by tile at tex
 // The separate count pass over the sorted keys (and its 8 bytes per key of reads) is gone.
 
-// sorts the 1024 keys a wave holds 16 per lane (blocked layout) ascending; see rs_local_kernel for the method
+// sorts the 1024 keys a wave holds 16 per lane (blocked layout) ascending; see rlw_rounds for the method
+template <bool LOW>
 __device__ __forceinline__ void rlw_sort(u64 (&k)[16], const u32 lane) {
     constexpr int KPT = 16;
     bool sorted;
@@ -1381,41 +1476,7 @@ __device__ __forceinline__ void rlw_sort(u64 (&k)[16], const u32 lane) {
         if (lane < 63) bad |= k[KPT - 1] > nxt ? 1u : 0u;
         sorted = __ballot(bad != 0) == 0ull;
     }
-    if (!sorted) {
-        rl_sort16(k);
-        for (int round = 0; round < RL_MAX_ROUNDS; round++) {
-            const u64 nxt = __shfl_down(k[0], 1, 64);
-            const bool ok = lane == 63 || k[KPT - 1] <= nxt;
-            if (__ballot(!ok) == 0ull) { sorted = true; break; }
-            const bool odd = round & 1;
-            const bool lower = ((lane ^ (u32)odd) & 1u) == 0;
-            const int partner = lower ? (int)lane + 1 : (int)lane - 1;
-            const bool active = partner >= 0 && partner < 64;
-            const int src = active ? partner : (int)lane;
-            u64 t[KPT];
-#pragma unroll
-            for (int r = 0; r < KPT; r++) t[r] = __shfl(k[KPT - 1 - r], src, 64);
-            if (active) {
-#pragma unroll
-                for (int r = 0; r < KPT; r++) {
-                    const bool pless = t[r] < k[r];
-                    k[r] = (lower == pless) ? t[r] : k[r];
-                }
-#pragma unroll
-                for (int lj = 3; lj >= 0; lj--) {
-                    const int jj = 1 << lj;
-#pragma unroll
-                    for (int r = 0; r < KPT; r++)
-                        if ((r & jj) == 0) rl_cex(k[r], k[r | jj], true);
-                }
-            }
-        }
-        if (!sorted) {
-            const u64 nxt = __shfl_down(k[0], 1, 64);
-            const bool ok = lane == 63 || k[KPT - 1] <= nxt;
-            sorted = __ballot(!ok) == 0ull;
-        }
-    }
+    if (!sorted) sorted = rlw_rounds<LOW>(k, lane);
     if (!sorted) {
 #pragma unroll
         for (int lk = 1; lk <= 10; lk++) {                        // full bitonic network over the wave
@@ -1456,6 +1517,7 @@ __device__ __forceinline__ void rlw_sort(u64 (&k)[16], const u32 lane) {
 #ifndef RLW_WINDOW
 #define RLW_WINDOW 1                   // the tile and both its boundaries out of ONE window of keys (one global round trip per tile)
 #endif
+template <bool LOW>
 __global__ __launch_bounds__(64) void rs_local_count_kernel(u64 *__restrict__ keys, u64 n, int pshift,
                                                             u8 *__restrict__ mark, u64 *__restrict__ bnd,
                                                             u32 *__restrict__ unfit, u32 *__restrict__ nunfit,
@@ -1541,7 +1603,7 @@ __global__ __launch_bounds__(64) void rs_local_count_kernel(u64 *__restrict__ ke
 #pragma unroll
     for (int r = 0; r < KPT; r++) k[r] = A[RL_PAD(lane * KPT + r)];
 #endif
-    rlw_sort(k, lane);
+    rlw_sort<LOW>(k, lane);
 #pragma unroll
     for (int r = 0; r < KPT; r++) A[RL_PAD(lane * KPT + r)] = k[r];
     // a key is a head when it differs from the key before it; the stretch starts at a bucket boundary
@@ -2470,6 +2532,16 @@ static int rs_bucket_mode() {          // DEBWT_BUCKET_PASS: 0 = never, 1 = wher
     return !e || !*e ? -1 : (atoi(e) != 0 ? 1 : 0);
 }
 
+static int rs_forced_digits() {        // DEBWT_PREFIX_DIGITS=<1..4>: that many prefix digits whatever n is (tests); 0 = by the rule
+    const char *e = getenv("DEBWT_PREFIX_DIGITS");
+    const int t = e && *e ? atoi(e) : 0;
+    return t >= 1 && t <= 4 ? t : 0;
+}
+static bool rs_finish_low() {          // DEBWT_FINISH_LOW=0: the bucket finish sorts whole keys at every pshift (A/B, tests)
+    const char *e = getenv("DEBWT_FINISH_LOW");
+    return !e || !*e || atoi(e) != 0;
+}
+
 RadixSplit radix_split(u64 n, int key_bits, int algo, const u64 *range, bool heavy) {
     algo &= 15;
     if (key_bits > 64) key_bits = 64;
@@ -2478,6 +2550,7 @@ RadixSplit radix_split(u64 n, int key_bits, int algo, const u64 *range, bool hea
     int T = 0;
     while ((n >> (8 * T)) > RS_BUCKET_TARGET && T < 4) T++;
     if (mode == 1 && T < 2) T = 2;
+    if (rs_forced_digits()) T = rs_forced_digits();
     RadixSplit sp{false, false, 0, 0, 0};
     if (algo != 3 || T == 0 || key_bits - 8 * T < 1) return sp;
     sp.hybrid = true;
@@ -2491,6 +2564,8 @@ RadixSplit radix_split(u64 n, int key_bits, int algo, const u64 *range, bool hea
 
 static std::atomic<u64> rs_bucket_launched{0};
 u64 radix_bucket_passes() { return rs_bucket_launched.load(std::memory_order_relaxed); }
+static std::atomic<u64> rs_low_finishes{0};
+u64 radix_low_finishes() { return rs_low_finishes.load(std::memory_order_relaxed); }
 
 hipError_t radix_text_hist_ranges(hipStream_t stream, const TextKeySrc &text, const u8 *range_of_bin, int key_bits,
                                   const int *shift, int nranges, u32 *counts) {
@@ -2571,6 +2646,11 @@ u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, con
         rs_bucket_launched.fetch_add(1, std::memory_order_relaxed);
         u64 *t = src; src = other; other = t;
     }
+    // buckets cut at bit 32 or below: a wave tile arrives ordered by its high words and sorts its low words only (rlw_rounds)
+    // This needs every key below 2^key_bits (the callers' contract: k-mers of 2k bits): the top digits then order the whole
+    // high word.  With stray bits above key_bits the low words of one key would be spliced onto the high word of another.
+    const bool low = pshift <= 32 && rs_finish_low();
+    if (low) rs_low_finishes.fetch_add(1, std::memory_order_relaxed);
     (void)hipMemsetAsync(ws.over, 0, 16, stream);
     u32 ntiles = (u32)((n + RL_H - 1) / RL_H), nwtiles = (u32)((n + RLW_H - 1) / RLW_H);
     u8 *mark = reinterpret_cast<u8 *>(ws.skew_list);          // one byte per 4096-key tile
@@ -2589,8 +2669,12 @@ u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, con
         (void)hipMemsetAsync(rle_ctr, 0, 16, stream);
         // (the other key buffer takes the distinct keys of the tiles that hold few: it is free until the all-HBM path of
         // oversize stretches, which then works in the buffer of the distinct keys instead)
-        rs_local_count_kernel<<<nwtiles, 64, 0, stream>>>(src, n, pshift, mark, rle_bnd, rle_unfit, rle_ctr, rle_tcnt, sink->mchar,
-                                                          sink->no_staging ? nullptr : other, sink->drop_sorted ? 1 : 0);
+        if (low)
+            rs_local_count_kernel<true><<<nwtiles, 64, 0, stream>>>(src, n, pshift, mark, rle_bnd, rle_unfit, rle_ctr, rle_tcnt, sink->mchar,
+                                                                    sink->no_staging ? nullptr : other, sink->drop_sorted ? 1 : 0);
+        else
+            rs_local_count_kernel<false><<<nwtiles, 64, 0, stream>>>(src, n, pshift, mark, rle_bnd, rle_unfit, rle_ctr, rle_tcnt, sink->mchar,
+                                                                     sink->no_staging ? nullptr : other, sink->drop_sorted ? 1 : 0);
         const u32 ugrid = nwtiles < 16384u ? nwtiles : 16384u;
 #if RLU_CLASSIFY
         u64 *const stg = sink->no_staging ? nullptr : other;
@@ -2602,7 +2686,8 @@ u64 *radix_sort_u64(hipStream_t stream, u64 *a, u64 *b, u64 n, int key_bits, con
 #endif
         rs_local_unfit_net_kernel<<<ugrid, 256, 0, stream>>>(src, n, rle_bnd, nwtiles, rle_unfit, rle_ctr, ws.over, ws.over_cap);
     } else {
-        rs_local_kernel<64><<<nwtiles, 64, 0, stream>>>(src, n, pshift, ws.over, ws.over_cap, mark);
+        if (low) rs_local_kernel<64, true><<<nwtiles, 64, 0, stream>>>(src, n, pshift, ws.over, ws.over_cap, mark);
+        else rs_local_kernel<64><<<nwtiles, 64, 0, stream>>>(src, n, pshift, ws.over, ws.over_cap, mark);
         rs_local_kernel<256><<<ntiles, 256, 0, stream>>>(src, n, pshift, ws.over, ws.over_cap, mark);
     }
     (void)hipMemcpyAsync(ws.h_over, ws.over, 16, hipMemcpyDeviceToHost, stream);

@@ -415,7 +415,8 @@ int debwt_kmer_count_sorted(debwt_ctx *ctx, uint64_t *kmers, uint64_t *counts, u
                             uint64_t *distinct);
 
 /* LSD radix sort of `count` 64-bit keys resident in HBM (d_keys, d_tmp: device pointers, both
- * `count` words; result in d_keys).  key_bits: significant low bits (1..64).
+ * `count` words; result in d_keys).  key_bits: significant low bits (1..64); every key must be below 2^key_bits -- the
+ * bucket finish relies on it (bits above key_bits are not ignored: with them the result is undefined, not merely misordered).
  * ms_per_pass (optional) receives the mean device time of one scatter pass. */
 int debwt_radix_sort_u64(debwt_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint64_t count, int key_bits,
                          float *ms_per_pass);
@@ -432,6 +433,10 @@ uint64_t debwt_radix_pair_passes(void);
  * environment restores the HBM pass everywhere, DEBWT_BUCKET_PASS=1 takes the bucket pass in every sort with a bucket
  * finish and gives every sort at least two prefix digits (tests: small inputs reach it). */
 uint64_t debwt_radix_bucket_passes(void);
+/* Sorts this process has run whose bucket finish took its low-word form (prefix buckets cut at bit 32 or below: only the low
+ * words of a wave tile are exchanged).  DEBWT_FINISH_LOW=0 in the environment keeps whole keys everywhere and this from
+ * counting up; DEBWT_PREFIX_DIGITS=<1..4> forces the number of prefix digits of every sort (tests: small inputs reach it). */
+uint64_t debwt_radix_low_finishes(void);
 
 /* Host-only: checksums of the special-region tables (`collect`'s specialSA / specialBwt / specialBranch / head / tail
  * tables, src/collect#$.c:118-157,348-602) that debwt_kmer_sort_rle builds on host threads for the loaded text layout;
