@@ -14,6 +14,8 @@
  *   deBWT-query extract -i OUT [--device D] --all | REGIONS.txt
  *   deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq
  *   deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq
+ *   deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--states FILE]
+ *   deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--states FILE]
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -81,6 +83,16 @@
  * letter as it came.  --report FILE writes a TSV of name, status (short, clean, fixed or weak), fixes, weak_before and
  * weak_after; stderr gets one summary line.  Both need OUT, OUT.#, OUT.$ and OUT.sa only, and -k is required.
  *
+ * graph writes the string graph of the indexed records as GFA 1 (debwt_fm_string_graph): a record that equals an earlier one
+ * is a duplicate, one that lies inside a longer record is contained, the others are kept.  One "S J * LN:i:len" line per
+ * kept record J (the 0-based number, as extract names records), then one "L a + b + <L>M" line per edge: the longest
+ * overlap of at least L bases (default 20) of record a's end with record b's start, strand + only, without the edges that
+ * two others explain (a -> j and j -> b laid end to end); --all-edges writes those too.  --states FILE gets
+ * J<TAB>kept|duplicate|contained per record.  unitigs follows the unbranched paths of that graph (debwt_fm_unitigs) and
+ * writes their sequences as FASTA, ">unitig_N reads=T len=BASES circular=0|1 first=J", in unitig order; a circular unitig is
+ * cut where it closes.  Both need OUT, OUT.#, OUT.$ and OUT.sa only (the text is restored on the GPU), take no file
+ * argument and write one summary line to stderr.
+ *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
  * that does not match OUT, OUT.# and OUT.$ is refused.
@@ -110,6 +122,8 @@ static void usage(void) {
             "       deBWT-query extract -i OUT [--device D] --all | REGIONS.txt\n"
             "       deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq\n"
             "       deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
+            "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--states FILE]\n"
+            "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--states FILE]\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
@@ -131,7 +145,10 @@ static void usage(void) {
             "kmers prints name<TAB>c0,c1,.. per read, the occurrences of its K-mers (* for a read shorter than K);\n"
             "correct writes the reads as FASTA with the substitution errors fixed that their K-mer counts single out (weak below\n"
             "T occurrences, default 3; at most R rounds, default 4; both strands unless --forward); --report FILE gets\n"
-            "name<TAB>status<TAB>fixes<TAB>weak_before<TAB>weak_after, stderr one summary line\n");
+            "name<TAB>status<TAB>fixes<TAB>weak_before<TAB>weak_after, stderr one summary line;\n"
+            "graph writes GFA 1: S lines for the records that are neither duplicates nor contained, L lines a + b + <L>M for the\n"
+            "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
+            "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -955,12 +972,107 @@ done:
     return ret;
 }
 
+/* ---- graph / unitigs --------------------------------------------------------------------------------------------------- */
+
+static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_edges, const char *states, int want_unitigs) {
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) return 1;
+    int ret = 1, rc = 0;
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    const uint64_t nrec = fi.nrec;
+    uint64_t *starts = malloc((nrec + 1) * 8), *eoff = malloc((nrec + 1) * 8), *uoff = malloc((nrec + 1) * 8), *boff = NULL;
+    uint8_t *state = malloc(nrec ? nrec : 1), *circ = malloc(nrec ? nrec : 1);
+    uint32_t *mem = malloc((nrec ? nrec : 1) * 4);
+    debwt_fm_edge *edges = NULL;
+    debwt_fm_extract_job *jobs = NULL;
+    char *bases = NULL;
+    FILE *sf = NULL;
+    if (!starts || !eoff || !uoff || !state || !circ || !mem) { fprintf(stderr, "out of memory\n"); goto done; }
+    rc = debwt_fm_record_starts(fm, starts, nrec);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    starts[nrec] = fi.n;                                  /* record r holds starts[r + 1] - 1 - starts[r] bases */
+    const uint32_t flags = all_edges ? DEBWT_FM_GRAPH_ALL_EDGES : 0u;
+    uint64_t cap = 4 * nrec + 16;                         /* first estimate; the exact count on DEBWT_ERANGE */
+    for (;;) {
+        free(edges);
+        edges = malloc(cap * sizeof *edges);
+        if (!edges) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_string_graph(fm, min_overlap, flags, state, eoff, edges, cap);
+        if (rc == DEBWT_ERANGE && eoff[nrec] > cap) { cap = eoff[nrec]; continue; }
+        break;
+    }
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    if (states) {
+        if (!(sf = fopen(states, "w"))) { fprintf(stderr, "cannot write %s\n", states); goto done; }
+        for (uint64_t i = 0; i < nrec; i++)
+            fprintf(sf, "%llu\t%s\n", (unsigned long long)i, state[i] == 0 ? "kept" : state[i] == 1 ? "duplicate" : "contained");
+        if (fclose(sf)) { sf = NULL; fprintf(stderr, "cannot write %s\n", states); goto done; }
+        sf = NULL;
+    }
+    debwt_fm_graph_stats st;
+    debwt_fm_graph_stats_get(fm, &st);
+    if (!want_unitigs) {
+        printf("H\tVN:Z:1.0\n");
+        for (uint64_t i = 0; i < nrec; i++)
+            if (state[i] == 0) printf("S\t%llu\t*\tLN:i:%llu\n", (unsigned long long)i, (unsigned long long)(starts[i + 1] - 1 - starts[i]));
+        for (uint64_t i = 0; i < nrec; i++)
+            for (uint64_t e = eoff[i]; e < eoff[i + 1]; e++)
+                printf("L\t%llu\t+\t%u\t+\t%uM\n", (unsigned long long)i, edges[e].record, edges[e].length);
+        fprintf(stderr, "graph: %llu records, %llu kept, %llu duplicates, %llu contained; %llu edges, %llu reducible, %llu written, %.1f ms\n",
+                (unsigned long long)nrec, (unsigned long long)st.kept, (unsigned long long)st.duplicates,
+                (unsigned long long)st.contained, (unsigned long long)st.edges, (unsigned long long)st.reducible,
+                (unsigned long long)eoff[nrec], st.ms_wall);
+        ret = fflush(stdout) ? 1 : 0;
+        goto done;
+    }
+    uint64_t nu = 0;
+    rc = debwt_fm_unitigs(state, eoff, edges, nrec, uoff, mem, circ, &nu);
+    if (rc) { fprintf(stderr, "unitigs: the graph is inconsistent\n"); goto done; }
+    /* every member but the last gives its first |S| - L_next bases; the last of a circular unitig is cut as well */
+    const uint64_t nm = uoff[nu];
+    jobs = malloc((nm ? nm : 1) * sizeof *jobs);
+    boff = malloc((nm + 1) * 8);
+    if (!jobs || !boff) { fprintf(stderr, "out of memory\n"); goto done; }
+    uint64_t total = 0, longest = 0;
+    for (uint64_t u = 0; u < nu; u++)
+        for (uint64_t x = uoff[u]; x < uoff[u + 1]; x++) {
+            const uint32_t v = mem[x];
+            uint64_t len = starts[v + 1] - 1 - starts[v];
+            if (x + 1 < uoff[u + 1] || circ[u]) len -= edges[eoff[v]].length;      /* a link's source has one out-edge */
+            jobs[x].record = v; jobs[x].reserved = 0; jobs[x].offset = 0; jobs[x].length = len;
+            total += len;
+        }
+    bases = malloc(total ? total : 1);
+    if (!bases) { fprintf(stderr, "out of memory\n"); goto done; }
+    rc = debwt_fm_extract(fm, jobs, nm, boff, bases, total);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    for (uint64_t u = 0; u < nu; u++) {
+        const uint64_t a = boff[uoff[u]], b = boff[uoff[u + 1]];
+        if (b - a > longest) longest = b - a;
+        printf(">unitig_%llu reads=%llu len=%llu circular=%u first=%u\n", (unsigned long long)u,
+               (unsigned long long)(uoff[u + 1] - uoff[u]), (unsigned long long)(b - a), circ[u], mem[uoff[u]]);
+        fwrite(bases + a, 1, b - a, stdout);
+        putchar('\n');
+    }
+    fprintf(stderr, "unitigs: %llu records, %llu kept; %llu edges, %llu irreducible; %llu unitigs, %llu bases, the longest %llu\n",
+            (unsigned long long)nrec, (unsigned long long)st.kept, (unsigned long long)st.edges,
+            (unsigned long long)eoff[nrec], (unsigned long long)nu, (unsigned long long)total, (unsigned long long)longest);
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    if (sf) fclose(sf);
+    free(starts); free(eoff); free(uoff); free(boff); free(state); free(circ); free(mem); free(edges); free(jobs); free(bases);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
 int main(int argc, char **argv) {
     if (argc < 2) { usage(); return 1; }
     const char *cmd = argv[1];
     int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 :
                !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
-               !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : -1;
+               !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : !strcmp(cmd, "graph") ? 9 :
+               !strcmp(cmd, "unitigs") ? 10 : -1;
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
     uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, min_overlap = 20, v64 = 0;
@@ -977,8 +1089,8 @@ int main(int argc, char **argv) {
     uint32_t flags = 0;
     debwt_fm_correct_opts ko;
     debwt_fm_correct_defaults(&ko);
-    const char *report = NULL;
-    int k_given = 0;
+    const char *report = NULL, *states = NULL;
+    int k_given = 0, all_edges = 0;
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
         if (a[0] != '-' || !a[1]) {
@@ -991,6 +1103,7 @@ int main(int argc, char **argv) {
         if (mode == 5 && !strcmp(a, "--longest")) { flags |= DEBWT_FM_OVERLAP_LONGEST; continue; }
         if (mode == 5 && !strcmp(a, "--no-self")) { no_self = 1; continue; }
         if (mode == 6 && !strcmp(a, "--all")) { all = 1; continue; }
+        if (mode == 9 && !strcmp(a, "--all-edges")) { all_edges = 1; continue; }
         if (mode == 8 && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
         if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mode == 4 && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
@@ -1047,7 +1160,7 @@ int main(int argc, char **argv) {
         else if ((mode == 3 || mode == 4) && !strcmp(a, "--min-len")) {
             if (parse_u64(v, &min_len) || min_len < 1 || min_len > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
         }
-        else if (mode == 5 && !strcmp(a, "--min-overlap")) {
+        else if ((mode == 5 || mode == 9 || mode == 10) && !strcmp(a, "--min-overlap")) {
             if (parse_u64(v, &min_overlap) || min_overlap < 1 || min_overlap > 0xFFFFFFFFull) { fprintf(stderr, "--min-overlap: a length of at least 1\n"); return 1; }
         }
         else if (mode == 5 && !strcmp(a, "--max-mismatches")) {
@@ -1071,12 +1184,17 @@ int main(int argc, char **argv) {
             ko.max_rounds = (uint32_t)v64;
         }
         else if (mode == 8 && !strcmp(a, "--report")) report = v;
+        else if ((mode == 9 || mode == 10) && !strcmp(a, "--states")) states = v;
         else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
     if (mode == 6) {
         if (!out || (all != 0) == (file != NULL)) { usage(); return 1; }
         return cmd_extract(out, file, (int)device);
+    }
+    if (mode == 9 || mode == 10) {
+        if (!out || file) { usage(); return 1; }
+        return cmd_graph(out, (int)device, (uint32_t)min_overlap, all_edges, states, mode == 10);
     }
     if (!out || !file) { usage(); return 1; }
     if (mode == 4) {

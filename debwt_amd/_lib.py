@@ -161,6 +161,19 @@ class DebwtFmOverlap(ctypes.Structure):
     _fields_ = [(n, ctypes.c_uint32) for n in ("record", "length", "strand", "flags")]
 
 
+class DebwtFmEdge(ctypes.Structure):
+    _fields_ = [("record", ctypes.c_uint32), ("length", ctypes.c_uint32)]
+
+
+class DebwtFmGraphStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("records", "kept", "duplicates", "contained", "hits", "edges", "reducible",
+                                                 "lookups", "launches", "scratch_bytes", "edge_bytes")] +
+                [(n, ctypes.c_float) for n in ("ms_walk", "ms_build", "ms_reduce", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DebwtFmJob(ctypes.Structure):
     _fields_ = [("pattern", ctypes.c_uint64), ("diag", ctypes.c_int64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32)]
 
@@ -304,6 +317,7 @@ SYMBOLS = [
     "debwt_fm_extract", "debwt_fm_extract_stats_get", "debwt_fm_restore_text", "debwt_fm_text_fetch",
     "debwt_fm_kmer_counts", "debwt_fm_kmer_stats_get", "debwt_fm_weak_trials", "debwt_fm_correct_defaults",
     "debwt_fm_correct", "debwt_fm_correct_stats_get",
+    "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
 ]
 
 
@@ -601,6 +615,15 @@ def lib():
                                    ctypes.POINTER(DebwtFmCorrectInfo)]
     L.debwt_fm_correct_stats_get.restype = ctypes.c_int
     L.debwt_fm_correct_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmCorrectStats)]
+    u8p, edgep = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(DebwtFmEdge)
+    L.debwt_fm_string_graph.restype = ctypes.c_int
+    L.debwt_fm_string_graph.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u64p, edgep, ctypes.c_uint64]
+    L.debwt_fm_edges_reduce.restype = ctypes.c_int
+    L.debwt_fm_edges_reduce.argtypes = [vp, u64p, ctypes.c_uint64, u64p, edgep, u8p]
+    L.debwt_fm_unitigs.restype = ctypes.c_int
+    L.debwt_fm_unitigs.argtypes = [u8p, u64p, edgep, ctypes.c_uint64, u64p, u32p, u8p, u64p]
+    L.debwt_fm_graph_stats_get.restype = ctypes.c_int
+    L.debwt_fm_graph_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmGraphStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

@@ -532,6 +532,33 @@ class FMIndex:
         self._chk(self._L.debwt_fm_correct_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def string_graph(self, min_overlap=20, reduce=True):
+        """The string graph of the indexed records (debwt_fm_string_graph): per record kept, duplicate (an earlier record
+        is equal) or contained (a substring of a longer record); among the kept records the longest suffix-prefix overlap
+        of at least min_overlap per ordered pair, strand 0; with reduce the transitive edges are dropped.  An index
+        without a text restores it first.  Returns a GraphResult."""
+        flags = 0 if reduce else GRAPH_ALL_EDGES
+        state = np.zeros(max(self.nrec, 1), dtype=np.uint8)
+        offs = np.zeros(self.nrec + 1, dtype=np.uint64)
+        cap = 4 * self.nrec + 16                              # first estimate; grown to the exact count on DEBWT_ERANGE
+        while True:
+            edges = np.zeros(cap, dtype=_EDGE_DTYPE)
+            rc = self._L.debwt_fm_string_graph(self._h, int(min_overlap), flags, state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                               _p64(offs), edges.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)), cap)
+            if rc == -5 and int(offs[self.nrec]) > cap:
+                cap = int(offs[self.nrec])
+                continue
+            self._chk(rc)
+            break
+        return GraphResult(self, state[:self.nrec], offs, edges[:int(offs[self.nrec])].copy(), bool(reduce))
+
+    def graph_stats(self):
+        """What the last string_graph() or edges_reduce() did (debwt_fm_graph_stats_get): records per state, hits walked,
+        edges, reducible edges, witness lists searched, launches, scratch and edge bytes, ms per phase and wall."""
+        st = _lib.DebwtFmGraphStats()
+        self._chk(self._L.debwt_fm_graph_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def attach_text(self, source=None, words=None, sep=None):
         """Give the index its text (debwt_fm_attach_text; n / 4 bytes of HBM), which extend() and map() read.  source: the
         DeBWT context the index was made from (device-to-device copy), or None with the host text words / sep as
@@ -870,6 +897,9 @@ _CORRECT_DTYPE = np.dtype([("flags", np.uint32), ("fixes", np.uint32), ("weak_be
 _TRIAL_DTYPE = np.dtype([("run_a", np.uint32), ("run_b", np.uint32), ("pos", np.uint32), ("window", np.uint32),
                          ("kind", np.uint32)])
 _OVERLAP_DTYPE = np.dtype([("record", np.uint32), ("length", np.uint32), ("strand", np.uint32), ("flags", np.uint32)])
+GRAPH_ALL_EDGES = 1                                    # option flag of debwt_fm_string_graph
+NODE_KEPT, NODE_DUPLICATE, NODE_CONTAINED = 0, 1, 2    # GraphResult.state
+_EDGE_DTYPE = np.dtype([("record", np.uint32), ("length", np.uint32)])
 _ALN_DTYPE = np.dtype([("score", np.int32), ("qbeg", np.uint32), ("qend", np.uint32), ("edits", np.uint32),
                        ("tbeg", np.uint64), ("tend", np.uint64)])
 _HIT_DTYPE = np.dtype([("pattern", np.uint64), ("flags", np.uint32), ("record", np.uint32), ("offset", np.uint64),
@@ -1145,6 +1175,89 @@ class OverlapResult:
     def mismatches(self):
         """mismatches per hit (np.uint8, flags bits 8-15): zeros for a result of FMIndex.overlaps"""
         return ((self.all_hits["flags"] >> 8) & 0xFF).astype(np.uint8)
+
+
+class GraphResult:
+    """String graph of FMIndex.string_graph.  state: per record NODE_KEPT, NODE_DUPLICATE or NODE_CONTAINED; record i's
+    out-edges are edges[offsets[i] .. offsets[i + 1]), a structured array of (record, length) ordered by (length descending,
+    record): record i's last `length` bases are the first `length` of `record`.  reduced: the edges are those of the
+    irreducible graph, which unitigs() needs."""
+
+    def __init__(self, index, state, offsets, edges, reduced):
+        self.index, self.state, self.offsets, self.edges, self.reduced = index, state, offsets, edges, reduced
+
+    def __len__(self):
+        return len(self.state)
+
+    def out(self, i):
+        """structured array (record, length) of record i's out-edges"""
+        return self.edges[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+    def unitigs(self):
+        """(offsets, members, circular) of the unbranched paths, see unitigs()"""
+        return unitigs(self.state, self.offsets, self.edges)
+
+    def sequences(self, index=None):
+        """The unitigs' sequences as a list of str, through FMIndex.extract of `index` (default: the graph's own): every
+        member but the last gives its first |S| - L_next bases, and the last of a circular unitig is cut by its overlap
+        with the first."""
+        index = self.index if index is None else index
+        uoff, mem, circ = self.unitigs()
+        starts = np.append(index.record_starts(), np.uint64(index.n))
+        jobs = []
+        for u in range(len(circ)):
+            m = [int(x) for x in mem[int(uoff[u]):int(uoff[u + 1])]]
+            for x, v in enumerate(m):
+                length = int(starts[v + 1]) - 1 - int(starts[v])
+                if x + 1 < len(m) or circ[u]:
+                    length -= int(self.out(v)["length"][0])    # a link's source has one out-edge
+                jobs.append((v, 0, length))
+        parts = index.extract(jobs)
+        return [b"".join(parts[int(uoff[u]):int(uoff[u + 1])]).decode() for u in range(len(circ))]
+
+
+def edges_reduce(index, reclen, offsets, edges):
+    """Transitive reduction of any edge list on the index's GPU (debwt_fm_edges_reduce).  reclen: the nodes' lengths;
+    node i's edges are edges[offsets[i] .. offsets[i + 1]), (record, length) with lengths descending, one length's records
+    in any order.  Returns keep, one np.uint8 per edge: 0 for an edge (i -> k, L) that some (i -> j, L_ij > L) and (j -> k,
+    reclen[j] - L_ij + L) explain.  A list out of that order, a repeated or out-of-range target, a self edge or a length
+    that covers a node raises DebwtError (DEBWT_EINVAL)."""
+    reclen = np.ascontiguousarray(reclen, dtype=np.uint64)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    e = np.ascontiguousarray(np.asarray(edges, dtype=_EDGE_DTYPE))
+    if len(offs) != len(reclen) + 1 or int(offs.max()) > len(e):
+        raise ValueError("offsets fit neither the nodes nor the edges")
+    keep = np.zeros(max(len(e), 1), dtype=np.uint8)
+    index._chk(index._L.debwt_fm_edges_reduce(index._h, _p64(reclen) if len(reclen) else None, len(reclen), _p64(offs),
+                                              e.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)),
+                                              keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+    return keep[:len(e)]
+
+
+def unitigs(state, offsets, edges):
+    """The unbranched paths of a graph over the kept nodes (state 0) on the host (debwt_fm_unitigs, no GPU).  u -> w is a
+    link iff w is u's only successor, u is w's only predecessor and w != u; a unitig is a maximal chain of links, a cycle
+    of links starts at its lowest node.  Returns (offsets, members, circular): unitig t's nodes are members[offsets[t] ..
+    offsets[t + 1]) in path order, unitigs by ascending first node, circular one np.uint8 each."""
+    state = np.ascontiguousarray(state, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    e = np.ascontiguousarray(np.asarray(edges, dtype=_EDGE_DTYPE))
+    nn = len(state)
+    if len(offs) != nn + 1 or int(offs.max()) > len(e):
+        raise ValueError("offsets fit neither the nodes nor the edges")
+    uoff = np.zeros(nn + 1, dtype=np.uint64)
+    mem = np.zeros(max(nn, 1), dtype=np.uint32)
+    circ = np.zeros(max(nn, 1), dtype=np.uint8)
+    nu = ctypes.c_uint64(0)
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    rc = _lib.lib().debwt_fm_unitigs(state.ctypes.data_as(u8p) if nn else None, _p64(offs),
+                                     e.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)) if len(e) else None, nn, _p64(uoff),
+                                     mem.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), circ.ctypes.data_as(u8p),
+                                     ctypes.byref(nu))
+    if rc:
+        raise DebwtError(rc)
+    k = int(nu.value)
+    return uoff[:k + 1].copy(), mem[:int(uoff[k])].copy(), circ[:k].copy()
 
 
 class MultiDeBWT:

@@ -36,6 +36,7 @@
 #include "fm_overlap_mm_kernels.h"
 #include "fm_extract_kernels.h"
 #include "fm_kmer_kernels.h"
+#include "fm_graph_kernels.h"
 
 namespace {
 
@@ -2982,6 +2983,8 @@ struct debwt_fm {
     DevBuf k_coff, k_counts, k_ctr, k_active, k_info, k_ntr, k_trials, k_trun, k_res;   // k-mer and correction scratch of one batch
     debwt_fm_kmer_stats k_stats{};
     debwt_fm_correct_stats c_stats{};
+    DevBuf g_coff, g_state, g_hbase, g_raw, g_flag, g_deg, g_oseg, g_edges, g_eoff, g_len, g_keep, g_out, g_ctr;   // string graph
+    debwt_fm_graph_stats g_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -6422,6 +6425,389 @@ extern "C" int debwt_fm_correct_stats_get(const debwt_fm *f, debwt_fm_correct_st
     return DEBWT_OK;
 }
 
+// ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
+// States come from one backward search per record over the attached text.  The kept records then go through the overlap
+// walk in the batches of debwt_fm_overlaps, unpacked from the text on the device; a batch's hits are expanded at most
+// DEBWT_FM_OVERLAP_HITS at a launch into o_hits and packed to 8 bytes each, the longest hit per (source, target) is
+// flagged, and the flagged ones are appended to E (g_edges, grown by doubling).  Per batch the run, hit and edge counts of
+// its sources reach the host, which lays the lists out; E itself stays in HBM until the reduction has run over it.
+
+namespace {
+
+static_assert(sizeof(debwt_fm_edge) == sizeof(FmEdge), "the graph kernels write debwt_fm_edge as FmEdge");
+
+struct FmGraphTimer {                                  // a timed stretch of the stream: begin(), launches, end(&ms)
+    debwt_fm *f;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    explicit FmGraphTimer(debwt_fm *f_) : f(f_) {}
+    ~FmGraphTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+    int init() {
+        HIPCHK(f, hipEventCreate(&e0));
+        HIPCHK(f, hipEventCreate(&e1));
+        return DEBWT_OK;
+    }
+    void begin() { (void)hipEventRecord(e0, f->stream); }
+    int end(float *acc) {
+        (void)hipEventRecord(e1, f->stream);
+        int rc = fm_sync(f);
+        if (rc) return rc;
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, e0, e1);
+        *acc += ms;
+        return DEBWT_OK;
+    }
+};
+
+// room for nedges edges in g_edges, the first `have` of them kept
+int fm_graph_reserve(debwt_fm *f, u64 have, u64 nedges) {
+    const size_t need = (size_t)std::max<u64>(nedges, 1) * sizeof(FmEdge);
+    if (need <= f->g_edges.cap) return DEBWT_OK;
+    HIPCHK(f, hipStreamSynchronize(f->stream));
+    size_t want = std::max(need, f->g_edges.cap * 2);
+    void *p = nullptr;
+    if (hipMalloc(&p, want) != hipSuccess) {
+        (void)hipGetLastError();
+        want = need;
+        if (hipMalloc(&p, want) != hipSuccess) {
+            (void)hipGetLastError();
+            f->err = "debwt_fm_string_graph: the edge list does not fit in device memory (" + std::to_string(nedges) +
+                     " edges so far, 8 bytes each)";
+            return DEBWT_ENOMEM;
+        }
+    }
+    if (have) {
+        hipError_t e = hipMemcpyAsync(p, f->g_edges.p, (size_t)have * sizeof(FmEdge), hipMemcpyDeviceToDevice, f->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(f->stream);
+        if (e != hipSuccess) { (void)hipFree(p); f->err = std::string("hipMemcpyAsync: ") + hipGetErrorString(e); return DEBWT_EDEVICE; }
+    }
+    if (f->g_edges.p) (void)hipFree(f->g_edges.p);
+    f->g_edges.p = p; f->g_edges.cap = want;
+    return DEBWT_OK;
+}
+
+// the keep bytes of definition 3 for the lists in g_eoff / `edges` (device), into g_keep
+int fm_graph_reduce(debwt_fm *f, FmGraphTimer &tm, u64 nnodes, const FmEdge *edges, u64 nedges) {
+    debwt_fm_graph_stats &st = f->g_stats;
+    FM_ENSURE(f, f->g_keep, (size_t)nedges);
+    FM_ENSURE(f, f->g_ctr, FM_GR_NCTR * 8);
+    HIPCHK(f, hipMemsetAsync(f->g_ctr.p, 0, FM_GR_NCTR * 8, f->stream));
+    tm.begin();
+    k_fm_graph_reduce<<<grid_for(nedges, 256), 256, 0, f->stream>>>(f->g_eoff.as<u64>(), nnodes, edges, nedges, f->g_len.as<u64>(),
+                                                                    f->g_keep.as<u8>(), f->g_ctr.as<u64>());
+    u64 h[FM_GR_NCTR];
+    HIPCHK(f, hipMemcpyAsync(h, f->g_ctr.p, sizeof h, hipMemcpyDeviceToHost, f->stream));
+    int rc = tm.end(&st.ms_reduce);
+    if (rc) return rc;
+    st.launches++;
+    st.lookups = h[FM_GR_LOOKUPS]; st.reducible = h[FM_GR_REDUCIBLE];
+    return DEBWT_OK;
+}
+
+// states (host and g_state) and E (g_edges, edge_offsets on the host)
+int fm_graph_edges(debwt_fm *f, FmGraphTimer &tm, u32 min_overlap, uint8_t *state, uint64_t *eoff) {
+    debwt_fm_graph_stats &st = f->g_stats;
+    const u64 nrec = f->nrec, n = f->n;
+    const std::vector<u64> &rs = f->rec_starts;
+    int rc;
+    if (!f->has_text && (rc = debwt_fm_restore_text(f))) return rc;
+    if ((rc = fm_overlap_table(f))) return rc;
+    std::vector<u64> coff(nrec + 1);                       // bases before each record
+    for (u64 i = 0; i < nrec; i++) coff[i] = rs[i] - i;
+    coff[nrec] = n - nrec;
+    for (u64 i = 0; i < nrec; i++)
+        if ((coff[i + 1] - coff[i]) >> 32) { f->err = "debwt_fm_string_graph: a record of 2^32 bases or more"; return DEBWT_EINVAL; }
+    FM_ENSURE(f, f->g_coff, (size_t)(nrec + 1) * 8);
+    FM_ENSURE(f, f->g_state, (size_t)nrec);
+    FM_ENSURE(f, f->g_ctr, FM_GR_NCTR * 8);
+    HIPCHK(f, hipMemcpyAsync(f->g_coff.p, coff.data(), (nrec + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(f->g_ctr.p, 0, FM_GR_NCTR * 8, f->stream));
+    tm.begin();
+    k_fm_graph_state<<<grid_for(nrec, 256), 256, 0, f->stream>>>(f->V, f->text.as<u64>(), f->g_coff.as<u64>(),
+                                                                 f->o_table.as<FmOvlRec>(), nrec, f->g_state.as<u8>());
+    HIPCHK(f, hipMemcpyAsync(state, f->g_state.p, nrec, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = tm.end(&st.ms_walk))) return rc;
+    st.launches++;
+    st.records = nrec;
+    for (u64 i = 0; i < nrec; i++) {
+        if (state[i] == 0) st.kept++;
+        else if (state[i] == 1) st.duplicates++;
+        else st.contained++;
+    }
+    const u64 slots = fm_env_u64("DEBWT_FM_OVERLAP_SLOTS", FM_OVL_SLOTS);
+    const u64 limit = std::max<u64>(fm_env_u64("DEBWT_FM_OVERLAP_HITS", FM_OVL_HITS), 1);
+    auto worst = [&](u64 i) {
+        const u64 m = coff[i + 1] - coff[i];
+        return state[i] == 0 && m >= min_overlap ? m - min_overlap + 1 : 0;
+    };
+    std::vector<u64> slot, rbase, hbase, oseg, nh;
+    std::vector<u32> nr, deg;
+    eoff[0] = 0;
+    for (u64 p0 = 0; p0 < nrec;) {
+        u64 p1 = p0 + 1, ws = worst(p0);                  // at least one record, however long
+        while (p1 < nrec && p1 - p0 < FM_BATCH_PATTERNS && coff[p1 + 1] - coff[p0] <= FM_BATCH_CHARS && ws + worst(p1) <= slots)
+            ws += worst(p1++);
+        const u64 np = p1 - p0, bytes = coff[p1] - coff[p0];
+        for (u64 j = p0; j < p1; j++) eoff[j + 1] = eoff[j];
+        if (!ws) { p0 = p1; continue; }                        // no kept record long enough: no edges
+        slot.resize(np + 1);
+        slot[0] = 0;
+        for (u64 j = 0; j < np; j++) slot[j + 1] = slot[j] + worst(p0 + j);
+        FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
+        FM_ENSURE(f, f->o_slot, (size_t)(np + 1) * 8);
+        FM_ENSURE(f, f->o_nruns, (size_t)np * 4);
+        FM_ENSURE(f, f->o_nhits, (size_t)np * 8);
+        FM_ENSURE(f, f->o_runs, (size_t)ws * sizeof(FmOvlRun));
+        FM_ENSURE(f, f->s_ctr, 64);
+        HIPCHK(f, hipMemcpyAsync(f->o_slot.p, slot.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemsetAsync(f->s_ctr.p, 0, 32, f->stream));
+        tm.begin();
+        k_fm_graph_unpack<<<grid_for(bytes, 256), 256, 0, f->stream>>>(f->text.as<u64>(), f->g_coff.as<u64>(), p0, np, bytes,
+                                                                       f->q_chars.as<u8>());
+        k_fm_overlap_walk<<<grid_for(np, 256), 256, 0, f->stream>>>(f->V, f->q_chars.as<u8>(), f->g_coff.as<u64>() + p0, coff[p0], np,
+                                                                    np, min_overlap, f->o_slot.as<u64>(), f->o_runs.as<FmOvlRun>(),
+                                                                    f->o_nruns.as<u32>(), f->o_nhits.as<u64>(), f->s_ctr.as<u64>());
+        nr.resize(np); nh.resize(np);
+        HIPCHK(f, hipMemcpyAsync(nr.data(), f->o_nruns.p, np * 4, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(f, hipMemcpyAsync(nh.data(), f->o_nhits.p, np * 8, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&st.ms_walk))) return rc;
+        st.launches += 2;
+        rbase.resize(np); hbase.resize(np + 1);
+        u64 nruns = 0, nhits = 0;
+        for (u64 j = 0; j < np; j++) {
+            if (nr[j] > slot[j + 1] - slot[j]) { f->err = "debwt_fm_string_graph: a record wrote more runs than its slots"; return DEBWT_EINTERNAL; }
+            rbase[j] = nruns; hbase[j] = nhits;
+            nruns += nr[j]; nhits += nh[j];
+        }
+        hbase[np] = nhits;
+        st.hits += nhits;
+        if (!nhits) { p0 = p1; continue; }
+        const u64 chunk = std::min(nhits, limit);
+        FM_ENSURE(f, f->o_rbase, (size_t)np * 8);
+        FM_ENSURE(f, f->g_hbase, (size_t)(np + 1) * 8);
+        FM_ENSURE(f, f->o_cruns, (size_t)nruns * sizeof(FmOvlRun));
+        FM_ENSURE(f, f->o_rout, (size_t)nruns * 8);
+        FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
+        FM_ENSURE(f, f->g_raw, (size_t)nhits * sizeof(FmEdge));
+        FM_ENSURE(f, f->g_flag, (size_t)nhits);
+        FM_ENSURE(f, f->g_deg, (size_t)np * 4);
+        FM_ENSURE(f, f->g_oseg, (size_t)(np + 1) * 8);
+        st.scratch_bytes = std::max<u64>(st.scratch_bytes, bytes + ws * sizeof(FmOvlRun) + np * 48 + nruns * 24 + chunk * 16 + nhits * 9);
+        HIPCHK(f, hipMemcpyAsync(f->o_rbase.p, rbase.data(), np * 8, hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->g_hbase.p, hbase.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        tm.begin();
+        k_fm_overlap_compact<<<grid_for(np, 256), 256, 0, f->stream>>>(f->g_coff.as<u64>() + p0, f->o_slot.as<u64>(), f->o_nruns.as<u32>(),
+                                                                       f->o_rbase.as<u64>(), f->g_hbase.as<u64>(), np, np,
+                                                                       f->o_runs.as<FmOvlRun>(), f->o_cruns.as<FmOvlRun>(),
+                                                                       f->o_rout.as<u64>());
+        st.launches++;
+        for (u64 g0 = 0; g0 < nhits; g0 += chunk) {
+            const u64 cnt = std::min(nhits - g0, chunk);
+            if (g0) tm.begin();
+            k_fm_overlap_expand<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_cruns.as<FmOvlRun>(), f->o_rout.as<u64>(), nruns,
+                                                                           f->o_table.as<FmOvlRec>(), g0, cnt, f->o_hits.as<uint4>());
+            if ((rc = tm.end(&st.ms_walk))) return rc;
+            tm.begin();
+            k_fm_graph_pack<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_hits.as<uint4>(), g0, cnt, f->g_hbase.as<u64>(), p0, np,
+                                                                       f->g_state.as<u8>(), f->g_raw.as<FmEdge>(), f->g_ctr.as<u64>());
+            if ((rc = tm.end(&st.ms_build))) return rc;
+            st.launches += 2;
+        }
+        tm.begin();
+        k_fm_graph_longest<<<grid_for(nhits, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), f->g_hbase.as<u64>(), np, nhits,
+                                                                        f->g_flag.as<u8>());
+        k_fm_graph_degree<<<grid_for(np, 256), 256, 0, f->stream>>>(f->g_flag.as<u8>(), f->g_hbase.as<u64>(), np, f->g_deg.as<u32>());
+        deg.resize(np);
+        HIPCHK(f, hipMemcpyAsync(deg.data(), f->g_deg.p, np * 4, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&st.ms_build))) return rc;
+        st.launches += 2;
+        oseg.resize(np + 1);
+        for (u64 j = 0; j < np; j++) { oseg[j] = eoff[p0 + j]; eoff[p0 + j + 1] = eoff[p0 + j] + deg[j]; }
+        oseg[np] = eoff[p1];
+        if (eoff[p1] > eoff[p0]) {
+            if ((rc = fm_graph_reserve(f, eoff[p0], eoff[p1]))) return rc;
+            HIPCHK(f, hipMemcpyAsync(f->g_oseg.p, oseg.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+            tm.begin();
+            k_fm_graph_scatter<<<grid_for(nhits, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), f->g_flag.as<u8>(), f->g_hbase.as<u64>(),
+                                                                            f->g_oseg.as<u64>(), np, nhits, f->g_edges.as<FmEdge>());
+            if ((rc = tm.end(&st.ms_build))) return rc;     // oseg is host memory
+            st.launches++;
+        }
+        p0 = p1;
+    }
+    u64 h[FM_GR_NCTR];
+    HIPCHK(f, hipMemcpyAsync(h, f->g_ctr.p, sizeof h, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    if (h[FM_GR_BADLEN]) {
+        f->err = "debwt_fm_string_graph: " + std::to_string(h[FM_GR_BADLEN]) + " overlaps between kept records cover one of them whole";
+        return DEBWT_EINTERNAL;
+    }
+    st.edges = eoff[nrec];
+    st.edge_bytes = eoff[nrec] * sizeof(FmEdge);
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_string_graph(debwt_fm *f, uint32_t min_overlap, uint32_t flags, uint8_t *state, uint64_t *edge_offsets,
+                                     debwt_fm_edge *edges, uint64_t capacity) {
+    if (!f || !state || !edge_offsets) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->g_stats = debwt_fm_graph_stats{};
+    if (!min_overlap) { f->err = "debwt_fm_string_graph: min_overlap must be at least 1"; return DEBWT_EINVAL; }
+    if (flags & ~DEBWT_FM_GRAPH_ALL_EDGES) { f->err = "debwt_fm_string_graph: unknown flags"; return DEBWT_EINVAL; }
+    if (f->nrec >> 32) { f->err = "debwt_fm_string_graph: 2^32 records or more"; return DEBWT_EINVAL; }
+    HIPCHK(f, hipSetDevice(f->device));
+    debwt_fm_graph_stats &st = f->g_stats;
+    const u64 nrec = f->nrec;
+    FmGraphTimer tm(f);
+    int rc = tm.init();
+    if (rc) return rc;
+    if ((rc = fm_graph_edges(f, tm, min_overlap, state, edge_offsets))) return rc;
+    const u64 ne = edge_offsets[nrec];
+    const FmEdge *d_final = f->g_edges.as<FmEdge>();
+    if (!(flags & DEBWT_FM_GRAPH_ALL_EDGES) && ne) {
+        std::vector<u64> len(nrec);
+        for (u64 i = 0; i < nrec; i++) len[i] = (i + 1 < nrec ? f->rec_starts[i + 1] : f->n) - 1 - f->rec_starts[i];
+        FM_ENSURE(f, f->g_eoff, (size_t)(nrec + 1) * 8);
+        FM_ENSURE(f, f->g_len, (size_t)nrec * 8);
+        HIPCHK(f, hipMemcpyAsync(f->g_eoff.p, edge_offsets, (nrec + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->g_len.p, len.data(), nrec * 8, hipMemcpyHostToDevice, f->stream));
+        if ((rc = fm_graph_reduce(f, tm, nrec, f->g_edges.as<FmEdge>(), ne))) return rc;
+        // compaction of the kept edges, as a batch's hits were compacted into E
+        std::vector<u32> deg(nrec);
+        FM_ENSURE(f, f->g_deg, (size_t)nrec * 4);
+        tm.begin();
+        k_fm_graph_degree<<<grid_for(nrec, 256), 256, 0, f->stream>>>(f->g_keep.as<u8>(), f->g_eoff.as<u64>(), nrec, f->g_deg.as<u32>());
+        HIPCHK(f, hipMemcpyAsync(deg.data(), f->g_deg.p, nrec * 4, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&st.ms_reduce))) return rc;
+        for (u64 i = 0; i < nrec; i++) edge_offsets[i + 1] = edge_offsets[i] + deg[i];
+        const u64 nk = edge_offsets[nrec];
+        if (nk != ne - st.reducible) { f->err = "debwt_fm_string_graph: the kept edges do not add up"; return DEBWT_EINTERNAL; }
+        FM_ENSURE(f, f->g_oseg, (size_t)(nrec + 1) * 8);
+        FM_ENSURE(f, f->g_out, (size_t)std::max<u64>(nk, 1) * sizeof(FmEdge));
+        HIPCHK(f, hipMemcpyAsync(f->g_oseg.p, edge_offsets, (nrec + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        tm.begin();
+        k_fm_graph_scatter<<<grid_for(ne, 256), 256, 0, f->stream>>>(f->g_edges.as<FmEdge>(), f->g_keep.as<u8>(), f->g_eoff.as<u64>(),
+                                                                     f->g_oseg.as<u64>(), nrec, ne, f->g_out.as<FmEdge>());
+        if ((rc = tm.end(&st.ms_reduce))) return rc;
+        st.launches += 2;
+        d_final = f->g_out.as<FmEdge>();
+    }
+    const u64 total = edge_offsets[nrec];
+    if (capacity < total || (total && !edges)) {
+        f->err = "debwt_fm_string_graph: capacity below the edges (edge_offsets[nrec] = " + std::to_string(total) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (total) {
+        HIPCHK(f, hipMemcpyAsync(edges, d_final, (size_t)total * sizeof(FmEdge), hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+        for (u64 i = 0; i < nrec; i++)                         // record order inside every length group
+            for (u64 a = edge_offsets[i]; a < edge_offsets[i + 1];) {
+                u64 e = a + 1;
+                while (e < edge_offsets[i + 1] && edges[e].length == edges[a].length) e++;
+                if (e - a > 1)
+                    std::sort(edges + a, edges + e, [](const debwt_fm_edge &x, const debwt_fm_edge &y) { return x.record < y.record; });
+                a = e;
+            }
+    }
+    st.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_edges_reduce(debwt_fm *f, const uint64_t *reclen, uint64_t nnodes, const uint64_t *edge_offsets,
+                                     const debwt_fm_edge *edges, uint8_t *keep) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->g_stats = debwt_fm_graph_stats{};
+    auto bad = [&](const std::string &why) { f->err = "debwt_fm_edges_reduce: " + why; return DEBWT_EINVAL; };
+    if (!edge_offsets || (nnodes && !reclen)) return bad("a NULL array");
+    if (nnodes >> 32) return bad("2^32 nodes or more");
+    for (u64 i = 0; i < nnodes; i++)
+        if (edge_offsets[i + 1] < edge_offsets[i]) return bad("offsets must not decrease");
+    const u64 e0 = edge_offsets[0], ne = edge_offsets[nnodes] - e0;
+    if (ne && (!edges || !keep)) return bad("a NULL array");
+    std::vector<u64> seen(nnodes, 0);                      // source + 1 of the last list that named the node
+    for (u64 i = 0; i < nnodes; i++)
+        for (u64 e = edge_offsets[i]; e < edge_offsets[i + 1]; e++) {
+            const debwt_fm_edge &x = edges[e];
+            const std::string at = "edge " + std::to_string(e) + " of source " + std::to_string(i);
+            if (x.record >= nnodes) return bad(at + " names node " + std::to_string(x.record) + " of " + std::to_string(nnodes));
+            if (x.record == i) return bad(at + " leads to its own source");
+            if (e > edge_offsets[i] && x.length > edges[e - 1].length) return bad(at + " is longer than the one before it");
+            if (seen[x.record] == i + 1) return bad(at + " repeats target " + std::to_string(x.record));
+            seen[x.record] = i + 1;
+            if (x.length >= std::min(reclen[i], reclen[x.record])) return bad(at + " is as long as one of its records");
+        }
+    debwt_fm_graph_stats &st = f->g_stats;
+    st.records = nnodes; st.edges = ne; st.edge_bytes = ne * sizeof(FmEdge);
+    if (!ne) return DEBWT_OK;
+    HIPCHK(f, hipSetDevice(f->device));
+    FmGraphTimer tm(f);
+    int rc = tm.init();
+    if (rc) return rc;
+    std::vector<u64> off(nnodes + 1);
+    for (u64 i = 0; i <= nnodes; i++) off[i] = edge_offsets[i] - e0;
+    FM_ENSURE(f, f->g_eoff, (size_t)(nnodes + 1) * 8);
+    FM_ENSURE(f, f->g_len, (size_t)nnodes * 8);
+    if ((rc = fm_graph_reserve(f, 0, ne))) return rc;
+    HIPCHK(f, hipMemcpyAsync(f->g_eoff.p, off.data(), (nnodes + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->g_len.p, reclen, nnodes * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->g_edges.p, edges + e0, (size_t)ne * sizeof(FmEdge), hipMemcpyHostToDevice, f->stream));
+    if ((rc = fm_graph_reduce(f, tm, nnodes, f->g_edges.as<FmEdge>(), ne))) return rc;
+    HIPCHK(f, hipMemcpyAsync(keep + e0, f->g_keep.p, (size_t)ne, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    st.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_unitigs(const uint8_t *state, const uint64_t *edge_offsets, const debwt_fm_edge *edges, uint64_t nnodes,
+                                uint64_t *unitig_offsets, uint32_t *members, uint8_t *circular, uint64_t *nunitigs) {
+    if (!edge_offsets || !unitig_offsets || !nunitigs || (nnodes && (!state || !members || !circular)) || (nnodes >> 32))
+        return DEBWT_EINVAL;
+    const u64 e0 = edge_offsets[0];
+    for (u64 i = 0; i < nnodes; i++)
+        if (edge_offsets[i + 1] < edge_offsets[i]) return DEBWT_EINVAL;
+    if (edge_offsets[nnodes] > e0 && !edges) return DEBWT_EINVAL;
+    constexpr u32 NONE = 0xFFFFFFFFu;
+    std::vector<u32> indeg(nnodes, 0), next(nnodes, NONE);
+    for (u64 i = 0; i < nnodes; i++)
+        for (u64 e = edge_offsets[i]; e < edge_offsets[i + 1]; e++) {
+            if (edges[e].record >= nnodes || state[i] != 0 || state[edges[e].record] != 0) return DEBWT_EINVAL;
+            indeg[edges[e].record]++;
+        }
+    std::vector<u8> has_in(nnodes, 0), on_chain(nnodes, 0);
+    for (u64 i = 0; i < nnodes; i++)
+        if (edge_offsets[i + 1] - edge_offsets[i] == 1) {
+            const u32 w = edges[edge_offsets[i]].record;
+            if (w != i && indeg[w] == 1) { next[i] = w; has_in[w] = 1; }
+        }
+    for (u64 i = 0; i < nnodes; i++)                           // the nodes that a node without an incoming link leads to
+        if (state[i] == 0 && !has_in[i])
+            for (u64 v = i; v != NONE; v = next[v]) on_chain[v] = 1;
+    u64 nu = 0, nm = 0;
+    unitig_offsets[0] = 0;
+    for (u64 i = 0; i < nnodes; i++) {
+        if (state[i] != 0 || (has_in[i] && on_chain[i])) continue;
+        if (!has_in[i]) {
+            for (u64 v = i; v != NONE; v = next[v]) members[nm++] = (u32)v;
+            circular[nu] = 0;
+        } else {                                               // the lowest node of a cycle: the ones after it get on_chain
+            u64 v = i;
+            do { members[nm++] = (u32)v; on_chain[v] = 1; v = next[v]; } while (v != i);
+            circular[nu] = 1;
+        }
+        unitig_offsets[++nu] = nm;
+    }
+    *nunitigs = nu;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_graph_stats_get(const debwt_fm *f, debwt_fm_graph_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->g_stats;
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
@@ -6432,7 +6818,8 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
                       &f->x_cig, &f->x_anchors, &f->o_table, &f->o_slot, &f->o_runs, &f->o_nruns, &f->o_nhits, &f->o_rbase,
                       &f->o_hbase, &f->o_cruns, &f->o_rout, &f->o_hits, &f->anchors, &f->e_jobs, &f->e_seg, &f->e_out, &f->e_ctr,
                       &f->e_sep, &f->k_table, &f->k_coff, &f->k_counts, &f->k_ctr, &f->k_active, &f->k_info, &f->k_ntr,
-                      &f->k_trials, &f->k_trun, &f->k_res})
+                      &f->k_trials, &f->k_trun, &f->k_res, &f->g_coff, &f->g_state, &f->g_hbase, &f->g_raw, &f->g_flag,
+                      &f->g_deg, &f->g_oseg, &f->g_edges, &f->g_eoff, &f->g_len, &f->g_keep, &f->g_out, &f->g_ctr})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -1115,6 +1115,62 @@ typedef struct {
 } debwt_fm_correct_stats;
 int debwt_fm_correct_stats_get(const debwt_fm *fm, debwt_fm_correct_stats *out);
 
+/* ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
+ * Records S_0 .. S_{nrec-1} are those of the index, numbered as in overlap hits; |S| is the length of S.
+ * 1. state[i] = 1 (duplicate) iff some j < i has S_j == S_i; otherwise 2 (contained) iff S_i is a substring of a strictly
+ *    longer record (a prefix, a suffix or an inner part); otherwise 0 (kept).  States do not depend on min_overlap.
+ * 2. E: for kept i and kept j != i, (i -> j, L) is in E iff L is the largest length with min_overlap <= L and
+ *    S_i[|S_i| - L ..) == S_j[0 .. L): DEBWT_FM_OVERLAP_LONGEST per pair, strand 0, self overlaps dropped.  Both ends are
+ *    kept, so L < min(|S_i|, |S_j|): DEBWT_EINTERNAL otherwise.  Out-list order per source: (L descending, record ascending).
+ * 3. (i -> k, L_ik) in E is reducible iff some j outside {i, k} has (i -> j, L_ij) in E with L_ij > L_ik and (j -> k, L_jk)
+ *    in E with L_jk == |S_j| - L_ij + L_ik.  E is read as it is before anything is removed.  The irreducible graph is E
+ *    minus its reducible edges.  Where the longest j -> k overlap is longer than the one that fits (periodic reads) no
+ *    witness is in E and the edge stays.
+ * 4. Unitigs over the irreducible graph: u -> w is a link iff outdeg(u) == 1, w is u's only successor, indeg(w) == 1 and
+ *    w != u.  A unitig is a maximal chain of links; a node with no incoming link starts one; a component in which every
+ *    node has an incoming link is a cycle, which starts at its lowest record and is flagged circular.  Every kept node is
+ *    in exactly one unitig, and unitigs are numbered by ascending first record.
+ * Strand 0 only: a read set sampled from both strands gives a strand-complete graph only if the collection holds the
+ * reverse complements (tail-to-tail overlaps are a limit of debwt_fm_overlaps).
+ *
+ * debwt_fm_string_graph writes state (nrec) and edge_offsets (nrec + 1) first, then the edges of the irreducible graph,
+ * or of E with DEBWT_FM_GRAPH_ALL_EDGES; DEBWT_ERANGE when capacity < edge_offsets[nrec] (the protocol of
+ * debwt_fm_locate; edges may be NULL then).  DEBWT_EINVAL for min_overlap 0 and unknown flags.  The records are read
+ * from the attached text; an index without one restores it first (debwt_fm_restore_text), so an index from
+ * debwt_fm_open answers as one from debwt_fm_create.  Only kept records are walked, in the batches of debwt_fm_overlaps
+ * (DEBWT_FM_OVERLAP_SLOTS, DEBWT_FM_OVERLAP_HITS; the result depends on neither).  E stays in HBM, 8 bytes an edge, from
+ * the walk to the reduction: DEBWT_ENOMEM with the edge count in debwt_fm_last_error when it does not fit. */
+typedef struct { uint32_t record, length; } debwt_fm_edge;
+#define DEBWT_FM_GRAPH_ALL_EDGES 1u    /* skip the reduction: return E */
+int debwt_fm_string_graph(debwt_fm *fm, uint32_t min_overlap, uint32_t flags,
+                          uint8_t *state /* nrec */, uint64_t *edge_offsets /* nrec + 1 */,
+                          debwt_fm_edge *edges, uint64_t capacity);
+/* Definition 3 on a caller's edge list, on the index's device and stream: keep[e] = 0 for a reducible edge, 1 otherwise.
+ * Source i's edges are edges[edge_offsets[i] .. edge_offsets[i + 1]), lengths descending; edges of one length may stand in
+ * any record order.  reclen[i] = |S_i|.  DEBWT_EINVAL with the reason in debwt_fm_last_error: decreasing offsets, a
+ * target >= nnodes, a target equal to the source, lengths not descending inside a source, a target repeated inside a
+ * source, L >= min(reclen[source], reclen[target]), nnodes of 2^32 or more. */
+int debwt_fm_edges_reduce(debwt_fm *fm, const uint64_t *reclen, uint64_t nnodes,
+                          const uint64_t *edge_offsets, const debwt_fm_edge *edges,
+                          uint8_t *keep /* one byte per edge */);
+/* Definition 4 on the host (no GPU), in time linear in nodes and edges.  Only nodes of state 0 take part; an edge from
+ * or to another node is DEBWT_EINVAL, as are decreasing offsets and a target >= nnodes.  members holds every kept node
+ * once, unitig u's in members[unitig_offsets[u] .. unitig_offsets[u + 1]) in path order; the first *nunitigs entries of
+ * circular and *nunitigs + 1 of unitig_offsets are meaningful. */
+int debwt_fm_unitigs(const uint8_t *state, const uint64_t *edge_offsets, const debwt_fm_edge *edges,
+                     uint64_t nnodes, uint64_t *unitig_offsets /* nnodes + 1 */, uint32_t *members /* nnodes */,
+                     uint8_t *circular /* nnodes */, uint64_t *nunitigs);
+/* what the last debwt_fm_string_graph or debwt_fm_edges_reduce did: records, the three states, overlap hits walked, edges
+ * of E, reducible edges, witness lists searched, kernel launches, the largest device scratch of a batch, the bytes of E
+ * resident, and the time of the walk (state search, walk, compaction, expansion), of the edge build and of the reduction
+ * (reduction and compaction of the kept edges), by events, and host wall time.  debwt_fm_edges_reduce fills records
+ * (nnodes), edges, reducible, lookups, launches, edge_bytes, ms_reduce and ms_wall. */
+typedef struct {
+    uint64_t records, kept, duplicates, contained, hits, edges, reducible, lookups, launches, scratch_bytes, edge_bytes;
+    float ms_walk, ms_build, ms_reduce, ms_wall;
+} debwt_fm_graph_stats;
+int debwt_fm_graph_stats_get(const debwt_fm *fm, debwt_fm_graph_stats *out);
+
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
