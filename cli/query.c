@@ -14,8 +14,8 @@
  *   deBWT-query extract -i OUT [--device D] --all | REGIONS.txt
  *   deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq
  *   deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq
- *   deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--states FILE]
- *   deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--states FILE]
+ *   deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]
+ *   deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -91,7 +91,11 @@
  * J<TAB>kept|duplicate|contained per record.  unitigs follows the unbranched paths of that graph (debwt_fm_unitigs) and
  * writes their sequences as FASTA, ">unitig_N reads=T len=BASES circular=0|1 first=J", in unitig order; a circular unitig is
  * cut where it closes.  Both need OUT, OUT.#, OUT.$ and OUT.sa only (the text is restored on the GPU), take no file
- * argument and write one summary line to stderr.
+ * argument and write one summary line to stderr.  With --both-strands every read takes part as it is (+) and
+ * reverse-complemented (-), from the same index (debwt_fm_string_graph_both, debwt_fm_unitigs_both): S lines and --states
+ * stay per read, the links are "L a +|- b +|- <L>M", and of an edge u -> v and its mirror v' -> u' (the same overlap seen
+ * from the other strand) the one whose pair of oriented numbers (2 * read + strand) is lower is written; unitigs writes
+ * every read once, in one orientation, and first=J+ or first=J- names the first read and its strand.
  *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
@@ -122,8 +126,8 @@ static void usage(void) {
             "       deBWT-query extract -i OUT [--device D] --all | REGIONS.txt\n"
             "       deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq\n"
             "       deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
-            "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--states FILE]\n"
-            "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--states FILE]\n"
+            "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]\n"
+            "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
@@ -148,7 +152,9 @@ static void usage(void) {
             "name<TAB>status<TAB>fixes<TAB>weak_before<TAB>weak_after, stderr one summary line;\n"
             "graph writes GFA 1: S lines for the records that are neither duplicates nor contained, L lines a + b + <L>M for the\n"
             "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
-            "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained\n");
+            "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained;\n"
+            "--both-strands takes every read on both strands (L a +|- b +|- <L>M, an edge and its mirror written once;\n"
+            "first=J+|- in the FASTA headers)\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -974,16 +980,22 @@ done:
 
 /* ---- graph / unitigs --------------------------------------------------------------------------------------------------- */
 
-static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_edges, const char *states, int want_unitigs) {
+/* the mirror of oriented node v of the both-strand graph: v ^ 1, or v itself for the one node of a self-rc read */
+static uint32_t mirror_node(const uint8_t *state, uint32_t v) {
+    return state[v & ~1u] == 0 && state[v | 1u] == 1 ? v : v ^ 1u;
+}
+
+static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_edges, const char *states, int want_unitigs,
+                     int both) {
     debwt_fm *fm = NULL;
     if (open_index(out, device, &fm)) return 1;
     int ret = 1, rc = 0;
     debwt_fm_info fi;
     debwt_fm_info_get(fm, &fi);
-    const uint64_t nrec = fi.nrec;
-    uint64_t *starts = malloc((nrec + 1) * 8), *eoff = malloc((nrec + 1) * 8), *uoff = malloc((nrec + 1) * 8), *boff = NULL;
-    uint8_t *state = malloc(nrec ? nrec : 1), *circ = malloc(nrec ? nrec : 1);
-    uint32_t *mem = malloc((nrec ? nrec : 1) * 4);
+    const uint64_t nrec = fi.nrec, nn = both ? 2 * nrec : nrec;       /* nodes: records, or 2r + o with --both-strands */
+    uint64_t *starts = malloc((nrec + 1) * 8), *eoff = malloc((nn + 1) * 8), *uoff = malloc((nn + 1) * 8), *boff = NULL;
+    uint8_t *state = malloc(nn ? nn : 1), *circ = malloc(nn ? nn : 1);
+    uint32_t *mem = malloc((nn ? nn : 1) * 4);
     debwt_fm_edge *edges = NULL;
     debwt_fm_extract_job *jobs = NULL;
     char *bases = NULL;
@@ -993,43 +1005,61 @@ static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     starts[nrec] = fi.n;                                  /* record r holds starts[r + 1] - 1 - starts[r] bases */
     const uint32_t flags = all_edges ? DEBWT_FM_GRAPH_ALL_EDGES : 0u;
-    uint64_t cap = 4 * nrec + 16;                         /* first estimate; the exact count on DEBWT_ERANGE */
+    uint64_t cap = 4 * nn + 16;                           /* first estimate; the exact count on DEBWT_ERANGE */
     for (;;) {
         free(edges);
         edges = malloc(cap * sizeof *edges);
         if (!edges) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = debwt_fm_string_graph(fm, min_overlap, flags, state, eoff, edges, cap);
-        if (rc == DEBWT_ERANGE && eoff[nrec] > cap) { cap = eoff[nrec]; continue; }
+        rc = both ? debwt_fm_string_graph_both(fm, min_overlap, flags, state, eoff, edges, cap)
+                  : debwt_fm_string_graph(fm, min_overlap, flags, state, eoff, edges, cap);
+        if (rc == DEBWT_ERANGE && eoff[nn] > cap) { cap = eoff[nn]; continue; }
         break;
     }
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     if (states) {
         if (!(sf = fopen(states, "w"))) { fprintf(stderr, "cannot write %s\n", states); goto done; }
-        for (uint64_t i = 0; i < nrec; i++)
-            fprintf(sf, "%llu\t%s\n", (unsigned long long)i, state[i] == 0 ? "kept" : state[i] == 1 ? "duplicate" : "contained");
+        for (uint64_t i = 0; i < nrec; i++) {
+            const uint8_t x = state[both ? 2 * i : i];        /* per read: the state of its first node */
+            fprintf(sf, "%llu\t%s\n", (unsigned long long)i, x == 0 ? "kept" : x == 1 ? "duplicate" : "contained");
+        }
         if (fclose(sf)) { sf = NULL; fprintf(stderr, "cannot write %s\n", states); goto done; }
         sf = NULL;
     }
     debwt_fm_graph_stats st;
     debwt_fm_graph_stats_get(fm, &st);
+    if (both) {
+        debwt_fm_graph_both_stats bs;
+        debwt_fm_graph_both_stats_get(fm, &bs);
+        st.kept = bs.kept; st.duplicates = bs.duplicates; st.contained = bs.contained;
+        st.edges = bs.edges; st.reducible = bs.reducible; st.ms_wall = bs.ms_wall;
+    }
+    uint64_t written = eoff[nn];
     if (!want_unitigs) {
         printf("H\tVN:Z:1.0\n");
         for (uint64_t i = 0; i < nrec; i++)
-            if (state[i] == 0) printf("S\t%llu\t*\tLN:i:%llu\n", (unsigned long long)i, (unsigned long long)(starts[i + 1] - 1 - starts[i]));
-        for (uint64_t i = 0; i < nrec; i++)
-            for (uint64_t e = eoff[i]; e < eoff[i + 1]; e++)
-                printf("L\t%llu\t+\t%u\t+\t%uM\n", (unsigned long long)i, edges[e].record, edges[e].length);
+            if (state[both ? 2 * i : i] == 0)
+                printf("S\t%llu\t*\tLN:i:%llu\n", (unsigned long long)i, (unsigned long long)(starts[i + 1] - 1 - starts[i]));
+        for (uint64_t i = 0; i < nn; i++)
+            for (uint64_t e = eoff[i]; e < eoff[i + 1]; e++) {
+                if (!both) { printf("L\t%llu\t+\t%u\t+\t%uM\n", (unsigned long long)i, edges[e].record, edges[e].length); continue; }
+                /* u -> v and its mirror v' -> u' are one GFA link: the lower of the two pairs is written */
+                const uint32_t u = (uint32_t)i, v = edges[e].record, mv = mirror_node(state, v), mu = mirror_node(state, u);
+                if (u > mv || (u == mv && v > mu)) { written--; continue; }
+                printf("L\t%u\t%c\t%u\t%c\t%uM\n", u >> 1, u & 1 ? '-' : '+', v >> 1, v & 1 ? '-' : '+', edges[e].length);
+            }
         fprintf(stderr, "graph: %llu records, %llu kept, %llu duplicates, %llu contained; %llu edges, %llu reducible, %llu written, %.1f ms\n",
                 (unsigned long long)nrec, (unsigned long long)st.kept, (unsigned long long)st.duplicates,
                 (unsigned long long)st.contained, (unsigned long long)st.edges, (unsigned long long)st.reducible,
-                (unsigned long long)eoff[nrec], st.ms_wall);
+                (unsigned long long)written, st.ms_wall);
         ret = fflush(stdout) ? 1 : 0;
         goto done;
     }
     uint64_t nu = 0;
-    rc = debwt_fm_unitigs(state, eoff, edges, nrec, uoff, mem, circ, &nu);
+    rc = both ? debwt_fm_unitigs_both(state, eoff, edges, nn, uoff, mem, circ, &nu)
+              : debwt_fm_unitigs(state, eoff, edges, nrec, uoff, mem, circ, &nu);
     if (rc) { fprintf(stderr, "unitigs: the graph is inconsistent\n"); goto done; }
-    /* every member but the last gives its first |S| - L_next bases; the last of a circular unitig is cut as well */
+    /* every member but the last gives its first |S| - L_next bases; the last of a circular unitig is cut as well.  With
+     * --both-strands a member 2r + 1 gives those of rc S_r: the last |S| - L_next bases of S_r, reverse-complemented below */
     const uint64_t nm = uoff[nu];
     jobs = malloc((nm ? nm : 1) * sizeof *jobs);
     boff = malloc((nm + 1) * 8);
@@ -1037,27 +1067,42 @@ static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_
     uint64_t total = 0, longest = 0;
     for (uint64_t u = 0; u < nu; u++)
         for (uint64_t x = uoff[u]; x < uoff[u + 1]; x++) {
-            const uint32_t v = mem[x];
-            uint64_t len = starts[v + 1] - 1 - starts[v];
-            if (x + 1 < uoff[u + 1] || circ[u]) len -= edges[eoff[v]].length;      /* a link's source has one out-edge */
-            jobs[x].record = v; jobs[x].reserved = 0; jobs[x].offset = 0; jobs[x].length = len;
+            const uint32_t v = mem[x], r = both ? v >> 1 : v;
+            uint64_t len = starts[r + 1] - 1 - starts[r], cut = 0;
+            if (x + 1 < uoff[u + 1] || circ[u]) cut = edges[eoff[v]].length;       /* a link's source has one out-edge */
+            len -= cut;
+            jobs[x].record = r; jobs[x].reserved = 0; jobs[x].offset = both && (v & 1) ? cut : 0; jobs[x].length = len;
             total += len;
         }
     bases = malloc(total ? total : 1);
     if (!bases) { fprintf(stderr, "out of memory\n"); goto done; }
     rc = debwt_fm_extract(fm, jobs, nm, boff, bases, total);
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    for (uint64_t x = 0; both && x < nm; x++) {
+        if (!(mem[x] & 1)) continue;
+        char *lo = bases + boff[x], *hi = bases + boff[x + 1];
+        while (lo < hi) {                                     /* in place; the middle base of an odd length meets itself */
+            const char a = *lo, b = *--hi;
+            *lo++ = b == 'A' ? 'T' : b == 'C' ? 'G' : b == 'G' ? 'C' : 'A';
+            if (lo <= hi) *hi = a == 'A' ? 'T' : a == 'C' ? 'G' : a == 'G' ? 'C' : 'A';
+        }
+    }
     for (uint64_t u = 0; u < nu; u++) {
         const uint64_t a = boff[uoff[u]], b = boff[uoff[u + 1]];
         if (b - a > longest) longest = b - a;
-        printf(">unitig_%llu reads=%llu len=%llu circular=%u first=%u\n", (unsigned long long)u,
-               (unsigned long long)(uoff[u + 1] - uoff[u]), (unsigned long long)(b - a), circ[u], mem[uoff[u]]);
+        if (both)
+            printf(">unitig_%llu reads=%llu len=%llu circular=%u first=%u%c\n", (unsigned long long)u,
+                   (unsigned long long)(uoff[u + 1] - uoff[u]), (unsigned long long)(b - a), circ[u], mem[uoff[u]] >> 1,
+                   mem[uoff[u]] & 1 ? '-' : '+');
+        else
+            printf(">unitig_%llu reads=%llu len=%llu circular=%u first=%u\n", (unsigned long long)u,
+                   (unsigned long long)(uoff[u + 1] - uoff[u]), (unsigned long long)(b - a), circ[u], mem[uoff[u]]);
         fwrite(bases + a, 1, b - a, stdout);
         putchar('\n');
     }
     fprintf(stderr, "unitigs: %llu records, %llu kept; %llu edges, %llu irreducible; %llu unitigs, %llu bases, the longest %llu\n",
             (unsigned long long)nrec, (unsigned long long)st.kept, (unsigned long long)st.edges,
-            (unsigned long long)eoff[nrec], (unsigned long long)nu, (unsigned long long)total, (unsigned long long)longest);
+            (unsigned long long)eoff[nn], (unsigned long long)nu, (unsigned long long)total, (unsigned long long)longest);
     ret = fflush(stdout) ? 1 : 0;
 done:
     if (sf) fclose(sf);
@@ -1090,7 +1135,7 @@ int main(int argc, char **argv) {
     debwt_fm_correct_opts ko;
     debwt_fm_correct_defaults(&ko);
     const char *report = NULL, *states = NULL;
-    int k_given = 0, all_edges = 0;
+    int k_given = 0, all_edges = 0, graph_both = 0;
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
         if (a[0] != '-' || !a[1]) {
@@ -1104,6 +1149,7 @@ int main(int argc, char **argv) {
         if (mode == 5 && !strcmp(a, "--no-self")) { no_self = 1; continue; }
         if (mode == 6 && !strcmp(a, "--all")) { all = 1; continue; }
         if (mode == 9 && !strcmp(a, "--all-edges")) { all_edges = 1; continue; }
+        if ((mode == 9 || mode == 10) && !strcmp(a, "--both-strands")) { graph_both = 1; continue; }
         if (mode == 8 && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
         if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mode == 4 && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
@@ -1194,7 +1240,7 @@ int main(int argc, char **argv) {
     }
     if (mode == 9 || mode == 10) {
         if (!out || file) { usage(); return 1; }
-        return cmd_graph(out, (int)device, (uint32_t)min_overlap, all_edges, states, mode == 10);
+        return cmd_graph(out, (int)device, (uint32_t)min_overlap, all_edges, states, mode == 10, graph_both);
     }
     if (!out || !file) { usage(); return 1; }
     if (mode == 4) {

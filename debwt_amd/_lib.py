@@ -174,6 +174,19 @@ class DebwtFmGraphStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmGraphBothStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("records", "kept", "duplicates", "contained", "hits", "edges", "reducible",
+                                                 "lookups", "launches", "scratch_bytes", "edge_bytes", "selfrc", "seeds",
+                                                 "seed_rows", "tail_hits")] +
+                [("edges_kind", ctypes.c_uint64 * 4)] +
+                [(n, ctypes.c_float) for n in ("ms_walk", "ms_build", "ms_reduce", "ms_wall", "ms_tail", "ms_merge")])
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_}
+        d["edges_kind"] = list(self.edges_kind)
+        return d
+
+
 class DebwtFmJob(ctypes.Structure):
     _fields_ = [("pattern", ctypes.c_uint64), ("diag", ctypes.c_int64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32)]
 
@@ -318,6 +331,7 @@ SYMBOLS = [
     "debwt_fm_kmer_counts", "debwt_fm_kmer_stats_get", "debwt_fm_weak_trials", "debwt_fm_correct_defaults",
     "debwt_fm_correct", "debwt_fm_correct_stats_get",
     "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
+    "debwt_fm_string_graph_both", "debwt_fm_unitigs_both", "debwt_fm_graph_both_stats_get",
 ]
 
 
@@ -624,6 +638,12 @@ def lib():
     L.debwt_fm_unitigs.argtypes = [u8p, u64p, edgep, ctypes.c_uint64, u64p, u32p, u8p, u64p]
     L.debwt_fm_graph_stats_get.restype = ctypes.c_int
     L.debwt_fm_graph_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmGraphStats)]
+    L.debwt_fm_string_graph_both.restype = ctypes.c_int
+    L.debwt_fm_string_graph_both.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u64p, edgep, ctypes.c_uint64]
+    L.debwt_fm_unitigs_both.restype = ctypes.c_int
+    L.debwt_fm_unitigs_both.argtypes = [u8p, u64p, edgep, ctypes.c_uint64, u64p, u32p, u8p, u64p]
+    L.debwt_fm_graph_both_stats_get.restype = ctypes.c_int
+    L.debwt_fm_graph_both_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmGraphBothStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

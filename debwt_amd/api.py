@@ -559,6 +559,35 @@ class FMIndex:
         self._chk(self._L.debwt_fm_graph_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def string_graph_both(self, min_overlap=20, reduce=True):
+        """The string graph over both strands (debwt_fm_string_graph_both): the graph string_graph() gives on the doubled
+        collection (S_0, rc S_0, S_1, ...), from this index alone.  Node 2r + o is read r as it is (o = 0) or
+        reverse-complemented (o = 1).  Returns a BiGraphResult."""
+        flags = 0 if reduce else GRAPH_ALL_EDGES
+        nn = 2 * self.nrec
+        state = np.zeros(max(nn, 1), dtype=np.uint8)
+        offs = np.zeros(nn + 1, dtype=np.uint64)
+        cap = 4 * nn + 16                                     # first estimate; grown to the exact count on DEBWT_ERANGE
+        while True:
+            edges = np.zeros(cap, dtype=_EDGE_DTYPE)
+            rc = self._L.debwt_fm_string_graph_both(self._h, int(min_overlap), flags,
+                                                    state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _p64(offs),
+                                                    edges.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)), cap)
+            if rc == -5 and int(offs[nn]) > cap:
+                cap = int(offs[nn])
+                continue
+            self._chk(rc)
+            break
+        return BiGraphResult(self, state[:nn], offs, edges[:int(offs[nn])].copy(), bool(reduce))
+
+    def graph_both_stats(self):
+        """What the last string_graph_both() did (debwt_fm_graph_both_stats_get): the fields of graph_stats() with the
+        states counted in reads, self-rc reads, tail seeds, seed rows located, tail hits verified, the edges of E per kind
+        (++, +-, -+, --) and ms of the tail search and of the merge beside the other phases."""
+        st = _lib.DebwtFmGraphBothStats()
+        self._chk(self._L.debwt_fm_graph_both_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def attach_text(self, source=None, words=None, sep=None):
         """Give the index its text (debwt_fm_attach_text; n / 4 bytes of HBM), which extend() and map() read.  source: the
         DeBWT context the index was made from (device-to-device copy), or None with the host text words / sep as
@@ -1258,6 +1287,75 @@ def unitigs(state, offsets, edges):
         raise DebwtError(rc)
     k = int(nu.value)
     return uoff[:k + 1].copy(), mem[:int(uoff[k])].copy(), circ[:k].copy()
+
+
+def unitigs_both(state, offsets, edges):
+    """The oriented unitigs of a graph over both strands on the host (debwt_fm_unitigs_both, no GPU): nodes 2r + o; a link
+    is one of unitigs() that does not lead to its source's mirror (v ^ 1) and touches no self-rc read (state[2r] == 0,
+    state[2r + 1] == 1).  Of a unitig and its mirror the one with the lower first member is returned, so every kept read
+    is in exactly one, in one orientation.  Returns (offsets, members, circular) as unitigs() does."""
+    state = np.ascontiguousarray(state, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    e = np.ascontiguousarray(np.asarray(edges, dtype=_EDGE_DTYPE))
+    nn = len(state)
+    if len(offs) != nn + 1 or int(offs.max()) > len(e):
+        raise ValueError("offsets fit neither the nodes nor the edges")
+    uoff = np.zeros(nn + 1, dtype=np.uint64)
+    mem = np.zeros(max(nn, 1), dtype=np.uint32)
+    circ = np.zeros(max(nn, 1), dtype=np.uint8)
+    nu = ctypes.c_uint64(0)
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    rc = _lib.lib().debwt_fm_unitigs_both(state.ctypes.data_as(u8p) if nn else None, _p64(offs),
+                                          e.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)) if len(e) else None, nn,
+                                          _p64(uoff), mem.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                          circ.ctypes.data_as(u8p), ctypes.byref(nu))
+    if rc:
+        raise DebwtError(rc)
+    k = int(nu.value)
+    return uoff[:k + 1].copy(), mem[:int(uoff[k])].copy(), circ[:k].copy()
+
+
+_RC = bytes.maketrans(b"ACGT", b"TGCA")
+
+
+class BiGraphResult:
+    """String graph over both strands of FMIndex.string_graph_both.  Node 2r + o is read r as it is (o = 0) or its reverse
+    complement (o = 1).  state: per node NODE_KEPT, NODE_DUPLICATE or NODE_CONTAINED (the second node of a self-rc read is
+    a duplicate of the first); node v's out-edges are edges[offsets[v] .. offsets[v + 1]), (record, length) with record
+    the target node, ordered by (length descending, record).  reduced: the irreducible graph, which unitigs() needs."""
+
+    def __init__(self, index, state, offsets, edges, reduced):
+        self.index, self.state, self.offsets, self.edges, self.reduced = index, state, offsets, edges, reduced
+
+    def __len__(self):
+        return len(self.state)
+
+    def out(self, v):
+        """structured array (record, length) of node v's out-edges"""
+        return self.edges[int(self.offsets[v]):int(self.offsets[v + 1])]
+
+    def unitigs(self):
+        """(offsets, members, circular) of the oriented unitigs, see unitigs_both()"""
+        return unitigs_both(self.state, self.offsets, self.edges)
+
+    def sequences(self, index=None):
+        """The unitigs' sequences as a list of str, through FMIndex.extract of `index` (default: the graph's own) and a
+        reverse complement on the host for the members of orientation 1: every member but the last gives the first
+        |S| - L_next bases of its oriented string, and the last of a circular unitig is cut by its overlap with the first."""
+        index = self.index if index is None else index
+        uoff, mem, circ = self.unitigs()
+        starts = np.append(index.record_starts(), np.uint64(index.n))
+        jobs = []
+        for u in range(len(circ)):
+            m = [int(x) for x in mem[int(uoff[u]):int(uoff[u + 1])]]
+            for x, v in enumerate(m):
+                r = v >> 1
+                full = int(starts[r + 1]) - 1 - int(starts[r])
+                cut = int(self.out(v)["length"][0]) if x + 1 < len(m) or circ[u] else 0   # a link's source has one out-edge
+                jobs.append((r, cut, full - cut) if v & 1 else (r, 0, full - cut))
+        parts = index.extract(jobs)
+        parts = [p.translate(_RC)[::-1] if int(v) & 1 else p for p, v in zip(parts, mem)]
+        return [b"".join(parts[int(uoff[u]):int(uoff[u + 1])]).decode() for u in range(len(circ))]
 
 
 class MultiDeBWT:

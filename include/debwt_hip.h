@@ -1130,8 +1130,8 @@ int debwt_fm_correct_stats_get(const debwt_fm *fm, debwt_fm_correct_stats *out);
  *    w != u.  A unitig is a maximal chain of links; a node with no incoming link starts one; a component in which every
  *    node has an incoming link is a cycle, which starts at its lowest record and is flagged circular.  Every kept node is
  *    in exactly one unitig, and unitigs are numbered by ascending first record.
- * Strand 0 only: a read set sampled from both strands gives a strand-complete graph only if the collection holds the
- * reverse complements (tail-to-tail overlaps are a limit of debwt_fm_overlaps).
+ * Strand 0 only; for a read set sampled from both strands debwt_fm_string_graph_both (below) gives the strand-complete
+ * graph from the same index.
  *
  * debwt_fm_string_graph writes state (nrec) and edge_offsets (nrec + 1) first, then the edges of the irreducible graph,
  * or of E with DEBWT_FM_GRAPH_ALL_EDGES; DEBWT_ERANGE when capacity < edge_offsets[nrec] (the protocol of
@@ -1170,6 +1170,48 @@ typedef struct {
     float ms_walk, ms_build, ms_reduce, ms_wall;
 } debwt_fm_graph_stats;
 int debwt_fm_graph_stats_get(const debwt_fm *fm, debwt_fm_graph_stats *out);
+
+/* ---- string graph over both strands (fm_bigraph_kernels.h) ------------------------------------------------------------
+ * Let D = (S_0, rc S_0, S_1, rc S_1, ...) be the doubled collection: record 2r + o of D is the oriented node (r, o), o = 1
+ * for the reverse complement.  The strand-complete graph of S is definitions 1-3 above applied to D, with node ids
+ * 2r + o; D is never built, and the index is the one of S.  It follows that state[2r] is 1 iff some q < r has S_q == S_r
+ * or S_q == rc S_r, else 2 iff S_r or rc S_r lies inside a strictly longer record, else 0; state[2r + 1] == state[2r]
+ * unless S_r == rc S_r (a self-rc read), where state[2r + 1] == 1: node (r, -) of a kept self-rc read does not exist and
+ * every relation that would name it names (r, +).  E and the irreducible graph are closed under u -> v  |->  v^1 -> u^1.
+ * 2r -> 2r + 1 and 2r + 1 -> 2r (a read that overlaps its own reverse complement) are edges; only v -> v is dropped.
+ * (i+ -> j+) and (i- -> j+) are the overlaps of debwt_fm_overlaps on strands 0 and 1; (i+ -> j-, L), where the last L
+ * bases of S_i are the reverse complement of the last L of S_j, is found by locating rc(last min_overlap bases of S_i)
+ * and comparing the rest in the attached text; (i- -> j-) is the mirror of (j+ -> i+).
+ *
+ * debwt_fm_string_graph_both writes state (2 nrec), edge_offsets (2 nrec + 1) and edges (.record = 2r + o) byte for byte
+ * as debwt_fm_string_graph does on an index of D, with its capacity protocol (DEBWT_ERANGE), its restore of a missing
+ * text and its DEBWT_ENOMEM.  DEBWT_EINVAL for min_overlap 0, flags other than DEBWT_FM_GRAPH_ALL_EDGES and 2^31 records
+ * or more.  The walk and the located seed rows go in the batches of debwt_fm_overlaps (DEBWT_FM_OVERLAP_SLOTS,
+ * DEBWT_FM_OVERLAP_HITS; the result depends on neither).  The work of the tail-to-tail search is the number of
+ * occurrences of the min_overlap-long seeds, not the number of overlaps. */
+int debwt_fm_string_graph_both(debwt_fm *fm, uint32_t min_overlap, uint32_t flags,
+                               uint8_t *state /* 2 * nrec */, uint64_t *edge_offsets /* 2 * nrec + 1 */,
+                               debwt_fm_edge *edges, uint64_t capacity);
+/* 4b. Oriented unitigs on the host (no GPU), in linear time, over the irreducible graph of debwt_fm_string_graph_both
+ * (nnodes = 2 nrec, even).  Read r is self-rc iff state[2r] == 0 and state[2r + 1] == 1.  u -> w is a link iff definition
+ * 4 makes it one, w != u^1, and neither u nor w belongs to a self-rc read.  The unitigs of definition 4 under this rule
+ * come in mirror pairs U, U' (U reversed, every member ^ 1; a mirror cycle rotated to its lowest member; the node of a
+ * self-rc read is its own mirror).  Of each pair the one with the lower first member is reported, numbered by ascending
+ * first member: every kept read is in exactly one reported unitig, in one orientation.  Arguments and errors as
+ * debwt_fm_unitigs; an odd nnodes is DEBWT_EINVAL. */
+int debwt_fm_unitigs_both(const uint8_t *state, const uint64_t *edge_offsets, const debwt_fm_edge *edges,
+                          uint64_t nnodes, uint64_t *unitig_offsets /* nnodes + 1 */, uint32_t *members /* nnodes */,
+                          uint8_t *circular /* nnodes */, uint64_t *nunitigs);
+/* what the last debwt_fm_string_graph_both did.  The fields of debwt_fm_graph_stats, the three states counted in reads
+ * (state[2r]); selfrc: kept self-rc reads; seeds: tail seeds searched, seed_rows: their occurrences located, tail_hits:
+ * occurrences that verified; edges_kind: the edges of E that are ++, +-, -+, -- (source, target); ms_tail: seed, locate
+ * and verify; ms_merge: the mirrors and the ordering of the lists; ms_walk, ms_build, ms_reduce, ms_wall as there. */
+typedef struct {
+    uint64_t records, kept, duplicates, contained, hits, edges, reducible, lookups, launches, scratch_bytes, edge_bytes;
+    uint64_t selfrc, seeds, seed_rows, tail_hits, edges_kind[4];
+    float ms_walk, ms_build, ms_reduce, ms_wall, ms_tail, ms_merge;
+} debwt_fm_graph_both_stats;
+int debwt_fm_graph_both_stats_get(const debwt_fm *fm, debwt_fm_graph_both_stats *out);
 
 void debwt_fm_destroy(debwt_fm *fm);
 
