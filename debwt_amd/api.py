@@ -537,20 +537,24 @@ class FMIndex:
         is equal) or contained (a substring of a longer record); among the kept records the longest suffix-prefix overlap
         of at least min_overlap per ordered pair, strand 0; with reduce the transitive edges are dropped.  An index
         without a text restores it first.  Returns a GraphResult."""
+        return GraphResult(self, *self._graph_call(self._L.debwt_fm_string_graph, self.nrec, min_overlap, reduce))
+
+    def _graph_call(self, fn, nn, min_overlap, reduce):
+        """(state, offsets, edges, reduced) of a string-graph call over nn nodes"""
         flags = 0 if reduce else GRAPH_ALL_EDGES
-        state = np.zeros(max(self.nrec, 1), dtype=np.uint8)
-        offs = np.zeros(self.nrec + 1, dtype=np.uint64)
-        cap = 4 * self.nrec + 16                              # first estimate; grown to the exact count on DEBWT_ERANGE
+        state = np.zeros(max(nn, 1), dtype=np.uint8)
+        offs = np.zeros(nn + 1, dtype=np.uint64)
+        cap = 4 * nn + 16                                     # first estimate; grown to the exact count on DEBWT_ERANGE
         while True:
             edges = np.zeros(cap, dtype=_EDGE_DTYPE)
-            rc = self._L.debwt_fm_string_graph(self._h, int(min_overlap), flags, state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
-                                               _p64(offs), edges.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)), cap)
-            if rc == -5 and int(offs[self.nrec]) > cap:
-                cap = int(offs[self.nrec])
+            rc = fn(self._h, int(min_overlap), flags, state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _p64(offs),
+                    edges.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)), cap)
+            if rc == -5 and int(offs[nn]) > cap:
+                cap = int(offs[nn])
                 continue
             self._chk(rc)
             break
-        return GraphResult(self, state[:self.nrec], offs, edges[:int(offs[self.nrec])].copy(), bool(reduce))
+        return state[:nn], offs, edges[:int(offs[nn])].copy(), bool(reduce)
 
     def graph_stats(self):
         """What the last string_graph() or edges_reduce() did (debwt_fm_graph_stats_get): records per state, hits walked,
@@ -563,22 +567,7 @@ class FMIndex:
         """The string graph over both strands (debwt_fm_string_graph_both): the graph string_graph() gives on the doubled
         collection (S_0, rc S_0, S_1, ...), from this index alone.  Node 2r + o is read r as it is (o = 0) or
         reverse-complemented (o = 1).  Returns a BiGraphResult."""
-        flags = 0 if reduce else GRAPH_ALL_EDGES
-        nn = 2 * self.nrec
-        state = np.zeros(max(nn, 1), dtype=np.uint8)
-        offs = np.zeros(nn + 1, dtype=np.uint64)
-        cap = 4 * nn + 16                                     # first estimate; grown to the exact count on DEBWT_ERANGE
-        while True:
-            edges = np.zeros(cap, dtype=_EDGE_DTYPE)
-            rc = self._L.debwt_fm_string_graph_both(self._h, int(min_overlap), flags,
-                                                    state.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _p64(offs),
-                                                    edges.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)), cap)
-            if rc == -5 and int(offs[nn]) > cap:
-                cap = int(offs[nn])
-                continue
-            self._chk(rc)
-            break
-        return BiGraphResult(self, state[:nn], offs, edges[:int(offs[nn])].copy(), bool(reduce))
+        return BiGraphResult(self, *self._graph_call(self._L.debwt_fm_string_graph_both, 2 * self.nrec, min_overlap, reduce))
 
     def graph_both_stats(self):
         """What the last string_graph_both() did (debwt_fm_graph_both_stats_get): the fields of graph_stats() with the
@@ -1206,11 +1195,8 @@ class OverlapResult:
         return ((self.all_hits["flags"] >> 8) & 0xFF).astype(np.uint8)
 
 
-class GraphResult:
-    """String graph of FMIndex.string_graph.  state: per record NODE_KEPT, NODE_DUPLICATE or NODE_CONTAINED; record i's
-    out-edges are edges[offsets[i] .. offsets[i + 1]), a structured array of (record, length) ordered by (length descending,
-    record): record i's last `length` bases are the first `length` of `record`.  reduced: the edges are those of the
-    irreducible graph, which unitigs() needs."""
+class _GraphArrays:
+    """what GraphResult and BiGraphResult share: the three arrays of a string graph and the out-list of a node"""
 
     def __init__(self, index, state, offsets, edges, reduced):
         self.index, self.state, self.offsets, self.edges, self.reduced = index, state, offsets, edges, reduced
@@ -1219,8 +1205,15 @@ class GraphResult:
         return len(self.state)
 
     def out(self, i):
-        """structured array (record, length) of record i's out-edges"""
+        """structured array (record, length) of the out-edges of record i (GraphResult) or node i (BiGraphResult)"""
         return self.edges[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+
+class GraphResult(_GraphArrays):
+    """String graph of FMIndex.string_graph.  state: per record NODE_KEPT, NODE_DUPLICATE or NODE_CONTAINED; record i's
+    out-edges are edges[offsets[i] .. offsets[i + 1]), a structured array of (record, length) ordered by (length descending,
+    record): record i's last `length` bases are the first `length` of `record`.  reduced: the edges are those of the
+    irreducible graph, which unitigs() needs."""
 
     def unitigs(self):
         """(offsets, members, circular) of the unbranched paths, see unitigs()"""
@@ -1268,6 +1261,11 @@ def unitigs(state, offsets, edges):
     link iff w is u's only successor, u is w's only predecessor and w != u; a unitig is a maximal chain of links, a cycle
     of links starts at its lowest node.  Returns (offsets, members, circular): unitig t's nodes are members[offsets[t] ..
     offsets[t + 1]) in path order, unitigs by ascending first node, circular one np.uint8 each."""
+    return _unitig_call(_lib.lib().debwt_fm_unitigs, state, offsets, edges)
+
+
+def _unitig_call(fn, state, offsets, edges):
+    """(offsets, members, circular) of debwt_fm_unitigs or debwt_fm_unitigs_both"""
     state = np.ascontiguousarray(state, dtype=np.uint8)
     offs = np.ascontiguousarray(offsets, dtype=np.uint64)
     e = np.ascontiguousarray(np.asarray(edges, dtype=_EDGE_DTYPE))
@@ -1279,10 +1277,8 @@ def unitigs(state, offsets, edges):
     circ = np.zeros(max(nn, 1), dtype=np.uint8)
     nu = ctypes.c_uint64(0)
     u8p = ctypes.POINTER(ctypes.c_uint8)
-    rc = _lib.lib().debwt_fm_unitigs(state.ctypes.data_as(u8p) if nn else None, _p64(offs),
-                                     e.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)) if len(e) else None, nn, _p64(uoff),
-                                     mem.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), circ.ctypes.data_as(u8p),
-                                     ctypes.byref(nu))
+    rc = fn(state.ctypes.data_as(u8p) if nn else None, _p64(offs), e.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)) if len(e) else None,
+            nn, _p64(uoff), mem.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), circ.ctypes.data_as(u8p), ctypes.byref(nu))
     if rc:
         raise DebwtError(rc)
     k = int(nu.value)
@@ -1294,45 +1290,17 @@ def unitigs_both(state, offsets, edges):
     is one of unitigs() that does not lead to its source's mirror (v ^ 1) and touches no self-rc read (state[2r] == 0,
     state[2r + 1] == 1).  Of a unitig and its mirror the one with the lower first member is returned, so every kept read
     is in exactly one, in one orientation.  Returns (offsets, members, circular) as unitigs() does."""
-    state = np.ascontiguousarray(state, dtype=np.uint8)
-    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-    e = np.ascontiguousarray(np.asarray(edges, dtype=_EDGE_DTYPE))
-    nn = len(state)
-    if len(offs) != nn + 1 or int(offs.max()) > len(e):
-        raise ValueError("offsets fit neither the nodes nor the edges")
-    uoff = np.zeros(nn + 1, dtype=np.uint64)
-    mem = np.zeros(max(nn, 1), dtype=np.uint32)
-    circ = np.zeros(max(nn, 1), dtype=np.uint8)
-    nu = ctypes.c_uint64(0)
-    u8p = ctypes.POINTER(ctypes.c_uint8)
-    rc = _lib.lib().debwt_fm_unitigs_both(state.ctypes.data_as(u8p) if nn else None, _p64(offs),
-                                          e.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)) if len(e) else None, nn,
-                                          _p64(uoff), mem.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                          circ.ctypes.data_as(u8p), ctypes.byref(nu))
-    if rc:
-        raise DebwtError(rc)
-    k = int(nu.value)
-    return uoff[:k + 1].copy(), mem[:int(uoff[k])].copy(), circ[:k].copy()
+    return _unitig_call(_lib.lib().debwt_fm_unitigs_both, state, offsets, edges)
 
 
 _RC = bytes.maketrans(b"ACGT", b"TGCA")
 
 
-class BiGraphResult:
+class BiGraphResult(_GraphArrays):
     """String graph over both strands of FMIndex.string_graph_both.  Node 2r + o is read r as it is (o = 0) or its reverse
     complement (o = 1).  state: per node NODE_KEPT, NODE_DUPLICATE or NODE_CONTAINED (the second node of a self-rc read is
     a duplicate of the first); node v's out-edges are edges[offsets[v] .. offsets[v + 1]), (record, length) with record
     the target node, ordered by (length descending, record).  reduced: the irreducible graph, which unitigs() needs."""
-
-    def __init__(self, index, state, offsets, edges, reduced):
-        self.index, self.state, self.offsets, self.edges, self.reduced = index, state, offsets, edges, reduced
-
-    def __len__(self):
-        return len(self.state)
-
-    def out(self, v):
-        """structured array (record, length) of node v's out-edges"""
-        return self.edges[int(self.offsets[v]):int(self.offsets[v + 1])]
 
     def unitigs(self):
         """(offsets, members, circular) of the oriented unitigs, see unitigs_both()"""

@@ -6428,16 +6428,23 @@ extern "C" int debwt_fm_correct_stats_get(const debwt_fm *f, debwt_fm_correct_st
     return DEBWT_OK;
 }
 
-// ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
+// ---- string graph of the indexed records, on one strand or on both (fm_graph_kernels.h, fm_bigraph_kernels.h) --------
+// debwt_fm_string_graph and debwt_fm_string_graph_both share one host path: fm_graph_found, then fm_graph_finish.
 // States come from one backward search per record over the attached text.  The kept records then go through the overlap
-// walk in the batches of debwt_fm_overlaps, unpacked from the text on the device; a batch's hits are expanded at most
-// DEBWT_FM_OVERLAP_HITS at a launch into o_hits and packed to 8 bytes each, the longest hit per (source, target) is
-// flagged, and the flagged ones are appended to E (g_edges, grown by doubling).  Per batch the run, hit and edge counts of
-// its sources reach the host, which lays the lists out; E itself stays in HBM until the reduction has run over it.
+// walk in the batches of debwt_fm_overlaps, unpacked from the text on the device, on one strand or on both.  A batch's hits
+// are expanded at most DEBWT_FM_OVERLAP_HITS at a launch into o_hits and packed to 8 bytes each into the batch's raw list
+// (g_raw), which has one segment per record (its hits) or three (strand-0 hits, located tail seeds, strand-1 hits); the
+// longest entry per (segment, target) is flagged, and the flagged ones are appended to g_edges, grown by doubling.  Per
+// batch the run, hit and edge counts of its records reach the host, which lays the lists out; the edges stay in HBM until
+// the reduction has run over them.
 
 namespace {
 
 static_assert(sizeof(debwt_fm_edge) == sizeof(FmEdge), "the graph kernels write debwt_fm_edge as FmEdge");
+static_assert((int)FM_BG_BADLEN == (int)FM_GR_BADLEN && (int)FM_BG_NCTR == (int)FM_GR_NCTR, "g_ctr and b_ctr are read back alike");
+
+// a builder's statistics struct says which of the two it is; both structs name the fields they share alike
+template <class St> constexpr bool fm_graph_both = std::is_same<St, debwt_fm_graph_both_stats>::value;
 
 struct FmGraphTimer {                                  // a timed stretch of the stream: begin(), launches, end(&ms)
     debwt_fm *f;
@@ -6462,7 +6469,7 @@ struct FmGraphTimer {                                  // a timed stretch of the
 };
 
 // room for nedges edges in g_edges, the first `have` of them kept
-int fm_graph_reserve(debwt_fm *f, u64 have, u64 nedges) {
+int fm_graph_reserve(debwt_fm *f, const char *who, u64 have, u64 nedges) {
     const size_t need = (size_t)std::max<u64>(nedges, 1) * sizeof(FmEdge);
     if (need <= f->g_edges.cap) return DEBWT_OK;
     HIPCHK(f, hipStreamSynchronize(f->stream));
@@ -6473,7 +6480,7 @@ int fm_graph_reserve(debwt_fm *f, u64 have, u64 nedges) {
         want = need;
         if (hipMalloc(&p, want) != hipSuccess) {
             (void)hipGetLastError();
-            f->err = "debwt_fm_string_graph: the edge list does not fit in device memory (" + std::to_string(nedges) +
+            f->err = std::string(who) + ": the edge list does not fit in device memory (" + std::to_string(nedges) +
                      " edges so far, 8 bytes each)";
             return DEBWT_ENOMEM;
         }
@@ -6488,9 +6495,10 @@ int fm_graph_reserve(debwt_fm *f, u64 have, u64 nedges) {
     return DEBWT_OK;
 }
 
-// the keep bytes of definition 3 for the lists in g_eoff / `edges` (device), into g_keep
-int fm_graph_reduce(debwt_fm *f, FmGraphTimer &tm, u64 nnodes, const FmEdge *edges, u64 nedges) {
-    debwt_fm_graph_stats &st = f->g_stats;
+// the keep bytes of definition 3 for the lists in g_eoff / `edges` (device), into g_keep; st counts the launch, the lists
+// searched, the reducible edges and the time
+template <class St>
+int fm_graph_reduce(debwt_fm *f, St &st, FmGraphTimer &tm, u64 nnodes, const FmEdge *edges, u64 nedges) {
     FM_ENSURE(f, f->g_keep, (size_t)nedges);
     FM_ENSURE(f, f->g_ctr, FM_GR_NCTR * 8);
     HIPCHK(f, hipMemsetAsync(f->g_ctr.p, 0, FM_GR_NCTR * 8, f->stream));
@@ -6506,148 +6514,344 @@ int fm_graph_reduce(debwt_fm *f, FmGraphTimer &tm, u64 nnodes, const FmEdge *edg
     return DEBWT_OK;
 }
 
-// states (host and g_state) and E (g_edges, edge_offsets on the host)
-// fm_bigraph_found below holds a copy of this batch loop (both strands, three segments per record): a change to the
-// batching, the compaction or the expansion here belongs there too.
-int fm_graph_edges(debwt_fm *f, FmGraphTimer &tm, u32 min_overlap, uint8_t *state, uint64_t *eoff) {
-    debwt_fm_graph_stats &st = f->g_stats;
-    const u64 nrec = f->nrec, n = f->n;
-    const std::vector<u64> &rs = f->rec_starts;
+// the text and the overlap table in place; coff, the bases before each record, on the host and in g_coff
+int fm_graph_text(debwt_fm *f, const char *who, std::vector<u64> &coff) {
+    const u64 nrec = f->nrec;
     int rc;
     if (!f->has_text && (rc = debwt_fm_restore_text(f))) return rc;
     if ((rc = fm_overlap_table(f))) return rc;
-    std::vector<u64> coff(nrec + 1);                       // bases before each record
-    for (u64 i = 0; i < nrec; i++) coff[i] = rs[i] - i;
-    coff[nrec] = n - nrec;
+    coff.resize(nrec + 1);
+    for (u64 i = 0; i < nrec; i++) coff[i] = f->rec_starts[i] - i;
+    coff[nrec] = f->n - nrec;
     for (u64 i = 0; i < nrec; i++)
-        if ((coff[i + 1] - coff[i]) >> 32) { f->err = "debwt_fm_string_graph: a record of 2^32 bases or more"; return DEBWT_EINVAL; }
+        if ((coff[i + 1] - coff[i]) >> 32) { f->err = std::string(who) + ": a record of 2^32 bases or more"; return DEBWT_EINVAL; }
     FM_ENSURE(f, f->g_coff, (size_t)(nrec + 1) * 8);
-    FM_ENSURE(f, f->g_state, (size_t)nrec);
-    FM_ENSURE(f, f->g_ctr, FM_GR_NCTR * 8);
     HIPCHK(f, hipMemcpyAsync(f->g_coff.p, coff.data(), (nrec + 1) * 8, hipMemcpyHostToDevice, f->stream));
-    HIPCHK(f, hipMemsetAsync(f->g_ctr.p, 0, FM_GR_NCTR * 8, f->stream));
-    tm.begin();
-    k_fm_graph_state<<<grid_for(nrec, 256), 256, 0, f->stream>>>(f->V, f->text.as<u64>(), f->g_coff.as<u64>(),
-                                                                 f->o_table.as<FmOvlRec>(), nrec, f->g_state.as<u8>());
-    HIPCHK(f, hipMemcpyAsync(state, f->g_state.p, nrec, hipMemcpyDeviceToHost, f->stream));
-    if ((rc = tm.end(&st.ms_walk))) return rc;
+    return DEBWT_OK;
+}
+
+// The states and the edges found, for either builder; eoff has NK nrec + 1 entries.
+// One strand: state per record (host and g_state), one segment per record, so eoff is edge_offsets and g_edges holds E.
+// Both strands: state per node (host and b_state), self-rc flags (b_self), three segments per record, so record i's ++, +-
+// and -+ edges stand in [eoff[3i], eoff[3i + 1]), [eoff[3i + 1], eoff[3i + 2]), [eoff[3i + 2], eoff[3i + 3]) of g_edges (A).
+// A batch has NS np items (item g: record p0 + g % np on strand g / np) and NK np segments.  On one strand the three base
+// tables of a batch coincide -- hits in item order, hits in (record, strand) order, raw segments -- and g_hbase is all three.
+template <class St>
+int fm_graph_found(debwt_fm *f, St &st, const char *who, FmGraphTimer &tm, u32 min_overlap, uint8_t *state, uint64_t *eoff) {
+    constexpr bool both = fm_graph_both<St>;
+    constexpr u64 NS = both ? 2 : 1, NK = both ? 3 : 1;        // strands per record, segments per record
+    const u64 nrec = f->nrec;
+    std::vector<u64> coff;
+    int rc = fm_graph_text(f, who, coff);
+    if (rc) return rc;
+    DevBuf &ctr = both ? f->b_ctr : f->g_ctr;
+    DevBuf &d_ihb = both ? f->o_hbase : f->g_hbase, &d_whb = both ? f->b_whb : f->g_hbase, &d_seg = both ? f->b_rawbase : f->g_hbase;
+    FM_ENSURE(f, ctr, FM_GR_NCTR * 8);
+    HIPCHK(f, hipMemsetAsync(ctr.p, 0, FM_GR_NCTR * 8, f->stream));
+    if constexpr (both) {
+        std::vector<u8> selfrc(nrec, 0);
+        FM_ENSURE(f, f->b_state, (size_t)nrec * 2);
+        FM_ENSURE(f, f->b_self, (size_t)nrec);
+        tm.begin();
+        k_fm_bigraph_state<<<grid_for(nrec, 256), 256, 0, f->stream>>>(f->V, f->text.as<u64>(), f->g_coff.as<u64>(), f->o_table.as<FmOvlRec>(),
+                                                                       nrec, f->b_state.as<u8>(), f->b_self.as<u8>());
+        HIPCHK(f, hipMemcpyAsync(state, f->b_state.p, nrec * 2, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(f, hipMemcpyAsync(selfrc.data(), f->b_self.p, nrec, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&st.ms_walk))) return rc;
+        for (u64 i = 0; i < nrec; i++)
+            if (state[2 * i] == 0) st.selfrc += selfrc[i];
+    } else {
+        FM_ENSURE(f, f->g_state, (size_t)nrec);
+        tm.begin();
+        k_fm_graph_state<<<grid_for(nrec, 256), 256, 0, f->stream>>>(f->V, f->text.as<u64>(), f->g_coff.as<u64>(),
+                                                                     f->o_table.as<FmOvlRec>(), nrec, f->g_state.as<u8>());
+        HIPCHK(f, hipMemcpyAsync(state, f->g_state.p, nrec, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&st.ms_walk))) return rc;
+    }
     st.launches++;
     st.records = nrec;
     for (u64 i = 0; i < nrec; i++) {
-        if (state[i] == 0) st.kept++;
-        else if (state[i] == 1) st.duplicates++;
+        if (state[NS * i] == 0) st.kept++;
+        else if (state[NS * i] == 1) st.duplicates++;
         else st.contained++;
     }
     const u64 slots = fm_env_u64("DEBWT_FM_OVERLAP_SLOTS", FM_OVL_SLOTS);
     const u64 limit = std::max<u64>(fm_env_u64("DEBWT_FM_OVERLAP_HITS", FM_OVL_HITS), 1);
-    auto worst = [&](u64 i) {
+    auto worst = [&](u64 i) {                                  // run slots of record i on one strand
         const u64 m = coff[i + 1] - coff[i];
-        return state[i] == 0 && m >= min_overlap ? m - min_overlap + 1 : 0;
+        return state[NS * i] == 0 && m >= min_overlap ? m - min_overlap + 1 : 0;
     };
-    std::vector<u64> slot, rbase, hbase, oseg, nh;
+    std::vector<u64> slot, rbase, ihb, whb, rawbase, tbase, oseg, nh, tc;
     std::vector<u32> nr, deg;
     eoff[0] = 0;
     for (u64 p0 = 0; p0 < nrec;) {
-        u64 p1 = p0 + 1, ws = worst(p0);                  // at least one record, however long
-        while (p1 < nrec && p1 - p0 < FM_BATCH_PATTERNS && coff[p1 + 1] - coff[p0] <= FM_BATCH_CHARS && ws + worst(p1) <= slots)
-            ws += worst(p1++);
-        const u64 np = p1 - p0, bytes = coff[p1] - coff[p0];
-        for (u64 j = p0; j < p1; j++) eoff[j + 1] = eoff[j];
+        u64 p1 = p0 + 1, ws = NS * worst(p0);                  // at least one record, however long
+        while (p1 < nrec && p1 - p0 < FM_BATCH_PATTERNS && coff[p1 + 1] - coff[p0] <= FM_BATCH_CHARS && ws + NS * worst(p1) <= slots)
+            ws += NS * worst(p1++);
+        const u64 np = p1 - p0, nit = NS * np, nseg = NK * np, bytes = coff[p1] - coff[p0];
+        for (u64 k = NK * p0; k < NK * p1; k++) eoff[k + 1] = eoff[k];
         if (!ws) { p0 = p1; continue; }                        // no kept record long enough: no edges
-        slot.resize(np + 1);
+        slot.resize(nit + 1);
         slot[0] = 0;
-        for (u64 j = 0; j < np; j++) slot[j + 1] = slot[j] + worst(p0 + j);
+        for (u64 g = 0; g < nit; g++) slot[g + 1] = slot[g] + worst(p0 + g % np);
         FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
-        FM_ENSURE(f, f->o_slot, (size_t)(np + 1) * 8);
-        FM_ENSURE(f, f->o_nruns, (size_t)np * 4);
-        FM_ENSURE(f, f->o_nhits, (size_t)np * 8);
+        FM_ENSURE(f, f->o_slot, (size_t)(nit + 1) * 8);
+        FM_ENSURE(f, f->o_nruns, (size_t)nit * 4);
+        FM_ENSURE(f, f->o_nhits, (size_t)nit * 8);
         FM_ENSURE(f, f->o_runs, (size_t)ws * sizeof(FmOvlRun));
         FM_ENSURE(f, f->s_ctr, 64);
-        HIPCHK(f, hipMemcpyAsync(f->o_slot.p, slot.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->o_slot.p, slot.data(), (nit + 1) * 8, hipMemcpyHostToDevice, f->stream));
         HIPCHK(f, hipMemsetAsync(f->s_ctr.p, 0, 32, f->stream));
         tm.begin();
         k_fm_graph_unpack<<<grid_for(bytes, 256), 256, 0, f->stream>>>(f->text.as<u64>(), f->g_coff.as<u64>(), p0, np, bytes,
                                                                        f->q_chars.as<u8>());
-        k_fm_overlap_walk<<<grid_for(np, 256), 256, 0, f->stream>>>(f->V, f->q_chars.as<u8>(), f->g_coff.as<u64>() + p0, coff[p0], np,
-                                                                    np, min_overlap, f->o_slot.as<u64>(), f->o_runs.as<FmOvlRun>(),
-                                                                    f->o_nruns.as<u32>(), f->o_nhits.as<u64>(), f->s_ctr.as<u64>());
-        nr.resize(np); nh.resize(np);
-        HIPCHK(f, hipMemcpyAsync(nr.data(), f->o_nruns.p, np * 4, hipMemcpyDeviceToHost, f->stream));
-        HIPCHK(f, hipMemcpyAsync(nh.data(), f->o_nhits.p, np * 8, hipMemcpyDeviceToHost, f->stream));
+        k_fm_overlap_walk<<<grid_for(nit, 256), 256, 0, f->stream>>>(f->V, f->q_chars.as<u8>(), f->g_coff.as<u64>() + p0, coff[p0], np,
+                                                                     nit, min_overlap, f->o_slot.as<u64>(), f->o_runs.as<FmOvlRun>(),
+                                                                     f->o_nruns.as<u32>(), f->o_nhits.as<u64>(), f->s_ctr.as<u64>());
+        nr.resize(nit); nh.resize(nit);
+        HIPCHK(f, hipMemcpyAsync(nr.data(), f->o_nruns.p, nit * 4, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(f, hipMemcpyAsync(nh.data(), f->o_nhits.p, nit * 8, hipMemcpyDeviceToHost, f->stream));
         if ((rc = tm.end(&st.ms_walk))) return rc;
         st.launches += 2;
-        rbase.resize(np); hbase.resize(np + 1);
-        u64 nruns = 0, nhits = 0;
-        for (u64 j = 0; j < np; j++) {
-            if (nr[j] > slot[j + 1] - slot[j]) { f->err = "debwt_fm_string_graph: a record wrote more runs than its slots"; return DEBWT_EINTERNAL; }
-            rbase[j] = nruns; hbase[j] = nhits;
-            nruns += nr[j]; nhits += nh[j];
-        }
-        hbase[np] = nhits;
-        st.hits += nhits;
-        if (!nhits) { p0 = p1; continue; }
-        const u64 chunk = std::min(nhits, limit);
-        FM_ENSURE(f, f->o_rbase, (size_t)np * 8);
-        FM_ENSURE(f, f->g_hbase, (size_t)(np + 1) * 8);
-        FM_ENSURE(f, f->o_cruns, (size_t)nruns * sizeof(FmOvlRun));
-        FM_ENSURE(f, f->o_rout, (size_t)nruns * 8);
-        FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
-        FM_ENSURE(f, f->g_raw, (size_t)nhits * sizeof(FmEdge));
-        FM_ENSURE(f, f->g_flag, (size_t)nhits);
-        FM_ENSURE(f, f->g_deg, (size_t)np * 4);
-        FM_ENSURE(f, f->g_oseg, (size_t)(np + 1) * 8);
-        st.scratch_bytes = std::max<u64>(st.scratch_bytes, bytes + ws * sizeof(FmOvlRun) + np * 48 + nruns * 24 + chunk * 16 + nhits * 9);
-        HIPCHK(f, hipMemcpyAsync(f->o_rbase.p, rbase.data(), np * 8, hipMemcpyHostToDevice, f->stream));
-        HIPCHK(f, hipMemcpyAsync(f->g_hbase.p, hbase.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
-        tm.begin();
-        k_fm_overlap_compact<<<grid_for(np, 256), 256, 0, f->stream>>>(f->g_coff.as<u64>() + p0, f->o_slot.as<u64>(), f->o_nruns.as<u32>(),
-                                                                       f->o_rbase.as<u64>(), f->g_hbase.as<u64>(), np, np,
-                                                                       f->o_runs.as<FmOvlRun>(), f->o_cruns.as<FmOvlRun>(),
-                                                                       f->o_rout.as<u64>());
-        st.launches++;
-        for (u64 g0 = 0; g0 < nhits; g0 += chunk) {
-            const u64 cnt = std::min(nhits - g0, chunk);
-            if (g0) tm.begin();
-            k_fm_overlap_expand<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_cruns.as<FmOvlRun>(), f->o_rout.as<u64>(), nruns,
-                                                                           f->o_table.as<FmOvlRec>(), g0, cnt, f->o_hits.as<uint4>());
-            if ((rc = tm.end(&st.ms_walk))) return rc;
+        if constexpr (both) {                                  // the tail seeds of the batch and their row counts
+            FM_ENSURE(f, f->b_row, (size_t)np * 8);
+            FM_ENSURE(f, f->b_cnt, (size_t)np * 8);
+            tc.resize(np);
             tm.begin();
-            k_fm_graph_pack<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_hits.as<uint4>(), g0, cnt, f->g_hbase.as<u64>(), p0, np,
-                                                                       f->g_state.as<u8>(), f->g_raw.as<FmEdge>(), f->g_ctr.as<u64>());
-            if ((rc = tm.end(&st.ms_build))) return rc;
-            st.launches += 2;
+            k_fm_bigraph_seed<<<grid_for(np, 256), 256, 0, f->stream>>>(f->V, f->text.as<u64>(), f->g_coff.as<u64>(), f->b_state.as<u8>(), p0,
+                                                                        np, min_overlap, f->b_row.as<u64>(), f->b_cnt.as<u64>(),
+                                                                        f->b_ctr.as<u64>());
+            HIPCHK(f, hipMemcpyAsync(tc.data(), f->b_cnt.p, np * 8, hipMemcpyDeviceToHost, f->stream));
+            if ((rc = tm.end(&st.ms_tail))) return rc;
+            st.launches++;
         }
+        // runs in item order; walk hits in item order (ihb) and in (record, strand) order (whb); raw segments by (record, kind)
+        rbase.resize(nit); whb.resize(nit + 1);
+        if constexpr (both) { ihb.resize(nit); rawbase.resize(nseg + 1); tbase.resize(np + 1); }
+        u64 nruns = 0, nhits = 0, ntail = 0, nraw = 0;
+        for (u64 j = 0; j < np; j++) {
+            for (u64 s = 0; s < NS; s++) {
+                const u64 g = s * np + j;
+                if (nr[g] > slot[g + 1] - slot[g]) { f->err = std::string(who) + ": a record wrote more runs than its slots"; return DEBWT_EINTERNAL; }
+                rbase[g] = nruns; whb[NS * j + s] = nhits;
+                if constexpr (both) ihb[g] = nhits;
+                nruns += nr[g]; nhits += nh[g];
+            }
+            if constexpr (both) {
+                rawbase[3 * j] = nraw; nraw += nh[j];
+                rawbase[3 * j + 1] = nraw; nraw += tc[j];
+                rawbase[3 * j + 2] = nraw; nraw += nh[np + j];
+                tbase[j] = ntail; ntail += tc[j];
+            }
+        }
+        whb[nit] = nhits;
+        st.hits += nhits;
+        if constexpr (both) { rawbase[nseg] = nraw; tbase[np] = ntail; st.seed_rows += ntail; }
+        else nraw = nhits;
+        if (!nraw) { p0 = p1; continue; }
+        const u64 chunk = std::min(std::max(nhits, ntail), limit);
+        FM_ENSURE(f, f->o_rbase, (size_t)nit * 8);
+        FM_ENSURE(f, d_whb, (size_t)(nit + 1) * 8);
+        FM_ENSURE(f, f->o_cruns, (size_t)std::max<u64>(nruns, 1) * sizeof(FmOvlRun));
+        FM_ENSURE(f, f->o_rout, (size_t)std::max<u64>(nruns, 1) * 8);
+        FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
+        FM_ENSURE(f, f->g_raw, (size_t)nraw * sizeof(FmEdge));
+        FM_ENSURE(f, f->g_flag, (size_t)nraw);
+        FM_ENSURE(f, f->g_deg, (size_t)nseg * 4);
+        FM_ENSURE(f, f->g_oseg, (size_t)(nseg + 1) * 8);
+        HIPCHK(f, hipMemcpyAsync(f->o_rbase.p, rbase.data(), nit * 8, hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(d_whb.p, whb.data(), (nit + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        if constexpr (both) {
+            FM_ENSURE(f, f->o_hbase, (size_t)nit * 8);
+            FM_ENSURE(f, f->b_rawbase, (size_t)(nseg + 1) * 8);
+            FM_ENSURE(f, f->b_tbase, (size_t)(np + 1) * 8);
+            FM_ENSURE(f, f->b_pos, (size_t)chunk * 8);
+            st.scratch_bytes = std::max<u64>(st.scratch_bytes, bytes + ws * sizeof(FmOvlRun) + np * 120 + nruns * 24 + chunk * 24 + nraw * 9);
+            HIPCHK(f, hipMemcpyAsync(f->o_hbase.p, ihb.data(), nit * 8, hipMemcpyHostToDevice, f->stream));
+            HIPCHK(f, hipMemcpyAsync(f->b_rawbase.p, rawbase.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, f->stream));
+            HIPCHK(f, hipMemcpyAsync(f->b_tbase.p, tbase.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        } else {
+            st.scratch_bytes = std::max<u64>(st.scratch_bytes, bytes + ws * sizeof(FmOvlRun) + np * 48 + nruns * 24 + chunk * 16 + nhits * 9);
+        }
+        if (nhits) {
+            tm.begin();
+            k_fm_overlap_compact<<<grid_for(nit, 256), 256, 0, f->stream>>>(f->g_coff.as<u64>() + p0, f->o_slot.as<u64>(), f->o_nruns.as<u32>(),
+                                                                            f->o_rbase.as<u64>(), d_ihb.as<u64>(), np, nit,
+                                                                            f->o_runs.as<FmOvlRun>(), f->o_cruns.as<FmOvlRun>(),
+                                                                            f->o_rout.as<u64>());
+            st.launches++;
+            for (u64 g0 = 0; g0 < nhits; g0 += chunk) {
+                const u64 cnt = std::min(nhits - g0, chunk);
+                if (g0) tm.begin();
+                k_fm_overlap_expand<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_cruns.as<FmOvlRun>(), f->o_rout.as<u64>(), nruns,
+                                                                               f->o_table.as<FmOvlRec>(), g0, cnt, f->o_hits.as<uint4>());
+                if ((rc = tm.end(&st.ms_walk))) return rc;
+                tm.begin();
+                if constexpr (both)
+                    k_fm_bigraph_pack<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_hits.as<uint4>(), g0, cnt, f->b_whb.as<u64>(),
+                                                                                 f->b_rawbase.as<u64>(), p0, np, f->b_state.as<u8>(),
+                                                                                 f->b_self.as<u8>(), f->g_raw.as<FmEdge>(), f->b_ctr.as<u64>());
+                else
+                    k_fm_graph_pack<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_hits.as<uint4>(), g0, cnt, f->g_hbase.as<u64>(), p0, np,
+                                                                               f->g_state.as<u8>(), f->g_raw.as<FmEdge>(), f->g_ctr.as<u64>());
+                if ((rc = tm.end(&st.ms_build))) return rc;
+                st.launches += 2;
+            }
+        }
+        if constexpr (both)
+            for (u64 g0 = 0; g0 < ntail; g0 += chunk) {        // the seeds' rows are the runs of the locate kernel
+                const u64 cnt = std::min(ntail - g0, chunk);
+                tm.begin();
+                k_fm_locate<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->V, f->sa.as<u64>(), f->sh, f->b_row.as<u64>(), f->b_tbase.as<u64>(), np,
+                                                                      g0, cnt, f->b_pos.as<u64>());
+                k_fm_bigraph_tail<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->text.as<u64>(), f->g_coff.as<u64>(), nrec, f->b_pos.as<u64>(), g0,
+                                                                             cnt, f->b_tbase.as<u64>(), f->b_rawbase.as<u64>(), p0, np,
+                                                                             min_overlap, f->b_state.as<u8>(), f->b_self.as<u8>(),
+                                                                             f->g_raw.as<FmEdge>(), f->b_ctr.as<u64>());
+                if ((rc = tm.end(&st.ms_tail))) return rc;
+                st.launches += 2;
+            }
         tm.begin();
-        k_fm_graph_longest<<<grid_for(nhits, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), f->g_hbase.as<u64>(), np, nhits,
-                                                                        f->g_flag.as<u8>());
-        k_fm_graph_degree<<<grid_for(np, 256), 256, 0, f->stream>>>(f->g_flag.as<u8>(), f->g_hbase.as<u64>(), np, f->g_deg.as<u32>());
-        deg.resize(np);
-        HIPCHK(f, hipMemcpyAsync(deg.data(), f->g_deg.p, np * 4, hipMemcpyDeviceToHost, f->stream));
+        if constexpr (both)                                    // not for one strand: it reads a whole segment per entry
+            k_fm_bigraph_longest<<<grid_for(nraw, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), d_seg.as<u64>(), nseg, nraw,
+                                                                             f->g_flag.as<u8>());
+        else
+            k_fm_graph_longest<<<grid_for(nraw, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), d_seg.as<u64>(), nseg, nraw,
+                                                                           f->g_flag.as<u8>());
+        k_fm_graph_degree<<<grid_for(nseg, 256), 256, 0, f->stream>>>(f->g_flag.as<u8>(), d_seg.as<u64>(), nseg, f->g_deg.as<u32>());
+        deg.resize(nseg);
+        HIPCHK(f, hipMemcpyAsync(deg.data(), f->g_deg.p, nseg * 4, hipMemcpyDeviceToHost, f->stream));
         if ((rc = tm.end(&st.ms_build))) return rc;
         st.launches += 2;
-        oseg.resize(np + 1);
-        for (u64 j = 0; j < np; j++) { oseg[j] = eoff[p0 + j]; eoff[p0 + j + 1] = eoff[p0 + j] + deg[j]; }
-        oseg[np] = eoff[p1];
-        if (eoff[p1] > eoff[p0]) {
-            if ((rc = fm_graph_reserve(f, eoff[p0], eoff[p1]))) return rc;
-            HIPCHK(f, hipMemcpyAsync(f->g_oseg.p, oseg.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        oseg.resize(nseg + 1);
+        for (u64 k = 0; k < nseg; k++) { oseg[k] = eoff[NK * p0 + k]; eoff[NK * p0 + k + 1] = eoff[NK * p0 + k] + deg[k]; }
+        oseg[nseg] = eoff[NK * p1];
+        if (eoff[NK * p1] > eoff[NK * p0]) {
+            if ((rc = fm_graph_reserve(f, who, eoff[NK * p0], eoff[NK * p1]))) return rc;
+            HIPCHK(f, hipMemcpyAsync(f->g_oseg.p, oseg.data(), (nseg + 1) * 8, hipMemcpyHostToDevice, f->stream));
             tm.begin();
-            k_fm_graph_scatter<<<grid_for(nhits, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), f->g_flag.as<u8>(), f->g_hbase.as<u64>(),
-                                                                            f->g_oseg.as<u64>(), np, nhits, f->g_edges.as<FmEdge>());
+            k_fm_graph_scatter<<<grid_for(nraw, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), f->g_flag.as<u8>(), d_seg.as<u64>(),
+                                                                           f->g_oseg.as<u64>(), nseg, nraw, f->g_edges.as<FmEdge>());
             if ((rc = tm.end(&st.ms_build))) return rc;     // oseg is host memory
             st.launches++;
         }
         p0 = p1;
     }
     u64 h[FM_GR_NCTR];
-    HIPCHK(f, hipMemcpyAsync(h, f->g_ctr.p, sizeof h, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(h, ctr.p, sizeof h, hipMemcpyDeviceToHost, f->stream));
     if ((rc = fm_sync(f))) return rc;
     if (h[FM_GR_BADLEN]) {
-        f->err = "debwt_fm_string_graph: " + std::to_string(h[FM_GR_BADLEN]) + " overlaps between kept records cover one of them whole";
+        f->err = std::string(who) + ": " + std::to_string(h[FM_GR_BADLEN]) + " overlaps between kept records cover one of them whole";
         return DEBWT_EINTERNAL;
     }
-    st.edges = eoff[nrec];
-    st.edge_bytes = eoff[nrec] * sizeof(FmEdge);
+    if constexpr (both) { st.seeds = h[FM_BG_SEEDS]; st.tail_hits = h[FM_BG_TAILS]; }
+    return DEBWT_OK;
+}
+
+// The end of either builder.  E is in g_edges, its nnodes lists in edge_offsets.  Unless all edges are asked for: the keep
+// bytes of the reduction, the degrees of the kept edges, the new offsets, the kept edges scattered into g_out, as a batch's
+// flagged entries were into g_edges.  Then the capacity protocol and the copy to the host.  The node lengths are computed
+// here, and only when the reduction runs.
+template <class St>
+int fm_graph_finish(debwt_fm *f, St &st, const char *who, FmGraphTimer &tm, u32 flags, u64 nnodes, uint64_t *edge_offsets,
+                    debwt_fm_edge *edges, u64 capacity) {
+    constexpr bool both = fm_graph_both<St>;
+    const u64 ne = edge_offsets[nnodes];
+    const FmEdge *d_final = f->g_edges.as<FmEdge>();
+    int rc;
+    if (!(flags & DEBWT_FM_GRAPH_ALL_EDGES) && ne) {
+        std::vector<u64> len(nnodes);
+        for (u64 v = 0; v < nnodes; v++) {
+            const u64 r = both ? v / 2 : v;
+            len[v] = (r + 1 < f->nrec ? f->rec_starts[r + 1] : f->n) - 1 - f->rec_starts[r];
+        }
+        FM_ENSURE(f, f->g_len, (size_t)nnodes * 8);
+        if constexpr (!both) {                                 // the merge of both strands has left the offsets in g_eoff
+            FM_ENSURE(f, f->g_eoff, (size_t)(nnodes + 1) * 8);
+            HIPCHK(f, hipMemcpyAsync(f->g_eoff.p, edge_offsets, (nnodes + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        }
+        HIPCHK(f, hipMemcpyAsync(f->g_len.p, len.data(), nnodes * 8, hipMemcpyHostToDevice, f->stream));
+        if ((rc = fm_graph_reduce(f, st, tm, nnodes, f->g_edges.as<FmEdge>(), ne))) return rc;
+        std::vector<u32> deg(nnodes);
+        FM_ENSURE(f, f->g_deg, (size_t)nnodes * 4);
+        tm.begin();
+        k_fm_graph_degree<<<grid_for(nnodes, 256), 256, 0, f->stream>>>(f->g_keep.as<u8>(), f->g_eoff.as<u64>(), nnodes, f->g_deg.as<u32>());
+        HIPCHK(f, hipMemcpyAsync(deg.data(), f->g_deg.p, nnodes * 4, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&st.ms_reduce))) return rc;
+        for (u64 i = 0; i < nnodes; i++) edge_offsets[i + 1] = edge_offsets[i] + deg[i];
+        const u64 nk = edge_offsets[nnodes];
+        if (nk != ne - st.reducible) { f->err = std::string(who) + ": the kept edges do not add up"; return DEBWT_EINTERNAL; }
+        FM_ENSURE(f, f->g_oseg, (size_t)(nnodes + 1) * 8);
+        FM_ENSURE(f, f->g_out, (size_t)std::max<u64>(nk, 1) * sizeof(FmEdge));
+        HIPCHK(f, hipMemcpyAsync(f->g_oseg.p, edge_offsets, (nnodes + 1) * 8, hipMemcpyHostToDevice, f->stream));
+        tm.begin();
+        k_fm_graph_scatter<<<grid_for(ne, 256), 256, 0, f->stream>>>(f->g_edges.as<FmEdge>(), f->g_keep.as<u8>(), f->g_eoff.as<u64>(),
+                                                                     f->g_oseg.as<u64>(), nnodes, ne, f->g_out.as<FmEdge>());
+        if ((rc = tm.end(&st.ms_reduce))) return rc;
+        st.launches += 2;
+        d_final = f->g_out.as<FmEdge>();
+    }
+    const u64 total = edge_offsets[nnodes];
+    if (capacity < total || (total && !edges)) {
+        f->err = std::string(who) + ": capacity below the edges (edge_offsets[" + (both ? "2 * nrec" : "nrec") + "] = " +
+                 std::to_string(total) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (total) {
+        HIPCHK(f, hipMemcpyAsync(edges, d_final, (size_t)total * sizeof(FmEdge), hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+    }
+    return DEBWT_OK;
+}
+
+// Definition 4, and with `both` definition 4b: no link to the source's mirror, none at a self-rc read, and of a unitig and
+// its mirror the one with the lower first member.
+int fm_unitigs(bool both, const uint8_t *state, const uint64_t *edge_offsets, const debwt_fm_edge *edges, uint64_t nnodes,
+               uint64_t *unitig_offsets, uint32_t *members, uint8_t *circular, uint64_t *nunitigs) {
+    if (!edge_offsets || !unitig_offsets || !nunitigs || (nnodes && (!state || !members || !circular)) || (nnodes >> 32))
+        return DEBWT_EINVAL;
+    const u64 e0 = edge_offsets[0];
+    for (u64 i = 0; i < nnodes; i++)
+        if (edge_offsets[i + 1] < edge_offsets[i]) return DEBWT_EINVAL;
+    if (edge_offsets[nnodes] > e0 && !edges) return DEBWT_EINVAL;
+    constexpr u32 NONE = 0xFFFFFFFFu;
+    std::vector<u32> indeg(nnodes, 0), next(nnodes, NONE);
+    for (u64 i = 0; i < nnodes; i++)
+        for (u64 e = edge_offsets[i]; e < edge_offsets[i + 1]; e++) {
+            if (edges[e].record >= nnodes || state[i] != 0 || state[edges[e].record] != 0) return DEBWT_EINVAL;
+            indeg[edges[e].record]++;
+        }
+    auto selfrc = [&](u64 v) { return state[v & ~1ull] == 0 && state[v | 1] == 1; };   // asked only with `both`: nnodes is even
+    std::vector<u8> has_in(nnodes, 0), on_chain(nnodes, 0);
+    for (u64 i = 0; i < nnodes; i++)
+        if (edge_offsets[i + 1] - edge_offsets[i] == 1) {
+            const u32 w = edges[edge_offsets[i]].record;
+            if (w != i && indeg[w] == 1 && !(both && (w == (i ^ 1) || selfrc(i) || selfrc(w)))) { next[i] = w; has_in[w] = 1; }
+        }
+    for (u64 i = 0; i < nnodes; i++)                           // the nodes that a node without an incoming link leads to
+        if (state[i] == 0 && !has_in[i])
+            for (u64 v = i; v != NONE; v = next[v]) on_chain[v] = 1;
+    // every unitig of the link rule in ascending first member; with `both` it stays only when its mirror starts no lower
+    u64 nu = 0, nm = 0;
+    unitig_offsets[0] = 0;
+    for (u64 i = 0; i < nnodes; i++) {
+        if (state[i] != 0 || (has_in[i] && on_chain[i])) continue;
+        const u64 m0 = nm;
+        u64 mirror_first = NONE;
+        if (!has_in[i]) {
+            u64 last = i;
+            for (u64 v = i; v != NONE; v = next[v]) { members[nm++] = (u32)v; last = v; }
+            if (both) mirror_first = selfrc(last) ? last : (last ^ 1);
+            circular[nu] = 0;
+        } else {                                               // the lowest node of a cycle: the ones after it get on_chain
+            u64 v = i;
+            do { members[nm++] = (u32)v; on_chain[v] = 1; mirror_first = std::min<u64>(mirror_first, v ^ 1); v = next[v]; } while (v != i);
+            circular[nu] = 1;
+        }
+        if (both && mirror_first < i) { nm = m0; continue; }   // the mirror has been, or will be, reported
+        unitig_offsets[++nu] = nm;
+    }
+    *nunitigs = nu;
     return DEBWT_OK;
 }
 
@@ -6656,6 +6860,7 @@ int fm_graph_edges(debwt_fm *f, FmGraphTimer &tm, u32 min_overlap, uint8_t *stat
 extern "C" int debwt_fm_string_graph(debwt_fm *f, uint32_t min_overlap, uint32_t flags, uint8_t *state, uint64_t *edge_offsets,
                                      debwt_fm_edge *edges, uint64_t capacity) {
     if (!f || !state || !edge_offsets) return DEBWT_EINVAL;
+    const char *who = "debwt_fm_string_graph";
     const auto t0 = std::chrono::steady_clock::now();
     f->g_stats = debwt_fm_graph_stats{};
     if (!min_overlap) { f->err = "debwt_fm_string_graph: min_overlap must be at least 1"; return DEBWT_EINVAL; }
@@ -6667,54 +6872,18 @@ extern "C" int debwt_fm_string_graph(debwt_fm *f, uint32_t min_overlap, uint32_t
     FmGraphTimer tm(f);
     int rc = tm.init();
     if (rc) return rc;
-    if ((rc = fm_graph_edges(f, tm, min_overlap, state, edge_offsets))) return rc;
-    const u64 ne = edge_offsets[nrec];
-    const FmEdge *d_final = f->g_edges.as<FmEdge>();
-    if (!(flags & DEBWT_FM_GRAPH_ALL_EDGES) && ne) {
-        std::vector<u64> len(nrec);
-        for (u64 i = 0; i < nrec; i++) len[i] = (i + 1 < nrec ? f->rec_starts[i + 1] : f->n) - 1 - f->rec_starts[i];
-        FM_ENSURE(f, f->g_eoff, (size_t)(nrec + 1) * 8);
-        FM_ENSURE(f, f->g_len, (size_t)nrec * 8);
-        HIPCHK(f, hipMemcpyAsync(f->g_eoff.p, edge_offsets, (nrec + 1) * 8, hipMemcpyHostToDevice, f->stream));
-        HIPCHK(f, hipMemcpyAsync(f->g_len.p, len.data(), nrec * 8, hipMemcpyHostToDevice, f->stream));
-        if ((rc = fm_graph_reduce(f, tm, nrec, f->g_edges.as<FmEdge>(), ne))) return rc;
-        // compaction of the kept edges, as a batch's hits were compacted into E
-        std::vector<u32> deg(nrec);
-        FM_ENSURE(f, f->g_deg, (size_t)nrec * 4);
-        tm.begin();
-        k_fm_graph_degree<<<grid_for(nrec, 256), 256, 0, f->stream>>>(f->g_keep.as<u8>(), f->g_eoff.as<u64>(), nrec, f->g_deg.as<u32>());
-        HIPCHK(f, hipMemcpyAsync(deg.data(), f->g_deg.p, nrec * 4, hipMemcpyDeviceToHost, f->stream));
-        if ((rc = tm.end(&st.ms_reduce))) return rc;
-        for (u64 i = 0; i < nrec; i++) edge_offsets[i + 1] = edge_offsets[i] + deg[i];
-        const u64 nk = edge_offsets[nrec];
-        if (nk != ne - st.reducible) { f->err = "debwt_fm_string_graph: the kept edges do not add up"; return DEBWT_EINTERNAL; }
-        FM_ENSURE(f, f->g_oseg, (size_t)(nrec + 1) * 8);
-        FM_ENSURE(f, f->g_out, (size_t)std::max<u64>(nk, 1) * sizeof(FmEdge));
-        HIPCHK(f, hipMemcpyAsync(f->g_oseg.p, edge_offsets, (nrec + 1) * 8, hipMemcpyHostToDevice, f->stream));
-        tm.begin();
-        k_fm_graph_scatter<<<grid_for(ne, 256), 256, 0, f->stream>>>(f->g_edges.as<FmEdge>(), f->g_keep.as<u8>(), f->g_eoff.as<u64>(),
-                                                                     f->g_oseg.as<u64>(), nrec, ne, f->g_out.as<FmEdge>());
-        if ((rc = tm.end(&st.ms_reduce))) return rc;
-        st.launches += 2;
-        d_final = f->g_out.as<FmEdge>();
-    }
-    const u64 total = edge_offsets[nrec];
-    if (capacity < total || (total && !edges)) {
-        f->err = "debwt_fm_string_graph: capacity below the edges (edge_offsets[nrec] = " + std::to_string(total) + ")";
-        return DEBWT_ERANGE;
-    }
-    if (total) {
-        HIPCHK(f, hipMemcpyAsync(edges, d_final, (size_t)total * sizeof(FmEdge), hipMemcpyDeviceToHost, f->stream));
-        if ((rc = fm_sync(f))) return rc;
-        for (u64 i = 0; i < nrec; i++)                         // record order inside every length group
-            for (u64 a = edge_offsets[i]; a < edge_offsets[i + 1];) {
-                u64 e = a + 1;
-                while (e < edge_offsets[i + 1] && edges[e].length == edges[a].length) e++;
-                if (e - a > 1)
-                    std::sort(edges + a, edges + e, [](const debwt_fm_edge &x, const debwt_fm_edge &y) { return x.record < y.record; });
-                a = e;
-            }
-    }
+    if ((rc = fm_graph_found(f, st, who, tm, min_overlap, state, edge_offsets))) return rc;
+    st.edges = edge_offsets[nrec];
+    st.edge_bytes = edge_offsets[nrec] * sizeof(FmEdge);
+    if ((rc = fm_graph_finish(f, st, who, tm, flags, nrec, edge_offsets, edges, capacity))) return rc;
+    for (u64 i = 0; i < nrec; i++)                             // record order inside every length group
+        for (u64 a = edge_offsets[i]; a < edge_offsets[i + 1];) {
+            u64 e = a + 1;
+            while (e < edge_offsets[i + 1] && edges[e].length == edges[a].length) e++;
+            if (e - a > 1)
+                std::sort(edges + a, edges + e, [](const debwt_fm_edge &x, const debwt_fm_edge &y) { return x.record < y.record; });
+            a = e;
+        }
     st.ms_wall = (float)fm_ms_since(t0);
     return DEBWT_OK;
 }
@@ -6754,11 +6923,11 @@ extern "C" int debwt_fm_edges_reduce(debwt_fm *f, const uint64_t *reclen, uint64
     for (u64 i = 0; i <= nnodes; i++) off[i] = edge_offsets[i] - e0;
     FM_ENSURE(f, f->g_eoff, (size_t)(nnodes + 1) * 8);
     FM_ENSURE(f, f->g_len, (size_t)nnodes * 8);
-    if ((rc = fm_graph_reserve(f, 0, ne))) return rc;
+    if ((rc = fm_graph_reserve(f, "debwt_fm_string_graph", 0, ne))) return rc;
     HIPCHK(f, hipMemcpyAsync(f->g_eoff.p, off.data(), (nnodes + 1) * 8, hipMemcpyHostToDevice, f->stream));
     HIPCHK(f, hipMemcpyAsync(f->g_len.p, reclen, nnodes * 8, hipMemcpyHostToDevice, f->stream));
     HIPCHK(f, hipMemcpyAsync(f->g_edges.p, edges + e0, (size_t)ne * sizeof(FmEdge), hipMemcpyHostToDevice, f->stream));
-    if ((rc = fm_graph_reduce(f, tm, nnodes, f->g_edges.as<FmEdge>(), ne))) return rc;
+    if ((rc = fm_graph_reduce(f, st, tm, nnodes, f->g_edges.as<FmEdge>(), ne))) return rc;
     HIPCHK(f, hipMemcpyAsync(keep + e0, f->g_keep.p, (size_t)ne, hipMemcpyDeviceToHost, f->stream));
     if ((rc = fm_sync(f))) return rc;
     st.ms_wall = (float)fm_ms_since(t0);
@@ -6767,44 +6936,7 @@ extern "C" int debwt_fm_edges_reduce(debwt_fm *f, const uint64_t *reclen, uint64
 
 extern "C" int debwt_fm_unitigs(const uint8_t *state, const uint64_t *edge_offsets, const debwt_fm_edge *edges, uint64_t nnodes,
                                 uint64_t *unitig_offsets, uint32_t *members, uint8_t *circular, uint64_t *nunitigs) {
-    if (!edge_offsets || !unitig_offsets || !nunitigs || (nnodes && (!state || !members || !circular)) || (nnodes >> 32))
-        return DEBWT_EINVAL;
-    const u64 e0 = edge_offsets[0];
-    for (u64 i = 0; i < nnodes; i++)
-        if (edge_offsets[i + 1] < edge_offsets[i]) return DEBWT_EINVAL;
-    if (edge_offsets[nnodes] > e0 && !edges) return DEBWT_EINVAL;
-    constexpr u32 NONE = 0xFFFFFFFFu;
-    std::vector<u32> indeg(nnodes, 0), next(nnodes, NONE);
-    for (u64 i = 0; i < nnodes; i++)
-        for (u64 e = edge_offsets[i]; e < edge_offsets[i + 1]; e++) {
-            if (edges[e].record >= nnodes || state[i] != 0 || state[edges[e].record] != 0) return DEBWT_EINVAL;
-            indeg[edges[e].record]++;
-        }
-    std::vector<u8> has_in(nnodes, 0), on_chain(nnodes, 0);
-    for (u64 i = 0; i < nnodes; i++)
-        if (edge_offsets[i + 1] - edge_offsets[i] == 1) {
-            const u32 w = edges[edge_offsets[i]].record;
-            if (w != i && indeg[w] == 1) { next[i] = w; has_in[w] = 1; }
-        }
-    for (u64 i = 0; i < nnodes; i++)                           // the nodes that a node without an incoming link leads to
-        if (state[i] == 0 && !has_in[i])
-            for (u64 v = i; v != NONE; v = next[v]) on_chain[v] = 1;
-    u64 nu = 0, nm = 0;
-    unitig_offsets[0] = 0;
-    for (u64 i = 0; i < nnodes; i++) {
-        if (state[i] != 0 || (has_in[i] && on_chain[i])) continue;
-        if (!has_in[i]) {
-            for (u64 v = i; v != NONE; v = next[v]) members[nm++] = (u32)v;
-            circular[nu] = 0;
-        } else {                                               // the lowest node of a cycle: the ones after it get on_chain
-            u64 v = i;
-            do { members[nm++] = (u32)v; on_chain[v] = 1; v = next[v]; } while (v != i);
-            circular[nu] = 1;
-        }
-        unitig_offsets[++nu] = nm;
-    }
-    *nunitigs = nu;
-    return DEBWT_OK;
+    return fm_unitigs(false, state, edge_offsets, edges, nnodes, unitig_offsets, members, circular, nunitigs);
 }
 
 extern "C" int debwt_fm_graph_stats_get(const debwt_fm *f, debwt_fm_graph_stats *out) {
@@ -6813,240 +6945,29 @@ extern "C" int debwt_fm_graph_stats_get(const debwt_fm *f, debwt_fm_graph_stats 
     return DEBWT_OK;
 }
 
-// ---- string graph over both strands (fm_bigraph_kernels.h) ------------------------------------------------------------
-// Per batch of records: the overlap walk on both strands and the tail seeds; the host lays three segments per record out
-// (strand-0 hits, located seed rows, strand-1 hits), the hits are expanded and packed and the seed rows located and
-// verified a chunk at a time into them, the longest entry per (segment, target) is flagged and the flagged ones appended
-// to A (g_edges): ++, +- and -+ of every record.  Then the mirrors of the ++ edges are counted per target, the lists of the
-// 2 nrec nodes laid out, every edge placed in its list (b_cat) and ranked into E (g_edges again).  The reduction and the
-// compaction of the kept edges are those of debwt_fm_string_graph.
-
-namespace {
-
-struct FmGraphStatsKeep {                                  // fm_graph_reduce counts into g_stats: borrowed here and put back
-    debwt_fm *f;
-    debwt_fm_graph_stats saved;
-    explicit FmGraphStatsKeep(debwt_fm *f_) : f(f_), saved(f_->g_stats) { f->g_stats = debwt_fm_graph_stats{}; }
-    ~FmGraphStatsKeep() { f->g_stats = saved; }
-};
-
-int fm_bigraph_reserve(debwt_fm *f, u64 have, u64 nedges) {
-    const int rc = fm_graph_reserve(f, have, nedges);
-    if (rc == DEBWT_ENOMEM)
-        f->err = "debwt_fm_string_graph_both: the edge list does not fit in device memory (" + std::to_string(nedges) +
-                 " edges so far, 8 bytes each)";
-    return rc;
-}
-
-// states (host and b_state), self-rc flags (host and b_self), and A: record i's ++, +- and -+ edges in
-// [aoff[3i], aoff[3i + 1]), [aoff[3i + 1], aoff[3i + 2]), [aoff[3i + 2], aoff[3i + 3]) of g_edges.
-// The batch loop (how records are cut into batches, walk, compaction, expansion in chunks, flags, degrees, scatter into
-// g_edges) is that of fm_graph_edges above, copied so that debwt_fm_string_graph stays as it is: a fix to either belongs
-// in both.
-int fm_bigraph_found(debwt_fm *f, FmGraphTimer &tm, u32 min_overlap, uint8_t *state, std::vector<u8> &selfrc, std::vector<u64> &aoff) {
-    debwt_fm_graph_both_stats &st = f->b_stats;
-    const u64 nrec = f->nrec, n = f->n;
-    const std::vector<u64> &rs = f->rec_starts;
-    int rc;
-    if (!f->has_text && (rc = debwt_fm_restore_text(f))) return rc;
-    if ((rc = fm_overlap_table(f))) return rc;
-    std::vector<u64> coff(nrec + 1);                       // bases before each record
-    for (u64 i = 0; i < nrec; i++) coff[i] = rs[i] - i;
-    coff[nrec] = n - nrec;
-    for (u64 i = 0; i < nrec; i++)
-        if ((coff[i + 1] - coff[i]) >> 32) { f->err = "debwt_fm_string_graph_both: a record of 2^32 bases or more"; return DEBWT_EINVAL; }
-    FM_ENSURE(f, f->g_coff, (size_t)(nrec + 1) * 8);
-    FM_ENSURE(f, f->b_state, (size_t)nrec * 2);
-    FM_ENSURE(f, f->b_self, (size_t)nrec);
-    FM_ENSURE(f, f->b_ctr, FM_BG_NCTR * 8);
-    HIPCHK(f, hipMemcpyAsync(f->g_coff.p, coff.data(), (nrec + 1) * 8, hipMemcpyHostToDevice, f->stream));
-    HIPCHK(f, hipMemsetAsync(f->b_ctr.p, 0, FM_BG_NCTR * 8, f->stream));
-    selfrc.assign(nrec, 0);
-    tm.begin();
-    k_fm_bigraph_state<<<grid_for(nrec, 256), 256, 0, f->stream>>>(f->V, f->text.as<u64>(), f->g_coff.as<u64>(), f->o_table.as<FmOvlRec>(),
-                                                                   nrec, f->b_state.as<u8>(), f->b_self.as<u8>());
-    HIPCHK(f, hipMemcpyAsync(state, f->b_state.p, nrec * 2, hipMemcpyDeviceToHost, f->stream));
-    HIPCHK(f, hipMemcpyAsync(selfrc.data(), f->b_self.p, nrec, hipMemcpyDeviceToHost, f->stream));
-    if ((rc = tm.end(&st.ms_walk))) return rc;
-    st.launches++;
-    st.records = nrec;
-    for (u64 i = 0; i < nrec; i++) {
-        if (state[2 * i] == 0) { st.kept++; st.selfrc += selfrc[i]; }
-        else if (state[2 * i] == 1) st.duplicates++;
-        else st.contained++;
-    }
-    const u64 slots = fm_env_u64("DEBWT_FM_OVERLAP_SLOTS", FM_OVL_SLOTS);
-    const u64 limit = std::max<u64>(fm_env_u64("DEBWT_FM_OVERLAP_HITS", FM_OVL_HITS), 1);
-    auto worst = [&](u64 i) {                                  // run slots of record i on both strands
-        const u64 m = coff[i + 1] - coff[i];
-        return state[2 * i] == 0 && m >= min_overlap ? 2 * (m - min_overlap + 1) : 0;
-    };
-    std::vector<u64> slot, rbase, ihb, whb, rawbase, tbase, oseg, nh, tc;
-    std::vector<u32> nr, deg;
-    aoff.assign(3 * nrec + 1, 0);
-    for (u64 p0 = 0; p0 < nrec;) {
-        u64 p1 = p0 + 1, ws = worst(p0);                  // at least one record, however long
-        while (p1 < nrec && p1 - p0 < FM_BATCH_PATTERNS && coff[p1 + 1] - coff[p0] <= FM_BATCH_CHARS && ws + worst(p1) <= slots)
-            ws += worst(p1++);
-        const u64 np = p1 - p0, nit = 2 * np, bytes = coff[p1] - coff[p0];
-        for (u64 k = 3 * p0; k < 3 * p1; k++) aoff[k + 1] = aoff[k];
-        if (!ws) { p0 = p1; continue; }                        // no kept record long enough: no edges
-        slot.resize(nit + 1);                                  // item g: record p0 + g % np on strand g / np
-        slot[0] = 0;
-        for (u64 g = 0; g < nit; g++) slot[g + 1] = slot[g] + worst(p0 + (g < np ? g : g - np)) / 2;
-        FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(bytes, 1));
-        FM_ENSURE(f, f->o_slot, (size_t)(nit + 1) * 8);
-        FM_ENSURE(f, f->o_nruns, (size_t)nit * 4);
-        FM_ENSURE(f, f->o_nhits, (size_t)nit * 8);
-        FM_ENSURE(f, f->o_runs, (size_t)ws * sizeof(FmOvlRun));
-        FM_ENSURE(f, f->s_ctr, 64);
-        FM_ENSURE(f, f->b_row, (size_t)np * 8);
-        FM_ENSURE(f, f->b_cnt, (size_t)np * 8);
-        HIPCHK(f, hipMemcpyAsync(f->o_slot.p, slot.data(), (nit + 1) * 8, hipMemcpyHostToDevice, f->stream));
-        HIPCHK(f, hipMemsetAsync(f->s_ctr.p, 0, 32, f->stream));
-        tm.begin();
-        k_fm_graph_unpack<<<grid_for(bytes, 256), 256, 0, f->stream>>>(f->text.as<u64>(), f->g_coff.as<u64>(), p0, np, bytes,
-                                                                       f->q_chars.as<u8>());
-        k_fm_overlap_walk<<<grid_for(nit, 256), 256, 0, f->stream>>>(f->V, f->q_chars.as<u8>(), f->g_coff.as<u64>() + p0, coff[p0], np,
-                                                                     nit, min_overlap, f->o_slot.as<u64>(), f->o_runs.as<FmOvlRun>(),
-                                                                     f->o_nruns.as<u32>(), f->o_nhits.as<u64>(), f->s_ctr.as<u64>());
-        nr.resize(nit); nh.resize(nit); tc.resize(np);
-        HIPCHK(f, hipMemcpyAsync(nr.data(), f->o_nruns.p, nit * 4, hipMemcpyDeviceToHost, f->stream));
-        HIPCHK(f, hipMemcpyAsync(nh.data(), f->o_nhits.p, nit * 8, hipMemcpyDeviceToHost, f->stream));
-        if ((rc = tm.end(&st.ms_walk))) return rc;
-        tm.begin();
-        k_fm_bigraph_seed<<<grid_for(np, 256), 256, 0, f->stream>>>(f->V, f->text.as<u64>(), f->g_coff.as<u64>(), f->b_state.as<u8>(), p0,
-                                                                    np, min_overlap, f->b_row.as<u64>(), f->b_cnt.as<u64>(),
-                                                                    f->b_ctr.as<u64>());
-        HIPCHK(f, hipMemcpyAsync(tc.data(), f->b_cnt.p, np * 8, hipMemcpyDeviceToHost, f->stream));
-        if ((rc = tm.end(&st.ms_tail))) return rc;
-        st.launches += 3;
-        // runs and walk hits in (record, strand) order; slots in (record, kind) order
-        rbase.resize(nit); ihb.resize(nit); whb.resize(nit + 1); rawbase.resize(3 * np + 1); tbase.resize(np + 1);
-        u64 nruns = 0, nhits = 0, ntail = 0, nraw = 0;
-        for (u64 j = 0; j < np; j++) {
-            for (u64 s = 0; s < 2; s++) {
-                const u64 g = s * np + j;
-                if (nr[g] > slot[g + 1] - slot[g]) { f->err = "debwt_fm_string_graph_both: a record wrote more runs than its slots"; return DEBWT_EINTERNAL; }
-                rbase[g] = nruns; ihb[g] = nhits; whb[2 * j + s] = nhits;
-                nruns += nr[g]; nhits += nh[g];
-            }
-            rawbase[3 * j] = nraw; nraw += nh[j];
-            rawbase[3 * j + 1] = nraw; nraw += tc[j];
-            rawbase[3 * j + 2] = nraw; nraw += nh[np + j];
-            tbase[j] = ntail; ntail += tc[j];
-        }
-        whb[nit] = nhits; rawbase[3 * np] = nraw; tbase[np] = ntail;
-        st.hits += nhits; st.seed_rows += ntail;
-        if (!nraw) { p0 = p1; continue; }
-        const u64 chunk = std::min(std::max(nhits, ntail), limit);
-        FM_ENSURE(f, f->o_rbase, (size_t)nit * 8);
-        FM_ENSURE(f, f->o_hbase, (size_t)nit * 8);
-        FM_ENSURE(f, f->b_whb, (size_t)(nit + 1) * 8);
-        FM_ENSURE(f, f->b_rawbase, (size_t)(3 * np + 1) * 8);
-        FM_ENSURE(f, f->b_tbase, (size_t)(np + 1) * 8);
-        FM_ENSURE(f, f->o_cruns, (size_t)std::max<u64>(nruns, 1) * sizeof(FmOvlRun));
-        FM_ENSURE(f, f->o_rout, (size_t)std::max<u64>(nruns, 1) * 8);
-        FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
-        FM_ENSURE(f, f->b_pos, (size_t)chunk * 8);
-        FM_ENSURE(f, f->g_raw, (size_t)nraw * sizeof(FmEdge));
-        FM_ENSURE(f, f->g_flag, (size_t)nraw);
-        FM_ENSURE(f, f->g_deg, (size_t)3 * np * 4);
-        FM_ENSURE(f, f->g_oseg, (size_t)(3 * np + 1) * 8);
-        st.scratch_bytes = std::max<u64>(st.scratch_bytes, bytes + ws * sizeof(FmOvlRun) + np * 120 + nruns * 24 + chunk * 24 + nraw * 9);
-        HIPCHK(f, hipMemcpyAsync(f->o_rbase.p, rbase.data(), nit * 8, hipMemcpyHostToDevice, f->stream));
-        HIPCHK(f, hipMemcpyAsync(f->o_hbase.p, ihb.data(), nit * 8, hipMemcpyHostToDevice, f->stream));
-        HIPCHK(f, hipMemcpyAsync(f->b_whb.p, whb.data(), (nit + 1) * 8, hipMemcpyHostToDevice, f->stream));
-        HIPCHK(f, hipMemcpyAsync(f->b_rawbase.p, rawbase.data(), (3 * np + 1) * 8, hipMemcpyHostToDevice, f->stream));
-        HIPCHK(f, hipMemcpyAsync(f->b_tbase.p, tbase.data(), (np + 1) * 8, hipMemcpyHostToDevice, f->stream));
-        if (nhits) {
-            tm.begin();
-            k_fm_overlap_compact<<<grid_for(nit, 256), 256, 0, f->stream>>>(f->g_coff.as<u64>() + p0, f->o_slot.as<u64>(), f->o_nruns.as<u32>(),
-                                                                            f->o_rbase.as<u64>(), f->o_hbase.as<u64>(), np, nit,
-                                                                            f->o_runs.as<FmOvlRun>(), f->o_cruns.as<FmOvlRun>(),
-                                                                            f->o_rout.as<u64>());
-            st.launches++;
-            for (u64 g0 = 0; g0 < nhits; g0 += chunk) {
-                const u64 cnt = std::min(nhits - g0, chunk);
-                if (g0) tm.begin();
-                k_fm_overlap_expand<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_cruns.as<FmOvlRun>(), f->o_rout.as<u64>(), nruns,
-                                                                               f->o_table.as<FmOvlRec>(), g0, cnt, f->o_hits.as<uint4>());
-                if ((rc = tm.end(&st.ms_walk))) return rc;
-                tm.begin();
-                k_fm_bigraph_pack<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_hits.as<uint4>(), g0, cnt, f->b_whb.as<u64>(),
-                                                                             f->b_rawbase.as<u64>(), p0, np, f->b_state.as<u8>(),
-                                                                             f->b_self.as<u8>(), f->g_raw.as<FmEdge>(), f->b_ctr.as<u64>());
-                if ((rc = tm.end(&st.ms_build))) return rc;
-                st.launches += 2;
-            }
-        }
-        for (u64 g0 = 0; g0 < ntail; g0 += chunk) {            // the seeds' rows are the runs of the locate kernel
-            const u64 cnt = std::min(ntail - g0, chunk);
-            tm.begin();
-            k_fm_locate<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->V, f->sa.as<u64>(), f->sh, f->b_row.as<u64>(), f->b_tbase.as<u64>(), np,
-                                                                  g0, cnt, f->b_pos.as<u64>());
-            k_fm_bigraph_tail<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->text.as<u64>(), f->g_coff.as<u64>(), nrec, f->b_pos.as<u64>(), g0,
-                                                                         cnt, f->b_tbase.as<u64>(), f->b_rawbase.as<u64>(), p0, np,
-                                                                         min_overlap, f->b_state.as<u8>(), f->b_self.as<u8>(),
-                                                                         f->g_raw.as<FmEdge>(), f->b_ctr.as<u64>());
-            if ((rc = tm.end(&st.ms_tail))) return rc;
-            st.launches += 2;
-        }
-        tm.begin();
-        k_fm_bigraph_longest<<<grid_for(nraw, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), f->b_rawbase.as<u64>(), 3 * np, nraw,
-                                                                         f->g_flag.as<u8>());
-        k_fm_graph_degree<<<grid_for(3 * np, 256), 256, 0, f->stream>>>(f->g_flag.as<u8>(), f->b_rawbase.as<u64>(), 3 * np,
-                                                                        f->g_deg.as<u32>());
-        deg.resize(3 * np);
-        HIPCHK(f, hipMemcpyAsync(deg.data(), f->g_deg.p, 3 * np * 4, hipMemcpyDeviceToHost, f->stream));
-        if ((rc = tm.end(&st.ms_build))) return rc;
-        st.launches += 2;
-        oseg.resize(3 * np + 1);
-        for (u64 k = 0; k < 3 * np; k++) { oseg[k] = aoff[3 * p0 + k]; aoff[3 * p0 + k + 1] = aoff[3 * p0 + k] + deg[k]; }
-        oseg[3 * np] = aoff[3 * p1];
-        if (aoff[3 * p1] > aoff[3 * p0]) {
-            if ((rc = fm_bigraph_reserve(f, aoff[3 * p0], aoff[3 * p1]))) return rc;
-            HIPCHK(f, hipMemcpyAsync(f->g_oseg.p, oseg.data(), (3 * np + 1) * 8, hipMemcpyHostToDevice, f->stream));
-            tm.begin();
-            k_fm_graph_scatter<<<grid_for(nraw, 256), 256, 0, f->stream>>>(f->g_raw.as<FmEdge>(), f->g_flag.as<u8>(), f->b_rawbase.as<u64>(),
-                                                                           f->g_oseg.as<u64>(), 3 * np, nraw, f->g_edges.as<FmEdge>());
-            if ((rc = tm.end(&st.ms_build))) return rc;     // oseg is host memory
-            st.launches++;
-        }
-        p0 = p1;
-    }
-    u64 h[FM_BG_NCTR];
-    HIPCHK(f, hipMemcpyAsync(h, f->b_ctr.p, sizeof h, hipMemcpyDeviceToHost, f->stream));
-    if ((rc = fm_sync(f))) return rc;
-    if (h[FM_BG_BADLEN]) {
-        f->err = "debwt_fm_string_graph_both: " + std::to_string(h[FM_BG_BADLEN]) + " overlaps between kept records cover one of them whole";
-        return DEBWT_EINTERNAL;
-    }
-    st.seeds = h[FM_BG_SEEDS]; st.tail_hits = h[FM_BG_TAILS];
-    return DEBWT_OK;
-}
-
-}  // namespace
+// ---- string graph over both strands: what comes between fm_graph_found and fm_graph_finish ---------------------------
+// fm_graph_found leaves A in g_edges: ++, +- and -+ of every record.  Here the mirrors of the ++ edges are counted per
+// target, the lists of the 2 nrec nodes laid out, every edge placed in its list (b_cat) and ranked into E (g_edges again),
+// which leaves every list in (length, target) order.  g_stats is not touched: debwt_fm_graph_stats_get goes on answering
+// for the last strand-0 call.
 
 extern "C" int debwt_fm_string_graph_both(debwt_fm *f, uint32_t min_overlap, uint32_t flags, uint8_t *state, uint64_t *edge_offsets,
                                           debwt_fm_edge *edges, uint64_t capacity) {
     if (!f || !state || !edge_offsets) return DEBWT_EINVAL;
+    const char *who = "debwt_fm_string_graph_both";
     const auto t0 = std::chrono::steady_clock::now();
     f->b_stats = debwt_fm_graph_both_stats{};
     if (!min_overlap) { f->err = "debwt_fm_string_graph_both: min_overlap must be at least 1"; return DEBWT_EINVAL; }
     if (flags & ~DEBWT_FM_GRAPH_ALL_EDGES) { f->err = "debwt_fm_string_graph_both: unknown flags"; return DEBWT_EINVAL; }
     if (f->nrec >> 31) { f->err = "debwt_fm_string_graph_both: 2^31 records or more"; return DEBWT_EINVAL; }
     HIPCHK(f, hipSetDevice(f->device));
-    FmGraphStatsKeep keep(f);
     debwt_fm_graph_both_stats &st = f->b_stats;
     const u64 nrec = f->nrec, nn = 2 * nrec;
     FmGraphTimer tm(f);
     int rc = tm.init();
     if (rc) return rc;
-    std::vector<u8> selfrc;
-    std::vector<u64> aoff;
-    if ((rc = fm_bigraph_found(f, tm, min_overlap, state, selfrc, aoff))) return rc;
-    // the mirrors of the ++ edges, the lists of the 2 nrec nodes, every edge to its list and to its rank
+    std::vector<uint64_t> aoff(3 * nrec + 1, 0);
+    if ((rc = fm_graph_found(f, st, who, tm, min_overlap, state, aoff.data()))) return rc;
     const u64 na = aoff[3 * nrec];
     std::vector<u32> mm(nrec, 0);
     if (na) {
@@ -7084,101 +7005,22 @@ extern "C" int debwt_fm_string_graph_both(debwt_fm *f, uint32_t min_overlap, uin
                                                                      f->g_eoff.as<u64>(), f->b_self.as<u8>(), f->b_cur.as<u32>(),
                                                                      f->b_cat.as<FmEdge>());
         if ((rc = tm.end(&st.ms_merge))) return rc;
-        if ((rc = fm_bigraph_reserve(f, 0, ne))) return rc;    // A has been read: E takes its place
+        if ((rc = fm_graph_reserve(f, who, 0, ne))) return rc; // A has been read: E takes its place
         tm.begin();
         k_fm_bigraph_rank<<<grid_for(ne, 256), 256, 0, f->stream>>>(f->b_cat.as<FmEdge>(), f->g_eoff.as<u64>(), nn, ne,
                                                                     f->g_edges.as<FmEdge>());
         if ((rc = tm.end(&st.ms_merge))) return rc;
         st.launches += 2;
     }
-    const FmEdge *d_final = f->g_edges.as<FmEdge>();
-    if (!(flags & DEBWT_FM_GRAPH_ALL_EDGES) && ne) {
-        std::vector<u64> len(nn);
-        for (u64 i = 0; i < nrec; i++) len[2 * i] = len[2 * i + 1] = (i + 1 < nrec ? f->rec_starts[i + 1] : f->n) - 1 - f->rec_starts[i];
-        FM_ENSURE(f, f->g_len, (size_t)nn * 8);
-        HIPCHK(f, hipMemcpyAsync(f->g_len.p, len.data(), nn * 8, hipMemcpyHostToDevice, f->stream));
-        if ((rc = fm_graph_reduce(f, tm, nn, f->g_edges.as<FmEdge>(), ne))) return rc;
-        std::vector<u32> deg(nn);
-        FM_ENSURE(f, f->g_deg, (size_t)nn * 4);
-        tm.begin();
-        k_fm_graph_degree<<<grid_for(nn, 256), 256, 0, f->stream>>>(f->g_keep.as<u8>(), f->g_eoff.as<u64>(), nn, f->g_deg.as<u32>());
-        HIPCHK(f, hipMemcpyAsync(deg.data(), f->g_deg.p, nn * 4, hipMemcpyDeviceToHost, f->stream));
-        if ((rc = tm.end(&f->g_stats.ms_reduce))) return rc;
-        for (u64 i = 0; i < nn; i++) edge_offsets[i + 1] = edge_offsets[i] + deg[i];
-        const u64 nk = edge_offsets[nn];
-        if (nk != ne - f->g_stats.reducible) { f->err = "debwt_fm_string_graph_both: the kept edges do not add up"; return DEBWT_EINTERNAL; }
-        FM_ENSURE(f, f->g_oseg, (size_t)(nn + 1) * 8);
-        FM_ENSURE(f, f->g_out, (size_t)std::max<u64>(nk, 1) * sizeof(FmEdge));
-        HIPCHK(f, hipMemcpyAsync(f->g_oseg.p, edge_offsets, (nn + 1) * 8, hipMemcpyHostToDevice, f->stream));
-        tm.begin();
-        k_fm_graph_scatter<<<grid_for(ne, 256), 256, 0, f->stream>>>(f->g_edges.as<FmEdge>(), f->g_keep.as<u8>(), f->g_eoff.as<u64>(),
-                                                                     f->g_oseg.as<u64>(), nn, ne, f->g_out.as<FmEdge>());
-        if ((rc = tm.end(&f->g_stats.ms_reduce))) return rc;
-        st.launches += 2 + f->g_stats.launches;
-        st.reducible = f->g_stats.reducible; st.lookups = f->g_stats.lookups; st.ms_reduce = f->g_stats.ms_reduce;
-        d_final = f->g_out.as<FmEdge>();
-    }
-    const u64 total = edge_offsets[nn];
-    if (capacity < total || (total && !edges)) {
-        f->err = "debwt_fm_string_graph_both: capacity below the edges (edge_offsets[2 * nrec] = " + std::to_string(total) + ")";
-        return DEBWT_ERANGE;
-    }
-    if (total) {                                               // the ranks left every list in (length, target) order
-        HIPCHK(f, hipMemcpyAsync(edges, d_final, (size_t)total * sizeof(FmEdge), hipMemcpyDeviceToHost, f->stream));
-        if ((rc = fm_sync(f))) return rc;
-    }
+    if ((rc = fm_graph_finish(f, st, who, tm, flags, nn, edge_offsets, edges, capacity))) return rc;
     st.ms_wall = (float)fm_ms_since(t0);
     return DEBWT_OK;
 }
 
 extern "C" int debwt_fm_unitigs_both(const uint8_t *state, const uint64_t *edge_offsets, const debwt_fm_edge *edges, uint64_t nnodes,
                                      uint64_t *unitig_offsets, uint32_t *members, uint8_t *circular, uint64_t *nunitigs) {
-    if (!edge_offsets || !unitig_offsets || !nunitigs || (nnodes && (!state || !members || !circular)) || (nnodes >> 32) || (nnodes & 1))
-        return DEBWT_EINVAL;
-    const u64 e0 = edge_offsets[0];
-    for (u64 i = 0; i < nnodes; i++)
-        if (edge_offsets[i + 1] < edge_offsets[i]) return DEBWT_EINVAL;
-    if (edge_offsets[nnodes] > e0 && !edges) return DEBWT_EINVAL;
-    constexpr u32 NONE = 0xFFFFFFFFu;
-    std::vector<u32> indeg(nnodes, 0), next(nnodes, NONE);
-    for (u64 i = 0; i < nnodes; i++)
-        for (u64 e = edge_offsets[i]; e < edge_offsets[i + 1]; e++) {
-            if (edges[e].record >= nnodes || state[i] != 0 || state[edges[e].record] != 0) return DEBWT_EINVAL;
-            indeg[edges[e].record]++;
-        }
-    auto selfrc = [&](u64 v) { return state[v & ~1ull] == 0 && state[v | 1] == 1; };
-    std::vector<u8> has_in(nnodes, 0), on_chain(nnodes, 0);
-    for (u64 i = 0; i < nnodes; i++)
-        if (edge_offsets[i + 1] - edge_offsets[i] == 1) {
-            const u32 w = edges[edge_offsets[i]].record;
-            if (w != i && w != (i ^ 1) && indeg[w] == 1 && !selfrc(i) && !selfrc(w)) { next[i] = w; has_in[w] = 1; }
-        }
-    for (u64 i = 0; i < nnodes; i++)                           // the nodes that a node without an incoming link leads to
-        if (state[i] == 0 && !has_in[i])
-            for (u64 v = i; v != NONE; v = next[v]) on_chain[v] = 1;
-    // every unitig of the link rule in ascending first member; it is written, and stays when its mirror starts no lower
-    u64 nu = 0, nm = 0;
-    unitig_offsets[0] = 0;
-    for (u64 i = 0; i < nnodes; i++) {
-        if (state[i] != 0 || (has_in[i] && on_chain[i])) continue;
-        const u64 m0 = nm;
-        u64 mirror_first;
-        if (!has_in[i]) {
-            u64 last = i;
-            for (u64 v = i; v != NONE; v = next[v]) { members[nm++] = (u32)v; last = v; }
-            mirror_first = selfrc(last) ? last : (last ^ 1);
-            circular[nu] = 0;
-        } else {                                               // the lowest node of a cycle: the ones after it get on_chain
-            u64 v = i;
-            mirror_first = NONE;
-            do { members[nm++] = (u32)v; on_chain[v] = 1; mirror_first = std::min<u64>(mirror_first, v ^ 1); v = next[v]; } while (v != i);
-            circular[nu] = 1;
-        }
-        if (mirror_first < i) { nm = m0; continue; }           // the mirror has been, or will be, reported
-        unitig_offsets[++nu] = nm;
-    }
-    *nunitigs = nu;
-    return DEBWT_OK;
+    if (nnodes & 1) return DEBWT_EINVAL;
+    return fm_unitigs(true, state, edge_offsets, edges, nnodes, unitig_offsets, members, circular, nunitigs);
 }
 
 extern "C" int debwt_fm_graph_both_stats_get(const debwt_fm *f, debwt_fm_graph_both_stats *out) {

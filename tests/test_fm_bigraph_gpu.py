@@ -160,6 +160,32 @@ def test_batches_do_not_change_results(api, main, monkeypatch):
         check(fm.string_graph_both(min_overlap=20, reduce=False), G, G.E)
 
 
+# Every field of graph_both_stats() that is no time, on the crafted set at min_overlap 20, by (limits, reduce).  Recorded on
+# an MI355X at the commit before the two graph builders shared one batch loop: they are sums and counts, and the batches
+# depend on the input and the two limits alone.  A difference means a launch, a batch or a buffer changed.
+_COUNTS = {"records": 449, "kept": 385, "duplicates": 10, "contained": 54, "hits": 3587, "edges": 5845, "edge_bytes": 46760,
+           "selfrc": 1, "seeds": 385, "seed_rows": 1498, "tail_hits": 1419, "edges_kind": [1500, 1419, 1426, 1500]}
+PINNED = {
+    (None, True): dict(_COUNTS, reducible=5098, lookups=5098, launches=18, scratch_bytes=1064397),
+    (None, False): dict(_COUNTS, reducible=0, lookups=0, launches=15, scratch_bytes=1064397),
+    ("64", True): dict(_COUNTS, reducible=5098, lookups=5098, launches=4211, scratch_bytes=13423),
+    ("64", False): dict(_COUNTS, reducible=0, lookups=0, launches=4208, scratch_bytes=13423),
+}
+
+
+@pytest.mark.parametrize("limits", [None, "64"])
+def test_stats_are_pinned(api, main, monkeypatch, limits):
+    fm = main[2]
+    for name in ("DEBWT_FM_OVERLAP_SLOTS", "DEBWT_FM_OVERLAP_HITS"):
+        monkeypatch.setenv(name, limits) if limits else monkeypatch.delenv(name, raising=False)
+    got = {}
+    for reduce in (True, False):
+        fm.string_graph_both(min_overlap=20, reduce=reduce)
+        got[limits, reduce] = {k: v for k, v in fm.graph_both_stats().items() if not k.startswith("ms_")}
+        print("PINNED[%r, %r] = %r" % (limits, reduce, got[limits, reduce]))
+    assert got == {k: v for k, v in PINNED.items() if k[0] == limits}
+
+
 def test_index_from_files_and_sample_steps(api, main):
     strs, _, own, _, graphs = main
     G = graphs[20]

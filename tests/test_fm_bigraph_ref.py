@@ -1,7 +1,8 @@
 """The string graph over both strands, no GPU: what follows from applying string_graph_ref.Graph to the doubled collection
 (the state fold rule, mirror symmetry of E and of the irreducible graph, every kept read in exactly one oriented unitig)
 on stranded read sets with crafted corners, and debwt_fm_unitigs_both (api.unitigs_both) against definition 4b taken
-literally, on those graphs, on hand-made ones and on bad input."""
+literally, on those graphs, on hand-made ones and on bad input; debwt_fm_unitigs (api.unitigs) on the same graphs against
+definition 4, which the rules of 4b must not reach."""
 import numpy as np
 import pytest
 
@@ -9,6 +10,7 @@ from bigraph_ref import (all_unitigs_both, crafted, doubled, fold_states, is_sel
                          unitigs_both)
 from overlap_ref import revcomp, synthetic_reads
 from string_graph_ref import KEPT, Graph, flat, repeat_reads, tiling
+from string_graph_ref import unitigs as plain_unitigs
 
 
 @pytest.fixture(scope="module")
@@ -145,6 +147,29 @@ def test_unitigs_both_hand_made(name):
         assert want == ([[0, 6]], [0])
     if name == "no edges":
         assert want == ([[0], [2]], [0, 0])
+
+
+def api_unitigs(state, lists):
+    from debwt_amd import api
+    offs, edges = flat(lists)
+    uoff, mem, circ = api.unitigs(state, offs, np.array(edges, dtype=api._EDGE_DTYPE).reshape(-1))
+    assert len(uoff) == len(circ) + 1 and int(uoff[0]) == 0
+    return [[int(x) for x in mem[int(uoff[u]):int(uoff[u + 1])]] for u in range(len(circ))], [int(c) for c in circ]
+
+
+def test_strand_zero_unitigs_keep_the_plain_rule(crafted_set):
+    """api.unitigs on a graph of 2 nrec nodes is definition 4 as string_graph_ref has it: none of the rules of
+    unitigs_both (no link to v ^ 1, none at a self-rc read, one of a mirror pair) reaches the strand-0 call."""
+    for name in sorted(HAND):
+        state, lists = HAND[name]
+        plain = plain_unitigs(state, lists)
+        assert api_unitigs(state, lists) == plain, name
+        if name in ("a link to the own mirror", "through a self-rc node"):
+            assert plain != api_unitigs_both(state, lists), name
+    assert plain_unitigs(*HAND["a link to the own mirror"]) == ([[0, 1]], [0])
+    assert plain_unitigs(*HAND["through a self-rc node"]) == ([[0, 2, 1]], [0])
+    for G in crafted_set[2].values():
+        assert api_unitigs(G.state, G.I) == (G.paths, G.circular)
 
 
 def test_unitigs_both_errors():

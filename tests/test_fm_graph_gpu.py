@@ -199,6 +199,31 @@ def test_batches_do_not_change_results(api, synth, monkeypatch):
         assert base > 20                                       # many batches, or many expansions of one batch
 
 
+# Every field of graph_stats() that is no time, on the synthetic reads at min_overlap 20, by (limits, reduce).  Recorded on
+# an MI355X at the commit before the two graph builders shared one batch loop: they are sums and counts, and the batches
+# depend on the input and the two limits alone.  A difference means a launch, a batch or a buffer changed.
+_COUNTS = {"records": 436, "kept": 375, "duplicates": 9, "contained": 52, "hits": 3493, "edges": 2921, "edge_bytes": 23368}
+PINNED = {
+    (None, True): dict(_COUNTS, reducible=2549, lookups=2549, launches=12, scratch_bytes=594839),
+    (None, False): dict(_COUNTS, reducible=0, lookups=0, launches=9, scratch_bytes=594839),
+    ("64", True): dict(_COUNTS, reducible=2549, lookups=2549, launches=3001, scratch_bytes=7034),
+    ("64", False): dict(_COUNTS, reducible=0, lookups=0, launches=2998, scratch_bytes=7034),
+}
+
+
+@pytest.mark.parametrize("limits", [None, "64"])
+def test_stats_are_pinned(api, synth, monkeypatch, limits):
+    strs, fm, _ = synth
+    for name in ("DEBWT_FM_OVERLAP_SLOTS", "DEBWT_FM_OVERLAP_HITS"):
+        monkeypatch.setenv(name, limits) if limits else monkeypatch.delenv(name, raising=False)
+    got = {}
+    for reduce in (True, False):
+        fm.string_graph(min_overlap=20, reduce=reduce)
+        got[limits, reduce] = {k: v for k, v in fm.graph_stats().items() if not k.startswith("ms_")}
+        print("PINNED[%r, %r] = %r" % (limits, reduce, got[limits, reduce]))
+    assert got == {k: v for k, v in PINNED.items() if k[0] == limits}
+
+
 # ---- the reduction alone -----------------------------------------------------------------------------------------------
 
 def reduce_on_gpu(api, fm, reclen, lists):
