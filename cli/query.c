@@ -15,7 +15,9 @@
  *   deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq
  *   deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq
  *   deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]
+ *                      [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]
  *   deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]
+ *                      [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]
  *
  * index ingests INPUT as deBWT does (same -t, same --iupac SEED: the same text), checks that OUT is that text's BWT while
  * it samples the suffix array every S rows (a power of two in 1..1024, default 32), and writes OUT.sa; exit status 1 when
@@ -96,6 +98,12 @@
  * stay per read, the links are "L a +|- b +|- <L>M", and of an edge u -> v and its mirror v' -> u' (the same overlap seen
  * from the other strand) the one whose pair of oriented numbers (2 * read + strand) is lower is written; unitigs writes
  * every read once, in one orientation, and first=J+ or first=J- names the first read and its strand.
+ * --clean clips the tips and pops the bubbles of the irreducible graph before it is written or walked
+ * (debwt_fm_graph_clean): a dead-end chain of at most N reads (--max-tip, default 4) beside a way that goes on, and all but
+ * the longest of the unbranched chains of at most N reads (--max-bubble, default 16) that lead from one read to one other,
+ * in at most R rounds (--clean-rounds, default 8); any of the three options implies --clean, and --all-edges does not go
+ * with it.  The reads removed get no S line and no L line, --states names them clipped or popped, and stderr gets a
+ * second summary line.  Without --clean the output is what it was.
  *
  * OUT.sa: 16 little-endian u64 header words -- magic, n, nrec, S, '$' row, the row census of OUT (4 words), the sample
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
@@ -127,7 +135,9 @@ static void usage(void) {
             "       deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq\n"
             "       deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
             "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]\n"
+            "                          [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]\n"
             "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]\n"
+            "                          [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]\n"
             "index writes OUT.sa (the suffix-array samples) and exits 1 when OUT is not the BWT of INPUT;\n"
             "count / locate print name<TAB>count[<TAB>record:offset,...] per pattern of a FASTA or FASTQ file;\n"
             "with --mismatches K (0..4), --both-strands or --best: name<TAB>total<TAB>c0,..,cK (count) or\n"
@@ -154,7 +164,10 @@ static void usage(void) {
             "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
             "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained;\n"
             "--both-strands takes every read on both strands (L a +|- b +|- <L>M, an edge and its mirror written once;\n"
-            "first=J+|- in the FASTA headers)\n");
+            "first=J+|- in the FASTA headers); --clean first clips dead-end chains of at most N reads (--max-tip, default 4) and\n"
+            "pops all but the longest of parallel chains of at most N reads (--max-bubble, default 16), in at most R rounds\n"
+            "(--clean-rounds, default 8; each of the three implies --clean; not with --all-edges): the reads removed get no S\n"
+            "and no L line and --states names them clipped or popped\n");
 }
 
 static int parse_u64(const char *s, uint64_t *out) {
@@ -986,7 +999,7 @@ static uint32_t mirror_node(const uint8_t *state, uint32_t v) {
 }
 
 static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_edges, const char *states, int want_unitigs,
-                     int both) {
+                     int both, const debwt_fm_clean_opts *clean) {
     debwt_fm *fm = NULL;
     if (open_index(out, device, &fm)) return 1;
     int ret = 1, rc = 0;
@@ -1016,11 +1029,21 @@ static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_
         break;
     }
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    if (clean) {                                          /* the states get clipped and popped, the edges at them go */
+        debwt_fm_clean_opts co = *clean;
+        co.flags = both ? DEBWT_FM_CLEAN_MIRRORED : 0u;
+        uint8_t *keep = malloc(eoff[nn] ? eoff[nn] : 1);
+        if (!keep) { fprintf(stderr, "out of memory\n"); goto done; }
+        rc = debwt_fm_graph_clean(fm, state, eoff, edges, nn, &co, state, keep);
+        if (!rc) rc = debwt_fm_edges_compact(eoff, edges, keep, nn, eoff, edges) ? DEBWT_EINTERNAL : 0;
+        free(keep);
+        if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    }
     if (states) {
         if (!(sf = fopen(states, "w"))) { fprintf(stderr, "cannot write %s\n", states); goto done; }
         for (uint64_t i = 0; i < nrec; i++) {
             const uint8_t x = state[both ? 2 * i : i];        /* per read: the state of its first node */
-            fprintf(sf, "%llu\t%s\n", (unsigned long long)i, x == 0 ? "kept" : x == 1 ? "duplicate" : "contained");
+            fprintf(sf, "%llu\t%s\n", (unsigned long long)i, x == 0 ? "kept" : x == 1 ? "duplicate" : x == 2 ? "contained" : x == DEBWT_FM_NODE_CLIPPED ? "clipped" : "popped");
         }
         if (fclose(sf)) { sf = NULL; fprintf(stderr, "cannot write %s\n", states); goto done; }
         sf = NULL;
@@ -1032,6 +1055,13 @@ static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_
         debwt_fm_graph_both_stats_get(fm, &bs);
         st.kept = bs.kept; st.duplicates = bs.duplicates; st.contained = bs.contained;
         st.edges = bs.edges; st.reducible = bs.reducible; st.ms_wall = bs.ms_wall;
+    }
+    if (clean) {
+        debwt_fm_clean_stats cs;
+        debwt_fm_clean_stats_get(fm, &cs);
+        fprintf(stderr, "clean: %llu rounds, %llu tips of %llu nodes clipped, %llu branches of %llu nodes popped; %llu edges left, %.1f ms\n",
+                (unsigned long long)cs.rounds, (unsigned long long)cs.tips, (unsigned long long)cs.tip_nodes,
+                (unsigned long long)cs.bubbles, (unsigned long long)cs.bubble_nodes, (unsigned long long)eoff[nn], cs.ms_wall);
     }
     uint64_t written = eoff[nn];
     if (!want_unitigs) {
@@ -1135,7 +1165,9 @@ int main(int argc, char **argv) {
     debwt_fm_correct_opts ko;
     debwt_fm_correct_defaults(&ko);
     const char *report = NULL, *states = NULL;
-    int k_given = 0, all_edges = 0, graph_both = 0;
+    int k_given = 0, all_edges = 0, graph_both = 0, clean = 0;
+    debwt_fm_clean_opts cl;
+    debwt_fm_clean_defaults(&cl);
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
         if (a[0] != '-' || !a[1]) {
@@ -1150,6 +1182,7 @@ int main(int argc, char **argv) {
         if (mode == 6 && !strcmp(a, "--all")) { all = 1; continue; }
         if (mode == 9 && !strcmp(a, "--all-edges")) { all_edges = 1; continue; }
         if ((mode == 9 || mode == 10) && !strcmp(a, "--both-strands")) { graph_both = 1; continue; }
+        if ((mode == 9 || mode == 10) && !strcmp(a, "--clean")) { clean = 1; continue; }
         if (mode == 8 && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
         if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mode == 4 && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
@@ -1231,6 +1264,18 @@ int main(int argc, char **argv) {
         }
         else if (mode == 8 && !strcmp(a, "--report")) report = v;
         else if ((mode == 9 || mode == 10) && !strcmp(a, "--states")) states = v;
+        else if ((mode == 9 || mode == 10) && !strcmp(a, "--max-tip")) {
+            if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-tip: a number of reads of at least 0\n"); return 1; }
+            cl.max_tip = (uint32_t)v64; clean = 1;
+        }
+        else if ((mode == 9 || mode == 10) && !strcmp(a, "--max-bubble")) {
+            if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-bubble: a number of reads of at least 0\n"); return 1; }
+            cl.max_bubble = (uint32_t)v64; clean = 1;
+        }
+        else if ((mode == 9 || mode == 10) && !strcmp(a, "--clean-rounds")) {
+            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--clean-rounds: a number of at least 1\n"); return 1; }
+            cl.max_rounds = (uint32_t)v64; clean = 1;
+        }
         else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
         else { usage(); return 1; }
     }
@@ -1239,8 +1284,9 @@ int main(int argc, char **argv) {
         return cmd_extract(out, file, (int)device);
     }
     if (mode == 9 || mode == 10) {
-        if (!out || file) { usage(); return 1; }
-        return cmd_graph(out, (int)device, (uint32_t)min_overlap, all_edges, states, mode == 10, graph_both);
+        if (!out || file || (clean && all_edges)) { usage(); return 1; }
+        if (clean && !cl.max_tip && !cl.max_bubble) { fprintf(stderr, "--clean: --max-tip and --max-bubble are both 0\n"); return 1; }
+        return cmd_graph(out, (int)device, (uint32_t)min_overlap, all_edges, states, mode == 10, graph_both, clean ? &cl : NULL);
     }
     if (!out || !file) { usage(); return 1; }
     if (mode == 4) {

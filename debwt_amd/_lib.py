@@ -187,6 +187,19 @@ class DebwtFmGraphBothStats(ctypes.Structure):
         return d
 
 
+class DebwtFmCleanOpts(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint32) for n in ("max_tip", "max_bubble", "max_rounds", "flags")]
+
+
+class DebwtFmCleanStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("nodes", "edges", "rounds", "tips", "tip_nodes", "bubbles", "bubble_nodes",
+                                                 "steps", "launches")] +
+                [(n, ctypes.c_float) for n in ("ms_clean", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DebwtFmJob(ctypes.Structure):
     _fields_ = [("pattern", ctypes.c_uint64), ("diag", ctypes.c_int64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32)]
 
@@ -332,6 +345,7 @@ SYMBOLS = [
     "debwt_fm_correct", "debwt_fm_correct_stats_get",
     "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
     "debwt_fm_string_graph_both", "debwt_fm_unitigs_both", "debwt_fm_graph_both_stats_get",
+    "debwt_fm_clean_defaults", "debwt_fm_graph_clean", "debwt_fm_edges_compact", "debwt_fm_clean_stats_get",
 ]
 
 
@@ -644,6 +658,14 @@ def lib():
     L.debwt_fm_unitigs_both.argtypes = [u8p, u64p, edgep, ctypes.c_uint64, u64p, u32p, u8p, u64p]
     L.debwt_fm_graph_both_stats_get.restype = ctypes.c_int
     L.debwt_fm_graph_both_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmGraphBothStats)]
+    L.debwt_fm_clean_defaults.restype = None
+    L.debwt_fm_clean_defaults.argtypes = [ctypes.POINTER(DebwtFmCleanOpts)]
+    L.debwt_fm_graph_clean.restype = ctypes.c_int
+    L.debwt_fm_graph_clean.argtypes = [vp, u8p, u64p, edgep, ctypes.c_uint64, ctypes.POINTER(DebwtFmCleanOpts), u8p, u8p]
+    L.debwt_fm_edges_compact.restype = ctypes.c_int
+    L.debwt_fm_edges_compact.argtypes = [u64p, edgep, u8p, ctypes.c_uint64, u64p, edgep]
+    L.debwt_fm_clean_stats_get.restype = ctypes.c_int
+    L.debwt_fm_clean_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmCleanStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

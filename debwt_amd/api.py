@@ -569,6 +569,13 @@ class FMIndex:
         reverse-complemented (o = 1).  Returns a BiGraphResult."""
         return BiGraphResult(self, *self._graph_call(self._L.debwt_fm_string_graph_both, 2 * self.nrec, min_overlap, reduce))
 
+    def clean_stats(self):
+        """What the last graph_clean() on this index did (debwt_fm_clean_stats_get): nodes, edges, rounds, tips clipped and
+        their nodes, branches popped and their nodes, nodes visited by the walks, launches, ms of the kernels and wall."""
+        st = _lib.DebwtFmCleanStats()
+        self._chk(self._L.debwt_fm_clean_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def graph_both_stats(self):
         """What the last string_graph_both() did (debwt_fm_graph_both_stats_get): the fields of graph_stats() with the
         states counted in reads, self-rc reads, tail seeds, seed rows located, tail hits verified, the edges of E per kind
@@ -917,6 +924,8 @@ _TRIAL_DTYPE = np.dtype([("run_a", np.uint32), ("run_b", np.uint32), ("pos", np.
 _OVERLAP_DTYPE = np.dtype([("record", np.uint32), ("length", np.uint32), ("strand", np.uint32), ("flags", np.uint32)])
 GRAPH_ALL_EDGES = 1                                    # option flag of debwt_fm_string_graph
 NODE_KEPT, NODE_DUPLICATE, NODE_CONTAINED = 0, 1, 2    # GraphResult.state
+NODE_CLIPPED, NODE_POPPED = 3, 4                       # states that graph_clean() writes: in a tip, in a popped branch
+CLEAN_MIRRORED = 1                                     # option flag of debwt_fm_graph_clean
 _EDGE_DTYPE = np.dtype([("record", np.uint32), ("length", np.uint32)])
 _ALN_DTYPE = np.dtype([("score", np.int32), ("qbeg", np.uint32), ("qend", np.uint32), ("edits", np.uint32),
                        ("tbeg", np.uint64), ("tend", np.uint64)])
@@ -1208,6 +1217,18 @@ class _GraphArrays:
         """structured array (record, length) of the out-edges of record i (GraphResult) or node i (BiGraphResult)"""
         return self.edges[int(self.offsets[i]):int(self.offsets[i + 1])]
 
+    def clean(self, max_tip=4, max_bubble=16, max_rounds=8):
+        """The graph with its tips clipped and its bubbles popped (graph_clean(), on the graph's index; mirrored for a
+        BiGraphResult): a new result of the same class whose state holds NODE_CLIPPED and NODE_POPPED for the nodes
+        removed and whose edges are those between the nodes left, in their order.  unitigs() and sequences() work on it
+        as before.  ValueError for a graph that is not reduced."""
+        if not self.reduced:
+            raise ValueError("clean() needs the irreducible graph (reduce=True)")
+        state, keep = graph_clean(self.index, self.state, self.offsets, self.edges, max_tip, max_bubble, max_rounds,
+                                  mirrored=isinstance(self, BiGraphResult))
+        offs, edges = edges_compact(self.offsets, self.edges, keep)
+        return type(self)(self.index, state, offs, edges, True)
+
 
 class GraphResult(_GraphArrays):
     """String graph of FMIndex.string_graph.  state: per record NODE_KEPT, NODE_DUPLICATE or NODE_CONTAINED; record i's
@@ -1254,6 +1275,50 @@ def edges_reduce(index, reclen, offsets, edges):
                                               e.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)),
                                               keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
     return keep[:len(e)]
+
+
+def graph_clean(index, state, offsets, edges, max_tip=4, max_bubble=16, max_rounds=8, mirrored=False):
+    """Tips and bubbles of any graph on the index's GPU (debwt_fm_graph_clean, definition 6 of debwt_hip.h).  state: one
+    byte per node, 0 for a node that takes part; node i's edges are edges[offsets[i] .. offsets[i + 1]).  A dead-end chain of
+    at most max_tip nodes at a junction that has another way on is clipped (NODE_CLIPPED); of the unbranched chains of at
+    most max_bubble nodes that lead from one junction to one node, all but the longest (then the one with the lowest node)
+    are popped (NODE_POPPED); rounds of both repeat until one removes nothing or max_rounds have run.  mirrored: the node
+    ids are 2r + o of a graph over both strands, and a bubble gets the same verdict from both ends.  Returns (state_out,
+    edge_keep), one np.uint8 per node and per edge.  An edge at a node whose state is not 0, a target out of range, no
+    phase to run (max_tip == max_bubble == 0) or max_rounds == 0 raises DebwtError (DEBWT_EINVAL)."""
+    state = np.ascontiguousarray(state, dtype=np.uint8)
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    e = np.ascontiguousarray(np.asarray(edges, dtype=_EDGE_DTYPE))
+    nn = len(state)
+    if len(offs) != nn + 1 or int(offs.max()) > len(e):
+        raise ValueError("offsets fit neither the nodes nor the edges")
+    opts = _lib.DebwtFmCleanOpts(int(max_tip), int(max_bubble), int(max_rounds), CLEAN_MIRRORED if mirrored else 0)
+    out = np.zeros(max(nn, 1), dtype=np.uint8)
+    keep = np.zeros(max(len(e), 1), dtype=np.uint8)
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    index._chk(index._L.debwt_fm_graph_clean(index._h, state.ctypes.data_as(u8p) if nn else None, _p64(offs),
+                                             e.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmEdge)) if len(e) else None, nn,
+                                             ctypes.byref(opts), out.ctypes.data_as(u8p), keep.ctypes.data_as(u8p)))
+    return out[:nn], keep[:len(e)]
+
+
+def edges_compact(offsets, edges, keep):
+    """(offsets_out, edges_out): the edges with keep != 0, in their order, on the host (debwt_fm_edges_compact)"""
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+    e = np.ascontiguousarray(np.asarray(edges, dtype=_EDGE_DTYPE))
+    keep = np.ascontiguousarray(keep, dtype=np.uint8)
+    if len(offs) < 1 or int(offs.max()) > len(e) or len(keep) != len(e):
+        raise ValueError("offsets and keep do not fit the edges")
+    nn = len(offs) - 1
+    out_offs = np.zeros(nn + 1, dtype=np.uint64)
+    out = np.zeros(max(len(e), 1), dtype=_EDGE_DTYPE)
+    edgep = ctypes.POINTER(_lib.DebwtFmEdge)
+    rc = _lib.lib().debwt_fm_edges_compact(_p64(offs), e.ctypes.data_as(edgep) if len(e) else None,
+                                           keep.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if len(e) else None, nn,
+                                           _p64(out_offs), out.ctypes.data_as(edgep))
+    if rc:
+        raise DebwtError(rc)
+    return out_offs, out[:int(out_offs[nn])].copy()
 
 
 def unitigs(state, offsets, edges):

@@ -38,6 +38,7 @@
 #include "fm_kmer_kernels.h"
 #include "fm_graph_kernels.h"
 #include "fm_bigraph_kernels.h"
+#include "fm_clean_kernels.h"
 
 namespace {
 
@@ -2988,6 +2989,8 @@ struct debwt_fm {
     debwt_fm_graph_stats g_stats{};
     DevBuf b_state, b_self, b_row, b_cnt, b_whb, b_rawbase, b_tbase, b_pos, b_aoff, b_mm, b_cur, b_cat, b_ctr;   // graph over both strands
     debwt_fm_graph_both_stats b_stats{};
+    DevBuf cl_state, cl_src, cl_cnt, cl_toff, cl_tin, cl_snap, cl_mark, cl_ctr;   // graph cleaning; edges and offsets in g_edges, g_eoff
+    debwt_fm_clean_stats cl_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -7029,6 +7032,154 @@ extern "C" int debwt_fm_graph_both_stats_get(const debwt_fm *f, debwt_fm_graph_b
     return DEBWT_OK;
 }
 
+// ---- graph cleaning (fm_clean_kernels.h) ----------------------------------------------------------------------------------
+// The caller's lists are checked on the host, uploaded once (g_eoff, g_edges) and transposed once; the in-degree counts
+// come back for the host to lay the in-lists out.  A round is at most six launches and one copy of the counters, which
+// tells the host whether the round removed anything.
+
+extern "C" void debwt_fm_clean_defaults(debwt_fm_clean_opts *o) {
+    if (!o) return;
+    o->max_tip = 4; o->max_bubble = 16; o->max_rounds = 8; o->flags = 0;
+}
+
+extern "C" int debwt_fm_graph_clean(debwt_fm *f, const uint8_t *state, const uint64_t *edge_offsets, const debwt_fm_edge *edges,
+                                    uint64_t nnodes, const debwt_fm_clean_opts *opts, uint8_t *state_out, uint8_t *edge_keep) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->cl_stats = debwt_fm_clean_stats{};
+    auto bad = [&](const std::string &why) { f->err = "debwt_fm_graph_clean: " + why; return DEBWT_EINVAL; };
+    if (!opts || !edge_offsets || (nnodes && (!state || !state_out))) return bad("a NULL array");
+    const u32 T = opts->max_tip, B = opts->max_bubble, R = opts->max_rounds;
+    if (!T && !B) return bad("max_tip and max_bubble are both 0");
+    if (!R) return bad("max_rounds must be at least 1");
+    if (opts->flags & ~DEBWT_FM_CLEAN_MIRRORED) return bad("unknown flags");
+    if (nnodes >> 32) return bad("2^32 nodes or more");
+    const bool mirrored = opts->flags & DEBWT_FM_CLEAN_MIRRORED;
+    if (mirrored && (nnodes & 1)) return bad("an odd number of nodes with DEBWT_FM_CLEAN_MIRRORED");
+    for (u64 i = 0; i < nnodes; i++)
+        if (edge_offsets[i + 1] < edge_offsets[i]) return bad("offsets must not decrease");
+    const u64 e0 = edge_offsets[0], ne = edge_offsets[nnodes] - e0;
+    if (ne && (!edges || !edge_keep)) return bad("a NULL array");
+    for (u64 i = 0; i < nnodes; i++)
+        for (u64 e = edge_offsets[i]; e < edge_offsets[i + 1]; e++) {
+            const u64 t = edges[e].record;
+            if (t < nnodes && state[i] == 0 && state[t] == 0) continue;
+            const std::string at = "edge " + std::to_string(e) + " of source " + std::to_string(i);
+            if (t >= nnodes) return bad(at + " names node " + std::to_string(t) + " of " + std::to_string(nnodes));
+            if (state[i] != 0) return bad(at + " leaves a node that is not alive");
+            return bad(at + " leads to node " + std::to_string(t) + ", which is not alive");
+        }
+    debwt_fm_clean_stats &st = f->cl_stats;
+    st.nodes = nnodes; st.edges = ne;
+    if (nnodes && state_out != state) std::memcpy(state_out, state, nnodes);   /* state_out may be state itself */
+    if (!ne) {                                                 // nothing to walk: the one round removes nothing
+        st.rounds = 1;
+        st.ms_wall = (float)fm_ms_since(t0);
+        return DEBWT_OK;
+    }
+    HIPCHK(f, hipSetDevice(f->device));
+    FmGraphTimer tm(f);
+    int rc = tm.init();
+    if (rc) return rc;
+    std::vector<u64> off(nnodes + 1);
+    for (u64 i = 0; i <= nnodes; i++) off[i] = edge_offsets[i] - e0;
+    FM_ENSURE(f, f->g_eoff, (size_t)(nnodes + 1) * 8);
+    FM_ENSURE(f, f->cl_state, (size_t)nnodes);
+    FM_ENSURE(f, f->cl_src, (size_t)ne * 4);
+    FM_ENSURE(f, f->cl_cnt, (size_t)nnodes * 4);
+    FM_ENSURE(f, f->cl_toff, (size_t)(nnodes + 1) * 8);
+    FM_ENSURE(f, f->cl_tin, (size_t)ne * 8);
+    FM_ENSURE(f, f->cl_snap, (size_t)nnodes * 16);
+    FM_ENSURE(f, f->cl_mark, (size_t)ne);
+    FM_ENSURE(f, f->cl_ctr, FM_CL_NCTR * 8);
+    if ((rc = fm_graph_reserve(f, "debwt_fm_graph_clean", 0, ne))) return rc;
+    HIPCHK(f, hipMemcpyAsync(f->g_eoff.p, off.data(), (nnodes + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->g_edges.p, edges + e0, (size_t)ne * sizeof(FmEdge), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->cl_state.p, state, nnodes, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(f->cl_cnt.p, 0, nnodes * 4, f->stream));
+    HIPCHK(f, hipMemsetAsync(f->cl_ctr.p, 0, FM_CL_NCTR * 8, f->stream));
+    const u64 *d_eoff = f->g_eoff.as<u64>();
+    const FmEdge *d_edges = f->g_edges.as<FmEdge>();
+    u8 *d_state = f->cl_state.as<u8>(), *d_mark = f->cl_mark.as<u8>();
+    u32 *d_src = f->cl_src.as<u32>(), *d_cnt = f->cl_cnt.as<u32>();
+    u64 *d_toff = f->cl_toff.as<u64>(), *d_tin = f->cl_tin.as<u64>(), *d_ctr = f->cl_ctr.as<u64>();
+    u32 *d_outdeg = f->cl_snap.as<u32>(), *d_indeg = d_outdeg + nnodes, *d_succ = d_indeg + nnodes, *d_pred = d_succ + nnodes;
+    const FmCleanSnap S{d_outdeg, d_indeg, d_succ, d_pred};
+    const u32 ge = grid_for(ne, 256), gn = grid_for(nnodes, 256);
+    // the transpose: in-degrees on the device, their running sum on the host, the edge numbers into their in-lists
+    std::vector<u32> cnt(nnodes);
+    tm.begin();
+    k_fm_clean_source<<<ge, 256, 0, f->stream>>>(d_eoff, nnodes, d_edges, ne, d_src, d_cnt);
+    HIPCHK(f, hipMemcpyAsync(cnt.data(), d_cnt, nnodes * 4, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = tm.end(&st.ms_clean))) return rc;
+    off[0] = 0;
+    for (u64 i = 0; i < nnodes; i++) off[i + 1] = off[i] + cnt[i];
+    if (off[nnodes] != ne) { f->err = "debwt_fm_graph_clean: the in-degrees do not add up"; return DEBWT_EINTERNAL; }
+    HIPCHK(f, hipMemcpyAsync(d_toff, off.data(), (nnodes + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(d_cnt, 0, nnodes * 4, f->stream));
+    tm.begin();
+    k_fm_clean_transpose<<<ge, 256, 0, f->stream>>>(d_edges, ne, d_toff, d_cnt, d_tin);
+    st.launches += 2;
+    u64 h[FM_CL_NCTR] = {};
+    for (u32 round = 0; round < R; round++) {
+        if (round) tm.begin();
+        const u64 before = h[FM_CL_TIP_NODES] + h[FM_CL_BUBBLE_NODES];
+        k_fm_clean_degree<<<gn, 256, 0, f->stream>>>(d_eoff, d_edges, d_toff, d_tin, d_src, d_state, nnodes, d_outdeg, d_indeg, d_succ, d_pred);
+        st.launches++;
+        if (T) {
+            k_fm_clean_tip_mark<<<ge, 256, 0, f->stream>>>(d_edges, d_src, ne, d_state, S, T, d_mark, d_ctr);
+            k_fm_clean_tip_apply<<<ge, 256, 0, f->stream>>>(d_eoff, d_edges, d_toff, d_tin, d_src, ne, S, T, d_mark, d_state, d_ctr);
+            st.launches += 2;
+        }
+        if (B) {
+            if (T) {                                           // the bubble phase reads the graph after the tips have gone
+                k_fm_clean_degree<<<gn, 256, 0, f->stream>>>(d_eoff, d_edges, d_toff, d_tin, d_src, d_state, nnodes, d_outdeg, d_indeg, d_succ, d_pred);
+                st.launches++;
+            }
+            k_fm_clean_bubble<<<gn, 256, 0, f->stream>>>(d_eoff, d_edges, d_state, nnodes, S, B, mirrored ? 1u : 0u, d_mark, d_ctr);
+            k_fm_clean_bubble_apply<<<ge, 256, 0, f->stream>>>(d_edges, ne, S, B, d_mark, d_state, d_ctr);
+            st.launches += 2;
+        }
+        HIPCHK(f, hipMemcpyAsync(h, d_ctr, sizeof h, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&st.ms_clean))) return rc;
+        st.rounds++;
+        if (h[FM_CL_TIP_NODES] + h[FM_CL_BUBBLE_NODES] == before) break;
+    }
+    st.tips = h[FM_CL_TIPS]; st.tip_nodes = h[FM_CL_TIP_NODES];
+    st.bubbles = h[FM_CL_BUBBLES]; st.bubble_nodes = h[FM_CL_BUBBLE_NODES];
+    st.steps = h[FM_CL_STEPS];
+    HIPCHK(f, hipMemcpyAsync(state_out, d_state, nnodes, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    for (u64 i = 0; i < nnodes; i++)
+        for (u64 e = edge_offsets[i]; e < edge_offsets[i + 1]; e++)
+            edge_keep[e] = state_out[i] == 0 && state_out[edges[e].record] == 0;
+    st.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_edges_compact(const uint64_t *edge_offsets, const debwt_fm_edge *edges, const uint8_t *keep, uint64_t nnodes,
+                                      uint64_t *offsets_out, debwt_fm_edge *edges_out) {
+    if (!edge_offsets || !offsets_out) return DEBWT_EINVAL;
+    for (u64 i = 0; i < nnodes; i++)
+        if (edge_offsets[i + 1] < edge_offsets[i]) return DEBWT_EINVAL;
+    if (edge_offsets[nnodes] > edge_offsets[0] && (!edges || !keep || !edges_out)) return DEBWT_EINVAL;
+    u64 o = 0;
+    for (u64 i = 0; i < nnodes; i++) {
+        const u64 a = edge_offsets[i], b = edge_offsets[i + 1];    // read before offsets_out[i + 1] is written: in place is fine
+        offsets_out[i] = o;
+        for (u64 e = a; e < b; e++)
+            if (keep[e]) edges_out[o++] = edges[e];
+    }
+    offsets_out[nnodes] = o;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_clean_stats_get(const debwt_fm *f, debwt_fm_clean_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->cl_stats;
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
@@ -7042,7 +7193,8 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
                       &f->k_trials, &f->k_trun, &f->k_res, &f->g_coff, &f->g_state, &f->g_hbase, &f->g_raw, &f->g_flag,
                       &f->g_deg, &f->g_oseg, &f->g_edges, &f->g_eoff, &f->g_len, &f->g_keep, &f->g_out, &f->g_ctr, &f->b_state,
                       &f->b_self, &f->b_row, &f->b_cnt, &f->b_whb, &f->b_rawbase, &f->b_tbase, &f->b_pos, &f->b_aoff, &f->b_mm,
-                      &f->b_cur, &f->b_cat, &f->b_ctr})
+                      &f->b_cur, &f->b_cat, &f->b_ctr, &f->cl_state, &f->cl_src, &f->cl_cnt, &f->cl_toff, &f->cl_tin, &f->cl_snap,
+                      &f->cl_mark, &f->cl_ctr})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -1213,6 +1213,60 @@ typedef struct {
 } debwt_fm_graph_both_stats;
 int debwt_fm_graph_both_stats_get(const debwt_fm *fm, debwt_fm_graph_both_stats *out);
 
+/* ---- graph cleaning: tips and bubbles (fm_clean_kernels.h) --------------------------------------------------------------
+ * 6. Over nnodes nodes with state bytes and the CSR lists edge_offsets / edges, with max_tip T, max_bubble B, max_rounds R.
+ *    A node is alive iff its state is 0.  Every phase works on a snapshot: out(v) and in(v) are the alive neighbours of an
+ *    alive v through the edges as given (one entry per edge), every decision of a phase reads the snapshot, and the
+ *    removals of a phase are applied together after it, so no result depends on an order of evaluation (as in 3).
+ *    Tip phase.  For w with outdeg(w) >= 2 and each x in out(w), follow the chain c_1 = x, c_2, ...: the edge is a tip iff
+ *    some m <= T has indeg(c_t) == 1 for every t <= m, outdeg(c_t) == 1 with c_{t+1} its successor for t < m, and
+ *    outdeg(c_m) == 0.  If at least one out-edge of w is no tip, the chains of all its tip edges are removed (c_1 .. c_m
+ *    get state 3, clipped); if every out-edge of w is a tip, nothing of w is removed.  The same rule runs on the transposed
+ *    snapshot (backward tips into a w with indeg(w) >= 2); both directions read one snapshot and their removals are
+ *    united.  No node is in a tip of either kind twice: a forward tip's nodes have indeg 1, so one edge leads into its
+ *    chain, and a backward tip's far end has indeg 0.
+ *    Bubble phase, on a new snapshot taken after the tip removals.  For w with outdeg(w) >= 2 and each x in out(w), walk
+ *    c_1 = x, c_2, ... while indeg(c) == 1 and outdeg(c) == 1, at most B nodes.  The walk yields a simple branch (a chain
+ *    of m >= 1 nodes and its end z) iff it stops at a node z with indeg(z) >= 2 and z != w; it yields none when
+ *    indeg(x) >= 2 (m == 0), when a chain node has outdeg != 1, and when it would need more than B nodes.  The simple
+ *    branches of w are grouped by z; a group of two or more is ranked by (m descending, key ascending), key being the
+ *    least node of the chain, or with DEBWT_FM_CLEAN_MIRRORED the least v >> 1, so that a mirrored bubble gets one verdict
+ *    from both ends.  If the best rank is held by one branch, the chains of all others of the group are removed (state 4,
+ *    popped); if two branches tie for it on m and key, nothing of the group is removed.
+ *    One round is a tip phase, then a bubble phase; rounds repeat until one removes nothing or R have run.  Every walk is
+ *    bounded by T or B, so cycles end.  With T == 0 there is no tip phase, with B == 0 no bubble phase.
+ * state_out is state with 3 and 4 written in; edge_keep[e] (indexed as edges) is 1 iff both ends of edge e are alive at
+ * the end.  With DEBWT_FM_CLEAN_MIRRORED (node ids 2r + o, as from debwt_fm_string_graph_both) and lists closed under
+ * u -> v  |->  v^1 -> u^1 the result is closed too: state_out[v] == 0 iff state_out[v ^ 1] == 0, but for the second node
+ * of a self-rc read.  Edge lengths are not read.  The lists are uploaded once and transposed once on the index's device
+ * and stream; a round changes states and counters only.
+ * DEBWT_EINVAL with the reason in debwt_fm_last_error: T == 0 and B == 0 together, R == 0, unknown flags, decreasing
+ * offsets, a target >= nnodes, an edge from or to a node that is not alive, an odd nnodes with DEBWT_FM_CLEAN_MIRRORED,
+ * nnodes of 2^32 or more.
+ * Not done here: isolated short unitigs stay (a read with an error in its middle has no overlap of min_overlap and stands
+ * alone), no edge is cut by its overlap ratio, and a bubble whose branches branch themselves is not popped. */
+#define DEBWT_FM_CLEAN_MIRRORED 1u
+#define DEBWT_FM_NODE_CLIPPED 3
+#define DEBWT_FM_NODE_POPPED 4
+typedef struct { uint32_t max_tip, max_bubble, max_rounds, flags; } debwt_fm_clean_opts;
+/* max_tip 4, max_bubble 16, max_rounds 8, no flags */
+void debwt_fm_clean_defaults(debwt_fm_clean_opts *o);
+int debwt_fm_graph_clean(debwt_fm *fm, const uint8_t *state, const uint64_t *edge_offsets, const debwt_fm_edge *edges,
+                         uint64_t nnodes, const debwt_fm_clean_opts *opts, uint8_t *state_out /* nnodes */,
+                         uint8_t *edge_keep /* one byte per edge */);
+/* The edges with keep[e] != 0, on the host (no GPU), order kept: offsets_out (nnodes + 1, from 0) and edges_out.
+ * DEBWT_EINVAL for decreasing offsets and a NULL array. */
+int debwt_fm_edges_compact(const uint64_t *edge_offsets, const debwt_fm_edge *edges, const uint8_t *keep, uint64_t nnodes,
+                           uint64_t *offsets_out, debwt_fm_edge *edges_out);
+/* what the last debwt_fm_graph_clean did: nodes and edges given, rounds run (the one that removed nothing included), tip
+ * chains clipped and their nodes, branches popped and their nodes (a tie group that stays counts nothing), nodes visited
+ * by the walks, kernel launches, the time of the kernels (transpose included) by events, and host wall time */
+typedef struct {
+    uint64_t nodes, edges, rounds, tips, tip_nodes, bubbles, bubble_nodes, steps, launches;
+    float ms_clean, ms_wall;
+} debwt_fm_clean_stats;
+int debwt_fm_clean_stats_get(const debwt_fm *fm, debwt_fm_clean_stats *out);
+
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
