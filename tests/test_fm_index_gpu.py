@@ -1,10 +1,11 @@
-"""FM-index over built rows (debwt_fm_*, FMIndex): count and locate against a numpy count of the text's windows, the
-full suffix array at s = 1, sum properties, indexes from saved files, refusal of rows that are not the text's BWT,
-the per-pattern cap and batches cut inside the library."""
+"""FM-index over built rows (debwt_fm_*, FMIndex): count and locate (in row order) against a numpy count of the text's
+windows and a CPU suffix array, the full suffix array at s = 1 against that array, sum properties, indexes from saved
+files, refusal of rows that are not the text's BWT, the per-pattern cap and batches cut inside the library."""
 import numpy as np
 import pytest
 
 from conftest import golden_id, golden_manifest, golden_outputs, golden_records
+from fm_definition import suffix_array
 
 pytestmark = pytest.mark.gpu
 MANIFEST = golden_manifest()
@@ -34,9 +35,10 @@ def text_of(recs):
 
 
 class Windows:
-    """every window of length L that holds no separator, sorted by its base-4 value"""
+    """every window of length L that holds no separator, sorted by its base-4 value; given the text's suffix array, the
+    windows of one value stand in row order (by the suffix that begins there), as locate reports them"""
 
-    def __init__(self, text, L):
+    def __init__(self, text, L, sa=None):
         n = len(text)
         m = n - L + 1
         v = np.zeros(m, dtype=np.uint64)
@@ -45,8 +47,12 @@ class Windows:
         for j in range(L):
             v = v * np.uint64(4) + sym[j:j + m]
             bad |= text[j:j + m] > 3
-        pos = np.nonzero(~bad)[0].astype(np.uint64)
-        v = v[~bad]
+        if sa is None:
+            pos = np.nonzero(~bad)[0]
+        else:
+            pos = sa[sa < m]
+            pos = pos[~bad[pos]]
+        v, pos = v[pos], pos.astype(np.uint64)
         o = np.argsort(v, kind="stable")
         self.keys, self.pos, self.L = v[o], pos[o], L
 
@@ -90,10 +96,10 @@ def sample_patterns(text, L, count, rng, mutate=0.1):
     return pats, out
 
 
-def check_index(fm, text, rng, lengths, locate_every, cache):
+def check_index(fm, text, sa, rng, lengths, locate_every, cache):
     for L in lengths:
         if L not in cache:
-            cache[L] = Windows(text, L)
+            cache[L] = Windows(text, L, sa)
         W = cache[L]
         pats, codes = sample_patterns(text, L, 60, rng)
         cnt = fm.count(pats)
@@ -102,7 +108,7 @@ def check_index(fm, text, rng, lengths, locate_every, cache):
         sel = list(range(0, len(pats), locate_every))
         got = fm.locate([pats[i] for i in sel])
         for g, i in zip(got, sel):
-            assert np.array_equal(np.sort(g), np.sort(want[i])), (L, i)
+            assert np.array_equal(g, want[i]), (L, i)                  # in row order
 
 
 @pytest.mark.parametrize("entry", K32, ids=golden_id)
@@ -117,13 +123,14 @@ def test_count_and_locate_against_windows(api, entry):
     rng = np.random.default_rng(n)
     big = n > BIG
     lengths = [1, 5, 12, 32] if big else [1, 2, 3, 5, 8, 13, 21, 32]
-    cache = {7: Windows(text, 7)}
+    sa = suffix_array(text)
+    cache = {7: Windows(text, 7, sa)}
     for s in (1, 4, 32):
         fm = d.fm_index(sa_sample=s)
         info = fm.info()
         assert info["n"] == n and info["nrec"] == len(recs) and info["samples"] == (n + s - 1) // s
         assert np.array_equal(fm.record_starts(), starts)
-        check_index(fm, text, rng, lengths if s == 32 else lengths[-2:], 4 if big else 1, cache)
+        check_index(fm, text, sa, rng, lengths if s == 32 else lengths[-2:], 4 if big else 1, cache)
         # patterns that exist only across a separator, 'N' and empty patterns: 0
         cross = []
         for st in starts[1:6]:
@@ -166,6 +173,7 @@ def test_full_suffix_array_at_s1(api):
     fm = d.fm_index(sa_sample=1)
     sa = fm.samples().astype(np.int64)
     assert len(sa) == n and np.array_equal(np.sort(sa), np.arange(n))
+    assert np.array_equal(sa, suffix_array(text))                  # the suffix array itself, every row
     L = ((words[np.arange(n) >> 5] >> (2 * (31 - (np.arange(n) & 31))).astype(np.uint64)) & np.uint64(3)).astype(np.uint8)
     L[hrows.astype(np.int64)] = 4
     L[drow] = 5
