@@ -577,6 +577,17 @@ static int default_range_cap(debwt_ctx *c, u64 per_key, u64 later, u64 caller_he
 
 // Cuts the prefix bins [bin_lo, bin_hi) of the census `hist` into key ranges of at most `cap` node instances each
 // (near-equal ranges; the reference balances its sort threads on the same census, src/mySort.c:98-110).
+// Key bounds of the prefix bins [lo, hi) at kb key bits (key_hi = 0: no upper bound).  A shard without bins needs bounds that
+// say so: [4096, 4096) -- a shard whose splitter target lies inside the last bin starts behind it -- has no first key (at
+// kb = 64 the shift wraps to 0), and [0, 0) -- more shards than keys -- has no last one; with key_lo = key_hi = 0 both read
+// "the whole key space": every key of the text scattered into the key buffer of a shard of 0 keys, every special suffix
+// claimed by it.  They are the empty range at the nearest bin bound that a key can stand for, like any other empty shard.
+static void bin_range_keys(u32 lo, u32 hi, int kb, u64 *key_lo, u64 *key_hi) {
+    if (lo >= hi) { *key_lo = *key_hi = (u64)std::min<u32>(std::max<u32>(lo, 1u), SHARD_BINS - 1) << (kb - 12); return; }
+    *key_lo = (u64)lo << (kb - 12);
+    *key_hi = hi == SHARD_BINS ? 0ull : ((u64)hi << (kb - 12));
+}
+
 static int cut_ranges(debwt_ctx *c, const u64 *hist, u32 bin_lo, u32 bin_hi, u64 cap, u64 Mshard) {
     c->ranges.clear();
     cap = std::min<u64>(cap, 0xFFFFFFF0ull - 1);
@@ -586,8 +597,7 @@ static int cut_ranges(debwt_ctx *c, const u64 *hist, u32 bin_lo, u32 bin_hi, u64
     const int kb = 2 * c->cfg.k;
     auto push = [&](u32 lo, u32 hi, u64 m, u64 base) {
         debwt_ctx::KeyRange q{};
-        q.key_lo = (u64)lo << (kb - 12);
-        q.key_hi = hi == SHARD_BINS ? 0ull : ((u64)hi << (kb - 12));
+        bin_range_keys(lo, hi, kb, &q.key_lo, &q.key_hi);
         q.M = m; q.Mbase = base;
         c->ranges.push_back(q);
     };
@@ -2133,8 +2143,7 @@ extern "C" int debwt_shard_set_range(debwt_ctx *c, uint32_t bin_lo, uint32_t bin
     if (c->stage < ST_LOADED) return DEBWT_ESTATE;
     if (m_keys > c->Mfull) return DEBWT_EINVAL;
     const int kb = 2 * c->cfg.k;                       // key bits; a bin is the top 12 of them
-    c->key_lo = (u64)bin_lo << (kb - 12);
-    c->key_hi = bin_hi == SHARD_BINS ? 0ull : ((u64)bin_hi << (kb - 12));   // 0: no upper bound (last shard)
+    bin_range_keys(bin_lo, bin_hi, kb, &c->key_lo, &c->key_hi);            // key_hi 0: no upper bound (last shard)
     c->M = c->Mctx = m_keys; c->Mbase = m_base;
     c->shard_planned = false; c->exchange = false; c->ranges.clear();
     c->stage = ST_LOADED;
@@ -2150,8 +2159,7 @@ extern "C" int debwt_shard_plan(debwt_ctx *c, const uint64_t *hist4096, uint32_t
     u64 m = 0;
     for (u32 b = bin_lo; b < bin_hi; b++) m += hist4096[b];
     if (m > c->Mfull) return DEBWT_EINVAL;
-    c->key_lo = (u64)bin_lo << (kb - 12);
-    c->key_hi = bin_hi == SHARD_BINS ? 0ull : ((u64)bin_hi << (kb - 12));
+    bin_range_keys(bin_lo, bin_hi, kb, &c->key_lo, &c->key_hi);
     c->M = c->Mctx = m; c->Mbase = m_base;
     u64 cap = c->range_cap;
     if (!cap) {
