@@ -131,6 +131,9 @@ static void usage(void) {
             "       deBWT-query map    -i OUT [--ref INPUT.fa[.gz] [-t T] [--iupac SEED]] [--device D] [--min-len L] [--band W]\n"
             "                          [--max-occ N] [--min-score S] [--chain [--max-gap G]]\n"
             "                          [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq\n"
+            "       deBWT-query pileup -i OUT [the options of map] [--min-mapq Q] [--region J[:BEG-END]] [--window N] READS.fa|.fq\n"
+            "       deBWT-query consensus -i OUT [the options of map] [--min-mapq Q] [--region J[:BEG-END]] [--window N]\n"
+            "                          [--min-depth D] [--min-permille P] [--variants FILE] READS.fa|.fq\n"
             "       deBWT-query extract -i OUT [--device D] --all | REGIONS.txt\n"
             "       deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq\n"
             "       deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
@@ -154,6 +157,13 @@ static void usage(void) {
             "at most G bases between two seeds, default 5000); --mate maps paired ends, read i of READS2 being the mate of\n"
             "read i of READS (tags pr:A:P|U, tl:i: template length, rs:i:1 rescued mate), --insert LO,HI bounds the template\n"
             "length instead of estimating it, --no-rescue leaves a mate without a seed unmapped;\n"
+            "pileup maps the reads as map does, piles the hits of mapping quality Q or more (default 20) up and prints, per\n"
+            "position that a read covers, record<TAB>offset (1-based)<TAB>reference base<TAB>depth<TAB>A<TAB>C<TAB>G<TAB>T<TAB>\n"
+            "deleted<TAB>insertions behind<TAB>other; consensus prints, per record (>J) or for the region, the called base in\n"
+            "upper case, the reference base in lower case where fewer than D reads (default 4) or less than P / 1000 of\n"
+            "them (default 600) agree, nothing for a called deletion, and a voted insertion behind its position; --variants\n"
+            "FILE gets record<TAB>offset<TAB>ref<TAB>alt (a base, - or +STRING)<TAB>depth<TAB>count; --region walks one record or a\n"
+            "part of it (0-based, end exclusive), --window N positions are piled up at a time (default 2^26);\n"
             "extract writes FASTA from the index alone: --all every record under the header >J (its 0-based number), or\n"
             "the regions of REGIONS.txt, one per line, J or J:BEG-END (0-based, end exclusive), under the region as given;\n"
             "kmers prints name<TAB>c0,c1,.. per read, the occurrences of its K-mers (* for a read shorter than K);\n"
@@ -919,6 +929,249 @@ done:
     return ret;
 }
 
+/* ---- pileup / consensus ----------------------------------------------------------------------------------------------- */
+
+#define PILE_BATCH_ALNS (1ull << 20)
+
+struct pile_args {
+    const char *ref, *mate, *region, *variants;
+    uint64_t threads, seed, window, min_mapq;
+    int iupac, chain, consensus;
+    uint32_t max_gap;
+    const debwt_fm_map_opts *mo;
+    const debwt_fm_pair_opts *po;
+    debwt_fm_pile_opts call;
+};
+
+/* reads -> alignments once (map, map --chain or map --mate), kept on the host; then the text is walked in windows of
+ * --window positions: the alignments are piled up in batches with DEBWT_FM_PILE_ADD, the table is fetched (pileup) or
+ * called and turned into consensus and variants (consensus) */
+static int cmd_pile(const char *out, const char *pfile, int device, const struct pile_args *A) {
+    struct patterns P, M, B;
+    memset(&P, 0, sizeof P); memset(&M, 0, sizeof M); memset(&B, 0, sizeof B);
+    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (A->mate && read_patterns(A->mate, &M)) { free_patterns(&P); free_patterns(&M); return 1; }
+    if (A->mate && P.n != M.n) {
+        fprintf(stderr, "--mate: %s holds %llu reads, %s holds %llu\n", A->mate, (unsigned long long)M.n, pfile, (unsigned long long)P.n);
+        free_patterns(&P); free_patterns(&M);
+        return 1;
+    }
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) { free_patterns(&P); free_patterns(&M); return 1; }
+    int ret = 1, rc = 0;
+    debwt_packed_text pt;
+    memset(&pt, 0, sizeof pt);
+    const uint64_t nr = A->mate ? 2 * P.n : P.n;
+    const char *seq = P.seq;
+    const uint64_t *off = P.off;
+    uint64_t cap = 4 * nr + 16, *coff = malloc((nr + 1) * 8), *starts = NULL, *acoff = NULL, *ooff = NULL, *vt = NULL, *ioff = NULL;
+    uint32_t *cig = NULL, *acig = NULL, *counts = NULL, *isup = NULL, *idep = NULL;
+    uint8_t *calls = NULL, *refb = NULL;
+    char *cons = NULL, *ibases = NULL;
+    debwt_fm_hit *hits = malloc((nr ? nr : 1) * sizeof *hits);
+    debwt_fm_pair_info *info = A->mate ? malloc((P.n ? P.n : 1) * sizeof *info) : NULL;
+    debwt_fm_pile_aln *alns = NULL, *bal = NULL;
+    debwt_fm_variant *vars = NULL;
+    debwt_fm_ins_event *ev = NULL;
+    FILE *vf = NULL;
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    starts = malloc((fi.nrec + 1) * 8);
+    ooff = malloc((fi.nrec + 1) * 8);
+    if (!coff || !hits || !starts || !ooff || (A->mate && !info)) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (A->mate) {                                        /* both mates interleaved, as map --mate does */
+        B.seq = malloc(P.len + M.len + 1);
+        B.off = malloc((nr + 1) * 8);
+        if (!B.seq || !B.off) { fprintf(stderr, "out of memory\n"); goto done; }
+        B.off[0] = 0;
+        for (uint64_t i = 0; i < P.n; i++) {
+            const uint64_t l1 = P.off[i + 1] - P.off[i], l2 = M.off[i + 1] - M.off[i];
+            memcpy(B.seq + B.off[2 * i], P.seq + P.off[i], l1);
+            B.off[2 * i + 1] = B.off[2 * i] + l1;
+            memcpy(B.seq + B.off[2 * i + 1], M.seq + M.off[i], l2);
+            B.off[2 * i + 2] = B.off[2 * i + 1] + l2;
+        }
+        seq = B.seq; off = B.off;
+    }
+    if (map_text(fm, out, A->ref, A->threads, A->iupac, A->seed, &fi, &pt)) goto done;
+    for (;;) {                                            /* grow to the exact op count on DEBWT_ERANGE */
+        free(cig);
+        cig = malloc(cap * 4);
+        if (!cig) { fprintf(stderr, "out of memory\n"); goto done; }
+        if (A->mate) rc = debwt_fm_map_pairs(fm, seq, off, P.n, A->po, hits, info, coff, cig, cap);
+        else if (A->chain) {
+            debwt_fm_chain_opts co;
+            debwt_fm_chain_defaults(&co);
+            co.map = *A->mo;
+            co.max_gap = A->max_gap;
+            rc = debwt_fm_map_chained(fm, seq, off, nr, &co, hits, coff, cig, cap, NULL, NULL, 0);
+        } else rc = debwt_fm_map(fm, seq, off, nr, A->mo, hits, coff, cig, cap);
+        if (rc == DEBWT_ERANGE && coff[nr] > cap) { cap = coff[nr]; continue; }
+        break;
+    }
+    if (!rc) rc = debwt_fm_record_starts(fm, starts, fi.nrec);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    starts[fi.nrec] = fi.n;
+    /* the alignments kept: mapped, at least --min-mapq; in read order, their CIGARs side by side */
+    uint64_t na = 0, nops = 0;
+    alns = malloc((nr ? nr : 1) * sizeof *alns);
+    bal = malloc(PILE_BATCH_ALNS * sizeof *bal);
+    acoff = malloc((nr + 1) * 8);
+    acig = malloc((coff[nr] ? coff[nr] : 1) * 4);
+    if (!alns || !bal || !acoff || !acig) { fprintf(stderr, "out of memory\n"); goto done; }
+    acoff[0] = 0;
+    for (uint64_t i = 0; i < nr; i++) {
+        const debwt_fm_hit *h = &hits[i];
+        if ((h->flags & DEBWT_FM_MAP_UNMAPPED) || h->mapq < A->min_mapq) continue;
+        alns[na].pattern = i; alns[na].tbeg = h->tbeg; alns[na].qbeg = h->qbeg;
+        alns[na].strand = (h->flags & DEBWT_FM_MAP_REVERSE) ? 1 : 0;
+        memcpy(acig + nops, cig + coff[i], (coff[i + 1] - coff[i]) * 4);
+        nops += coff[i + 1] - coff[i];
+        acoff[++na] = nops;
+    }
+    /* the positions walked: the whole text, or one region in extract's form */
+    uint64_t gbeg = 0, gend = fi.n, r0 = 0, r1 = fi.nrec;
+    if (A->region) {
+        uint64_t rec = 0, beg = 0, end = 0;
+        int whole = 0;
+        if (parse_region(A->region, &rec, &beg, &end, &whole)) { fprintf(stderr, "--region: '%s' is not J or J:BEG-END\n", A->region); goto done; }
+        const uint64_t len = rec < fi.nrec ? starts[rec + 1] - 1 - starts[rec] : 0;
+        if (whole) end = len;
+        if (rec >= fi.nrec || beg >= end || end > len) { fprintf(stderr, "--region: '%s' is empty or lies outside its record\n", A->region); goto done; }
+        gbeg = starts[rec] + beg; gend = starts[rec] + end; r0 = rec; r1 = rec + 1;
+    }
+    const uint64_t W = A->window < gend - gbeg ? A->window : gend - gbeg;
+    calls = malloc(W); refb = malloc(W);
+    counts = A->consensus ? NULL : malloc(W * 32);
+    if (!calls || !refb || (!A->consensus && !counts)) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (A->variants && !(vf = fopen(A->variants, "w"))) { fprintf(stderr, "cannot write %s\n", A->variants); goto done; }
+    uint64_t vcap = 0, ecap = 0, ccap = 0, open_rec = ~0ull;
+    for (uint64_t wb = gbeg; wb < gend; wb += W) {
+        const uint64_t we = wb + W < gend ? wb + W : gend;
+        for (uint64_t a0 = 0, first = 1; first || a0 < na; a0 += PILE_BATCH_ALNS, first = 0) {
+            const uint64_t a1 = a0 + PILE_BATCH_ALNS < na ? a0 + PILE_BATCH_ALNS : na;
+            const uint64_t p0 = a1 > a0 ? alns[a0].pattern : 0, p1 = a1 > a0 ? alns[a1 - 1].pattern + 1 : 0;
+            for (uint64_t a = a0; a < a1; a++) { bal[a - a0] = alns[a]; bal[a - a0].pattern -= p0; }
+            rc = debwt_fm_pileup(fm, seq, off + p0, p1 - p0, bal, a1 - a0, acoff + a0, acig, wb, we, first ? 0u : DEBWT_FM_PILE_ADD);
+            if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+        }
+        uint64_t nv = 0;
+        rc = debwt_fm_pile_call(fm, &A->call, calls, refb, vars, vcap, &nv);
+        if (rc == DEBWT_ERANGE && nv > vcap) {
+            free(vars);
+            vars = malloc(nv * sizeof *vars);
+            vcap = vars ? nv : 0;
+            if (!vars) { fprintf(stderr, "out of memory\n"); goto done; }
+            rc = debwt_fm_pile_call(fm, &A->call, calls, refb, vars, vcap, &nv);
+        }
+        if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+        if (!A->consensus) {
+            uint64_t win[2];
+            rc = debwt_fm_pile_fetch(fm, win, counts, W);
+            if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+            uint64_t r = r0;
+            for (uint64_t t = wb; t < we; t++) {
+                const uint32_t *c = counts + (t - wb) * 8;
+                const uint64_t d = (uint64_t)c[0] + c[1] + c[2] + c[3] + c[4];
+                if (!d) continue;
+                while (t >= starts[r + 1]) r++;
+                printf("%llu\t%llu\t%c\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", (unsigned long long)r, (unsigned long long)(t - starts[r] + 1),
+                       "ACGTN"[refb[t - wb] > 4 ? 4 : refb[t - wb]], (unsigned long long)d, c[0], c[1], c[2], c[3], c[4], c[5], c[6]);
+            }
+            continue;
+        }
+        /* consensus: the insertions behind the flagged variants, voted; then the strings of this window */
+        uint64_t nf = 0, nev = 0, nb = 0;
+        for (uint64_t k = 0; k < nv; k++) nf += (vars[k].call & 0x10) != 0;
+        free(vt); free(ioff); free(isup); free(idep); free(ibases);
+        vt = malloc((nf ? nf : 1) * 8); ioff = malloc((nf + 1) * 8); isup = malloc((nf ? nf : 1) * 4); idep = malloc((nf ? nf : 1) * 4);
+        ibases = NULL;
+        if (!vt || !ioff || !isup || !idep) { fprintf(stderr, "out of memory\n"); goto done; }
+        nf = 0;
+        for (uint64_t k = 0; k < nv; k++)
+            if (vars[k].call & 0x10) { vt[nf] = vars[k].t; idep[nf] = vars[k].depth; nf++; }
+        if (nf) {
+            rc = debwt_fm_pile_insertions(fm, nr, off, alns, na, acoff, acig, vt, nf, ev, ecap, &nev);
+            if (rc == DEBWT_ERANGE && nev > ecap) {
+                free(ev);
+                ev = malloc(nev * sizeof *ev);
+                ecap = ev ? nev : 0;
+                if (!ev) { fprintf(stderr, "out of memory\n"); goto done; }
+                rc = debwt_fm_pile_insertions(fm, nr, off, alns, na, acoff, acig, vt, nf, ev, ecap, &nev);
+            }
+            if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+        }
+        ioff[0] = 0;
+        for (int pass = 0; pass < 2; pass++) {            /* the lengths of the voted strings, then the strings */
+            uint64_t e0 = 0;
+            for (uint64_t k = 0; k < nf; k++) {
+                uint64_t e1 = e0, len = 0;
+                while (e1 < nev && ev[e1].t == vt[k]) e1++;
+                rc = debwt_fm_ins_vote(seq, off, nr, alns, na, ev + e0, e1 - e0, pass ? ibases + ioff[k] : NULL,
+                                       pass ? ioff[k + 1] - ioff[k] : 0, &len, &isup[k]);
+                if (rc && !(rc == DEBWT_ERANGE && !pass)) { fprintf(stderr, "the insertion vote failed\n"); goto done; }
+                if (!pass) ioff[k + 1] = ioff[k] + len;
+                e0 = e1;
+            }
+            if (!pass) {
+                nb = ioff[nf];
+                ibases = malloc(nb ? nb : 1);
+                if (!ibases) { fprintf(stderr, "out of memory\n"); goto done; }
+            }
+        }
+        rc = debwt_fm_consensus(refb, calls, wb, we, vt, ioff, ibases, isup, idep, nf, A->call.min_permille, starts, fi.nrec, fi.n,
+                                ooff, cons, ccap);
+        if (rc == DEBWT_ERANGE) {
+            free(cons);
+            ccap = ooff[fi.nrec];
+            cons = malloc(ccap ? ccap : 1);
+            if (!cons) { fprintf(stderr, "out of memory\n"); goto done; }
+            rc = debwt_fm_consensus(refb, calls, wb, we, vt, ioff, ibases, isup, idep, nf, A->call.min_permille, starts, fi.nrec,
+                                    fi.n, ooff, cons, ccap);
+        }
+        if (rc) { fprintf(stderr, "the consensus failed\n"); goto done; }
+        for (uint64_t r = r0; r < r1; r++) {
+            const uint64_t rs = starts[r], re = starts[r + 1] - 1;
+            if (re <= wb || rs >= we) continue;           /* no base of the record in this window */
+            if (open_rec != r) {
+                if (open_rec != ~0ull) putchar('\n');
+                if (A->region) printf(">%s\n", A->region); else printf(">%llu\n", (unsigned long long)r);
+                open_rec = r;
+            }
+            fwrite(cons + ooff[r], 1, ooff[r + 1] - ooff[r], stdout);
+        }
+        if (vf) {
+            uint64_t r = r0, kf = 0;
+            for (uint64_t k = 0; k < nv; k++) {
+                const debwt_fm_variant *v = &vars[k];
+                while (v->t >= starts[r + 1]) r++;
+                const uint32_t b = v->call & 15u;
+                if (b != v->ref)
+                    fprintf(vf, "%llu\t%llu\t%c\t%c\t%u\t%u\n", (unsigned long long)r, (unsigned long long)(v->t - starts[r] + 1),
+                            "ACGT"[v->ref & 3], b == 4 ? '-' : "ACGT"[b & 3], v->depth, v->count);
+                if (v->call & 0x10) {
+                    fprintf(vf, "%llu\t%llu\t%c\t+", (unsigned long long)r, (unsigned long long)(v->t - starts[r] + 1), "ACGT"[v->ref & 3]);
+                    fwrite(ibases + ioff[kf], 1, ioff[kf + 1] - ioff[kf], vf);
+                    fprintf(vf, "\t%u\t%u\n", v->depth, isup[kf]);
+                    kf++;
+                }
+            }
+        }
+    }
+    if (A->consensus && open_rec != ~0ull) putchar('\n');
+    ret = fflush(stdout) ? 1 : 0;
+    if (vf && fflush(vf)) ret = 1;
+done:
+    if (vf) fclose(vf);
+    debwt_free_packed(&pt);
+    free(coff); free(cig); free(hits); free(info); free(starts); free(ooff); free(alns); free(bal); free(acoff); free(acig);
+    free(counts); free(calls); free(refb); free(vars); free(ev); free(vt); free(ioff); free(isup); free(idep); free(ibases); free(cons);
+    debwt_fm_destroy(fm);
+    free(B.seq); free(B.off);
+    free_patterns(&P); free_patterns(&M);
+    return ret;
+}
+
 /* ---- kmers / correct -------------------------------------------------------------------------------------------------- */
 
 static int cmd_kmers(const char *out, const char *pfile, int device, uint32_t k, uint32_t flags) {
@@ -1147,7 +1400,8 @@ int main(int argc, char **argv) {
     int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 :
                !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
                !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : !strcmp(cmd, "graph") ? 9 :
-               !strcmp(cmd, "unitigs") ? 10 : -1;
+               !strcmp(cmd, "unitigs") ? 10 : !strcmp(cmd, "pileup") ? 11 : !strcmp(cmd, "consensus") ? 12 : -1;
+    const int mapping = mode == 4 || mode == 11 || mode == 12;   /* the commands that map reads first */
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
     uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, min_overlap = 20, v64 = 0;
@@ -1168,6 +1422,10 @@ int main(int argc, char **argv) {
     int k_given = 0, all_edges = 0, graph_both = 0, clean = 0;
     debwt_fm_clean_opts cl;
     debwt_fm_clean_defaults(&cl);
+    struct pile_args pa;
+    memset(&pa, 0, sizeof pa);
+    pa.window = 1ull << 26; pa.min_mapq = 20;
+    debwt_fm_pile_defaults(&pa.call);
     for (int i = 2; i < argc; i++) {
         const char *a = argv[i];
         if (a[0] != '-' || !a[1]) {
@@ -1184,9 +1442,9 @@ int main(int argc, char **argv) {
         if ((mode == 9 || mode == 10) && !strcmp(a, "--both-strands")) { graph_both = 1; continue; }
         if ((mode == 9 || mode == 10) && !strcmp(a, "--clean")) { clean = 1; continue; }
         if (mode == 8 && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
-        if (mode == 4 && !strcmp(a, "--chain")) { chain = 1; continue; }
-        if (mode == 4 && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
-        if (mode != 4 && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
+        if (mapping && !strcmp(a, "--chain")) { chain = 1; continue; }
+        if (mapping && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
+        if (!mapping && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
             fprintf(stderr, "%s: only with map\n", a);
             return 1;
         }
@@ -1194,11 +1452,11 @@ int main(int argc, char **argv) {
         const char *v = argv[++i];
         if (!strcmp(a, "-i")) out = v;
         else if (!strcmp(a, "--device")) { if (parse_u64(v, &device) || device > 255) { fprintf(stderr, "--device: a GPU ordinal\n"); return 1; } }
-        else if ((mode == 0 || mode == 4) && !strcmp(a, "-t")) {
+        else if ((mode == 0 || mapping) && !strcmp(a, "-t")) {
             if (parse_u64(v, &threads) || threads < 1) { fprintf(stderr, "-t: thread number must be a positive integer\n"); return 1; }
             if (threads > 256) threads = 256;
         }
-        else if ((mode == 0 || mode == 4) && !strcmp(a, "--iupac")) { if (parse_u64(v, &seed)) { fprintf(stderr, "--iupac: a seed\n"); return 1; } iupac = 1; }
+        else if ((mode == 0 || mapping) && !strcmp(a, "--iupac")) { if (parse_u64(v, &seed)) { fprintf(stderr, "--iupac: a seed\n"); return 1; } iupac = 1; }
         else if (mode == 0 && !strcmp(a, "--sa")) {
             if (parse_u64(v, &s) || s < 1 || s > 1024 || (s & (s - 1))) { fprintf(stderr, "--sa: a power of two in 1..1024\n"); return 1; }
         }
@@ -1206,25 +1464,37 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &K) || K > 4) { fprintf(stderr, "--mismatches: a count in 0..4\n"); return 1; }
             search = 1;
         }
-        else if (mode == 4 && !strcmp(a, "--ref")) ref = v;
-        else if (mode == 4 && !strcmp(a, "--band")) {
+        else if (mapping && !strcmp(a, "--ref")) ref = v;
+        else if (mapping && !strcmp(a, "--band")) {
             if (parse_u64(v, &v64) || v64 > 63) { fprintf(stderr, "--band: a half-width in 0..63\n"); return 1; }
             mo.band = (uint32_t)v64;
         }
-        else if (mode == 4 && !strcmp(a, "--max-occ")) {
+        else if (mapping && !strcmp(a, "--max-occ")) {
             if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-occ: a count of at least 1\n"); return 1; }
             mo.max_occ = (uint32_t)v64;
         }
-        else if (mode == 4 && !strcmp(a, "--min-score")) {
+        else if (mapping && !strcmp(a, "--min-score")) {
             if (parse_u64(v, &v64) || v64 > 0x7FFFFFFFull) { fprintf(stderr, "--min-score: a score of at least 0\n"); return 1; }
             mo.min_score = (int32_t)v64;
         }
-        else if (mode == 4 && !strcmp(a, "--max-gap")) {
+        else if (mapping && !strcmp(a, "--max-gap")) {
             if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-gap: a length of at least 0\n"); return 1; }
             co.max_gap = (uint32_t)v64; gap_given = 1;
         }
-        else if (mode == 4 && !strcmp(a, "--mate")) mate = v;
-        else if (mode == 4 && !strcmp(a, "--insert")) {
+        else if (mapping && !strcmp(a, "--mate")) mate = v;
+        else if (mode >= 11 && !strcmp(a, "--min-mapq")) { if (parse_u64(v, &pa.min_mapq) || pa.min_mapq > 60) { fprintf(stderr, "--min-mapq: a quality in 0..60\n"); return 1; } }
+        else if (mode >= 11 && !strcmp(a, "--region")) pa.region = v;
+        else if (mode >= 11 && !strcmp(a, "--window")) { if (parse_u64(v, &pa.window) || pa.window < 1 || pa.window > (1ull << 32)) { fprintf(stderr, "--window: positions per table, 1..2^32\n"); return 1; } }
+        else if (mode >= 11 && !strcmp(a, "--min-depth")) {
+            if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-depth: a depth of at least 0\n"); return 1; }
+            pa.call.min_depth = (uint32_t)v64;
+        }
+        else if (mode >= 11 && !strcmp(a, "--min-permille")) {
+            if (parse_u64(v, &v64) || v64 > 1000) { fprintf(stderr, "--min-permille: a share in 0..1000\n"); return 1; }
+            pa.call.min_permille = (uint32_t)v64;
+        }
+        else if (mode == 12 && !strcmp(a, "--variants")) pa.variants = v;
+        else if (mapping && !strcmp(a, "--insert")) {
             uint64_t lo = 0, hi = 0;
             char buf[48];
             const char *comma = strchr(v, ',');
@@ -1236,7 +1506,7 @@ int main(int argc, char **argv) {
             }
             po.ins_lo = (uint32_t)lo; po.ins_hi = (uint32_t)hi; insert_given = 1;
         }
-        else if ((mode == 3 || mode == 4) && !strcmp(a, "--min-len")) {
+        else if ((mode == 3 || mapping) && !strcmp(a, "--min-len")) {
             if (parse_u64(v, &min_len) || min_len < 1 || min_len > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
         }
         else if ((mode == 5 || mode == 9 || mode == 10) && !strcmp(a, "--min-overlap")) {
@@ -1289,13 +1559,19 @@ int main(int argc, char **argv) {
         return cmd_graph(out, (int)device, (uint32_t)min_overlap, all_edges, states, mode == 10, graph_both, clean ? &cl : NULL);
     }
     if (!out || !file) { usage(); return 1; }
-    if (mode == 4) {
-        if (!ref) fprintf(stderr, "map: no --ref INPUT.fa[.gz]: the text is restored from %s.sa and the BWT\n", out);
+    if (mapping) {
+        if (!ref) fprintf(stderr, "%s: no --ref INPUT.fa[.gz]: the text is restored from %s.sa and the BWT\n", cmd, out);
         if (gap_given && !chain) { fprintf(stderr, "--max-gap: only with --chain\n"); return 1; }
         if (mate && chain) { fprintf(stderr, "--mate: not with --chain (pairs are mapped with the fixed band)\n"); return 1; }
         if (insert_given && !mate) { fprintf(stderr, "--insert: only with --mate\n"); return 1; }
         if (no_rescue && !mate) { fprintf(stderr, "--no-rescue: only with --mate\n"); return 1; }
         mo.min_len = (uint32_t)min_len;
+        if (mate) { po.map = mo; if (no_rescue) po.max_rescue = 0; }
+        if (mode >= 11) {
+            pa.ref = ref; pa.mate = mate; pa.threads = threads; pa.seed = seed; pa.iupac = iupac; pa.chain = chain;
+            pa.consensus = mode == 12; pa.max_gap = co.max_gap; pa.mo = &mo; pa.po = &po;
+            return cmd_pile(out, file, (int)device, &pa);
+        }
         if (mate) {
             po.map = mo;
             if (no_rescue) po.max_rescue = 0;

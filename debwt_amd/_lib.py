@@ -200,6 +200,33 @@ class DebwtFmCleanStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmPileAln(ctypes.Structure):
+    _fields_ = [("pattern", ctypes.c_uint64), ("tbeg", ctypes.c_uint64), ("qbeg", ctypes.c_uint32), ("strand", ctypes.c_uint32)]
+
+
+class DebwtFmPileOpts(ctypes.Structure):
+    _fields_ = [("min_depth", ctypes.c_uint32), ("min_permille", ctypes.c_uint32)]
+
+
+class DebwtFmVariant(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_uint64), ("depth", ctypes.c_uint32), ("count", ctypes.c_uint32), ("ins", ctypes.c_uint32),
+                ("ref", ctypes.c_uint8), ("call", ctypes.c_uint8)]
+
+
+class DebwtFmInsEvent(ctypes.Structure):
+    _fields_ = [("t", ctypes.c_uint64), ("aln", ctypes.c_uint64), ("qpos", ctypes.c_uint32), ("len", ctypes.c_uint32)]
+
+
+class DebwtFmPileStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("alignments", "ops", "m_columns", "d_bases", "i_ops", "ev_base", "ev_other",
+                                                 "ev_del", "ev_ins", "launches", "group", "table_bytes", "call_positions",
+                                                 "call_variants")] +
+                [(n, ctypes.c_float) for n in ("ms_plan", "ms_kernel", "ms_wall", "ms_call", "ms_call_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class DebwtFmJob(ctypes.Structure):
     _fields_ = [("pattern", ctypes.c_uint64), ("diag", ctypes.c_int64), ("record", ctypes.c_uint32), ("strand", ctypes.c_uint32)]
 
@@ -346,6 +373,8 @@ SYMBOLS = [
     "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
     "debwt_fm_string_graph_both", "debwt_fm_unitigs_both", "debwt_fm_graph_both_stats_get",
     "debwt_fm_clean_defaults", "debwt_fm_graph_clean", "debwt_fm_edges_compact", "debwt_fm_clean_stats_get",
+    "debwt_fm_pileup", "debwt_fm_pile_fetch", "debwt_fm_pile_release", "debwt_fm_pile_defaults", "debwt_fm_pile_call",
+    "debwt_fm_pile_insertions", "debwt_fm_ins_vote", "debwt_fm_consensus", "debwt_fm_pile_stats_get",
 ]
 
 
@@ -666,6 +695,31 @@ def lib():
     L.debwt_fm_edges_compact.argtypes = [u64p, edgep, u8p, ctypes.c_uint64, u64p, edgep]
     L.debwt_fm_clean_stats_get.restype = ctypes.c_int
     L.debwt_fm_clean_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmCleanStats)]
+    alnp, evp = ctypes.POINTER(DebwtFmPileAln), ctypes.POINTER(DebwtFmInsEvent)
+    L.debwt_fm_pileup.restype = ctypes.c_int
+    L.debwt_fm_pileup.argtypes = [vp, ctypes.c_char_p, u64p, ctypes.c_uint64, alnp, ctypes.c_uint64, u64p, u32p,
+                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32]
+    L.debwt_fm_pile_fetch.restype = ctypes.c_int
+    L.debwt_fm_pile_fetch.argtypes = [vp, u64p, u32p, ctypes.c_uint64]
+    L.debwt_fm_pile_release.restype = ctypes.c_int
+    L.debwt_fm_pile_release.argtypes = [vp]
+    L.debwt_fm_pile_defaults.restype = None
+    L.debwt_fm_pile_defaults.argtypes = [ctypes.POINTER(DebwtFmPileOpts)]
+    L.debwt_fm_pile_call.restype = ctypes.c_int
+    L.debwt_fm_pile_call.argtypes = [vp, ctypes.POINTER(DebwtFmPileOpts), u8p, u8p, ctypes.POINTER(DebwtFmVariant),
+                                     ctypes.c_uint64, u64p]
+    L.debwt_fm_pile_insertions.restype = ctypes.c_int
+    L.debwt_fm_pile_insertions.argtypes = [vp, ctypes.c_uint64, u64p, alnp, ctypes.c_uint64, u64p, u32p, u64p, ctypes.c_uint64,
+                                           evp, ctypes.c_uint64, u64p]
+    L.debwt_fm_ins_vote.restype = ctypes.c_int
+    L.debwt_fm_ins_vote.argtypes = [ctypes.c_char_p, u64p, ctypes.c_uint64, alnp, ctypes.c_uint64, evp, ctypes.c_uint64,
+                                    ctypes.c_char_p, ctypes.c_uint64, u64p, u32p]
+    L.debwt_fm_consensus.restype = ctypes.c_int
+    L.debwt_fm_consensus.argtypes = [u8p, u8p, ctypes.c_uint64, ctypes.c_uint64, u64p, u64p, ctypes.c_char_p, u32p, u32p,
+                                     ctypes.c_uint64, ctypes.c_uint32, u64p, ctypes.c_uint64, ctypes.c_uint64, u64p,
+                                     ctypes.c_char_p, ctypes.c_uint64]
+    L.debwt_fm_pile_stats_get.restype = ctypes.c_int
+    L.debwt_fm_pile_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmPileStats)]
     L.debwt_fm_destroy.restype = None
     L.debwt_fm_destroy.argtypes = [vp]
     _lib = L

@@ -254,6 +254,8 @@ class DeBWT:
 
 def _patterns(patterns):
     """(concatenated bytes, offsets) of one str/bytes pattern or a sequence of them"""
+    if isinstance(patterns, tuple) and len(patterns) == 2 and isinstance(patterns[1], np.ndarray):
+        return patterns                                       # made by an earlier _patterns()
     if isinstance(patterns, (str, bytes, bytearray)):
         patterns = [patterns]
     enc = [p.encode() if isinstance(p, str) else bytes(p) for p in patterns]
@@ -878,6 +880,85 @@ class FMIndex:
         self._chk(self._L.debwt_fm_map_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def pileup(self, patterns, alns, window=None, add=False):
+        """Pile alignments up into per-position counts (debwt_fm_pileup, definition 7 of debwt_hip.h).  alns: (rows, offsets,
+        cigars) -- rows of (pattern, tbeg, qbeg, strand) or an array of _PILE_ALN_DTYPE, and the BAM-coded CIGARs as
+        extend() and map() return them; MapResult.pileup and ExtendResult.pileup build it.  window: (wbeg, wend) global
+        text positions, None for the whole text.  add=True adds to the resident table of the same window instead of
+        clearing it, so reads can arrive in batches.  The table stays on the device; returns a PileupResult."""
+        buf, offs = _patterns(patterns)
+        rows, coff, cg = _pile_alns(alns)
+        wbeg, wend = (0, self.n) if window is None else (int(window[0]), int(window[1]))
+        if wbeg < 0 or wend < 0:
+            raise DebwtError(-1, "a negative window bound")
+        self._chk(self._L.debwt_fm_pileup(self._h, buf, _p64(offs), len(offs) - 1,
+                                          rows.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmPileAln)), len(coff) - 1, _p64(coff),
+                                          cg.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), wbeg, wend,
+                                          PILE_ADD if add else 0))
+        return PileupResult(self, buf, offs, (rows[:len(coff) - 1], coff, cg), (wbeg, wend))
+
+    def pile_fetch(self):
+        """The resident table (debwt_fm_pile_fetch): ((wbeg, wend), counts) with counts W x 8 uint32 -- A, C, G, T,
+        deletions, insertions anchored here, other characters, unused."""
+        win = np.zeros(2, dtype=np.uint64)
+        rc = self._L.debwt_fm_pile_fetch(self._h, _p64(win), None, 0)
+        if rc != -5:
+            self._chk(rc)
+        W = int(win[1] - win[0])
+        counts = np.zeros((W, 8), dtype=np.uint32)
+        self._chk(self._L.debwt_fm_pile_fetch(self._h, _p64(win), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), W))
+        return (int(win[0]), int(win[1])), counts
+
+    def pile_release(self):
+        """Free the resident table (debwt_fm_pile_release)."""
+        self._chk(self._L.debwt_fm_pile_release(self._h))
+
+    def pile_call(self, min_depth=4, min_permille=600):
+        """Definition 8 on the resident table (debwt_fm_pile_call): (calls, ref, variants).  min_depth and min_permille are
+        knobs, not measurements."""
+        win = np.zeros(2, dtype=np.uint64)
+        rc = self._L.debwt_fm_pile_fetch(self._h, _p64(win), None, 0)
+        if rc != -5:
+            self._chk(rc)
+        W = int(win[1] - win[0])
+        o = _lib.DebwtFmPileOpts(int(min_depth), int(min_permille))
+        calls, ref = np.zeros(W, dtype=np.uint8), np.zeros(W, dtype=np.uint8)
+        u8p = ctypes.POINTER(ctypes.c_uint8)
+        nv = ctypes.c_uint64(0)
+        var = np.zeros(1, dtype=_VARIANT_DTYPE)
+        rc = self._L.debwt_fm_pile_call(self._h, ctypes.byref(o), calls.ctypes.data_as(u8p), ref.ctypes.data_as(u8p),
+                                        var.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmVariant)), 0, ctypes.byref(nv))
+        if rc == -5 and nv.value:
+            var = np.zeros(nv.value, dtype=_VARIANT_DTYPE)
+            rc = self._L.debwt_fm_pile_call(self._h, ctypes.byref(o), calls.ctypes.data_as(u8p), ref.ctypes.data_as(u8p),
+                                            var.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmVariant)), len(var), ctypes.byref(nv))
+        self._chk(rc)
+        return calls, ref, var[:nv.value]
+
+    def pile_insertions(self, patterns, alns, positions):
+        """The I ops of the alignments anchored at one of `positions` (ascending), as an array of (t, aln, qpos, len)
+        ordered by (t, aln, qpos) (debwt_fm_pile_insertions)."""
+        _, offs = _patterns(patterns)
+        rows, coff, cg = _pile_alns(alns)
+        pos = np.ascontiguousarray(positions, dtype=np.uint64)
+        ne = ctypes.c_uint64(0)
+        ev = np.zeros(1, dtype=_INS_EVENT_DTYPE)
+        args = (self._h, len(offs) - 1, _p64(offs), rows.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmPileAln)), len(coff) - 1,
+                _p64(coff), cg.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _p64(pos) if len(pos) else None, len(pos))
+        rc = self._L.debwt_fm_pile_insertions(*args, ev.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmInsEvent)), 0, ctypes.byref(ne))
+        if rc == -5 and ne.value:
+            ev = np.zeros(ne.value, dtype=_INS_EVENT_DTYPE)
+            rc = self._L.debwt_fm_pile_insertions(*args, ev.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmInsEvent)), len(ev),
+                                                  ctypes.byref(ne))
+        self._chk(rc)
+        return ev[:ne.value]
+
+    def pile_stats(self):
+        """What the last pileup() and the last call on its table did (debwt_fm_pile_stats_get)."""
+        st = _lib.DebwtFmPileStats()
+        self._chk(self._L.debwt_fm_pile_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def locate_hits(self, result, max_per_pattern=None):
         """Text positions of a SearchResult's hits (debwt_fm_locate on its ranges): per pattern a tuple of uint64
         positions, uint8 strands and uint8 mismatches, ascending by (position, strand).  max_per_pattern caps the rows
@@ -933,6 +1014,12 @@ _HIT_DTYPE = np.dtype([("pattern", np.uint64), ("flags", np.uint32), ("record", 
                        ("qbeg", np.uint32), ("qend", np.uint32), ("tbeg", np.uint64), ("tend", np.uint64),
                        ("score", np.int32), ("sub", np.int32), ("mapq", np.uint32), ("edits", np.uint32),
                        ("diag", np.int64)])
+PILE_ADD = 1                                           # option flag of debwt_fm_pileup
+PILE_NO_CALL, PILE_DELETION, PILE_INS_BIT = 5, 4, 0x10   # call bytes of debwt_fm_pile_call
+_PILE_ALN_DTYPE = np.dtype([("pattern", np.uint64), ("tbeg", np.uint64), ("qbeg", np.uint32), ("strand", np.uint32)])
+_VARIANT_DTYPE = np.dtype([("t", np.uint64), ("depth", np.uint32), ("count", np.uint32), ("ins", np.uint32),
+                           ("ref", np.uint8), ("call", np.uint8)], align=True)
+_INS_EVENT_DTYPE = np.dtype([("t", np.uint64), ("aln", np.uint64), ("qpos", np.uint32), ("len", np.uint32)])
 _ANCHOR_DTYPE = np.dtype([("qbeg", np.uint32), ("reserved", np.uint32), ("diag", np.int64)])
 _PAIR_DTYPE = np.dtype([("tlen", np.int64), ("pair_score", np.int32), ("pair_sub", np.int32), ("reserved", np.uint32)],
                        align=True)
@@ -1049,6 +1136,151 @@ def pair_select(c1, c2, ins_lo, ins_hi, unpaired_penalty=17, min_score=30):
     return {n: int(getattr(ch, n)) for n, _ in _lib.DebwtFmPairChoice._fields_}
 
 
+def _pile_alns(alns):
+    """(rows of _PILE_ALN_DTYPE with at least one element, cigar offsets, cigars with at least one element)"""
+    rows, coff, cg = alns
+    if not (isinstance(rows, np.ndarray) and rows.dtype == _PILE_ALN_DTYPE):
+        lst = [tuple(int(x) for x in r) for r in rows]
+        for r in lst:
+            if len(r) != 4 or min(r) < 0 or r[0] >= 2 ** 64 or r[1] >= 2 ** 64 or r[2] >= 2 ** 32 or r[3] >= 2 ** 32:
+                raise DebwtError(-1, "an alignment with a negative or oversized field")
+        rows = np.array(lst, dtype=_PILE_ALN_DTYPE) if lst else np.zeros(0, dtype=_PILE_ALN_DTYPE)
+    coff = np.ascontiguousarray(coff, dtype=np.uint64)
+    if len(coff) != len(rows) + 1:
+        raise ValueError("cigar offsets: one more than alignments expected")
+    cg = np.ascontiguousarray(cg, dtype=np.uint32)
+    if len(rows) == 0:
+        rows = np.zeros(1, dtype=_PILE_ALN_DTYPE)
+    if len(cg) == 0:
+        cg = np.zeros(1, dtype=np.uint32)
+    return np.ascontiguousarray(rows), coff, cg
+
+
+def ins_vote(patterns, alns, events):
+    """The vote over the insertion events of one position (debwt_fm_ins_vote, host only): (string, support).  alns: the
+    alignment rows the events name; the most frequent inserted string wins, ties go to the shorter, then the smaller."""
+    L = _lib.lib()
+    buf, offs = _patterns(patterns)
+    rows, _, _ = _pile_alns((alns, np.zeros(len(alns) + 1, dtype=np.uint64), np.zeros(0, dtype=np.uint32)))
+    ev = np.ascontiguousarray(events, dtype=_INS_EVENT_DTYPE)
+    evp = ev.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmInsEvent)) if len(ev) else None
+    n, sup = ctypes.c_uint64(0), ctypes.c_uint32(0)
+    args = (buf, _p64(offs), len(offs) - 1, rows.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmPileAln)), len(alns), evp, len(ev))
+    rc = L.debwt_fm_ins_vote(*args, None, 0, ctypes.byref(n), ctypes.byref(sup))
+    if rc not in (0, -5):
+        raise DebwtError(rc)
+    out = ctypes.create_string_buffer(max(n.value, 1))
+    rc = L.debwt_fm_ins_vote(*args, out, n.value, ctypes.byref(n), ctypes.byref(sup))
+    if rc:
+        raise DebwtError(rc)
+    return out.raw[:n.value].decode(), sup.value
+
+
+def consensus(ref, calls, window, insertions, rec_starts, n, min_permille=600):
+    """The consensus of every record inside a window (debwt_fm_consensus, host only): a list of nrec strings.  ref, calls:
+    as FMIndex.pile_call returns them; insertions: (t, string, support, depth) ascending by t."""
+    L = _lib.lib()
+    ref = np.ascontiguousarray(ref, dtype=np.uint8)
+    calls = np.ascontiguousarray(calls, dtype=np.uint8)
+    ins = sorted((int(t), s.encode() if isinstance(s, str) else bytes(s), int(sup), int(d)) for t, s, sup, d in insertions)
+    it = np.array([i[0] for i in ins], dtype=np.uint64)
+    ioff = np.zeros(len(ins) + 1, dtype=np.uint64)
+    if ins:
+        np.cumsum([len(i[1]) for i in ins], out=ioff[1:])
+    isup = np.array([i[2] for i in ins], dtype=np.uint32)
+    idep = np.array([i[3] for i in ins], dtype=np.uint32)
+    starts = np.ascontiguousarray(rec_starts, dtype=np.uint64)
+    nrec = len(starts)
+    ooff = np.zeros(nrec + 1, dtype=np.uint64)
+    u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+    args = (ref.ctypes.data_as(u8p), calls.ctypes.data_as(u8p), int(window[0]), int(window[1]),
+            _p64(it) if ins else None, _p64(ioff), b"".join(i[1] for i in ins), isup.ctypes.data_as(u32p) if ins else None,
+            idep.ctypes.data_as(u32p) if ins else None, len(ins), int(min_permille), _p64(starts), nrec, int(n), _p64(ooff))
+    rc = L.debwt_fm_consensus(*args, None, 0)
+    if rc not in (0, -5):
+        raise DebwtError(rc)
+    total = int(ooff[nrec])
+    out = ctypes.create_string_buffer(max(total, 1))
+    rc = L.debwt_fm_consensus(*args, out, total)
+    if rc:
+        raise DebwtError(rc)
+    raw = out.raw
+    return [raw[int(ooff[r]):int(ooff[r + 1])].decode() for r in range(nrec)]
+
+
+class PileupResult:
+    """The table FMIndex.pileup left on the device: window (wbeg, wend); counts (W x 8 uint32: A, C, G, T, deletions,
+    insertions anchored here, other characters, unused) and depth (the sum of the first five) are fetched on first use.
+    The table belongs to the index: the next pileup() without add=True replaces it, so fetch or call before that.
+    call() and consensus() see the insertions of this call's alignments only."""
+
+    def __init__(self, index, buf, offs, alns, window):
+        self.index, self.window, self.alns = index, window, alns
+        self._buf, self._offs, self._counts = buf, offs, None
+
+    @property
+    def counts(self):
+        if self._counts is None:
+            win, self._counts = self.index.pile_fetch()
+            if win != self.window:
+                raise DebwtError(-4, "the resident table is no longer this result's")
+        return self._counts
+
+    @property
+    def depth(self):
+        return self.counts[:, :5].sum(axis=1, dtype=np.uint64)
+
+    def call(self, min_depth=4, min_permille=600):
+        calls, ref, var = self.index.pile_call(min_depth, min_permille)
+        return CallResult(self, calls, ref, var, int(min_permille))
+
+    def consensus(self, min_depth=4, min_permille=600):
+        """(record, consensus string) of every record that has a base inside the window."""
+        return self.call(min_depth, min_permille).consensus()
+
+
+class CallResult:
+    """Calls of PileupResult.call: calls and ref (uint8 per position of the window), variants (structured: t, depth, count,
+    ins, ref, call), insertions() and consensus()."""
+
+    def __init__(self, pile, calls, ref, variants, min_permille):
+        self.pile, self.calls, self.ref, self.variants, self.min_permille = pile, calls, ref, variants, min_permille
+        self._ins = None
+
+    def insertions(self):
+        """[(t, voted string, support, depth)] for every variant with the insertion bit, ascending by t."""
+        if self._ins is None:
+            p = self.pile
+            flagged = self.variants[(self.variants["call"] & PILE_INS_BIT) != 0]
+            ev = p.index.pile_insertions((p._buf, p._offs), p.alns, flagged["t"])
+            out = []
+            for v in flagged:
+                s, sup = ins_vote((p._buf, p._offs), p.alns[0], ev[ev["t"] == v["t"]])
+                out.append((int(v["t"]), s, sup, int(v["depth"])))
+            self._ins = out
+        return self._ins
+
+    def consensus(self):
+        p = self.pile
+        starts = p.index.record_starts()
+        seqs = consensus(self.ref, self.calls, p.window, self.insertions(), starts, p.index.n, self.min_permille)
+        ends = np.append(starts[1:], np.uint64(p.index.n)) - np.uint64(1)
+        return [(r, seqs[r]) for r in range(len(starts)) if max(int(starts[r]), p.window[0]) < min(int(ends[r]), p.window[1])]
+
+
+def _hits_alns(res, keep):
+    idx = np.flatnonzero(keep)
+    rows = np.zeros(len(idx), dtype=_PILE_ALN_DTYPE)
+    coff = np.zeros(len(idx) + 1, dtype=np.uint64)
+    lens = (res.offsets[idx + 1] - res.offsets[idx]).astype(np.int64)
+    if len(idx):
+        np.cumsum(lens, out=coff[1:])
+    # op k of the kept hits is op (first op of its hit) + (k - first kept op of its hit) of the result
+    src = np.repeat(res.offsets[idx].astype(np.int64) - coff[:-1].astype(np.int64), lens) + np.arange(int(lens.sum()))
+    cg = np.asarray(res.cigars)[src]
+    return idx, rows, coff, cg.astype(np.uint32)
+
+
 class ExtendResult:
     """Alignments of FMIndex.extend, one per job: numpy arrays score, qbeg, qend, tbeg, tend, edits ([qbeg, qend) in the
     query string, i.e. in the reverse complement for strand 1; [tbeg, tend) global text positions); cigar(i) as text and
@@ -1069,6 +1301,21 @@ class ExtendResult:
 
     def cigar(self, i):
         return None if self.offsets is None else cigar_string(self.ops(i))
+
+    def alignments(self, jobs):
+        """The alignments with a positive score as FMIndex.pileup takes them; jobs: the rows given to extend()."""
+        if self.offsets is None:
+            raise ValueError("alignments without a traceback (extend(cigar=False)) cannot be piled up")
+        idx, rows, coff, cg = _hits_alns(self, self.score > 0)
+        jobs = [tuple(int(x) for x in j) for j in jobs]
+        rows["pattern"] = [jobs[i][0] for i in idx]
+        rows["strand"] = [jobs[i][1] for i in idx]
+        rows["tbeg"], rows["qbeg"] = self.tbeg[idx], self.qbeg[idx]
+        return rows, coff, cg
+
+    def pileup(self, index, patterns, jobs, window=None, add=False):
+        """FMIndex.pileup of the jobs that aligned (score > 0)."""
+        return index.pileup(patterns, self.alignments(jobs), window=window, add=add)
 
 
 class MapResult:
@@ -1093,6 +1340,18 @@ class MapResult:
 
     def cigar(self, i):
         return cigar_string(self.ops(i))
+
+    def alignments(self, min_mapq=0):
+        """The mapped hits of at least min_mapq as FMIndex.pileup takes them."""
+        idx, rows, coff, cg = _hits_alns(self, self.mapped & (self.mapq >= min_mapq))
+        rows["pattern"], rows["tbeg"], rows["qbeg"] = self.pattern[idx], self.tbeg[idx], self.qbeg[idx]
+        rows["strand"] = self.strand[idx]
+        return rows, coff, cg
+
+    def pileup(self, index, patterns, min_mapq=0, window=None, add=False):
+        """FMIndex.pileup of the mapped hits of at least min_mapq.  patterns: the reads that were mapped -- for map_pairs
+        the mates interleaved (mate 1, mate 2 of pair 0, ...), the order of its hits."""
+        return index.pileup(patterns, self.alignments(min_mapq), window=window, add=add)
 
     def anchors(self, i):
         if self.anchor_offsets is None:

@@ -39,6 +39,7 @@
 #include "fm_graph_kernels.h"
 #include "fm_bigraph_kernels.h"
 #include "fm_clean_kernels.h"
+#include "fm_pile_kernels.h"
 
 namespace {
 
@@ -2999,6 +3000,11 @@ struct debwt_fm {
     debwt_fm_graph_both_stats b_stats{};
     DevBuf cl_state, cl_src, cl_cnt, cl_toff, cl_tin, cl_snap, cl_mark, cl_ctr;   // graph cleaning; edges and offsets in g_edges, g_eoff
     debwt_fm_clean_stats cl_stats{};
+    DevBuf p_table;              // pileup: the table of the window [p_wbeg, p_wend), 32 bytes per position
+    bool has_ptable = false;
+    u64 p_wbeg = 0, p_wend = 0;
+    DevBuf p_codes, p_aln, p_coff, p_cig, p_span, p_ctr, p_sep, p_calls, p_vcnt, p_vbase, p_vars;   // pileup scratch of one call
+    debwt_fm_pile_stats p_stats{};
     VIndex V{};
     std::vector<u64> rec_starts;
     float ms_rank = 0.f, ms_samples = 0.f;
@@ -3271,7 +3277,7 @@ extern "C" int debwt_fm_info_get(const debwt_fm *f, debwt_fm_info *out) {
     out->n = f->n; out->nrec = f->nrec; out->sa_sample = f->s; out->samples = f->nsamp;
     out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap + (f->has_text ? f->text.cap : 0) +
                         (f->has_otable ? f->o_table.cap : 0) + (f->has_anchors ? f->anchors.cap : 0) +
-                        (f->has_ktable ? f->k_table.cap : 0);
+                        (f->has_ktable ? f->k_table.cap : 0) + (f->has_ptable ? f->p_table.cap : 0);
     out->ms_rank = f->ms_rank; out->ms_samples = f->ms_samples;
     for (int q = 0; q < 4; q++) out->census[q] = f->census[q];
     return DEBWT_OK;
@@ -7188,6 +7194,373 @@ extern "C" int debwt_fm_clean_stats_get(const debwt_fm *f, debwt_fm_clean_stats 
     return DEBWT_OK;
 }
 
+// ---- pileup, calls and consensus (fm_pile_kernels.h) -----------------------------------------------------------------------
+// A call uploads the reads, the alignments and the CIGARs once; the validity pass runs before anything touches the table,
+// so a refused call leaves the table as it was.  The table, its window and the separator list stay with the index.
+
+namespace {
+
+static_assert(sizeof(debwt_fm_pile_aln) == sizeof(FmPileAln) && sizeof(debwt_fm_variant) == sizeof(FmPileVar) &&
+              sizeof(debwt_fm_ins_event) == sizeof(FmPileIns), "pileup structs of the ABI and of the kernels differ");
+
+// why alignment g breaks definition 7 (the device found that it does)
+std::string fm_pile_why(const uint64_t *offsets, u64 npat, const debwt_fm_pile_aln &A, const uint32_t *ops, u64 nops, u64 n) {
+    if (A.pattern >= npat) return "pattern " + std::to_string(A.pattern) + " of " + std::to_string(npat);
+    if (A.strand > 1) return "strand " + std::to_string(A.strand);
+    u64 q = 0, t = 0;
+    for (u64 o = 0; o < nops; o++) {
+        const u32 kind = ops[o] & 15u, len = ops[o] >> 4;
+        if (kind > 2) return "op code " + std::to_string(kind);
+        if (!len) return "an op of length 0";
+        if ((o == 0 || o + 1 == nops) && kind) return "a CIGAR that does not begin and end with M";
+        if (kind != 2) q += len;
+        if (kind != 1) t += len;
+    }
+    if ((u64)A.qbeg + q > offsets[A.pattern + 1] - offsets[A.pattern]) return "query bases past the end of the read";
+    if (A.tbeg > n || t > n - A.tbeg) return "text past position n";
+    return "nothing";
+}
+
+// reads (when given), alignments and CIGARs to the device and through the validity pass: q_off, p_aln, p_coff, p_cig,
+// p_span, p_ctr (cleared first; h receives the counters)
+int fm_pile_plan(debwt_fm *f, const std::string &who, const uint64_t *offsets, u64 npat, const debwt_fm_pile_aln *alns, u64 naln,
+                 const uint64_t *coff, const uint32_t *cigar, FmGraphTimer &tm, float *ms, u64 (&h)[FM_PL_NCTR]) {
+    auto bad = [&](const std::string &why) { f->err = who + ": " + why; return DEBWT_EINVAL; };
+    if (!offsets || !coff || (naln && !alns)) return bad("a NULL array");
+    for (u64 i = 0; i < npat; i++)
+        if (offsets[i + 1] < offsets[i]) return bad("offsets must not decrease");
+    for (u64 g = 0; g < naln; g++)
+        if (coff[g + 1] < coff[g]) return bad("cigar_offsets must not decrease");
+    const u64 c0 = coff[0], nops = coff[naln] - c0;
+    if (nops && !cigar) return bad("a NULL array");
+    for (u64 k = 0; k < FM_PL_NCTR; k++) h[k] = 0;
+    h[FM_PL_BAD] = ~0ull;
+    FM_ENSURE(f, f->p_ctr, FM_PL_NCTR * 8);
+    HIPCHK(f, hipMemcpyAsync(f->p_ctr.p, h, sizeof h, hipMemcpyHostToDevice, f->stream));
+    if (!naln) return fm_sync(f);
+    std::vector<u64> off(naln + 1);
+    for (u64 g = 0; g <= naln; g++) off[g] = coff[g] - c0;
+    FM_ENSURE(f, f->q_off, (size_t)(npat + 1) * 8);
+    FM_ENSURE(f, f->p_aln, (size_t)naln * sizeof(FmPileAln));
+    FM_ENSURE(f, f->p_coff, (size_t)(naln + 1) * 8);
+    FM_ENSURE(f, f->p_cig, (size_t)std::max<u64>(nops, 1) * 4);
+    FM_ENSURE(f, f->p_span, (size_t)naln * 8);
+    std::vector<u64> poff(npat + 1);                           // from 0, like the characters that are uploaded
+    for (u64 i = 0; i <= npat; i++) poff[i] = offsets[i] - offsets[0];
+    HIPCHK(f, hipMemcpyAsync(f->q_off.p, poff.data(), (npat + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->p_aln.p, alns, naln * sizeof(FmPileAln), hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemcpyAsync(f->p_coff.p, off.data(), (naln + 1) * 8, hipMemcpyHostToDevice, f->stream));
+    if (nops) HIPCHK(f, hipMemcpyAsync(f->p_cig.p, cigar + c0, nops * 4, hipMemcpyHostToDevice, f->stream));
+    tm.begin();
+    k_fm_pile_plan<<<grid_for(naln, 256), 256, 0, f->stream>>>(f->q_off.as<u64>(), npat, f->p_aln.as<FmPileAln>(), naln,
+                                                               f->p_coff.as<u64>(), f->p_cig.as<u32>(), f->n, f->p_span.as<u64>(),
+                                                               f->p_ctr.as<u64>());
+    HIPCHK(f, hipMemcpyAsync(h, f->p_ctr.p, sizeof h, hipMemcpyDeviceToHost, f->stream));
+    int rc = tm.end(ms);
+    if (rc) return rc;
+    if (h[FM_PL_BAD] != ~0ull) {
+        const u64 g = h[FM_PL_BAD];
+        if (g >= naln) { f->err = who + ": the validity pass named an alignment that does not exist"; return DEBWT_EINTERNAL; }
+        return bad("alignment " + std::to_string(g) + ": " + fm_pile_why(offsets, npat, alns[g], cigar + coff[g], coff[g + 1] - coff[g], f->n));
+    }
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_pileup(debwt_fm *f, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                               const debwt_fm_pile_aln *alns, uint64_t naln, const uint64_t *cigar_offsets, const uint32_t *cigar,
+                               uint64_t wbeg, uint64_t wend, uint32_t flags) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    const std::string who = "debwt_fm_pileup";
+    auto bad = [&](const std::string &why) { f->err = who + ": " + why; return DEBWT_EINVAL; };
+    if (flags & ~DEBWT_FM_PILE_ADD) return bad("unknown flags");
+    if (wend <= wbeg || wend > f->n) return bad("the window must be a non-empty part of [0, n)");
+    const bool add = (flags & DEBWT_FM_PILE_ADD) && f->has_ptable;
+    if (add && (wbeg != f->p_wbeg || wend != f->p_wend)) return bad("DEBWT_FM_PILE_ADD with a window that is not the resident table's");
+    if (!offsets) return bad("a NULL array");
+    if (offsets[npat] < offsets[0]) return bad("offsets must not decrease");
+    const u64 nchars = offsets[npat] - offsets[0];
+    if (nchars && !patterns) return bad("a NULL array");
+    // the counters of the call before this one stay in p_stats until this one has passed the validity pass
+    debwt_fm_pile_stats st{};
+    st.call_positions = f->p_stats.call_positions; st.call_variants = f->p_stats.call_variants;
+    st.ms_call = f->p_stats.ms_call; st.ms_call_wall = f->p_stats.ms_call_wall;
+    HIPCHK(f, hipSetDevice(f->device));
+    FmGraphTimer tm(f);
+    int rc = tm.init();
+    if (rc) return rc;
+    u64 h[FM_PL_NCTR];
+    if ((rc = fm_pile_plan(f, who, offsets, npat, alns, naln, cigar_offsets, cigar, tm, &st.ms_plan, h))) return rc;
+    if (naln) st.launches++;
+    const u64 W = wend - wbeg;
+    if (W > (~(size_t)0 >> 6)) { f->err = who + ": the window is too large for one table"; return DEBWT_ENOMEM; }
+    if (!add) {
+        f->has_ptable = false;
+        FM_ENSURE(f, f->p_table, (size_t)W * 32);
+        HIPCHK(f, hipMemsetAsync(f->p_table.p, 0, (size_t)W * 32, f->stream));
+        f->p_wbeg = wbeg; f->p_wend = wend;
+        f->has_ptable = true;
+    }
+    st.alignments = naln; st.ops = h[FM_PL_OPS]; st.m_columns = h[FM_PL_MCOLS]; st.d_bases = h[FM_PL_DBASES]; st.i_ops = h[FM_PL_IOPS];
+    st.table_bytes = (u64)W * 32;
+    if (naln && st.ops) {
+        // the reads as 4-bit codes, staged once for the call; the characters are padded to whole words of 8
+        const u64 nwords = (nchars + 7) >> 3;
+        FM_ENSURE(f, f->q_chars, (size_t)std::max<u64>(nwords, 1) * 8);
+        FM_ENSURE(f, f->p_codes, (size_t)std::max<u64>(nwords, 1) * 4);
+        if (nwords) HIPCHK(f, hipMemsetAsync(f->q_chars.as<u8>() + (nwords - 1) * 8, 0, 8, f->stream));
+        if (nchars) HIPCHK(f, hipMemcpyAsync(f->q_chars.p, patterns + offsets[0], nchars, hipMemcpyHostToDevice, f->stream));
+        const char *form = getenv("DEBWT_PILE_FORM");
+        u32 G = st.m_columns / naln >= 256 ? 64 : 16;
+        if (form && !strcmp(form, "lane")) G = 1;
+        else if (form && !strcmp(form, "group16")) G = 16;
+        else if (form && !strcmp(form, "group64")) G = 64;
+        else if (form && *form && strcmp(form, "group")) return bad("DEBWT_PILE_FORM must be lane, group, group16 or group64");
+        const u32 *d_codes = f->p_codes.as<u32>();
+        const u64 *d_off = f->q_off.as<u64>(), *d_coff = f->p_coff.as<u64>(), *d_span = f->p_span.as<u64>();
+        const FmPileAln *d_aln = f->p_aln.as<FmPileAln>();
+        const u32 *d_cig = f->p_cig.as<u32>();
+        u32 *d_tab = f->p_table.as<u32>();
+        u64 *d_ctr = f->p_ctr.as<u64>();
+        if (grid_for(naln * G, 256) == 0 || naln * G > (u64)0x7FFFFFFF * 256) { f->err = who + ": too many alignments for one call"; return DEBWT_ERANGE; }
+        if (nwords) k_fm_pile_stage<<<grid_for(nwords, 256), 256, 0, f->stream>>>(f->q_chars.as<u8>(), nwords, f->p_codes.as<u32>());
+        tm.begin();
+        const u32 grid = grid_for(naln * G, 256);
+        if (G == 1) k_fm_pile_count_lane<<<grid, 256, 0, f->stream>>>(d_codes, d_off, d_aln, naln, d_coff, d_cig, d_span, wbeg, wend, d_tab, d_ctr);
+        else if (G == 16) k_fm_pile_count_group<16><<<grid, 256, 0, f->stream>>>(d_codes, d_off, d_aln, naln, d_coff, d_cig, d_span, wbeg, wend, d_tab, d_ctr);
+        else k_fm_pile_count_group<64><<<grid, 256, 0, f->stream>>>(d_codes, d_off, d_aln, naln, d_coff, d_cig, d_span, wbeg, wend, d_tab, d_ctr);
+        HIPCHK(f, hipMemcpyAsync(h, f->p_ctr.p, sizeof h, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&st.ms_kernel))) return rc;
+        st.launches += nwords ? 2 : 1;
+        st.group = G;
+        st.ev_base = h[FM_PL_EV_BASE]; st.ev_other = h[FM_PL_EV_OTHER]; st.ev_del = h[FM_PL_EV_DEL]; st.ev_ins = h[FM_PL_EV_INS];
+    } else if ((rc = fm_sync(f))) return rc;
+    st.ms_wall = (float)fm_ms_since(t0);
+    f->p_stats = st;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_pile_fetch(debwt_fm *f, uint64_t *window, uint32_t *counts, uint64_t capacity) {
+    if (!f || !window) return DEBWT_EINVAL;
+    if (!f->has_ptable) { f->err = "debwt_fm_pile_fetch: no table (debwt_fm_pileup)"; return DEBWT_ESTATE; }
+    window[0] = f->p_wbeg; window[1] = f->p_wend;
+    const u64 W = f->p_wend - f->p_wbeg;
+    if (capacity < W) { f->err = "debwt_fm_pile_fetch: capacity below the window"; return DEBWT_ERANGE; }
+    if (!counts) return DEBWT_EINVAL;
+    HIPCHK(f, hipSetDevice(f->device));
+    HIPCHK(f, hipMemcpyAsync(counts, f->p_table.p, (size_t)W * 32, hipMemcpyDeviceToHost, f->stream));
+    return fm_sync(f);
+}
+
+extern "C" int debwt_fm_pile_release(debwt_fm *f) {
+    if (!f) return DEBWT_EINVAL;
+    HIPCHK(f, hipSetDevice(f->device));
+    HIPCHK(f, hipStreamSynchronize(f->stream));
+    if (f->p_table.p) { (void)hipFree(f->p_table.p); f->p_table.p = nullptr; f->p_table.cap = 0; }
+    f->has_ptable = false;
+    f->p_wbeg = f->p_wend = 0;
+    return DEBWT_OK;
+}
+
+extern "C" void debwt_fm_pile_defaults(debwt_fm_pile_opts *o) {
+    if (!o) return;
+    o->min_depth = 4; o->min_permille = 600;
+}
+
+extern "C" int debwt_fm_pile_call(debwt_fm *f, const debwt_fm_pile_opts *opts, uint8_t *calls, uint8_t *ref,
+                                  debwt_fm_variant *variants, uint64_t capacity, uint64_t *nvars) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!calls || !nvars) { f->err = "debwt_fm_pile_call: a NULL array"; return DEBWT_EINVAL; }
+    if (!f->has_ptable) { f->err = "debwt_fm_pile_call: no table (debwt_fm_pileup)"; return DEBWT_ESTATE; }
+    debwt_fm_pile_opts o;
+    debwt_fm_pile_defaults(&o);
+    if (opts) o = *opts;
+    int rc;
+    if (!f->has_text && (rc = debwt_fm_restore_text(f))) return rc;
+    HIPCHK(f, hipSetDevice(f->device));
+    FmGraphTimer tm(f);
+    if ((rc = tm.init())) return rc;
+    const u64 wbeg = f->p_wbeg, W = f->p_wend - wbeg, nrec = f->nrec, nblocks = (W + 255) / 256;
+    std::vector<u64> sep(nrec);
+    for (u64 r = 0; r + 1 < nrec; r++) sep[r] = f->rec_starts[r + 1] - 1;
+    sep[nrec - 1] = f->n - 1;
+    FM_ENSURE(f, f->p_sep, (size_t)nrec * 8);
+    FM_ENSURE(f, f->p_calls, (size_t)W * 2);
+    FM_ENSURE(f, f->p_vcnt, (size_t)nblocks * 4);
+    FM_ENSURE(f, f->p_vbase, (size_t)nblocks * 8);
+    HIPCHK(f, hipMemcpyAsync(f->p_sep.p, sep.data(), nrec * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(f->p_vcnt.p, 0, nblocks * 4, f->stream));
+    u8 *d_calls = f->p_calls.as<u8>(), *d_ref = d_calls + W;
+    std::vector<u32> vcnt(nblocks);
+    float ms = 0.f;
+    tm.begin();
+    k_fm_pile_call<false><<<(u32)nblocks, 256, 0, f->stream>>>(f->p_table.as<u32>(), f->text.as<u64>(), f->p_sep.as<u64>(), nrec, wbeg, W,
+                                                              o.min_depth, o.min_permille, d_calls, d_ref, f->p_vcnt.as<u32>(), nullptr, nullptr);
+    HIPCHK(f, hipMemcpyAsync(vcnt.data(), f->p_vcnt.p, nblocks * 4, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(calls, d_calls, W, hipMemcpyDeviceToHost, f->stream));
+    if (ref) HIPCHK(f, hipMemcpyAsync(ref, d_ref, W, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = tm.end(&ms))) return rc;
+    std::vector<u64> vbase(nblocks + 1, 0);
+    for (u64 b = 0; b < nblocks; b++) vbase[b + 1] = vbase[b] + vcnt[b];
+    const u64 total = vbase[nblocks];
+    *nvars = total;
+    f->p_stats.call_positions = W; f->p_stats.call_variants = total;
+    if (capacity < total) { f->err = "debwt_fm_pile_call: capacity below the number of variants"; return DEBWT_ERANGE; }
+    if (total) {
+        if (!variants) { f->err = "debwt_fm_pile_call: a NULL array"; return DEBWT_EINVAL; }
+        FM_ENSURE(f, f->p_vars, (size_t)total * sizeof(FmPileVar));
+        HIPCHK(f, hipMemcpyAsync(f->p_vbase.p, vbase.data(), nblocks * 8, hipMemcpyHostToDevice, f->stream));
+        tm.begin();
+        k_fm_pile_call<true><<<(u32)nblocks, 256, 0, f->stream>>>(f->p_table.as<u32>(), f->text.as<u64>(), f->p_sep.as<u64>(), nrec, wbeg, W,
+                                                                 o.min_depth, o.min_permille, d_calls, d_ref, f->p_vcnt.as<u32>(),
+                                                                 f->p_vbase.as<u64>(), f->p_vars.as<FmPileVar>());
+        HIPCHK(f, hipMemcpyAsync(variants, f->p_vars.p, total * sizeof(FmPileVar), hipMemcpyDeviceToHost, f->stream));
+        if ((rc = tm.end(&ms))) return rc;
+    }
+    f->p_stats.ms_call = ms;
+    f->p_stats.ms_call_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_pile_insertions(debwt_fm *f, uint64_t npat, const uint64_t *offsets, const debwt_fm_pile_aln *alns,
+                                        uint64_t naln, const uint64_t *cigar_offsets, const uint32_t *cigar,
+                                        const uint64_t *positions, uint64_t npos, debwt_fm_ins_event *events, uint64_t capacity,
+                                        uint64_t *nevents) {
+    if (!f) return DEBWT_EINVAL;
+    const std::string who = "debwt_fm_pile_insertions";
+    auto bad = [&](const std::string &why) { f->err = who + ": " + why; return DEBWT_EINVAL; };
+    if (!nevents || (npos && !positions)) return bad("a NULL array");
+    for (u64 k = 1; k < npos; k++)
+        if (positions[k] <= positions[k - 1]) return bad("positions must ascend strictly");
+    HIPCHK(f, hipSetDevice(f->device));
+    FmGraphTimer tm(f);
+    int rc = tm.init();
+    if (rc) return rc;
+    u64 h[FM_PL_NCTR];
+    float ms = 0.f;
+    if ((rc = fm_pile_plan(f, who, offsets, npat, alns, naln, cigar_offsets, cigar, tm, &ms, h))) return rc;
+    *nevents = 0;
+    if (!naln || !npos || !h[FM_PL_IOPS]) return DEBWT_OK;
+    FM_ENSURE(f, f->p_sep, (size_t)npos * 8);                  // the positions; the call kernel uploads its separators anew
+    FM_ENSURE(f, f->p_vcnt, (size_t)naln * 4);
+    FM_ENSURE(f, f->p_vbase, (size_t)naln * 8);
+    HIPCHK(f, hipMemcpyAsync(f->p_sep.p, positions, npos * 8, hipMemcpyHostToDevice, f->stream));
+    std::vector<u32> acnt(naln);
+    const u32 grid = grid_for(naln, 256);
+    k_fm_pile_ins<false><<<grid, 256, 0, f->stream>>>(f->p_aln.as<FmPileAln>(), naln, f->p_coff.as<u64>(), f->p_cig.as<u32>(),
+                                                      f->p_span.as<u64>(), f->p_sep.as<u64>(), npos, f->p_vcnt.as<u32>(), nullptr, nullptr);
+    HIPCHK(f, hipMemcpyAsync(acnt.data(), f->p_vcnt.p, naln * 4, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    std::vector<u64> abase(naln + 1, 0);
+    for (u64 g = 0; g < naln; g++) abase[g + 1] = abase[g] + acnt[g];
+    const u64 total = abase[naln];
+    *nevents = total;
+    if (capacity < total) { f->err = who + ": capacity below the number of events"; return DEBWT_ERANGE; }
+    if (!total) return DEBWT_OK;
+    if (!events) return bad("a NULL array");
+    FM_ENSURE(f, f->p_vars, (size_t)total * sizeof(FmPileIns));
+    HIPCHK(f, hipMemcpyAsync(f->p_vbase.p, abase.data(), naln * 8, hipMemcpyHostToDevice, f->stream));
+    k_fm_pile_ins<true><<<grid, 256, 0, f->stream>>>(f->p_aln.as<FmPileAln>(), naln, f->p_coff.as<u64>(), f->p_cig.as<u32>(),
+                                                     f->p_span.as<u64>(), f->p_sep.as<u64>(), npos, f->p_vcnt.as<u32>(),
+                                                     f->p_vbase.as<u64>(), f->p_vars.as<FmPileIns>());
+    HIPCHK(f, hipMemcpyAsync(events, f->p_vars.p, total * sizeof(FmPileIns), hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    // written in (alignment, op) order; a stable sort by position leaves (t, aln, qpos)
+    std::stable_sort(events, events + total, [](const debwt_fm_ins_event &a, const debwt_fm_ins_event &b) { return a.t < b.t; });
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_ins_vote(const char *patterns, const uint64_t *offsets, uint64_t npat, const debwt_fm_pile_aln *alns,
+                                 uint64_t naln, const debwt_fm_ins_event *events, uint64_t nevents, char *out, uint64_t capacity,
+                                 uint64_t *len, uint32_t *support) {
+    if (!len || !support || (nevents && (!patterns || !offsets || !alns || !events))) return DEBWT_EINVAL;
+    std::vector<std::string> strs;
+    strs.reserve(nevents);
+    for (u64 k = 0; k < nevents; k++) {
+        const debwt_fm_ins_event &e = events[k];
+        if (e.aln >= naln) return DEBWT_EINVAL;
+        const debwt_fm_pile_aln &A = alns[e.aln];
+        if (A.pattern >= npat || A.strand > 1) return DEBWT_EINVAL;
+        const u64 base = offsets[A.pattern], m = offsets[A.pattern + 1] - base;
+        if ((u64)e.qpos + e.len > m) return DEBWT_EINVAL;
+        std::string s(e.len, 'N');
+        for (u32 x = 0; x < e.len; x++) {
+            const u64 i = (u64)e.qpos + x;
+            const char ch = patterns[base + (A.strand ? m - 1 - i : i)];
+            const char *hit = strchr("ACGT", ch & ~0x20);
+            if (ch && hit) s[x] = A.strand ? "TGCA"[hit - "ACGT"] : *hit;
+        }
+        strs.push_back(std::move(s));
+    }
+    // equal strings side by side, shorter first, then in lexicographic order: the first run of the largest size wins
+    std::sort(strs.begin(), strs.end(), [](const std::string &a, const std::string &b) {
+        return a.size() != b.size() ? a.size() < b.size() : a < b;
+    });
+    u64 best = 0, best_n = 0;
+    for (u64 i = 0; i < strs.size();) {
+        u64 j = i;
+        while (j < strs.size() && strs[j] == strs[i]) j++;
+        if (j - i > best_n) { best = i; best_n = j - i; }
+        i = j;
+    }
+    *support = (uint32_t)best_n;
+    *len = best_n ? strs[best].size() : 0;
+    if (capacity < *len) return DEBWT_ERANGE;
+    if (*len) {
+        if (!out) return DEBWT_EINVAL;
+        memcpy(out, strs[best].data(), *len);
+    }
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_consensus(const uint8_t *ref, const uint8_t *calls, uint64_t wbeg, uint64_t wend, const uint64_t *ins_t,
+                                  const uint64_t *ins_offsets, const char *ins_bases, const uint32_t *ins_support,
+                                  const uint32_t *ins_depth, uint64_t nins, uint32_t min_permille, const uint64_t *rec_starts,
+                                  uint64_t nrec, uint64_t n, uint64_t *out_offsets, char *out, uint64_t capacity) {
+    if (!ref || !calls || !rec_starts || !out_offsets || wend <= wbeg || wend > n || !nrec) return DEBWT_EINVAL;
+    if (nins && (!ins_t || !ins_offsets || !ins_support || !ins_depth)) return DEBWT_EINVAL;
+    for (u64 k = 1; k < nins; k++)
+        if (ins_t[k] <= ins_t[k - 1]) return DEBWT_EINVAL;
+    for (u64 k = 0; k < nins; k++)
+        if (ins_offsets[k + 1] < ins_offsets[k] || (ins_offsets[k + 1] > ins_offsets[k] && !ins_bases)) return DEBWT_EINVAL;
+    // two passes over the same walk: the lengths, then the letters
+    for (int pass = 0; pass < 2; pass++) {
+        u64 o = 0, k = 0;
+        for (u64 r = 0; r < nrec; r++) {
+            const u64 rs = rec_starts[r], re = (r + 1 < nrec ? rec_starts[r + 1] : n) - 1;   // the record's bases: [rs, re)
+            if (re < rs || re >= n) return DEBWT_EINVAL;
+            if (!pass) out_offsets[r] = o;
+            for (u64 t = std::max<u64>(rs, wbeg); t < std::min<u64>(re, wend); t++) {
+                const u32 c = calls[t - wbeg], b = c & 15u, rf = ref[t - wbeg];
+                if (b < 4) { if (pass) out[o] = "ACGT"[b]; o++; }
+                else if (b == 5 && rf < 4) { if (pass) out[o] = "acgt"[rf]; o++; }
+                if (!(c & 0x10u)) continue;
+                while (k < nins && ins_t[k] < t) k++;
+                if (k < nins && ins_t[k] == t && (u64)ins_support[k] * 1000 >= (u64)min_permille * ins_depth[k]) {
+                    const u64 L = ins_offsets[k + 1] - ins_offsets[k];
+                    if (pass) memcpy(out + o, ins_bases + ins_offsets[k], L);
+                    o += L;
+                }
+            }
+        }
+        if (!pass) {
+            out_offsets[nrec] = o;
+            if (capacity < o) return DEBWT_ERANGE;
+            if (o && !out) return DEBWT_EINVAL;
+        }
+    }
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_pile_stats_get(const debwt_fm *f, debwt_fm_pile_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->p_stats;
+    return DEBWT_OK;
+}
+
 extern "C" void debwt_fm_destroy(debwt_fm *f) {
     if (!f) return;
     (void)hipSetDevice(f->device);
@@ -7202,7 +7575,8 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
                       &f->g_deg, &f->g_oseg, &f->g_edges, &f->g_eoff, &f->g_len, &f->g_keep, &f->g_out, &f->g_ctr, &f->b_state,
                       &f->b_self, &f->b_row, &f->b_cnt, &f->b_whb, &f->b_rawbase, &f->b_tbase, &f->b_pos, &f->b_aoff, &f->b_mm,
                       &f->b_cur, &f->b_cat, &f->b_ctr, &f->cl_state, &f->cl_src, &f->cl_cnt, &f->cl_toff, &f->cl_tin, &f->cl_snap,
-                      &f->cl_mark, &f->cl_ctr})
+                      &f->cl_mark, &f->cl_ctr, &f->p_table, &f->p_codes, &f->p_aln, &f->p_coff, &f->p_cig, &f->p_span, &f->p_ctr,
+                      &f->p_sep, &f->p_calls, &f->p_vcnt, &f->p_vbase, &f->p_vars})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -1267,6 +1267,100 @@ typedef struct {
 } debwt_fm_clean_stats;
 int debwt_fm_clean_stats_get(const debwt_fm *fm, debwt_fm_clean_stats *out);
 
+/* ---- pileup of alignments, calls and consensus (fm_pile_kernels.h) ---------------------------------------------------
+ * Definition 7 (pileup).  Input: the reads as the mapper takes them (patterns / offsets / npat; offsets[0] need not be 0,
+ * so a caller can pass a run of reads of a larger set: only patterns[offsets[0] .. offsets[npat]) is uploaded); naln alignments, each a
+ * debwt_fm_pile_aln {pattern, tbeg, qbeg, strand}; their CIGARs through cigar_offsets (naln + 1) and cigar, BAM-coded
+ * (len << 4 | op, M 0, I 1, D 2) exactly as debwt_fm_extend, debwt_fm_map, debwt_fm_map_chained and debwt_fm_map_pairs
+ * return them; a window [wbeg, wend) of global text positions.
+ *    Query string.  Q is the pattern (strand 0) or its reverse complement (strand 1); qbeg is a coordinate in Q, as in
+ *    debwt_fm_extend.  The CIGAR reads left to right along the text, from query index qbeg and text position tbeg.
+ *    Events.  Each adds 1 to counts[t - wbeg][slot], and only when wbeg <= t < wend:
+ *      a column of an M op at (i, t): the code of Q[i] is the slot, A 0, C 1, G 2, T 3 (either case); any other
+ *      character goes to slot 6;
+ *      every text position t of a D op: slot 4;
+ *      an I op: slot 5 at t = (text position of the next text-consuming column) - 1, the last base before the insertion.
+ *    Slot 7 is never written: the stride of 8 uint32_t keeps a position at 32 bytes.
+ *    Validity.  An alignment with an empty CIGAR contributes nothing.  DEBWT_EINVAL, with nothing counted and the table
+ *    as it was, for: an op code above 2; an op of length 0; a CIGAR whose first or last op is not M; pattern >= npat;
+ *    strand > 1; qbeg + the consumed query bases > the read's length; tbeg + the consumed text > n; wend <= wbeg or
+ *    wend > n; decreasing cigar_offsets.  (A first or last op that is a gap has no anchor -- an insertion before tbeg
+ *    would count at tbeg - 1, outside the alignment -- and the local recurrence of debwt_fm_extend never returns one: a
+ *    gap costs o + e > 0, so an optimal local alignment that began or ended with one would score more without it.)
+ *    Alignments are not checked against record boundaries.
+ * The table stays in HBM, owned by the index, as the attached text is (32 bytes x the window, counted in
+ * debwt_fm_info.device_bytes; DEBWT_ENOMEM when it does not fit).  Without DEBWT_FM_PILE_ADD a call clears the table
+ * first; with it the call adds to the resident table, which must be of the same window (DEBWT_EINVAL otherwise; with no
+ * table resident the flag changes nothing), so reads can arrive in batches: the result does not depend on the batching.
+ * Counts are 32-bit and wrap at 2^32 adds to one slot.  DEBWT_PILE_FORM (environment, read per call): "lane" counts with
+ * one lane per alignment instead of a group of lanes per alignment; the tables are identical. */
+#define DEBWT_FM_PILE_ADD 1u
+typedef struct { uint64_t pattern; uint64_t tbeg; uint32_t qbeg, strand; } debwt_fm_pile_aln;
+int debwt_fm_pileup(debwt_fm *fm, const char *patterns, const uint64_t *offsets, uint64_t npat,
+                    const debwt_fm_pile_aln *alns, uint64_t naln, const uint64_t *cigar_offsets, const uint32_t *cigar,
+                    uint64_t wbeg, uint64_t wend, uint32_t flags);
+/* the resident table to the host: window[0] = wbeg, window[1] = wend (written first), counts 8 words per position;
+ * DEBWT_ERANGE when capacity (in positions) is below wend - wbeg, DEBWT_ESTATE without a table */
+int debwt_fm_pile_fetch(debwt_fm *fm, uint64_t *window, uint32_t *counts, uint64_t capacity);
+/* frees the table; DEBWT_OK when there is none */
+int debwt_fm_pile_release(debwt_fm *fm);
+/* Definition 8 (calls), on the resident table (DEBWT_ESTATE without one).  The text is restored first when the index has
+ * none (debwt_fm_restore_text).
+ *    ref[t]: the text's base code 0..3, or 4 at a position that holds no base of a record (separators, end marker).
+ *    Depth d = counts[0] + ... + counts[4]; slot 6 is ignored.
+ *    best = the slot in 0..4 with the largest count; on a tie ref[t] when ref[t] is among the tied slots, else the lowest.
+ *    A position is called iff ref[t] != 4, d >= min_depth and counts[best] * 1000 >= min_permille * d.
+ *    calls[t - wbeg] = best for a called position, 5 otherwise; bit 0x10 is set when the position is called and
+ *    counts[5] * 1000 >= min_permille * d.
+ *    Variants: the called positions with best != ref[t] or bit 0x10, in ascending t; depth = d (saturated at 2^32 - 1),
+ *    count = counts[best], ins = counts[5], call = the call byte.
+ * calls (wend - wbeg bytes) and ref (the same; may be NULL) are written first, then *nvars = the number of variants;
+ * DEBWT_ERANGE when capacity is below it.  opts NULL: the defaults, min_depth 4 and min_permille 600 -- knobs chosen by
+ * hand, not measurements: a majority of 60 % of at least 4 reads. */
+typedef struct { uint32_t min_depth, min_permille; } debwt_fm_pile_opts;
+typedef struct { uint64_t t; uint32_t depth, count, ins; uint8_t ref, call; } debwt_fm_variant;
+void debwt_fm_pile_defaults(debwt_fm_pile_opts *opts);
+int debwt_fm_pile_call(debwt_fm *fm, const debwt_fm_pile_opts *opts, uint8_t *calls, uint8_t *ref,
+                       debwt_fm_variant *variants, uint64_t capacity, uint64_t *nvars);
+/* The insertions behind the counts of slot 5: one event per I op of the alignments (as given to debwt_fm_pileup; the same
+ * validity) that is anchored at one of `positions` (npos of them, strictly ascending: normally the variants with bit
+ * 0x10).  qpos: the query index in Q of the first inserted base, len: the op's length, aln: the alignment.  Events are
+ * ordered by (t, aln, qpos).  *nevents is written first; DEBWT_ERANGE when capacity is below it.  No table is needed. */
+typedef struct { uint64_t t, aln; uint32_t qpos, len; } debwt_fm_ins_event;
+int debwt_fm_pile_insertions(debwt_fm *fm, uint64_t npat, const uint64_t *offsets, const debwt_fm_pile_aln *alns, uint64_t naln,
+                             const uint64_t *cigar_offsets, const uint32_t *cigar, const uint64_t *positions, uint64_t npos,
+                             debwt_fm_ins_event *events, uint64_t capacity, uint64_t *nevents);
+/* The vote over the events of ONE position (host only, no GPU).  The string of an event is Q[qpos, qpos + len) of its
+ * alignment written with A, C, G, T and N for any other character.  The most frequent string wins; ties go to the shorter
+ * string, then to the lexicographically smaller.  out receives it without a terminator, *len its length (written first;
+ * DEBWT_ERANGE when capacity is below it), *support its number of events.  No events: length 0, support 0.
+ * DEBWT_EINVAL for an event that names an alignment >= naln or bases outside its read. */
+int debwt_fm_ins_vote(const char *patterns, const uint64_t *offsets, uint64_t npat, const debwt_fm_pile_aln *alns, uint64_t naln,
+                      const debwt_fm_ins_event *events, uint64_t nevents, char *out, uint64_t capacity, uint64_t *len,
+                      uint32_t *support);
+/* The consensus of every record inside a window (host only, no GPU).  ref and calls: wend - wbeg bytes as
+ * debwt_fm_pile_call wrote them.  Insertions: nins voted strings, insertion i anchored at ins_t[i] (ascending), its bases
+ * ins_bases[ins_offsets[i] .. ins_offsets[i + 1]), its support and the depth of its position.  rec_starts (nrec,
+ * ascending; the text has n positions) as debwt_fm_record_starts gives them.  Per position of a record inside the window:
+ * the called base in upper case; the reference base in lower case where no call was made; nothing for a called deletion;
+ * then, at a position with bit 0x10 that has a voted string with support * 1000 >= min_permille * depth, that string.
+ * out_offsets (nrec + 1) is written first: record r's consensus is out[out_offsets[r] .. out_offsets[r + 1]), empty for a
+ * record outside the window.  DEBWT_ERANGE when capacity < out_offsets[nrec]. */
+int debwt_fm_consensus(const uint8_t *ref, const uint8_t *calls, uint64_t wbeg, uint64_t wend, const uint64_t *ins_t,
+                       const uint64_t *ins_offsets, const char *ins_bases, const uint32_t *ins_support,
+                       const uint32_t *ins_depth, uint64_t nins, uint32_t min_permille, const uint64_t *rec_starts,
+                       uint64_t nrec, uint64_t n, uint64_t *out_offsets, char *out, uint64_t capacity);
+/* what the last debwt_fm_pileup did (alignments, ops, and the input's M columns, D bases and I ops; the adds made inside
+ * the window by kind: bases, other characters, deletions, insertions; kernel launches; group: lanes per alignment of the
+ * counting kernel, 1 for the lane form; the table's bytes; kernel time by events of the validity pass and of the counting
+ * kernel; host wall time), and the last debwt_fm_pile_call (positions, variants, kernel time, wall time) */
+typedef struct {
+    uint64_t alignments, ops, m_columns, d_bases, i_ops, ev_base, ev_other, ev_del, ev_ins, launches, group, table_bytes;
+    uint64_t call_positions, call_variants;
+    float ms_plan, ms_kernel, ms_wall, ms_call, ms_call_wall;
+} debwt_fm_pile_stats;
+int debwt_fm_pile_stats_get(const debwt_fm *fm, debwt_fm_pile_stats *out);
+
 void debwt_fm_destroy(debwt_fm *fm);
 
 #ifdef __cplusplus
