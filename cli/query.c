@@ -13,7 +13,8 @@
  *                      [--mate READS2.fa|.fq [--insert LO,HI] [--no-rescue]] READS.fa|.fq
  *   deBWT-query extract -i OUT [--device D] --all | REGIONS.txt
  *   deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq
- *   deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq
+ *   deBWT-query correct -i OUT -k K [--device D] [--min-count T|auto] [--rounds R] [--forward] [--report FILE] READS.fa|.fq
+ *   deBWT-query spectrum -i OUT -k K [--device D] [--forward] [--bins N] [--list FILE [--at-least A] [--at-most B]]
  *   deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]
  *                      [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]
  *   deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]
@@ -84,6 +85,19 @@
  * writes them as FASTA to stdout, the names unchanged, one line per sequence; a fixed base is in upper case, every other
  * letter as it came.  --report FILE writes a TSV of name, status (short, clean, fixed or weak), fixes, weak_before and
  * weak_after; stderr gets one summary line.  Both need OUT, OUT.#, OUT.$ and OUT.sa only, and -k is required.
+ * --min-count auto takes T from the K-mer spectrum of the collection (its valley, see spectrum; same K, same strands, 256
+ * bins), names it on stderr and exits 1 with a message when the spectrum has no valley.
+ *
+ * spectrum prints the K-mer spectrum of the indexed collection (debwt_fm_spectrum; K in 1..32, both strands unless
+ * --forward: a K-mer and its reverse complement are one K-mer under the smaller of the two, and one that is its own
+ * reverse complement counts twice, as in kmers --both-strands).  No reads are needed: every distinct K-mer is met once by
+ * a walk over the index.  stdout: the lines "# k", "# strands", "# distinct", "# total", "# valley", "# peak" and
+ * "# est_size" (name, TAB, value), then mult<TAB>distinct for every non-empty bin of the histogram of N bins (2..4096,
+ * default 256); the last bin holds N - 1 and above and is printed as >=N-1.  valley is the first multiplicity whose
+ * successor has more K-mers (K-mers below it are weak), peak the fullest bin behind it, est_size the K-mers from the
+ * valley on divided by the peak; all three are 0 when the histogram only falls.  --list FILE gets KMER<TAB>mult for every
+ * distinct K-mer of multiplicity A (--at-least, default 1) to B (--at-most, default 2^32 - 1), in the order of the
+ * K-mers (debwt_fm_kmer_list).  It needs OUT, OUT.#, OUT.$ and OUT.sa only and takes no file argument.
  *
  * graph writes the string graph of the indexed records as GFA 1 (debwt_fm_string_graph): a record that equals an earlier one
  * is a duplicate, one that lies inside a longer record is contained, the others are kept.  One "S J * LN:i:len" line per
@@ -136,7 +150,8 @@ static void usage(void) {
             "                          [--min-depth D] [--min-permille P] [--variants FILE] READS.fa|.fq\n"
             "       deBWT-query extract -i OUT [--device D] --all | REGIONS.txt\n"
             "       deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq\n"
-            "       deBWT-query correct -i OUT -k K [--device D] [--min-count T] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
+            "       deBWT-query correct -i OUT -k K [--device D] [--min-count T|auto] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
+            "       deBWT-query spectrum -i OUT -k K [--device D] [--forward] [--bins N] [--list FILE [--at-least A] [--at-most B]]\n"
             "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]\n"
             "                          [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]\n"
             "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]\n"
@@ -169,7 +184,12 @@ static void usage(void) {
             "kmers prints name<TAB>c0,c1,.. per read, the occurrences of its K-mers (* for a read shorter than K);\n"
             "correct writes the reads as FASTA with the substitution errors fixed that their K-mer counts single out (weak below\n"
             "T occurrences, default 3; at most R rounds, default 4; both strands unless --forward); --report FILE gets\n"
-            "name<TAB>status<TAB>fixes<TAB>weak_before<TAB>weak_after, stderr one summary line;\n"
+            "name<TAB>status<TAB>fixes<TAB>weak_before<TAB>weak_after, stderr one summary line; --min-count auto takes T from\n"
+            "the valley of the spectrum and exits 1 when there is none;\n"
+            "spectrum prints # k, # strands, # distinct, # total, # valley, # peak and # est_size (name<TAB>value), then\n"
+            "mult<TAB>distinct per non-empty bin of the histogram of the distinct K-mers (K in 1..32; N bins, 2..4096, default\n"
+            "256, the last printed as >=N-1; both strands unless --forward); --list FILE gets KMER<TAB>mult of the K-mers of\n"
+            "multiplicity A (--at-least, default 1) to B (--at-most), in K-mer order;\n"
             "graph writes GFA 1: S lines for the records that are neither duplicates nor contained, L lines a + b + <L>M for the\n"
             "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
             "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained;\n"
@@ -1203,17 +1223,34 @@ done:
     return ret;
 }
 
-static int cmd_correct(const char *out, const char *pfile, int device, const debwt_fm_correct_opts *o, const char *report) {
+static int cmd_correct(const char *out, const char *pfile, int device, const debwt_fm_correct_opts *opts, int auto_count,
+                       const char *report) {
     struct patterns P;
     if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
     if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
-    int ret = 1;
+    int ret = 1, rc;
+    debwt_fm_correct_opts ko = *opts, *o = &ko;
     char *fixed = malloc(P.len ? P.len : 1);
     debwt_fm_correct_info *info = malloc((P.n ? P.n : 1) * sizeof *info);
     FILE *rf = NULL;
     if (!fixed || !info) { fprintf(stderr, "out of memory\n"); goto done; }
-    int rc = debwt_fm_correct(fm, P.seq, P.off, P.n, o, fixed, info);
+    if (auto_count) {                                     /* the valley of the spectrum at this K and these strands */
+        uint64_t hist[256];
+        debwt_fm_spectrum_totals tot;
+        debwt_fm_spectrum_summary sum;
+        rc = debwt_fm_spectrum(fm, ko.k, ko.flags, 256, hist, &tot);
+        if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+        debwt_fm_spectrum_threshold(hist, 256, tot.total, &sum);
+        if (!sum.valley) {
+            fprintf(stderr, "correct: --min-count auto: the %u-mer spectrum of the collection has no valley\n", ko.k);
+            goto done;
+        }
+        ko.min_count = (uint32_t)sum.valley;
+        fprintf(stderr, "correct: --min-count auto: %u (the valley of the %u-mer spectrum, peak %llu)\n", ko.min_count, ko.k,
+                (unsigned long long)sum.peak);
+    }
+    rc = debwt_fm_correct(fm, P.seq, P.off, P.n, o, fixed, info);
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     if (report && !(rf = fopen(report, "w"))) { fprintf(stderr, "cannot write %s\n", report); goto done; }
     for (uint64_t i = 0; i < P.n; i++) {
@@ -1240,6 +1277,60 @@ done:
     if (rf) fclose(rf);
     free(fixed); free(info);
     free_patterns(&P);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
+/* ---- spectrum ---------------------------------------------------------------------------------------------------------- */
+
+static int cmd_spectrum(const char *out, int device, uint32_t k, uint32_t flags, uint32_t bins, const char *list,
+                        uint32_t at_least, uint32_t at_most) {
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) return 1;
+    int ret = 1;
+    uint64_t *hist = calloc(bins, 8), *codes = NULL, count = 0;
+    uint32_t *mults = NULL;
+    FILE *lf = NULL;
+    debwt_fm_spectrum_totals tot;
+    debwt_fm_spectrum_summary sum;
+    if (!hist) { fprintf(stderr, "out of memory\n"); goto done; }
+    int rc = debwt_fm_spectrum(fm, k, flags, bins, hist, &tot);
+    if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    debwt_fm_spectrum_threshold(hist, bins, tot.total, &sum);
+    printf("# k\t%u\n# strands\t%s\n# distinct\t%llu\n# total\t%llu\n# valley\t%llu\n# peak\t%llu\n# est_size\t%llu\n", k,
+           flags & DEBWT_FM_BOTH_STRANDS ? "both" : "forward", (unsigned long long)tot.distinct, (unsigned long long)tot.total,
+           (unsigned long long)sum.valley, (unsigned long long)sum.peak, (unsigned long long)sum.est_size);
+    for (uint32_t c = 1; c < bins; c++)
+        if (hist[c]) printf("%s%u\t%llu\n", c == bins - 1 ? ">=" : "", c, (unsigned long long)hist[c]);
+    if (list) {
+        rc = debwt_fm_kmer_list(fm, k, flags, at_least, at_most, NULL, NULL, 0, &count);
+        if (rc && rc != DEBWT_ERANGE) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+        codes = malloc((count ? count : 1) * 8); mults = malloc((count ? count : 1) * 4);
+        if (!codes || !mults) { fprintf(stderr, "out of memory\n"); goto done; }
+        if (count && (rc = debwt_fm_kmer_list(fm, k, flags, at_least, at_most, codes, mults, count, &count))) {
+            fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
+            goto done;
+        }
+        if (!(lf = fopen(list, "w"))) { fprintf(stderr, "cannot write %s\n", list); goto done; }
+        char w[33];
+        w[k] = 0;
+        for (uint64_t i = 0; i < count; i++) {
+            for (uint32_t j = 0; j < k; j++) w[j] = "ACGT"[(codes[i] >> (2 * (k - 1 - j))) & 3];
+            fprintf(lf, "%s\t%u\n", w, mults[i]);
+        }
+        if (fclose(lf)) { lf = NULL; fprintf(stderr, "cannot write %s\n", list); goto done; }
+        lf = NULL;
+    }
+    debwt_fm_spectrum_stats st;
+    debwt_fm_spectrum_stats_get(fm, &st);
+    fprintf(stderr, "spectrum: k = %u, %s, %llu distinct, %llu in all; valley %llu, peak %llu, size about %llu%s; %.1f ms\n", k,
+            flags & DEBWT_FM_BOTH_STRANDS ? "both strands" : "forward", (unsigned long long)tot.distinct,
+            (unsigned long long)tot.total, (unsigned long long)sum.valley, (unsigned long long)sum.peak,
+            (unsigned long long)sum.est_size, sum.valley ? "" : " (no valley)", st.ms_wall);
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    if (lf) fclose(lf);
+    free(hist); free(codes); free(mults);
     debwt_fm_destroy(fm);
     return ret;
 }
@@ -1400,7 +1491,8 @@ int main(int argc, char **argv) {
     int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 :
                !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
                !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : !strcmp(cmd, "graph") ? 9 :
-               !strcmp(cmd, "unitigs") ? 10 : !strcmp(cmd, "pileup") ? 11 : !strcmp(cmd, "consensus") ? 12 : -1;
+               !strcmp(cmd, "unitigs") ? 10 : !strcmp(cmd, "pileup") ? 11 : !strcmp(cmd, "consensus") ? 12 :
+               !strcmp(cmd, "spectrum") ? 13 : -1;
     const int mapping = mode == 4 || mode == 11 || mode == 12;   /* the commands that map reads first */
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
@@ -1419,7 +1511,9 @@ int main(int argc, char **argv) {
     debwt_fm_correct_opts ko;
     debwt_fm_correct_defaults(&ko);
     const char *report = NULL, *states = NULL;
-    int k_given = 0, all_edges = 0, graph_both = 0, clean = 0;
+    int k_given = 0, all_edges = 0, graph_both = 0, clean = 0, auto_count = 0, filter_given = 0;
+    const char *list = NULL;
+    uint64_t bins = 256, at_least = 1, at_most = 0xFFFFFFFFull;
     debwt_fm_clean_opts cl;
     debwt_fm_clean_defaults(&cl);
     struct pile_args pa;
@@ -1441,7 +1535,7 @@ int main(int argc, char **argv) {
         if (mode == 9 && !strcmp(a, "--all-edges")) { all_edges = 1; continue; }
         if ((mode == 9 || mode == 10) && !strcmp(a, "--both-strands")) { graph_both = 1; continue; }
         if ((mode == 9 || mode == 10) && !strcmp(a, "--clean")) { clean = 1; continue; }
-        if (mode == 8 && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
+        if ((mode == 8 || mode == 13) && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
         if (mapping && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mapping && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
         if (!mapping && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
@@ -1524,7 +1618,25 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "-k: a k-mer length of at least 1\n"); return 1; }
             ko.k = (uint32_t)v64; k_given = 1;
         }
+        else if (mode == 13 && !strcmp(a, "-k")) {
+            if (parse_u64(v, &v64) || v64 < 1 || v64 > 32) { fprintf(stderr, "-k: a k-mer length in 1..32\n"); return 1; }
+            ko.k = (uint32_t)v64; k_given = 1;
+        }
+        else if (mode == 13 && !strcmp(a, "--bins")) {
+            if (parse_u64(v, &bins) || bins < 2 || bins > 4096) { fprintf(stderr, "--bins: a number of bins in 2..4096\n"); return 1; }
+        }
+        else if (mode == 13 && !strcmp(a, "--list")) list = v;
+        else if (mode == 13 && !strcmp(a, "--at-least")) {
+            if (parse_u64(v, &at_least) || at_least < 1 || at_least > 0xFFFFFFFFull) { fprintf(stderr, "--at-least: a multiplicity of at least 1\n"); return 1; }
+            filter_given = 1;
+        }
+        else if (mode == 13 && !strcmp(a, "--at-most")) {
+            if (parse_u64(v, &at_most) || at_most < 1 || at_most > 0xFFFFFFFFull) { fprintf(stderr, "--at-most: a multiplicity of at least 1\n"); return 1; }
+            filter_given = 1;
+        }
+        else if (mode == 8 && !strcmp(a, "--min-count") && !strcmp(v, "auto")) auto_count = 1;
         else if (mode == 8 && !strcmp(a, "--min-count")) {
+            auto_count = 0;
             if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-count: a count of at least 1\n"); return 1; }
             ko.min_count = (uint32_t)v64;
         }
@@ -1558,6 +1670,13 @@ int main(int argc, char **argv) {
         if (clean && !cl.max_tip && !cl.max_bubble) { fprintf(stderr, "--clean: --max-tip and --max-bubble are both 0\n"); return 1; }
         return cmd_graph(out, (int)device, (uint32_t)min_overlap, all_edges, states, mode == 10, graph_both, clean ? &cl : NULL);
     }
+    if (mode == 13) {
+        if (!out || file) { usage(); return 1; }
+        if (!k_given) { fprintf(stderr, "%s: -k K is required\n", cmd); usage(); return 1; }
+        if (filter_given && !list) { fprintf(stderr, "--at-least, --at-most: only with --list\n"); return 1; }
+        if (at_least > at_most) { fprintf(stderr, "--at-least: above --at-most\n"); return 1; }
+        return cmd_spectrum(out, (int)device, ko.k, ko.flags, (uint32_t)bins, list, (uint32_t)at_least, (uint32_t)at_most);
+    }
     if (!out || !file) { usage(); return 1; }
     if (mapping) {
         if (!ref) fprintf(stderr, "%s: no --ref INPUT.fa[.gz]: the text is restored from %s.sa and the BWT\n", cmd, out);
@@ -1583,7 +1702,7 @@ int main(int argc, char **argv) {
     if (mode == 7 || mode == 8) {
         if (!k_given) { fprintf(stderr, "%s: -k K is required\n", cmd); usage(); return 1; }
         if (mode == 7) return cmd_kmers(out, file, (int)device, ko.k, flags);
-        return cmd_correct(out, file, (int)device, &ko, report);
+        return cmd_correct(out, file, (int)device, &ko, auto_count, report);
     }
     if (mode == 5) {
         if (permille_given && !ovl_mm) { fprintf(stderr, "--max-error-permille: only with --max-mismatches\n"); usage(); return 1; }

@@ -123,6 +123,26 @@ class DebwtFmKmerStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class DebwtFmSpectrumTotals(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("distinct", "total", "overflow_total")]
+
+
+class DebwtFmSpectrumSummary(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("valley", "peak", "est_size")]
+
+
+class DebwtFmSpectrumStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("chunks", "launches", "levels", "expanded", "leaves", "lookups", "steps",
+                                                 "line_reads", "wave_steps", "scratch_bytes", "items_limit")] +
+                [("level_intervals", ctypes.c_uint64 * 33), ("table_q", ctypes.c_uint32), ("reserved", ctypes.c_uint32)] +
+                [(n, ctypes.c_float) for n in ("ms_table", "ms_kernel", "ms_wall")])
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n, _ in self._fields_ if n not in ("reserved", "level_intervals")}
+        d["level_intervals"] = [int(x) for x in self.level_intervals]
+        return d
+
+
 CORRECT_MAX_ROUNDS = 16
 
 
@@ -370,6 +390,7 @@ SYMBOLS = [
     "debwt_fm_extract", "debwt_fm_extract_stats_get", "debwt_fm_restore_text", "debwt_fm_text_fetch",
     "debwt_fm_kmer_counts", "debwt_fm_kmer_stats_get", "debwt_fm_weak_trials", "debwt_fm_correct_defaults",
     "debwt_fm_correct", "debwt_fm_correct_stats_get",
+    "debwt_fm_spectrum", "debwt_fm_kmer_list", "debwt_fm_spectrum_threshold", "debwt_fm_spectrum_stats_get",
     "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
     "debwt_fm_string_graph_both", "debwt_fm_unitigs_both", "debwt_fm_graph_both_stats_get",
     "debwt_fm_clean_defaults", "debwt_fm_graph_clean", "debwt_fm_edges_compact", "debwt_fm_clean_stats_get",
@@ -672,6 +693,16 @@ def lib():
                                    ctypes.POINTER(DebwtFmCorrectInfo)]
     L.debwt_fm_correct_stats_get.restype = ctypes.c_int
     L.debwt_fm_correct_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmCorrectStats)]
+    L.debwt_fm_spectrum.restype = ctypes.c_int
+    L.debwt_fm_spectrum.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u64p,
+                                    ctypes.POINTER(DebwtFmSpectrumTotals)]
+    L.debwt_fm_kmer_list.restype = ctypes.c_int
+    L.debwt_fm_kmer_list.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, u64p, u32p,
+                                     ctypes.c_uint64, u64p]
+    L.debwt_fm_spectrum_threshold.restype = ctypes.c_int
+    L.debwt_fm_spectrum_threshold.argtypes = [u64p, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(DebwtFmSpectrumSummary)]
+    L.debwt_fm_spectrum_stats_get.restype = ctypes.c_int
+    L.debwt_fm_spectrum_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmSpectrumStats)]
     u8p, edgep = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(DebwtFmEdge)
     L.debwt_fm_string_graph.restype = ctypes.c_int
     L.debwt_fm_string_graph.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u64p, edgep, ctypes.c_uint64]

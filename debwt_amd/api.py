@@ -509,13 +509,62 @@ class FMIndex:
         self._chk(self._L.debwt_fm_kmer_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def spectrum(self, k, strands="both", bins=256):
+        """The k-mer spectrum of the indexed collection (debwt_fm_spectrum): every distinct k-mer inside a record is met
+        once by a walk over the index; strands "both" counts a k-mer with its reverse complement under the smaller code
+        (a k-mer that is its own reverse complement counts twice, as in kmer_counts).  hist[c] is the number of distinct
+        k-mers of multiplicity c, the last bin holds bins - 1 and above.  No reads and no attached text are needed.
+        Returns a SpectrumResult."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        hist = np.zeros(max(int(bins), 1), dtype=np.uint64)
+        tot = _lib.DebwtFmSpectrumTotals()
+        self._chk(self._L.debwt_fm_spectrum(self._h, int(k), SEARCH_BOTH_STRANDS if strands == "both" else 0, int(bins),
+                                            _p64(hist), ctypes.byref(tot)))
+        return SpectrumResult(int(k), strands, hist, int(tot.distinct), int(tot.total), int(tot.overflow_total))
+
+    def kmer_list(self, k, strands="both", min_count=1, max_count=2**32 - 1):
+        """The distinct k-mers with min_count <= multiplicity <= max_count (debwt_fm_kmer_list), ascending by code:
+        (codes uint64, counts uint32).  A code holds A, C, G, T as 0..3 with the first character in the most significant
+        digit (kmer_string turns it back into letters); counts are clamped at 2^32 - 1."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
+        flags = SEARCH_BOTH_STRANDS if strands == "both" else 0
+        n = ctypes.c_uint64(0)
+        args = (self._h, int(k), flags, int(min_count), int(max_count))
+        rc = self._L.debwt_fm_kmer_list(*args, None, None, 0, ctypes.byref(n))      # the sizing call: ERANGE names the count
+        if rc != -5:
+            self._chk(rc)
+        codes = np.zeros(max(n.value, 1), dtype=np.uint64)
+        counts = np.zeros(max(n.value, 1), dtype=np.uint32)
+        if n.value:
+            self._chk(self._L.debwt_fm_kmer_list(*args, _p64(codes), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                 n.value, ctypes.byref(n)))
+        return codes[:n.value], counts[:n.value]
+
+    def spectrum_stats(self):
+        """What the last spectrum or kmer_list call did (debwt_fm_spectrum_stats_get): chunks, launches, levels, intervals
+        expanded and per depth, leaves, reverse-complement look-ups, rank steps and lines, wave steps, scratch bytes, the
+        limit in force, the table's q and ms."""
+        st = _lib.DebwtFmSpectrumStats()
+        self._chk(self._L.debwt_fm_spectrum_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def correct(self, patterns, k, min_count=3, rounds=4, strands="both"):
         """k-mer read correction on the device (debwt_fm_correct): per read and round, a run of weak k-mers (count below
         min_count) that has the signature of one substitution is fixed when exactly one other base makes the k-mer next
-        to the solid ones solid.  Bytes that are not fixed stay as given.  Returns (reads, info): the reads as a list of
-        bytes and a structured array of flags (CORRECT_SHORT / CLEAN / FIXED / WEAK), fixes, weak_before, weak_after."""
+        to the solid ones solid.  Bytes that are not fixed stay as given.  min_count "auto" takes the valley of the
+        spectrum at this k and these strands (256 bins) and raises ValueError when the spectrum has none.  Returns
+        (reads, info): the reads as a list of bytes and a structured array of flags (CORRECT_SHORT / CLEAN / FIXED /
+        WEAK), fixes, weak_before, weak_after."""
         if strands not in ("forward", "both"):
             raise ValueError('strands must be "forward" or "both"')
+        if isinstance(min_count, str):
+            if min_count != "auto":
+                raise ValueError('min_count must be a number or "auto"')
+            min_count = self.spectrum(k, strands=strands, bins=256).threshold()["valley"]
+            if not min_count:
+                raise ValueError(f"min_count=\"auto\": the {k}-mer spectrum of the collection has no valley")
         buf, offs = _patterns(patterns)
         npat = len(offs) - 1
         opts = _lib.DebwtFmCorrectOpts(k=int(k), min_count=int(min_count), max_rounds=int(rounds),
@@ -1062,6 +1111,26 @@ def weak_trials(counts, k, min_count):
     return out
 
 
+def spectrum_threshold(hist, total):
+    """Valley, peak and size estimate of a k-mer spectrum on the host (debwt_fm_spectrum_threshold, no GPU): valley = the
+    smallest c in 1..bins-3 with hist[c + 1] > hist[c], peak = the fullest bin in valley+1..bins-2 (the smallest on ties),
+    est_size = (total - the k-mers below the valley) // peak; all 0 when the histogram has no valley."""
+    h = np.ascontiguousarray(hist, dtype=np.uint64)
+    out = _lib.DebwtFmSpectrumSummary()
+    rc = _lib.lib().debwt_fm_spectrum_threshold(_p64(h) if len(h) else None, len(h), int(total), ctypes.byref(out))
+    if rc:
+        raise DebwtError(rc)
+    return {"valley": int(out.valley), "peak": int(out.peak), "est_size": int(out.est_size)}
+
+
+def kmer_string(code, k):
+    """The letters of a k-mer code (A, C, G, T = 0..3, the first character in the most significant digit)."""
+    code, k = int(code), int(k)
+    if not 1 <= k <= 32 or not 0 <= code < 4 ** k:
+        raise ValueError("k must be 1..32 and the code below 4^k")
+    return "".join("ACGT"[(code >> (2 * (k - 1 - i))) & 3] for i in range(k))
+
+
 def overlap_longest(hits, offsets):
     """The reduction of overlaps(longest=True) on the host (debwt_fm_overlap_longest, no GPU): hits (structured array of
     record, length, strand, flags) in the order of OverlapResult, pattern i's in offsets[i] .. offsets[i + 1]; per
@@ -1436,6 +1505,19 @@ class KmerResult:
 
     def profile(self, i):
         return self.counts[int(self.offsets[i]):int(self.offsets[i + 1])]
+
+
+class SpectrumResult:
+    """Spectrum of FMIndex.spectrum: hist (uint64, hist[0] = 0, the last bin holds bins - 1 and above), distinct (the sum
+    of hist), total (the sum of the multiplicities) and overflow_total (that sum over the last bin); threshold(): valley,
+    peak and est_size (spectrum_threshold)."""
+
+    def __init__(self, k, strands, hist, distinct, total, overflow_total):
+        self.k, self.strands, self.hist = k, strands, hist
+        self.distinct, self.total, self.overflow_total = distinct, total, overflow_total
+
+    def threshold(self):
+        return spectrum_threshold(self.hist, self.total)
 
 
 class OverlapResult:

@@ -36,6 +36,7 @@
 #include "fm_overlap_mm_kernels.h"
 #include "fm_extract_kernels.h"
 #include "fm_kmer_kernels.h"
+#include "fm_spectrum_kernels.h"
 #include "fm_graph_kernels.h"
 #include "fm_bigraph_kernels.h"
 #include "fm_clean_kernels.h"
@@ -2994,6 +2995,8 @@ struct debwt_fm {
     DevBuf k_coff, k_counts, k_ctr, k_active, k_info, k_ntr, k_trials, k_trun, k_res;   // k-mer and correction scratch of one batch
     debwt_fm_kmer_stats k_stats{};
     debwt_fm_correct_stats c_stats{};
+    DevBuf sp_front, sp_codes, sp_mults, sp_ctr, sp_hist, sp_gsum;   // spectrum: two frontiers, list staging, counters, histogram, granule sums
+    debwt_fm_spectrum_stats sp_stats{};
     DevBuf g_coff, g_state, g_hbase, g_raw, g_flag, g_deg, g_oseg, g_edges, g_eoff, g_len, g_keep, g_out, g_ctr;   // string graph
     debwt_fm_graph_stats g_stats{};
     DevBuf b_state, b_self, b_row, b_cnt, b_whb, b_rawbase, b_tbase, b_pos, b_aoff, b_mm, b_cur, b_cat, b_ctr;   // graph over both strands
@@ -6445,6 +6448,222 @@ extern "C" int debwt_fm_correct_stats_get(const debwt_fm *f, debwt_fm_correct_st
     return DEBWT_OK;
 }
 
+// ---- k-mer spectrum of the indexed collection (fm_spectrum_kernels.h) --------------------------------------------------
+// The start entries (table order) are cut into chunks on the host from the sums of 1024-entry granules, which a sizing
+// kernel makes per call; only a granule that a cut falls into is fetched.  A chunk is a run of launches without a host
+// round trip: cursors cleared, start, one expansion per level over the chunk's bound, leaves.  The histogram and the
+// totals stay on the device until the end; list members are staged on the device and flushed when the staging could
+// overflow, then sorted on the host.
+
+namespace {
+
+constexpr u64 FM_SPECTRUM_ITEMS = 1ull << 22;          // sum of hi - lo over the start entries of a chunk: 192 MiB of frontiers
+constexpr u64 FM_SPECTRUM_STAGE = 1ull << 16;          // least list staging (members), so small chunks do not flush one by one
+
+struct FmSpecChunk { u64 i0, i1, sum, entries; };
+
+// chunks of the table's entries [0, 4^q): runs of entries whose sizes sum to at most limit; an entry above it goes alone
+int fm_spectrum_plan(debwt_fm *f, u32 q, u64 limit, std::vector<FmSpecChunk> *chunks, debwt_fm_spectrum_stats *st) {
+    if (!q) { chunks->push_back(FmSpecChunk{0, 1, f->n, 1}); return DEBWT_OK; }
+    const u64 T = 1ull << (2 * q), G = FM_SPEC_GRANULE, ng = (T + G - 1) / G;
+    FM_ENSURE(f, f->sp_gsum, (size_t)ng * 16);
+    k_fm_spectrum_sizes<<<(u32)ng, 256, 0, f->stream>>>(f->k_table.as<u64>(), T, f->sp_gsum.as<u64>());
+    st->launches++;
+    std::vector<u64> gs(2 * ng), gran(2 * G);
+    HIPCHK(f, hipMemcpyAsync(gs.data(), f->sp_gsum.p, (size_t)ng * 16, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    u64 loaded = ~0ull;
+    for (u64 i = 0; i < T;) {
+        FmSpecChunk c{i, i, 0, 0};
+        while (i < T) {
+            const u64 g = i / G;
+            if (i % G == 0 && c.sum + gs[2 * g] <= limit) {     // the whole granule fits
+                c.sum += gs[2 * g]; c.entries += gs[2 * g + 1];
+                i = std::min<u64>(T, i + G);
+                if (c.sum >= limit) break;
+                continue;
+            }
+            if (loaded != g) {
+                const u64 cnt = std::min<u64>(G, T - g * G);
+                HIPCHK(f, hipMemcpyAsync(gran.data(), f->k_table.as<u64>() + 2 * g * G, (size_t)cnt * 16, hipMemcpyDeviceToHost, f->stream));
+                if ((rc = fm_sync(f))) return rc;
+                loaded = g;
+            }
+            const u64 lo = gran[2 * (i - g * G)], hi = gran[2 * (i - g * G) + 1], size = hi > lo ? hi - lo : 0;
+            if (!size) { i++; continue; }
+            if (c.entries && c.sum + size > limit) break;
+            c.sum += size; c.entries++; i++;
+            if (c.sum >= limit) break;
+        }
+        c.i1 = i;
+        if (c.entries) chunks->push_back(c);
+    }
+    return DEBWT_OK;
+}
+
+struct FmSpecList {                                     // the list side of a run; null for a histogram
+    u32 min_mult, max_mult;
+    u64 capacity;                                       // 0: count only
+    std::vector<std::pair<u64, u32>> members;
+    u64 count = 0;
+};
+
+// members staged on the device to the host
+int fm_spectrum_flush(debwt_fm *f, FmSpecList *ls, std::vector<u64> *hc, std::vector<u32> *hm, u64 stage) {
+    u64 cnt = 0;
+    HIPCHK(f, hipMemcpyAsync(&cnt, f->sp_ctr.as<u64>() + FM_SP_LIST, 8, hipMemcpyDeviceToHost, f->stream));
+    int rc = fm_sync(f);
+    if (rc) return rc;
+    if (cnt > stage) { f->err = "spectrum: the list staging overflowed"; return DEBWT_EINTERNAL; }
+    ls->count += cnt;
+    if (cnt && ls->count <= ls->capacity) {
+        hc->resize(cnt); hm->resize(cnt);
+        HIPCHK(f, hipMemcpyAsync(hc->data(), f->sp_codes.p, (size_t)cnt * 8, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(f, hipMemcpyAsync(hm->data(), f->sp_mults.p, (size_t)cnt * 4, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+        for (u64 i = 0; i < cnt; i++) ls->members.emplace_back((*hc)[i], (*hm)[i]);
+    }
+    HIPCHK(f, hipMemsetAsync(f->sp_ctr.as<u64>() + FM_SP_LIST, 0, 8, f->stream));
+    return DEBWT_OK;
+}
+
+// the walk of both calls: hist (nbins u64, host) and totals for the histogram, ls for the list
+int fm_spectrum_run(debwt_fm *f, const char *what, u32 k, u32 flags, u32 nbins, uint64_t *hist, debwt_fm_spectrum_totals *totals,
+                    FmSpecList *ls) {
+    const auto t0 = std::chrono::steady_clock::now();
+    f->sp_stats = debwt_fm_spectrum_stats{};
+    debwt_fm_spectrum_stats &st = f->sp_stats;
+    if (k < 1 || k > FM_SPEC_MAX_K) { f->err = std::string(what) + ": k must be 1..32"; return DEBWT_EINVAL; }
+    if (flags & ~DEBWT_FM_BOTH_STRANDS) { f->err = std::string(what) + ": unknown flags"; return DEBWT_EINVAL; }
+    u32 q = 0;
+    int rc = fm_kmer_env_q(f, &q);
+    if (rc) return rc;
+    if (k < q) q = 0;
+    const u64 limit = fm_env_u64("DEBWT_FM_SPECTRUM_ITEMS", FM_SPECTRUM_ITEMS);
+    const u32 both = (flags & DEBWT_FM_BOTH_STRANDS) ? 1u : 0u;
+    st.items_limit = limit;
+    HIPCHK(f, hipSetDevice(f->device));
+    FmKmerCall ev;                                             // its two events
+    HIPCHK(f, hipEventCreate(&ev.e0));
+    HIPCHK(f, hipEventCreate(&ev.e1));
+    debwt_fm_kmer_stats kst{};
+    if ((rc = fm_kmer_table(f, q, &kst))) return rc;
+    st.table_q = q; st.ms_table = kst.ms_table; st.launches = kst.launches;
+    std::vector<FmSpecChunk> chunks;
+    if ((rc = fm_spectrum_plan(f, q, limit, &chunks, &st))) return rc;
+    u64 cap = 1;
+    for (const FmSpecChunk &c : chunks) cap = std::max<u64>(cap, c.sum);
+    const bool stage_list = ls && ls->capacity;
+    const u64 stage = stage_list ? std::max<u64>(cap, FM_SPECTRUM_STAGE) : 0;
+    FM_ENSURE(f, f->sp_front, (size_t)cap * 48);
+    FM_ENSURE(f, f->sp_ctr, FM_SP_NCTR * 8);
+    if (hist) FM_ENSURE(f, f->sp_hist, (size_t)nbins * 8);
+    if (stage_list) { FM_ENSURE(f, f->sp_codes, (size_t)stage * 8); FM_ENSURE(f, f->sp_mults, (size_t)stage * 4); }
+    st.scratch_bytes = cap * 48 + FM_SP_NCTR * 8 + (hist ? (u64)nbins * 8 : 0) + stage * 12 + (q ? ((1ull << (2 * q)) + 1023) / 1024 * 16 : 0);
+    HIPCHK(f, hipMemsetAsync(f->sp_ctr.p, 0, FM_SP_NCTR * 8, f->stream));
+    if (hist) HIPCHK(f, hipMemsetAsync(f->sp_hist.p, 0, (size_t)nbins * 8, f->stream));
+    u64 *front[2] = {f->sp_front.as<u64>(), f->sp_front.as<u64>() + 3 * cap}, *ctr = f->sp_ctr.as<u64>();
+    const u64 *table = q ? f->k_table.as<u64>() : nullptr;
+    std::vector<u64> hc;
+    std::vector<u32> hm;
+    u64 staged = 0;                                            // bound of the members on the device
+    st.levels = k - q;
+    (void)hipEventRecord(ev.e0, f->stream);
+    for (const FmSpecChunk &c : chunks) {
+        if (stage_list && staged + c.sum > stage) {
+            if ((rc = fm_spectrum_flush(f, ls, &hc, &hm, stage))) return rc;
+            staged = 0;
+        }
+        HIPCHK(f, hipMemsetAsync(ctr + FM_SP_CUR, 0, (FM_SPEC_MAX_K + 2) * 8, f->stream));
+        k_fm_spectrum_start<<<grid_for(c.i1 - c.i0, 256), 256, 0, f->stream>>>(f->V, table, c.i0, c.i1, q, front[0], cap, ctr);
+        u64 bound = c.entries;                                 // of the frontier of depth d
+        for (u32 d = q; d < k; d++) {
+            bound = std::min<u64>(bound, c.sum);
+            k_fm_spectrum_expand<<<grid_for(bound, 256), 256, 0, f->stream>>>(f->V, front[(d - q) & 1], front[(d - q + 1) & 1], cap, d, ctr);
+            bound = bound > c.sum / 4 ? c.sum : bound * 4;
+        }
+        bound = std::min<u64>(bound, c.sum);
+        k_fm_spectrum_leaves<<<grid_for(bound, 256), 256, hist ? nbins * 4 : 0, f->stream>>>(
+            f->V, table, q, front[(k - q) & 1], cap, k, both, nbins, hist ? f->sp_hist.as<u64>() : nullptr,
+            ls ? ls->min_mult : 0, ls ? ls->max_mult : 0, stage_list ? f->sp_codes.as<u64>() : nullptr,
+            stage_list ? f->sp_mults.as<u32>() : nullptr, stage, ctr);
+        st.launches += 2 + (k - q);
+        st.chunks++;
+        staged += c.sum;
+    }
+    (void)hipEventRecord(ev.e1, f->stream);
+    if (stage_list) { if ((rc = fm_spectrum_flush(f, ls, &hc, &hm, stage))) return rc; }
+    u64 h[FM_SP_NCTR];
+    HIPCHK(f, hipMemcpyAsync(h, ctr, FM_SP_NCTR * 8, hipMemcpyDeviceToHost, f->stream));
+    if (hist) HIPCHK(f, hipMemcpyAsync(hist, f->sp_hist.p, (size_t)nbins * 8, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    (void)hipEventElapsedTime(&st.ms_kernel, ev.e0, ev.e1);
+    if (h[FM_SP_CLIPPED]) { f->err = std::string(what) + ": a frontier outgrew its bound"; return DEBWT_EINTERNAL; }
+    for (u32 d = 0; d <= FM_SPEC_MAX_K; d++) st.level_intervals[d] = h[FM_SP_LEVEL + d];
+    for (u32 d = 0; d < k; d++) st.expanded += st.level_intervals[d];
+    st.leaves = st.level_intervals[k]; st.lookups = h[FM_SP_LOOKUPS]; st.steps = st.expanded + h[FM_SP_STEPS];
+    st.line_reads = h[FM_SP_READS]; st.wave_steps = h[FM_SP_WSTEPS];
+    if (totals) {                                              // the bins below the last give their own share of both sums
+        *totals = debwt_fm_spectrum_totals{0, h[FM_SP_OVER], h[FM_SP_OVER]};
+        for (u32 c = 0; c < nbins; c++) { totals->distinct += hist[c]; if (c + 1 < nbins) totals->total += (u64)c * hist[c]; }
+    }
+    if (ls && !stage_list) ls->count = h[FM_SP_LIST];
+    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return DEBWT_OK;
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_spectrum(debwt_fm *f, uint32_t k, uint32_t flags, uint32_t nbins, uint64_t *hist,
+                                 debwt_fm_spectrum_totals *totals) {
+    if (!f || !hist || !totals) return DEBWT_EINVAL;
+    if (nbins < 2 || nbins > FM_SPEC_MAX_BINS) { f->err = "debwt_fm_spectrum: nbins must be 2..4096"; return DEBWT_EINVAL; }
+    return fm_spectrum_run(f, "debwt_fm_spectrum", k, flags, nbins, hist, totals, nullptr);
+}
+
+extern "C" int debwt_fm_kmer_list(debwt_fm *f, uint32_t k, uint32_t flags, uint32_t min_mult, uint32_t max_mult,
+                                  uint64_t *codes, uint32_t *mults, uint64_t capacity, uint64_t *count) {
+    if (!f || !count || (capacity && (!codes || !mults))) return DEBWT_EINVAL;
+    if (!min_mult || min_mult > max_mult) { f->err = "debwt_fm_kmer_list: min_mult must be 1..max_mult"; return DEBWT_EINVAL; }
+    FmSpecList ls{min_mult, max_mult, capacity, {}, 0};
+    int rc = fm_spectrum_run(f, "debwt_fm_kmer_list", k, flags, 0, nullptr, nullptr, &ls);
+    if (rc) return rc;
+    *count = ls.count;
+    if (capacity < ls.count) {
+        f->err = "debwt_fm_kmer_list: capacity below the members (count = " + std::to_string(ls.count) + ")";
+        return DEBWT_ERANGE;
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    std::sort(ls.members.begin(), ls.members.end());           // codes are distinct: the order is that of the codes
+    for (u64 i = 0; i < ls.count; i++) { codes[i] = ls.members[i].first; mults[i] = ls.members[i].second; }
+    f->sp_stats.ms_wall += (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_spectrum_threshold(const uint64_t *hist, uint32_t nbins, uint64_t total, debwt_fm_spectrum_summary *out) {
+    if (!hist || !out || nbins < 2 || nbins > FM_SPEC_MAX_BINS) return DEBWT_EINVAL;
+    *out = debwt_fm_spectrum_summary{0, 0, 0};
+    u32 valley = 0;
+    for (u32 c = 1; c + 3 <= nbins; c++)
+        if (hist[c + 1] > hist[c]) { valley = c; break; }
+    if (!valley) return DEBWT_OK;
+    u32 peak = valley + 1;
+    for (u32 c = valley + 1; c + 2 <= nbins; c++)
+        if (hist[c] > hist[peak]) peak = c;
+    u64 below = 0;
+    for (u32 c = 1; c < valley; c++) below += (u64)c * hist[c];
+    out->valley = valley; out->peak = peak;
+    out->est_size = (total > below ? total - below : 0) / peak;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_spectrum_stats_get(const debwt_fm *f, debwt_fm_spectrum_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->sp_stats;
+    return DEBWT_OK;
+}
+
 // ---- string graph of the indexed records, on one strand or on both (fm_graph_kernels.h, fm_bigraph_kernels.h) --------
 // debwt_fm_string_graph and debwt_fm_string_graph_both share one host path: fm_graph_found, then fm_graph_finish.
 // States come from one backward search per record over the attached text.  The kept records then go through the overlap
@@ -7571,7 +7790,8 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
                       &f->x_cig, &f->x_anchors, &f->o_table, &f->o_slot, &f->o_runs, &f->o_nruns, &f->o_nhits, &f->o_rbase,
                       &f->o_hbase, &f->o_cruns, &f->o_rout, &f->o_hits, &f->anchors, &f->e_jobs, &f->e_seg, &f->e_out, &f->e_ctr,
                       &f->e_sep, &f->k_table, &f->k_coff, &f->k_counts, &f->k_ctr, &f->k_active, &f->k_info, &f->k_ntr,
-                      &f->k_trials, &f->k_trun, &f->k_res, &f->g_coff, &f->g_state, &f->g_hbase, &f->g_raw, &f->g_flag,
+                      &f->k_trials, &f->k_trun, &f->k_res, &f->sp_front, &f->sp_codes, &f->sp_mults, &f->sp_ctr, &f->sp_hist,
+                      &f->sp_gsum, &f->g_coff, &f->g_state, &f->g_hbase, &f->g_raw, &f->g_flag,
                       &f->g_deg, &f->g_oseg, &f->g_edges, &f->g_eoff, &f->g_len, &f->g_keep, &f->g_out, &f->g_ctr, &f->b_state,
                       &f->b_self, &f->b_row, &f->b_cnt, &f->b_whb, &f->b_rawbase, &f->b_tbase, &f->b_pos, &f->b_aoff, &f->b_mm,
                       &f->b_cur, &f->b_cat, &f->b_ctr, &f->cl_state, &f->cl_src, &f->cl_cnt, &f->cl_toff, &f->cl_tin, &f->cl_snap,

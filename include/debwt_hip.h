@@ -1115,6 +1115,66 @@ typedef struct {
 } debwt_fm_correct_stats;
 int debwt_fm_correct_stats_get(const debwt_fm *fm, debwt_fm_correct_stats *out);
 
+/* ---- Definition 9 (spectrum): the k-mer spectrum of the indexed collection (fm_spectrum_kernels.h) -------------------
+ * k is in 1..32.  A k-mer W is written as a u64 code: A, C, G, T = 0..3, the first character in the most significant
+ * digit, value below 4^k; code order equals string order.  occ W is as in the k-mer section above: the occurrences inside
+ * one record, what debwt_fm_count answers; a k-mer that would span a separator or the end does not exist.
+ *   Forward.  D is the set of W with occ W > 0, mult W = occ W.
+ *   DEBWT_FM_BOTH_STRANDS.  D is the set of canonical codes m = min(W, revcomp W) with occ m + occ revcomp m > 0, and
+ *   mult m = cnt of the k-mer section = occ m + occ revcomp m.  A k-mer equal to its own reverse complement therefore has
+ *   mult 2 occ, exactly the number debwt_fm_correct compares with min_count.
+ * Histogram, nbins in 2..4096: hist[0] = 0; for 1 <= c < nbins - 1 hist[c] = the number of W in D with mult = c;
+ * hist[nbins - 1] = the number with mult >= nbins - 1.  Totals: distinct = |D| = the sum of hist, total = the sum of
+ * mult over D, overflow_total = the sum of mult over the members of the last bin.
+ *   forward:       total = the sum over the records S of max(0, |S| - k + 1);
+ *   both strands:  total = the forward total + the sum of occ over the k-mers that equal their own reverse complement
+ *                  (not twice the forward total: W and revcomp W share one member).
+ * List: the members of D with min_mult <= mult <= max_mult, ascending by code, mult clamped to u32 (2^32 - 1) before it
+ * is compared and written.
+ * Threshold (host, no GPU): valley = the smallest c in 1..nbins-3 with hist[c + 1] > hist[c]; peak = the c in
+ * valley+1..nbins-2 with the largest hist[c], the smallest such c on ties; without such a c, valley = peak = 0 ("no
+ * valley").  est_size = (total - the sum over c < valley of c * hist[c]) / peak, integer division, 0 when peak = 0.  The
+ * min_count taken from a spectrum is valley: k-mers below it are weak.
+ *
+ * The walk.  A frontier entry is (lo, hi, code) of one string with a non-empty row interval.  The walk starts from the
+ * non-empty entries of the prefix table of the k-mer section (same q, same DEBWT_FM_KMER_TABLE_Q, built by the first call
+ * that needs it and counted in device_bytes) or, when k < q or q = 0, from [0, n); each level prepends A, C, G, T to every
+ * entry with one read of its rank line(s), so every distinct k-mer is met once.  Both strands: a leaf looks up occ of its
+ * reverse complement (k - q steps from the table) and emits the member when it holds the canonical code, or when its
+ * reverse complement does not occur.  The start entries are cut, in table order, into chunks whose sum of hi - lo is at
+ * most DEBWT_FM_SPECTRUM_ITEMS (environment, read per call; default 2^22; an entry above the limit goes alone); the
+ * children of an interval are disjoint parts of it, so that sum bounds every frontier of the chunk.  Device scratch, each
+ * buffer with up to 25 % slack: 48 bytes (60 for a list) per item of max(the limit, the largest start entry), 16 bytes per
+ * 1024 table entries, and below 1 MiB of counters, histogram and list staging: about 200 MiB at the default (240 for a
+ * list).  Without a table the one start entry is [0, n): 48 n bytes.  No result depends on the limit or on q.  Neither
+ * call needs an attached text.  The list is sorted on the host. */
+typedef struct { uint64_t distinct, total, overflow_total; } debwt_fm_spectrum_totals;
+typedef struct { uint64_t valley, peak, est_size; } debwt_fm_spectrum_summary;
+/* DEBWT_EINVAL for k outside 1..32, nbins outside 2..4096, flags other than DEBWT_FM_BOTH_STRANDS and NULL outputs */
+int debwt_fm_spectrum(debwt_fm *fm, uint32_t k, uint32_t flags, uint32_t nbins, uint64_t *hist,
+                      debwt_fm_spectrum_totals *totals);
+/* count is written first; DEBWT_ERANGE when capacity < count (the protocol of debwt_fm_locate; capacity 0 with NULL
+ * arrays is the sizing call).  DEBWT_EINVAL for k outside 1..32, unknown flags, min_mult = 0, min_mult > max_mult, a NULL
+ * count and NULL arrays with capacity > 0. */
+int debwt_fm_kmer_list(debwt_fm *fm, uint32_t k, uint32_t flags, uint32_t min_mult, uint32_t max_mult,
+                       uint64_t *codes, uint32_t *mults, uint64_t capacity, uint64_t *count);
+/* host only; DEBWT_EINVAL for NULL and nbins outside 2..4096 */
+int debwt_fm_spectrum_threshold(const uint64_t *hist, uint32_t nbins, uint64_t total, debwt_fm_spectrum_summary *out);
+/* what the last debwt_fm_spectrum or debwt_fm_kmer_list did: chunks, kernel launches (the table's levels and the sizing
+ * pass included), levels walked per chunk (k - start depth), intervals expanded (one fm_occ4 each), leaves (intervals of
+ * depth k), reverse-complement look-ups, rank steps (expansions plus the fm_occ2 of the look-ups), rank lines read, wave
+ * steps (64 per wave of an expansion, 64 x the longest look-up of a wave: steps / wave_steps is the share of lanes
+ * busy), the scratch of the call (sized by its largest chunk), the limit in force, the intervals of every depth
+ * (level_intervals[d], d = start depth .. k), the table's q (0: none used), the time to build the table (events; 0 when
+ * it existed), the time from the first chunk to the last kernel (events) and host wall time */
+typedef struct {
+    uint64_t chunks, launches, levels, expanded, leaves, lookups, steps, line_reads, wave_steps, scratch_bytes, items_limit;
+    uint64_t level_intervals[33];
+    uint32_t table_q, reserved;
+    float ms_table, ms_kernel, ms_wall;
+} debwt_fm_spectrum_stats;
+int debwt_fm_spectrum_stats_get(const debwt_fm *fm, debwt_fm_spectrum_stats *out);
+
 /* ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
  * Records S_0 .. S_{nrec-1} are those of the index, numbered as in overlap hits; |S| is the length of S.
  * 1. state[i] = 1 (duplicate) iff some j < i has S_j == S_i; otherwise 2 (contained) iff S_i is a substring of a strictly
