@@ -427,6 +427,11 @@ class FMIndex:
         strands "both" adds the overlaps of the reverse complement (strand 1: the record begins with the reverse
         complement of the pattern's FIRST `length` bases).  longest: per (pattern, strand, record) only the largest
         length.  No attached text is needed.  Returns an OverlapResult."""
+        return self._overlaps(patterns, strands, longest, lambda buf, offs, npat, flags, *out: self._L.debwt_fm_overlaps(
+            self._h, buf, offs, npat, int(min_overlap), flags, *out))
+
+    def _overlaps(self, patterns, strands, longest, call):
+        """overlaps() and overlaps_mm(): call(buf, offsets, npat, flags, hit_offsets, hits, capacity) is the bound C call"""
         if strands not in ("forward", "both"):
             raise ValueError('strands must be "forward" or "both"')
         flags = (SEARCH_BOTH_STRANDS if strands == "both" else 0) | (OVERLAP_LONGEST if longest else 0)
@@ -436,8 +441,7 @@ class FMIndex:
         cap = 4 * npat + 16                                   # first estimate; grown to the exact count on DEBWT_ERANGE
         while True:
             hits = np.zeros(cap, dtype=_OVERLAP_DTYPE)
-            rc = self._L.debwt_fm_overlaps(self._h, buf, _p64(offs), npat, int(min_overlap), flags, _p64(hoff),
-                                           hits.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmOverlap)), cap)
+            rc = call(buf, _p64(offs), npat, flags, _p64(hoff), hits.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmOverlap)), cap)
             if rc == -5 and int(hoff[npat]) > cap:
                 cap = int(hoff[npat])
                 continue
@@ -458,24 +462,8 @@ class FMIndex:
         columns and, with error_permille R > 0, in at most R / 1000 of them; a character outside ACGTacgt is a mismatch.
         Patterns hold at most 1024 bytes.  strands and longest as in overlaps(); the order is that of overlaps(), and
         mismatches=0 gives its result.  Returns an OverlapResult whose mismatches() are the counts per hit."""
-        if strands not in ("forward", "both"):
-            raise ValueError('strands must be "forward" or "both"')
-        flags = (SEARCH_BOTH_STRANDS if strands == "both" else 0) | (OVERLAP_LONGEST if longest else 0)
-        buf, offs = _patterns(patterns)
-        npat = len(offs) - 1
-        hoff = np.zeros(npat + 1, dtype=np.uint64)
-        cap = 4 * npat + 16                                   # first estimate; grown to the exact count on DEBWT_ERANGE
-        while True:
-            hits = np.zeros(cap, dtype=_OVERLAP_DTYPE)
-            rc = self._L.debwt_fm_overlaps_mm(self._h, buf, _p64(offs), npat, int(min_overlap), int(mismatches),
-                                              int(error_permille), flags, _p64(hoff),
-                                              hits.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmOverlap)), cap)
-            if rc == -5 and int(hoff[npat]) > cap:
-                cap = int(hoff[npat])
-                continue
-            self._chk(rc)
-            break
-        return OverlapResult(self, hoff, hits[:int(hoff[npat])].copy())
+        return self._overlaps(patterns, strands, longest, lambda buf, offs, npat, flags, *out: self._L.debwt_fm_overlaps_mm(
+            self._h, buf, offs, npat, int(min_overlap), int(mismatches), int(error_permille), flags, *out))
 
     def overlaps_mm_stats(self):
         """What the last overlaps_mm call did (debwt_fm_overlaps_mm_stats_get): batches, launches and re-run launches, runs,

@@ -3036,6 +3036,13 @@ int fm_sync(debwt_fm *f) {
     return DEBWT_OK;
 }
 
+// the two events a call times its launches with, destroyed on every way out
+struct FmEvents {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~FmEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+    int init(debwt_fm *f) { HIPCHK(f, hipEventCreate(&a)); HIPCHK(f, hipEventCreate(&b)); return DEBWT_OK; }
+};
+
 // a temporary device buffer, released on every way out
 struct FmTmp {
     void *p = nullptr;
@@ -3381,6 +3388,16 @@ u64 fm_env_u64(const char *name, u64 dflt) {
     return v ? v : dflt;
 }
 
+// fn(t, nt) for t = 0 .. nt - 1 on nt host threads: one per 65536 of weight, at most 16 and at most the machine's
+template <class Fn>
+void fm_host_threads(u64 weight, Fn fn) {
+    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), weight / 65536 + 1}));
+    std::vector<std::thread> th;
+    for (unsigned t = 1; t < nt; t++) th.emplace_back([&fn, t, nt] { fn(t, nt); });
+    fn(0, nt);
+    for (auto &x : th) x.join();
+}
+
 struct FmSearchRun {
     debwt_fm *f;
     const u8 *chars; const u64 *off; u64 base;
@@ -3551,18 +3568,11 @@ extern "C" int debwt_fm_search(debwt_fm *f, const char *patterns, const uint64_t
         }
     }
     std::vector<u64>().swap(raw);
-    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), nh / 65536 + 1}));
-    auto work = [&](unsigned t) {
+    fm_host_threads(nh, [&](unsigned t, unsigned nt) {
         for (u64 i = t; i < npat; i += nt)
             std::sort(sorted.begin() + start[i], sorted.begin() + start[i + 1],
                       [](const Hit &x, const Hit &y) { return x.key != y.key ? x.key < y.key : x.lo < y.lo; });
-    };
-    {
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
-    }
+    });
     for (u64 h = 0; h < nh; h++) {
         ranges[2 * h] = sorted[h].lo; ranges[2 * h + 1] = sorted[h].hi;
         hit_info[h] = (u32)sorted[h].key;
@@ -3736,6 +3746,9 @@ extern "C" int debwt_fm_mems_stats_get(const debwt_fm *f, debwt_fm_mems_stats *o
 // strand), k_fm_overlap_compact moves the runs there deepest first, and k_fm_overlap_expand writes the hits at most
 // DEBWT_FM_OVERLAP_HITS at a launch, straight into the caller's array.  One run is one (pattern, strand, length) group in
 // row order; the host sorts every group of two or more by record on up to 16 threads.
+// debwt_fm_overlaps and debwt_fm_overlaps_mm share one host path behind their walks: fm_overlaps_call (the batch loop, the
+// longest reduction, the capacity protocol) and fm_overlaps_expand, templates over the statistics struct.  Each call
+// gives its own two steps: cut and walk the next batch, and put the batch's runs into o_cruns and o_rout.
 
 namespace {
 
@@ -3779,8 +3792,13 @@ int fm_overlap_table(debwt_fm *f) {
 }
 
 struct FmOvlBatch {
-    u64 p0 = 0, np = 0, nit = 0, nruns = 0, nhits = 0;
-    std::vector<u64> slot, rbase, hbase, per;              // per: hits per pattern of the batch
+    u64 p0 = 0, np = 0, nruns = 0, nhits = 0;
+    std::vector<u64> per;                                  // hits per pattern of the batch
+    u64 nit = 0;                                           // the exact walk's: items, their slots, first run and first hit
+    std::vector<u64> slot, rbase, hbase;
+    std::vector<uint4> raw;                                // the mismatch walk's: runs as the levels wrote them,
+    std::vector<FmOvlRun> cruns;                           // ordered in k_fm_overlap_expand's layout,
+    std::vector<u64> rout;                                 // and the first hit number of each
 };
 
 // the walk of one batch: fills b (run and hit layout in (pattern, strand) order) and the counters
@@ -3839,43 +3857,50 @@ int fm_overlaps_walk(debwt_fm *f, const char *patterns, const uint64_t *offsets,
     return DEBWT_OK;
 }
 
-// the hits of a walked batch into dst (b.nhits of them), in the documented order
-int fm_overlaps_expand(debwt_fm *f, const FmOvlBatch &b, u64 limit, hipEvent_t e0, hipEvent_t e1, debwt_fm_overlap *dst) {
+// the exact call's runs step: the walked batch's runs from their slots to o_cruns, with o_rout.  ev.a is recorded in
+// front of the compaction, so the first expansion launch is timed together with it.
+int fm_overlaps_compact(debwt_fm *f, const FmOvlBatch &b, u64 chunk, FmEvents &ev) {
     debwt_fm_overlaps_stats &st = f->o_stats;
-    if (!b.nhits) return DEBWT_OK;
-    const u64 chunk = std::min(b.nhits, limit);
     FM_ENSURE(f, f->o_rbase, (size_t)b.nit * 8);
     FM_ENSURE(f, f->o_hbase, (size_t)b.nit * 8);
-    FM_ENSURE(f, f->o_cruns, (size_t)b.nruns * sizeof(FmOvlRun));
-    FM_ENSURE(f, f->o_rout, (size_t)b.nruns * 8);
-    FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
     st.scratch_bytes = std::max<u64>(st.scratch_bytes, b.slot[b.nit] * sizeof(FmOvlRun) + b.nit * 36 + b.nruns * 24 + chunk * 16);
     HIPCHK(f, hipMemcpyAsync(f->o_rbase.p, b.rbase.data(), b.nit * 8, hipMemcpyHostToDevice, f->stream));
     HIPCHK(f, hipMemcpyAsync(f->o_hbase.p, b.hbase.data(), b.nit * 8, hipMemcpyHostToDevice, f->stream));
-    (void)hipEventRecord(e0, f->stream);
+    (void)hipEventRecord(ev.a, f->stream);
     k_fm_overlap_compact<<<grid_for(b.nit, 256), 256, 0, f->stream>>>(f->q_off.as<u64>(), f->o_slot.as<u64>(), f->o_nruns.as<u32>(),
                                                                       f->o_rbase.as<u64>(), f->o_hbase.as<u64>(), b.np, b.nit,
                                                                       f->o_runs.as<FmOvlRun>(), f->o_cruns.as<FmOvlRun>(),
                                                                       f->o_rout.as<u64>());
     st.launches++;
+    return DEBWT_OK;
+}
+
+// The hits of a walked batch into dst (b.nhits of them), in the documented order.  runs(f, b, chunk, ev) fills o_cruns
+// and o_rout, which are reserved here, and records ev.a behind its uploads: the first launch is timed from there.
+template <class St, class Runs>
+int fm_overlaps_expand(debwt_fm *f, St &st, const FmOvlBatch &b, u64 limit, FmEvents &ev, Runs &runs, debwt_fm_overlap *dst) {
+    if (!b.nhits) return DEBWT_OK;
+    const u64 chunk = std::min(b.nhits, limit);
+    FM_ENSURE(f, f->o_cruns, (size_t)b.nruns * sizeof(FmOvlRun));
+    FM_ENSURE(f, f->o_rout, (size_t)b.nruns * 8);
+    FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
+    if (int rc = runs(f, b, chunk, ev)) return rc;
     for (u64 g0 = 0; g0 < b.nhits; g0 += chunk) {
         const u64 cnt = std::min(b.nhits - g0, chunk);
-        if (g0) (void)hipEventRecord(e0, f->stream);
+        if (g0) (void)hipEventRecord(ev.a, f->stream);
         k_fm_overlap_expand<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_cruns.as<FmOvlRun>(), f->o_rout.as<u64>(), b.nruns,
                                                                        f->o_table.as<FmOvlRec>(), g0, cnt, f->o_hits.as<uint4>());
-        (void)hipEventRecord(e1, f->stream);
+        (void)hipEventRecord(ev.b, f->stream);
         HIPCHK(f, hipMemcpyAsync(dst + g0, f->o_hits.p, cnt * sizeof(uint4), hipMemcpyDeviceToHost, f->stream));
-        int rc = fm_sync(f);                                   // the next launch reuses o_hits
-        if (rc) return rc;
+        if (int rc = fm_sync(f)) return rc;                    // the next launch reuses o_hits
         float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventElapsedTime(&ms, ev.a, ev.b);
         st.ms_kernel += ms; st.launches++;
     }
-    // record order inside every (pattern, strand, length) group
+    // record order inside every (pattern, strand, length) group, whatever runs it is made of
     std::vector<u64> start(b.np + 1, 0);
     for (u64 j = 0; j < b.np; j++) start[j + 1] = start[j] + b.per[j];
-    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), b.nhits / 65536 + 1}));
-    auto work = [&](unsigned t) {
+    fm_host_threads(b.nhits, [&](unsigned t, unsigned nt) {
         for (u64 j = t; j < b.np; j += nt)
             for (u64 a = start[j]; a < start[j + 1];) {
                 u64 e = a + 1;
@@ -3884,11 +3909,53 @@ int fm_overlaps_expand(debwt_fm *f, const FmOvlBatch &b, u64 limit, hipEvent_t e
                     std::sort(dst + a, dst + e, [](const debwt_fm_overlap &x, const debwt_fm_overlap &y) { return x.record < y.record; });
                 a = e;
             }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &x : th) x.join();
+    });
+    return DEBWT_OK;
+}
+
+// What both calls do behind their argument checks.  walk(p0, ev, &b) cuts the batch that starts at pattern p0 and walks
+// it; runs as in fm_overlaps_expand.  Once the hits so far exceed the capacity the batches are only counted.
+template <class St, class Walk, class Runs>
+int fm_overlaps_call(debwt_fm *f, St &st, const char *who, std::chrono::steady_clock::time_point t0, u64 npat, u32 flags,
+                     uint64_t *hit_offsets, debwt_fm_overlap *hits, u64 capacity, Walk walk, Runs runs) {
+    const bool longest = (flags & DEBWT_FM_OVERLAP_LONGEST) != 0;
+    const u64 limit = fm_env_u64("DEBWT_FM_OVERLAP_HITS", FM_OVL_HITS);
+    st.patterns = npat;
+    FmEvents ev;
+    int rc = ev.init(f);
+    if (rc) return rc;
+    FmOvlBatch b;
+    std::vector<debwt_fm_overlap> tmp;                     // DEBWT_FM_OVERLAP_LONGEST: a batch's hits before the reduction
+    std::vector<uint64_t> loc;
+    bool fits = true;                                      // false once the hits so far exceed the capacity: count only
+    for (u64 p0 = 0; p0 < npat; p0 += b.np) {
+        if ((rc = walk(p0, ev, &b))) return rc;
+        const u64 at = hit_offsets[p0];
+        if (longest) {
+            tmp.resize(b.nhits);
+            if ((rc = fm_overlaps_expand(f, st, b, limit, ev, runs, tmp.data()))) return rc;
+            loc.assign(b.np + 1, 0);
+            for (u64 j = 0; j < b.np; j++) loc[j + 1] = loc[j] + b.per[j];
+            if ((rc = debwt_fm_overlap_longest(tmp.data(), loc.data(), b.np, loc.data()))) {
+                f->err = std::string(who) + ": a batch's hits are not in order"; return DEBWT_EINTERNAL;
+            }
+            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = at + loc[j + 1];
+            fits = fits && hits && at + loc[b.np] <= capacity;   // a NULL array never fits here, even for no hits
+            if (fits && loc[b.np]) memcpy(hits + at, tmp.data(), loc[b.np] * sizeof(debwt_fm_overlap));
+        } else {
+            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = hit_offsets[p0 + j] + b.per[j];
+            fits = fits && (hits || !b.nhits) && at + b.nhits <= capacity;
+            if (fits && (rc = fm_overlaps_expand(f, st, b, limit, ev, runs, hits + at))) return rc;
+        }
+        st.batches++;
+    }
+    const u64 total = hit_offsets[npat];
+    st.hits = total;
+    if (!fits || capacity < total) {
+        f->err = std::string(who) + ": capacity below the hits (hit_offsets[npat] = " + std::to_string(total) + ")";
+        return DEBWT_ERANGE;
+    }
+    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return DEBWT_OK;
 }
 
@@ -3962,63 +4029,28 @@ extern "C" int debwt_fm_overlaps(debwt_fm *f, const char *patterns, const uint64
     int rc = fm_overlap_table(f);
     if (rc) return rc;
     const u64 nstr = (flags & DEBWT_FM_BOTH_STRANDS) ? 2 : 1;
-    const bool longest = (flags & DEBWT_FM_OVERLAP_LONGEST) != 0;
     const u64 slots = fm_env_u64("DEBWT_FM_OVERLAP_SLOTS", FM_OVL_SLOTS);
-    const u64 limit = fm_env_u64("DEBWT_FM_OVERLAP_HITS", FM_OVL_HITS);
-    debwt_fm_overlaps_stats &st = f->o_stats;
-    st.patterns = npat;
-    hipEvent_t e0, e1;
-    HIPCHK(f, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
-    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{e0, e1};
     auto worst = [&](u64 i) {
         const u64 m = offsets[i + 1] - offsets[i];
         return nstr * (m >= min_overlap ? m - min_overlap + 1 : 0);
     };
-    FmOvlBatch b;
-    std::vector<debwt_fm_overlap> tmp;                     // DEBWT_FM_OVERLAP_LONGEST: a batch's hits before the reduction
-    std::vector<uint64_t> loc;
-    bool fits = true;                                      // false once the hits so far exceed the capacity: count only
-    for (u64 p0 = 0; p0 < npat;) {
+    auto walk = [&](u64 p0, FmEvents &ev, FmOvlBatch *b) {
         u64 p1 = p0 + 1, ws = worst(p0);                  // at least one pattern, however long
         while (p1 < npat && p1 - p0 < FM_BATCH_PATTERNS && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS &&
                ws + worst(p1) <= slots)
             ws += worst(p1++);
-        if ((rc = fm_overlaps_walk(f, patterns, offsets, p0, p1, min_overlap, nstr, e0, e1, &b))) return rc;
-        const u64 at = hit_offsets[p0];
-        if (longest) {
-            tmp.resize(b.nhits);
-            if ((rc = fm_overlaps_expand(f, b, limit, e0, e1, tmp.data()))) return rc;
-            loc.assign(b.np + 1, 0);
-            for (u64 j = 0; j < b.np; j++) loc[j + 1] = loc[j] + b.per[j];
-            if ((rc = debwt_fm_overlap_longest(tmp.data(), loc.data(), b.np, loc.data()))) {
-                f->err = "debwt_fm_overlaps: a batch's hits are not in order"; return DEBWT_EINTERNAL;
-            }
-            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = at + loc[j + 1];
-            fits = fits && hits && at + loc[b.np] <= capacity;
-            if (fits && loc[b.np]) memcpy(hits + at, tmp.data(), loc[b.np] * sizeof(debwt_fm_overlap));
-        } else {
-            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = hit_offsets[p0 + j] + b.per[j];
-            fits = fits && (hits || !b.nhits) && at + b.nhits <= capacity;
-            if (fits && (rc = fm_overlaps_expand(f, b, limit, e0, e1, hits + at))) return rc;
-        }
-        st.batches++;
-        p0 = p1;
-    }
-    const u64 total = hit_offsets[npat];
-    st.hits = total;
-    if (!fits || capacity < total) {
-        f->err = "debwt_fm_overlaps: capacity below the hits (hit_offsets[npat] = " + std::to_string(total) + ")";
-        return DEBWT_ERANGE;
-    }
+        return fm_overlaps_walk(f, patterns, offsets, p0, p1, min_overlap, nstr, ev.a, ev.b, b);
+    };
+    if ((rc = fm_overlaps_call(f, f->o_stats, "debwt_fm_overlaps", t0, npat, flags, hit_offsets, hits, capacity, walk,
+                               fm_overlaps_compact)))
+        return rc;
     if (maxlen == 0xFFFFFFFFull)                           // the table's lengths stop at 2^32 - 1: such overlaps from the starts
-        for (u64 h = 0; h < total; h++)
+        for (u64 h = 0; h < hit_offsets[npat]; h++)
             if (hits[h].length == 0xFFFFFFFFu) {
                 const u64 r = hits[h].record;
                 const u64 len = (r + 1 < f->nrec ? f->rec_starts[r + 1] - 1 : f->n - 1) - f->rec_starts[r];
                 hits[h].flags = (hits[h].flags & ~DEBWT_FM_OVERLAP_CONTAINS) | (len == 0xFFFFFFFFull ? DEBWT_FM_OVERLAP_CONTAINS : 0u);
             }
-    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return DEBWT_OK;
 }
 
@@ -4033,9 +4065,9 @@ extern "C" int debwt_fm_overlaps_stats_get(const debwt_fm *f, debwt_fm_overlaps_
 // L + 1's buffer, which is drained before the next chunk of L, and its runs into the run buffer, which comes back to the
 // host after every chunk.  One item asks for at most 4 * 1024 children and 1024 + 1 runs, and the buffers hold at least
 // that, so every chunk finishes.  The host orders the batch's runs by (pattern, strand, length descending, first entry),
-// which gives the exact hit counts, uploads them with their first hit numbers, and k_fm_overlap_mm_expand writes the hits
-// at most DEBWT_FM_OVERLAP_HITS at a launch straight into the caller's array.  A (pattern, strand, length) group may be
-// made of several runs (one per work item); the host sorts every group of two or more hits by record.
+// which gives the exact hit counts, and uploads them with their first hit numbers in place of the exact call's compaction;
+// from there on the path is the exact call's (fm_overlaps_call, fm_overlaps_expand, k_fm_overlap_expand).  A (pattern,
+// strand, length) group may be made of several runs (one per work item), so its hits are sorted by record as a whole.
 
 namespace {
 
@@ -4093,16 +4125,9 @@ int fm_overlap_mm_drain(FmOvlMmRun &r, u32 level, u64 count) {
     return DEBWT_OK;
 }
 
-struct FmOvlMmBatch {
-    u64 p0 = 0, np = 0, nruns = 0, nhits = 0;
-    std::vector<uint4> raw;                                // runs as the levels wrote them
-    std::vector<FmOvlRun> cruns;                           // ordered, in k_fm_overlap_mm_expand's layout
-    std::vector<u64> rout, per;                            // first hit number per run; hits per pattern of the batch
-};
-
 // the levels of one batch, then its runs in order: fills b
 int fm_overlaps_mm_walk(debwt_fm *f, const char *patterns, const uint64_t *offsets, u64 p0, u64 p1, u64 nstr, FmOvlMmRun &r,
-                        FmOvlMmBatch *b) {
+                        FmOvlBatch *b) {
     debwt_fm_overlaps_mm_stats &st = f->om_stats;
     const u64 np = p1 - p0, base = offsets[p0], bytes = offsets[p1] - base;
     b->p0 = p0; b->np = np;
@@ -4127,8 +4152,7 @@ int fm_overlaps_mm_walk(debwt_fm *f, const char *patterns, const uint64_t *offse
         std::vector<u64> at(start.begin(), start.end() - 1);
         for (u64 k = 0; k < nr; k++) b->cruns[at[b->raw[k].x]++] = b->raw[k];
     }
-    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), nr / 65536 + 1}));
-    auto work = [&](unsigned t) {
+    fm_host_threads(nr, [&](unsigned t, unsigned nt) {
         for (u64 j = t; j < np; j += nt) {
             const u32 m = (u32)(offsets[p0 + j + 1] - offsets[p0 + j]);
             FmOvlRun *a = b->cruns.data() + start[j], *e = b->cruns.data() + start[j + 1];
@@ -4144,62 +4168,11 @@ int fm_overlaps_mm_walk(debwt_fm *f, const char *patterns, const uint64_t *offse
             }
             b->per[j] = h;
         }
-    };
-    {
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
-        work(0);
-        for (auto &x : th) x.join();
-    }
+    });
     u64 h = 0;
     for (u64 k = 0; k < nr; k++) { b->rout[k] = h; h += b->cruns[k].z; }
     b->nruns = nr; b->nhits = h;
     st.runs += nr;
-    return DEBWT_OK;
-}
-
-// the hits of a walked batch into dst (b.nhits of them), in the documented order
-int fm_overlaps_mm_expand(debwt_fm *f, const FmOvlMmBatch &b, u64 limit, u64 fixed, hipEvent_t e0, hipEvent_t e1, debwt_fm_overlap *dst) {
-    debwt_fm_overlaps_mm_stats &st = f->om_stats;
-    if (!b.nhits) return DEBWT_OK;
-    const u64 chunk = std::min(b.nhits, limit);
-    FM_ENSURE(f, f->o_cruns, (size_t)b.nruns * sizeof(FmOvlRun));
-    FM_ENSURE(f, f->o_rout, (size_t)b.nruns * 8);
-    FM_ENSURE(f, f->o_hits, (size_t)chunk * sizeof(uint4));
-    st.scratch_bytes = std::max<u64>(st.scratch_bytes, fixed + b.nruns * 24 + chunk * 16);
-    HIPCHK(f, hipMemcpyAsync(f->o_cruns.p, b.cruns.data(), b.nruns * sizeof(FmOvlRun), hipMemcpyHostToDevice, f->stream));
-    HIPCHK(f, hipMemcpyAsync(f->o_rout.p, b.rout.data(), b.nruns * 8, hipMemcpyHostToDevice, f->stream));
-    for (u64 g0 = 0; g0 < b.nhits; g0 += chunk) {
-        const u64 cnt = std::min(b.nhits - g0, chunk);
-        (void)hipEventRecord(e0, f->stream);
-        k_fm_overlap_mm_expand<<<grid_for(cnt, 256), 256, 0, f->stream>>>(f->o_cruns.as<FmOvlRun>(), f->o_rout.as<u64>(), b.nruns,
-                                                                          f->o_table.as<FmOvlRec>(), g0, cnt, f->o_hits.as<uint4>());
-        (void)hipEventRecord(e1, f->stream);
-        HIPCHK(f, hipMemcpyAsync(dst + g0, f->o_hits.p, cnt * sizeof(uint4), hipMemcpyDeviceToHost, f->stream));
-        int rc = fm_sync(f);                                   // the next launch reuses o_hits
-        if (rc) return rc;
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        st.ms_kernel += ms; st.launches++;
-    }
-    // record order inside every (pattern, strand, length) group, whatever runs it is made of
-    std::vector<u64> start(b.np + 1, 0);
-    for (u64 j = 0; j < b.np; j++) start[j + 1] = start[j] + b.per[j];
-    const unsigned nt = (unsigned)std::max<u64>(1, std::min<u64>({16, std::max(1u, std::thread::hardware_concurrency()), b.nhits / 65536 + 1}));
-    auto work = [&](unsigned t) {
-        for (u64 j = t; j < b.np; j += nt)
-            for (u64 a = start[j]; a < start[j + 1];) {
-                u64 e = a + 1;
-                while (e < start[j + 1] && dst[e].strand == dst[a].strand && dst[e].length == dst[a].length) e++;
-                if (e - a > 1)
-                    std::sort(dst + a, dst + e, [](const debwt_fm_overlap &x, const debwt_fm_overlap &y) { return x.record < y.record; });
-                a = e;
-            }
-    };
-    std::vector<std::thread> th;
-    for (unsigned t = 1; t < nt; t++) th.emplace_back(work, t);
-    work(0);
-    for (auto &x : th) x.join();
     return DEBWT_OK;
 }
 
@@ -4230,60 +4203,32 @@ extern "C" int debwt_fm_overlaps_mm(debwt_fm *f, const char *patterns, const uin
     int rc = fm_overlap_table(f);
     if (rc) return rc;
     const u64 nstr = (flags & DEBWT_FM_BOTH_STRANDS) ? 2 : 1;
-    const bool longest = (flags & DEBWT_FM_OVERLAP_LONGEST) != 0;
     // per buffer at least what one item can ask for (4 children per step, 1024 steps; a run per step and one on arrival)
     const u64 cap = std::max<u64>(fm_env_u64("DEBWT_FM_OVERLAP_ITEMS", FM_OVL_MM_ITEMS), 4 * FM_SEARCH_MAX_LEN + 64);
     const u64 batch = std::min<u64>(fm_env_u64("DEBWT_FM_OVERLAP_BATCH", FM_BATCH_PATTERNS), FM_BATCH_PATTERNS);
-    const u64 limit = fm_env_u64("DEBWT_FM_OVERLAP_HITS", FM_OVL_HITS);
     for (u32 l = 1; l <= max_mismatches; l++) if ((rc = fm_search_buf(f, f->s_items[l], (size_t)cap * 24))) return rc;
     if ((rc = fm_search_buf(f, f->s_hits, (size_t)cap * sizeof(uint4)))) return rc;
     if ((rc = fm_search_buf(f, f->s_ctr, 64))) return rc;
     debwt_fm_overlaps_mm_stats &st = f->om_stats;
-    st.patterns = npat;
     const u64 fixed = (u64)max_mismatches * cap * 24 + cap * sizeof(uint4);   // the level and run buffers this call may fill
     st.scratch_bytes = fixed;
     FmOvlMmRun r{};
     r.f = f; r.kmax = max_mismatches; r.min_overlap = min_overlap; r.permille = max_error_permille; r.cap = cap;
     for (u32 l = 0; l <= FM_SEARCH_MAX_K; l++) r.hint[l] = ~0ull;
-    HIPCHK(f, hipEventCreate(&r.e0));
-    if (hipEventCreate(&r.e1) != hipSuccess) { (void)hipEventDestroy(r.e0); f->err = "hipEventCreate"; return DEBWT_EDEVICE; }
-    struct Ev { hipEvent_t a, b; ~Ev() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } ev{r.e0, r.e1};
-    FmOvlMmBatch b;
-    std::vector<debwt_fm_overlap> tmp;                     // DEBWT_FM_OVERLAP_LONGEST: a batch's hits before the reduction
-    std::vector<uint64_t> loc;
-    bool fits = true;                                      // false once the hits so far exceed the capacity: count only
-    for (u64 p0 = 0; p0 < npat;) {
+    auto walk = [&](u64 p0, FmEvents &ev, FmOvlBatch *b) {
         u64 p1 = p0 + 1;
         while (p1 < npat && p1 - p0 < batch && offsets[p1 + 1] - offsets[p0] <= FM_BATCH_CHARS) p1++;
-        if ((rc = fm_overlaps_mm_walk(f, patterns, offsets, p0, p1, nstr, r, &b))) return rc;
-        const u64 at = hit_offsets[p0];
-        if (longest) {
-            tmp.resize(b.nhits);
-            if ((rc = fm_overlaps_mm_expand(f, b, limit, fixed, r.e0, r.e1, tmp.data()))) return rc;
-            loc.assign(b.np + 1, 0);
-            for (u64 j = 0; j < b.np; j++) loc[j + 1] = loc[j] + b.per[j];
-            if ((rc = debwt_fm_overlap_longest(tmp.data(), loc.data(), b.np, loc.data()))) {
-                f->err = "debwt_fm_overlaps_mm: a batch's hits are not in order"; return DEBWT_EINTERNAL;
-            }
-            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = at + loc[j + 1];
-            fits = fits && hits && at + loc[b.np] <= capacity;
-            if (fits && loc[b.np]) memcpy(hits + at, tmp.data(), loc[b.np] * sizeof(debwt_fm_overlap));
-        } else {
-            for (u64 j = 0; j < b.np; j++) hit_offsets[p0 + j + 1] = hit_offsets[p0 + j] + b.per[j];
-            fits = fits && (hits || !b.nhits) && at + b.nhits <= capacity;
-            if (fits && (rc = fm_overlaps_mm_expand(f, b, limit, fixed, r.e0, r.e1, hits + at))) return rc;
-        }
-        st.batches++;
-        p0 = p1;
-    }
-    const u64 total = hit_offsets[npat];
-    st.hits = total;
-    if (!fits || capacity < total) {
-        f->err = "debwt_fm_overlaps_mm: capacity below the hits (hit_offsets[npat] = " + std::to_string(total) + ")";
-        return DEBWT_ERANGE;
-    }
-    st.ms_wall = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return DEBWT_OK;
+        r.e0 = ev.a; r.e1 = ev.b;
+        return fm_overlaps_mm_walk(f, patterns, offsets, p0, p1, nstr, r, b);
+    };
+    auto runs = [&](debwt_fm *f, const FmOvlBatch &b, u64 chunk, FmEvents &ev) -> int {
+        st.scratch_bytes = std::max<u64>(st.scratch_bytes, fixed + b.nruns * 24 + chunk * 16);
+        HIPCHK(f, hipMemcpyAsync(f->o_cruns.p, b.cruns.data(), b.nruns * sizeof(FmOvlRun), hipMemcpyHostToDevice, f->stream));
+        HIPCHK(f, hipMemcpyAsync(f->o_rout.p, b.rout.data(), b.nruns * 8, hipMemcpyHostToDevice, f->stream));
+        (void)hipEventRecord(ev.a, f->stream);
+        return DEBWT_OK;
+    };
+    return fm_overlaps_call(f, st, "debwt_fm_overlaps_mm", t0, npat, flags, hit_offsets, hits, capacity, walk, runs);
 }
 
 extern "C" int debwt_fm_overlaps_mm_stats_get(const debwt_fm *f, debwt_fm_overlaps_mm_stats *out) {
@@ -4334,11 +4279,6 @@ void fm_ext_launch(bool trace, u32 grid, u32 block, size_t lds, hipStream_t s, c
                                                        sc.gap_extend, lds_per_job, flags, best, cells);
 }
 
-struct FmExtEvents {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~FmExtEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 // jobs [0, njobs) -> out; with `trace` also ops per job (cig_n) and the ops of all jobs in job order (cig).  The
 // arguments were validated by the caller; statistics are added to f->x_stats.
 int fm_extend_run(debwt_fm *f, const char *patterns, const uint64_t *offsets, const debwt_fm_job *jobs, u64 njobs,
@@ -4350,9 +4290,8 @@ int fm_extend_run(debwt_fm *f, const char *patterns, const uint64_t *offsets, co
     if (!njobs) return DEBWT_OK;
     const u64 limit = fm_env_u64("DEBWT_FM_EXTEND_BYTES", FM_EXTEND_BYTES);
     const int G = w < 16 ? 16 : w < 32 ? 32 : 64;
-    FmExtEvents ev;
-    HIPCHK(f, hipEventCreate(&ev.a));
-    HIPCHK(f, hipEventCreate(&ev.b));
+    FmEvents ev;
+    if (int rc = ev.init(f)) return rc;
     std::vector<FmExtJob> dj;
     std::vector<u64> src;                                // job index of every device job
     std::vector<char> chars;
@@ -4846,9 +4785,8 @@ int fm_chain_run(debwt_fm *f, const char *patterns, const uint64_t *offsets, con
     if (!njobs) return DEBWT_OK;
     const u64 limit = fm_env_u64("DEBWT_FM_EXTEND_BYTES", FM_EXTEND_BYTES);
     const int G = 2 * w + 1 <= 16 ? 16 : 2 * w + 1 <= 32 ? 32 : 64;
-    FmExtEvents ev;
-    HIPCHK(f, hipEventCreate(&ev.a));
-    HIPCHK(f, hipEventCreate(&ev.b));
+    FmEvents ev;
+    if (int rc = ev.init(f)) return rc;
     std::vector<FmChainJob> dj;
     std::vector<FmChainAnchor> da;
     std::vector<u64> src;                                // job index of every device job
@@ -5358,9 +5296,8 @@ int fm_window_run(debwt_fm *f, const char *patterns, const uint64_t *offsets, co
     if (trace) { cig_n->assign(njobs, 0); cig->clear(); }
     if (!njobs) return DEBWT_OK;
     const u64 limit = fm_env_u64("DEBWT_FM_EXTEND_BYTES", FM_EXTEND_BYTES);
-    FmExtEvents ev;
-    HIPCHK(f, hipEventCreate(&ev.a));
-    HIPCHK(f, hipEventCreate(&ev.b));
+    FmEvents ev;
+    if (int rc = ev.init(f)) return rc;
     std::vector<FmWinJob> dj;
     std::vector<u64> src;                                // job index of every device job
     std::vector<char> chars;

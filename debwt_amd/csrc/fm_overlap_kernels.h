@@ -17,7 +17,7 @@
 struct FmOvlRec { u32 record, length; };
 
 // A run as the walk writes it: x = depth (overlap length), y = first entry of srows, z = entries, w unused.  As the
-// compaction writes it: w = strand | 2 when the depth is the whole query.
+// compaction writes it: w = strand | 2 when the depth is the whole query; the mismatch call's host adds mismatches << 8.
 typedef uint4 FmOvlRun;
 
 // Items [0, nitems): item g is pattern g % np on strand g / np, as in k_fm_mems.  Item g writes its runs in ascending
@@ -88,9 +88,11 @@ __global__ __launch_bounds__(256) void k_fm_overlap_compact(const u64 *__restric
     }
 }
 
-// Expansion: one lane per hit g in [g0, g0 + count) of the batch.  Run k covers hits [run_out[k], run_out[k + 1]) (the
-// last one to the batch's end); the hit is entry y + (g - run_out[k]) of the record table.  out[t]: record, length,
-// strand, flags (1: the record is as long as the overlap, 2: the query is), in row order inside one run.
+// Expansion, for the exact and the mismatch call alike: one lane per hit g in [g0, g0 + count) of the batch.  Run k covers
+// hits [run_out[k], run_out[k + 1]) (the last one to the batch's end); the hit is entry y + (g - run_out[k]) of the
+// record table.  A run's w: bit 0 the strand, bit 1 set when the length is the whole query, bits 8..15 the mismatches --
+// zero from k_fm_overlap_compact, the level from the host's ordering of k_fm_overlap_mm's runs.  out[t]: record, length,
+// strand, flags (1: the record is as long as the overlap, 2: the query is, mismatches << 8), in row order inside one run.
 __global__ __launch_bounds__(256) void k_fm_overlap_expand(const FmOvlRun *__restrict__ cruns, const u64 *__restrict__ run_out,
                                                            u64 nruns, const FmOvlRec *__restrict__ table, u64 g0, u64 count,
                                                            uint4 *__restrict__ out) {
@@ -104,5 +106,5 @@ __global__ __launch_bounds__(256) void k_fm_overlap_expand(const FmOvlRun *__res
     }
     const FmOvlRun r = cruns[lo];
     const FmOvlRec e = table[(u64)r.y + (g - run_out[lo])];
-    out[t] = make_uint4(e.record, r.x, r.w & 1u, (e.length == r.x ? 1u : 0u) | (r.w & 2u));
+    out[t] = make_uint4(e.record, r.x, r.w & 1u, (e.length == r.x ? 1u : 0u) | (r.w & 0xFF02u));
 }

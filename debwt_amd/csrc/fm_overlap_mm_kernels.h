@@ -6,7 +6,7 @@
 // mismatch count: nothing is deduplicated.
 //   k_fm_overlap_mm         one lane per item of one level: children into the next level's buffer, one run (pattern, first
 //                           srows entry, entries, d | level << 16 | strand << 24) per state that holds record starts
-//   k_fm_overlap_mm_expand  one lane per hit of the host-ordered runs: (record, length, strand, flags | mismatches << 8)
+// The host orders the runs and k_fm_overlap_expand (fm_overlap_kernels.h) writes their hits, mismatches in flags >> 8.
 // Single TU: included by debwt_hip.hip only, after fm_overlap_kernels.h.
 #pragma once
 #include "common.h"
@@ -103,23 +103,4 @@ __global__ __launch_bounds__(256) void k_fm_overlap_mm(VIndex V, const u8 *__res
         atomicAdd((unsigned long long *)&ctr[3], (unsigned long long)wr);
         atomicAdd((unsigned long long *)&ctr[4], (unsigned long long)(64 * wmax));
     }
-}
-
-// Expansion of the runs as the host ordered them: x = length, y = first entry of srows, z = entries, w = strand | 2 when
-// the length is the whole query | mismatches << 8; run k covers hits [run_out[k], run_out[k + 1]) of the batch (the last
-// one to the batch's end).  One lane per hit g in [g0, g0 + count): out[t] = record, length, strand, flags.
-__global__ __launch_bounds__(256) void k_fm_overlap_mm_expand(const FmOvlRun *__restrict__ cruns, const u64 *__restrict__ run_out,
-                                                              u64 nruns, const FmOvlRec *__restrict__ table, u64 g0, u64 count,
-                                                              uint4 *__restrict__ out) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    const u64 g = g0 + t;
-    u64 lo = 0, hi = nruns;                                    // last run with run_out[k] <= g
-    while (hi - lo > 1) {
-        const u64 mid = (lo + hi) >> 1;
-        if (run_out[mid] <= g) lo = mid; else hi = mid;
-    }
-    const FmOvlRun r = cruns[lo];
-    const FmOvlRec e = table[(u64)r.y + (g - run_out[lo])];
-    out[t] = make_uint4(e.record, r.x, r.w & 1u, (e.length == r.x ? 1u : 0u) | (r.w & 0xFF02u));
 }

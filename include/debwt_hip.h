@@ -584,7 +584,9 @@ int debwt_fm_mems_stats_get(const debwt_fm *fm, debwt_fm_mems_stats *out);
  * and a pattern of 2^32 bytes or more.  No attached text is needed: an index from debwt_fm_open answers as one from
  * debwt_fm_create.
  * DEBWT_FM_OVERLAP_LONGEST keeps per (pattern, strand, record) only the largest L: a subsequence of the full result, bit
- * for bit what debwt_fm_overlap_longest makes of it (capacity then counts the kept hits).
+ * for bit what debwt_fm_overlap_longest makes of it (capacity then counts the kept hits).  With this flag a NULL hits
+ * never fits: a call without any hit and with hits NULL answers DEBWT_ERANGE (hit_offsets[npat] = 0), and DEBWT_OK without
+ * the flag; debwt_fm_overlaps_mm does the same.
  * The first call makes the record table (for every separator row the record that starts there and its length, 8 bytes
  * per record, from a locate of the '#' suffixes: DEBWT_EINTERNAL if one does not land on a record start) and keeps it
  * with the index: it is counted in debwt_fm_info.device_bytes from then on.

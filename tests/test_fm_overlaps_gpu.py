@@ -208,6 +208,77 @@ def test_errors_and_capacity(api, synth):
     assert tuples(fm.overlaps([strs[0]], min_overlap=len(strs[0]) + 1), 0) == []
 
 
+def test_capacity_across_batches(api, synth, monkeypatch):
+    """the count-only state is carried from batch to batch: the capacity runs out in the first batch, in the last one, or
+    never, and the offsets are whole every time"""
+    from debwt_amd import _lib
+    strs, fm = synth
+    pats = [p.encode() for p in strs[:40] + extra_queries(strs, 20)]
+    buf = b"".join(pats)
+    offs = np.zeros(len(pats) + 1, dtype=np.uint64)
+    np.cumsum([len(p) for p in pats], out=offs[1:])
+    L = _lib.lib()
+    n = len(pats)
+    hoff = np.zeros(n + 1, dtype=np.uint64)
+
+    def call(min_overlap, flags, cap, null=False):
+        h = np.zeros(max(cap, 1), dtype=api._OVERLAP_DTYPE)
+        hoff[:] = 77
+        rc = L.debwt_fm_overlaps(fm._h, buf, api._p64(offs), n, min_overlap, flags, api._p64(hoff),
+                                 None if null else h.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmOverlap)), cap)
+        return rc, h[:cap]
+
+    monkeypatch.delenv("DEBWT_FM_OVERLAP_HITS", raising=False)
+    for flags in (0, 1, 2, 3):
+        monkeypatch.delenv("DEBWT_FM_OVERLAP_SLOTS", raising=False)
+        res = fm.overlaps(pats, min_overlap=20, strands="both" if flags & 1 else "forward", longest=bool(flags & 2))
+        total, first = len(res.all_hits), int(res.offsets[1])
+        assert 1 <= first < total                               # pattern 0 is in the first batch whatever the limits
+        monkeypatch.setenv("DEBWT_FM_OVERLAP_SLOTS", "64")
+        for cap, null in ((0, True), (first - 1, False), (total - 1, False)):
+            rc, _ = call(20, flags, cap, null)
+            assert rc == -5 and np.array_equal(hoff, res.offsets), (flags, cap)
+            assert fm.overlaps_stats()["batches"] > 3 and fm.overlaps_stats()["hits"] == total
+        rc, h = call(20, flags, total)
+        assert rc == 0 and np.array_equal(hoff, res.offsets) and np.array_equal(h, res.all_hits)
+        assert fm.overlaps_stats()["batches"] > 3
+    # No pattern has a hit, no array is given: without LONGEST nothing is missing and the call succeeds; with LONGEST a
+    # NULL array never fits, so the call asks for room for 0 hits.  The two branches have differed since the call came
+    # in; the difference is pinned as recorded on the parent of the fold, not repaired.
+    longer = max(len(p) for p in pats) + 1
+    for flags, want in ((0, 0), (1, 0), (2, -5), (3, -5)):
+        rc, _ = call(longer, flags, 0, null=True)
+        assert rc == want and not hoff.any(), flags
+        assert fm.overlaps_stats()["hits"] == 0 and fm.overlaps_stats()["batches"] >= 1
+
+
+# Every field of overlaps_stats() that is no time, for strs + extra_queries(strs, L) on both strands, by (L, longest,
+# limits); limits "64" sets DEBWT_FM_OVERLAP_SLOTS and DEBWT_FM_OVERLAP_HITS.  Recorded on an MI355X at ad9150c, the commit
+# before the exact and the mismatch call shared one host path, twice with equal values: they are sums and counts, and the
+# batches depend on the input and the two limits alone.  A difference means a launch, a batch or a buffer changed.
+_WALK = {"patterns": 443, "steps": 38107, "line_reads": 42607}
+PINNED = {
+    (1, False, None): dict(_WALK, batches=1, launches=3, runs=8712, hits=133999, wave_steps=60416, scratch_bytes=3531208),
+    (20, True, None): dict(_WALK, batches=1, launches=3, runs=3997, hits=3960, wave_steps=60416, scratch_bytes=1072912),
+    (1, False, "64"): dict(_WALK, batches=442, launches=3165, runs=8712, hits=133999, wave_steps=2249152, scratch_bytes=18536),
+    (20, True, "64"): dict(_WALK, batches=442, launches=1320, runs=3997, hits=3960, wave_steps=2249152, scratch_bytes=16784),
+}
+
+
+@pytest.mark.parametrize("limits", [None, "64"])
+def test_stats_are_pinned(api, synth, monkeypatch, limits):
+    strs, fm = synth
+    for name in ("DEBWT_FM_OVERLAP_SLOTS", "DEBWT_FM_OVERLAP_HITS"):
+        monkeypatch.setenv(name, limits) if limits else monkeypatch.delenv(name, raising=False)
+    got = {}
+    for L, longest in ((1, False), (20, True)):
+        res = fm.overlaps(strs + extra_queries(strs, L), min_overlap=L, strands="both", longest=longest)
+        assert not (res.all_hits["flags"] & np.uint32(~3 & 0xFFFFFFFF)).any()   # no mismatch bits from the shared expansion
+        got[L, longest, limits] = {k: v for k, v in fm.overlaps_stats().items() if not k.startswith("ms_")}
+        print("PINNED[%r, %r, %r] = %r" % (L, longest, limits, got[L, longest, limits]))
+    assert got == {k: v for k, v in PINNED.items() if k[2] == limits}
+
+
 def test_index_from_files(api):
     entry = entry_named("shared_ends_duplicates")
     recs = golden_records(entry)

@@ -231,6 +231,80 @@ def test_errors_and_capacity(api, synth):
     assert len(empty) == 0 and len(empty.all_hits) == 0
 
 
+def test_capacity_across_batches(api, synth, monkeypatch):
+    """the count-only state is carried from batch to batch: the capacity runs out in the first batch, in the last one, or
+    never, and the offsets are whole every time"""
+    from debwt_amd import _lib
+    _, _, qs, fm = synth
+    pats = [p.encode() for p in qs]
+    buf = b"".join(pats)
+    offs = np.zeros(len(pats) + 1, dtype=np.uint64)
+    np.cumsum([len(p) for p in pats], out=offs[1:])
+    L = _lib.lib()
+    n = len(pats)
+    hoff = np.zeros(n + 1, dtype=np.uint64)
+
+    def call(min_overlap, flags, cap, null=False):
+        h = np.zeros(max(cap, 1), dtype=api._OVERLAP_DTYPE)
+        hoff[:] = 77
+        rc = L.debwt_fm_overlaps_mm(fm._h, buf, api._p64(offs), n, min_overlap, 2, 0, flags, api._p64(hoff),
+                                    None if null else h.ctypes.data_as(ctypes.POINTER(_lib.DebwtFmOverlap)), cap)
+        return rc, h[:cap]
+
+    for name in ("DEBWT_FM_OVERLAP_ITEMS", "DEBWT_FM_OVERLAP_HITS"):
+        monkeypatch.delenv(name, raising=False)
+    for flags in (0, 1, 2, 3):
+        monkeypatch.delenv("DEBWT_FM_OVERLAP_BATCH", raising=False)
+        res = fm.overlaps_mm(qs, min_overlap=20, mismatches=2, strands="both" if flags & 1 else "forward", longest=bool(flags & 2))
+        total, first = len(res.all_hits), int(res.offsets[1])
+        assert 1 <= first and int(res.offsets[50]) < total      # hits in the first batch of 50 patterns and behind it
+        monkeypatch.setenv("DEBWT_FM_OVERLAP_BATCH", "50")
+        for cap, null in ((0, True), (first - 1, False), (total - 1, False)):
+            rc, _ = call(20, flags, cap, null)
+            assert rc == -5 and np.array_equal(hoff, res.offsets), (flags, cap)
+            assert fm.overlaps_mm_stats()["batches"] == (n + 49) // 50 > 3 and fm.overlaps_mm_stats()["hits"] == total
+        rc, h = call(20, flags, total)
+        assert rc == 0 and np.array_equal(hoff, res.offsets) and np.array_equal(h, res.all_hits)
+        assert fm.overlaps_mm_stats()["batches"] == (n + 49) // 50
+    # No pattern has a hit, no array is given: without LONGEST nothing is missing and the call succeeds; with LONGEST a
+    # NULL array never fits, so the call asks for room for 0 hits.  The two branches have differed since the call came
+    # in; the difference is pinned as recorded on the parent of the fold, not repaired.
+    longer = max(len(p) for p in pats) + 1
+    for flags, want in ((0, 0), (1, 0), (2, -5), (3, -5)):
+        rc, _ = call(longer, flags, 0, null=True)
+        assert rc == want and not hoff.any(), flags
+        assert fm.overlaps_mm_stats()["hits"] == 0 and fm.overlaps_mm_stats()["batches"] == (n + 49) // 50
+
+
+# Every field of overlaps_mm_stats() that is no time, for the 165 queries at min_overlap 20 with 2 mismatches on both
+# strands, by (longest, limits); limits True sets DEBWT_FM_OVERLAP_ITEMS=1, DEBWT_FM_OVERLAP_HITS=64 and
+# DEBWT_FM_OVERLAP_BATCH=50.  Recorded on an MI355X at ad9150c, the commit before the exact and the mismatch call shared
+# one host path, in two runs that agreed in every field but wave_steps (604096 and 604992 without limits: the order in
+# which a level's children land decides which items share a wave), which is therefore left out.  A difference in any
+# other field means a launch, a batch or a buffer changed.
+_WALK = {"patterns": 165, "runs": 1424, "steps": 177008, "line_reads": 208341, "items": [330, 6655, 48152, 0, 0]}
+PINNED = {
+    (False, False): dict(_WALK, batches=1, launches=4, retries=0, hits=1455, scratch_bytes=536928368),
+    (True, False): dict(_WALK, batches=1, launches=4, retries=0, hits=1339, scratch_bytes=536928368),
+    (False, True): dict(_WALK, batches=4, launches=90, retries=6, hits=1455, scratch_bytes=278904),
+    (True, True): dict(_WALK, batches=4, launches=90, retries=6, hits=1339, scratch_bytes=278904),
+}
+
+
+@pytest.mark.parametrize("limits", [False, True])
+def test_stats_are_pinned(api, synth, monkeypatch, limits):
+    strs, _, pats, fm = synth
+    assert len(pats) == 165
+    for name, v in (("DEBWT_FM_OVERLAP_ITEMS", "1"), ("DEBWT_FM_OVERLAP_HITS", "64"), ("DEBWT_FM_OVERLAP_BATCH", "50")):
+        monkeypatch.setenv(name, v) if limits else monkeypatch.delenv(name, raising=False)
+    got = {}
+    for longest in (False, True):
+        fm.overlaps_mm(pats, min_overlap=20, mismatches=2, strands="both", longest=longest)
+        got[longest, limits] = {k: v for k, v in fm.overlaps_mm_stats().items() if not k.startswith("ms_") and k != "wave_steps"}
+        print("PINNED[%r, %r] = %r" % (longest, limits, got[longest, limits]))
+    assert got == {k: v for k, v in PINNED.items() if k[1] == limits}
+
+
 def test_index_from_files(api):
     entry = entry_named("shared_ends_duplicates")
     recs = golden_records(entry)
