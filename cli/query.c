@@ -15,6 +15,7 @@
  *   deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq
  *   deBWT-query correct -i OUT -k K [--device D] [--min-count T|auto] [--rounds R] [--forward] [--report FILE] READS.fa|.fq
  *   deBWT-query spectrum -i OUT -k K [--device D] [--forward] [--bins N] [--list FILE [--at-least A] [--at-most B]]
+ *   deBWT-query lcp    -i OUT [--device D] [--max-lcp C] [--lcp FILE] [--sa FILE] [--da FILE] [--profile K]
  *   deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]
  *                      [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]
  *   deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]
@@ -99,6 +100,16 @@
  * distinct K-mer of multiplicity A (--at-least, default 1) to B (--at-most, default 2^32 - 1), in the order of the
  * K-mers (debwt_fm_kmer_list).  It needs OUT, OUT.#, OUT.$ and OUT.sa only and takes no file argument.
  *
+ * lcp builds the suffix array, the LCP array and the record array of the indexed collection on the GPU
+ * (debwt_fm_esa_build, Definition 10 of debwt_hip.h): lcp[r] is the common prefix of the suffixes of rows r - 1 and r of
+ * OUT, cut at the first separator of either, stored as min(lcp, C) with --max-lcp C (default: no cap).  --lcp FILE, --sa
+ * FILE and --da FILE get the arrays as raw little-endian files of n entries: u32 LCP values, u64 text positions, u32
+ * record numbers.  stdout: one line "# n=N max=M max_row=R prev=J:OFF pos=J:OFF mean=X" (TAB-separated; M the largest
+ * stored value, R the first row that holds it, prev and pos the places of the suffixes of rows R - 1 and R as
+ * record:offset -- the longest repeat -- and X the mean of the stored values with six decimals); with --profile K (1..4096,
+ * at most C) K lines k<TAB>distinct follow, the number of distinct strings of k bases inside records for k = 1..K.  It
+ * needs OUT, OUT.#, OUT.$ and OUT.sa only (the text is restored on the GPU) and takes no file argument.
+ *
  * graph writes the string graph of the indexed records as GFA 1 (debwt_fm_string_graph): a record that equals an earlier one
  * is a duplicate, one that lies inside a longer record is contained, the others are kept.  One "S J * LN:i:len" line per
  * kept record J (the 0-based number, as extract names records), then one "L a + b + <L>M" line per edge: the longest
@@ -152,6 +163,7 @@ static void usage(void) {
             "       deBWT-query kmers  -i OUT -k K [--device D] [--both-strands] READS.fa|.fq\n"
             "       deBWT-query correct -i OUT -k K [--device D] [--min-count T|auto] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
             "       deBWT-query spectrum -i OUT -k K [--device D] [--forward] [--bins N] [--list FILE [--at-least A] [--at-most B]]\n"
+            "       deBWT-query lcp    -i OUT [--device D] [--max-lcp C] [--lcp FILE] [--sa FILE] [--da FILE] [--profile K]\n"
             "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]\n"
             "                          [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]\n"
             "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]\n"
@@ -190,6 +202,10 @@ static void usage(void) {
             "mult<TAB>distinct per non-empty bin of the histogram of the distinct K-mers (K in 1..32; N bins, 2..4096, default\n"
             "256, the last printed as >=N-1; both strands unless --forward); --list FILE gets KMER<TAB>mult of the K-mers of\n"
             "multiplicity A (--at-least, default 1) to B (--at-most), in K-mer order;\n"
+            "lcp builds suffix array, LCP array and record array of the collection: --lcp, --sa and --da FILE get them as raw\n"
+            "little-endian u32, u64 and u32 arrays of n entries (LCP values cut at separators and capped at C with --max-lcp C);\n"
+            "stdout gets # n=N<TAB>max=M<TAB>max_row=R<TAB>prev=J:OFF<TAB>pos=J:OFF<TAB>mean=X and, with --profile K (1..4096, at\n"
+            "most C), k<TAB>distinct for k = 1..K, the distinct strings of k bases inside records;\n"
             "graph writes GFA 1: S lines for the records that are neither duplicates nor contained, L lines a + b + <L>M for the\n"
             "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
             "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained;\n"
@@ -1335,6 +1351,77 @@ done:
     return ret;
 }
 
+/* ---- lcp --------------------------------------------------------------------------------------------------------------- */
+
+/* one kept array to a raw file, in pieces */
+static int write_esa_array(debwt_fm *fm, int which, size_t width, uint64_t n, const char *path) {
+    const uint64_t piece = 1ull << 22;
+    void *buf = malloc((size_t)(n < piece ? (n ? n : 1) : piece) * width);
+    FILE *f = fopen(path, "wb");
+    int ret = 1;
+    if (!buf) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (!f) { fprintf(stderr, "cannot write %s\n", path); goto done; }
+    for (uint64_t lo = 0; lo < n; lo += piece) {
+        const uint64_t cnt = n - lo < piece ? n - lo : piece;
+        if (debwt_fm_esa_fetch(fm, which, lo, cnt, buf)) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+        if (fwrite(buf, width, cnt, f) != cnt) { fprintf(stderr, "cannot write %s\n", path); goto done; }
+    }
+    ret = 0;
+done:
+    if (f && fclose(f)) { fprintf(stderr, "cannot write %s\n", path); ret = 1; }
+    free(buf);
+    return ret;
+}
+
+/* the record of text position p: the last start at or before it (starts: nrec entries, ascending) */
+static uint64_t record_of(const uint64_t *starts, uint64_t nrec, uint64_t p) {
+    uint64_t lo = 0, hi = nrec;
+    while (hi - lo > 1) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (starts[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+static int cmd_lcp(const char *out, int device, uint32_t max_lcp, const char *lcp_file, const char *sa_file, const char *da_file,
+                   uint32_t kmax) {
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) return 1;
+    int ret = 1;
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    uint64_t *starts = malloc(fi.nrec * 8), *distinct = calloc(kmax ? kmax : 1, 8);
+    debwt_fm_esa_summary sm;
+    debwt_fm_esa_stats st;
+    if (!starts || !distinct) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (debwt_fm_record_starts(fm, starts, fi.nrec) ||
+        debwt_fm_esa_build(fm, max_lcp, (sa_file ? DEBWT_FM_ESA_SA : 0u) | (da_file ? DEBWT_FM_ESA_DA : 0u)) ||
+        debwt_fm_esa_summary_get(fm, &sm) || (kmax && debwt_fm_esa_profile(fm, kmax, distinct))) {
+        fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
+        goto done;
+    }
+    if (lcp_file && write_esa_array(fm, DEBWT_FM_ESA_LCP_ARRAY, 4, fi.n, lcp_file)) goto done;
+    if (sa_file && write_esa_array(fm, DEBWT_FM_ESA_SA_ARRAY, 8, fi.n, sa_file)) goto done;
+    if (da_file && write_esa_array(fm, DEBWT_FM_ESA_DA_ARRAY, 4, fi.n, da_file)) goto done;
+    const uint64_t ra = record_of(starts, fi.nrec, sm.pos_prev), rb = record_of(starts, fi.nrec, sm.pos);
+    printf("# n=%llu\tmax=%llu\tmax_row=%llu\tprev=%llu:%llu\tpos=%llu:%llu\tmean=%.6f\n", (unsigned long long)sm.n,
+           (unsigned long long)sm.max, (unsigned long long)sm.max_row, (unsigned long long)ra,
+           (unsigned long long)(sm.pos_prev - starts[ra]), (unsigned long long)rb, (unsigned long long)(sm.pos - starts[rb]),
+           (double)sm.sum / (double)sm.n);
+    for (uint32_t k = 1; k <= kmax; k++) printf("%u\t%llu\n", k, (unsigned long long)distinct[k - 1]);
+    debwt_fm_esa_stats_get(fm, &st);
+    fprintf(stderr, "lcp: %llu rows, max %llu at row %llu, %llu capped; %llu chunks of %llu, %.2f symbols compared per position; "
+                    "walk %.1f, scatter %.1f, plcp %.1f, rows %.1f ms, %.1f ms in all\n",
+            (unsigned long long)sm.n, (unsigned long long)sm.max, (unsigned long long)sm.max_row, (unsigned long long)sm.capped,
+            (unsigned long long)st.chunks, (unsigned long long)st.chunk_len, (double)st.symbols_compared / (double)sm.n,
+            st.ms_walk, st.ms_scatter, st.ms_plcp, st.ms_rows, st.ms_wall);
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(starts); free(distinct);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
 /* ---- graph / unitigs --------------------------------------------------------------------------------------------------- */
 
 /* the mirror of oriented node v of the both-strand graph: v ^ 1, or v itself for the one node of a self-rc read */
@@ -1492,7 +1579,7 @@ int main(int argc, char **argv) {
                !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
                !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : !strcmp(cmd, "graph") ? 9 :
                !strcmp(cmd, "unitigs") ? 10 : !strcmp(cmd, "pileup") ? 11 : !strcmp(cmd, "consensus") ? 12 :
-               !strcmp(cmd, "spectrum") ? 13 : -1;
+               !strcmp(cmd, "spectrum") ? 13 : !strcmp(cmd, "lcp") ? 14 : -1;
     const int mapping = mode == 4 || mode == 11 || mode == 12;   /* the commands that map reads first */
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
@@ -1512,7 +1599,8 @@ int main(int argc, char **argv) {
     debwt_fm_correct_defaults(&ko);
     const char *report = NULL, *states = NULL;
     int k_given = 0, all_edges = 0, graph_both = 0, clean = 0, auto_count = 0, filter_given = 0;
-    const char *list = NULL;
+    const char *list = NULL, *lcp_file = NULL, *esa_sa_file = NULL, *da_file = NULL;
+    uint64_t max_lcp = 0, profile_k = 0;
     uint64_t bins = 256, at_least = 1, at_most = 0xFFFFFFFFull;
     debwt_fm_clean_opts cl;
     debwt_fm_clean_defaults(&cl);
@@ -1634,6 +1722,15 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &at_most) || at_most < 1 || at_most > 0xFFFFFFFFull) { fprintf(stderr, "--at-most: a multiplicity of at least 1\n"); return 1; }
             filter_given = 1;
         }
+        else if (mode == 14 && !strcmp(a, "--max-lcp")) {
+            if (parse_u64(v, &max_lcp) || max_lcp < 1 || max_lcp > 0xFFFFFFFFull) { fprintf(stderr, "--max-lcp: a cap of at least 1\n"); return 1; }
+        }
+        else if (mode == 14 && !strcmp(a, "--lcp")) lcp_file = v;
+        else if (mode == 14 && !strcmp(a, "--sa")) esa_sa_file = v;
+        else if (mode == 14 && !strcmp(a, "--da")) da_file = v;
+        else if (mode == 14 && !strcmp(a, "--profile")) {
+            if (parse_u64(v, &profile_k) || profile_k < 1 || profile_k > DEBWT_FM_ESA_MAX_K) { fprintf(stderr, "--profile: a length in 1..%u\n", DEBWT_FM_ESA_MAX_K); return 1; }
+        }
         else if (mode == 8 && !strcmp(a, "--min-count") && !strcmp(v, "auto")) auto_count = 1;
         else if (mode == 8 && !strcmp(a, "--min-count")) {
             auto_count = 0;
@@ -1676,6 +1773,11 @@ int main(int argc, char **argv) {
         if (filter_given && !list) { fprintf(stderr, "--at-least, --at-most: only with --list\n"); return 1; }
         if (at_least > at_most) { fprintf(stderr, "--at-least: above --at-most\n"); return 1; }
         return cmd_spectrum(out, (int)device, ko.k, ko.flags, (uint32_t)bins, list, (uint32_t)at_least, (uint32_t)at_most);
+    }
+    if (mode == 14) {
+        if (!out || file) { usage(); return 1; }
+        if (max_lcp && profile_k > max_lcp) { fprintf(stderr, "--profile: above --max-lcp\n"); return 1; }
+        return cmd_lcp(out, (int)device, (uint32_t)max_lcp, lcp_file, esa_sa_file, da_file, (uint32_t)profile_k);
     }
     if (!out || !file) { usage(); return 1; }
     if (mapping) {

@@ -143,6 +143,22 @@ class DebwtFmSpectrumStats(ctypes.Structure):
         return d
 
 
+class DebwtFmEsaSummary(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_uint64) for n in ("n", "max", "max_row", "sum", "capped", "pos_prev", "pos", "cap")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class DebwtFmEsaStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("walk_items", "walk_steps", "walk_wave_steps", "chunks", "chunk_len",
+                                                 "symbols_compared", "plcp_wave_steps", "build_bytes", "kept_bytes")] +
+                [(n, ctypes.c_float) for n in ("ms_walk", "ms_scatter", "ms_plcp", "ms_rows", "ms_text", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 CORRECT_MAX_ROUNDS = 16
 
 
@@ -391,6 +407,8 @@ SYMBOLS = [
     "debwt_fm_kmer_counts", "debwt_fm_kmer_stats_get", "debwt_fm_weak_trials", "debwt_fm_correct_defaults",
     "debwt_fm_correct", "debwt_fm_correct_stats_get",
     "debwt_fm_spectrum", "debwt_fm_kmer_list", "debwt_fm_spectrum_threshold", "debwt_fm_spectrum_stats_get",
+    "debwt_fm_esa_build", "debwt_fm_esa_fetch", "debwt_fm_esa_summary_get", "debwt_fm_esa_profile", "debwt_fm_esa_release",
+    "debwt_fm_esa_stats_get",
     "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
     "debwt_fm_string_graph_both", "debwt_fm_unitigs_both", "debwt_fm_graph_both_stats_get",
     "debwt_fm_clean_defaults", "debwt_fm_graph_clean", "debwt_fm_edges_compact", "debwt_fm_clean_stats_get",
@@ -703,6 +721,18 @@ def lib():
     L.debwt_fm_spectrum_threshold.argtypes = [u64p, ctypes.c_uint32, ctypes.c_uint64, ctypes.POINTER(DebwtFmSpectrumSummary)]
     L.debwt_fm_spectrum_stats_get.restype = ctypes.c_int
     L.debwt_fm_spectrum_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmSpectrumStats)]
+    L.debwt_fm_esa_build.restype = ctypes.c_int
+    L.debwt_fm_esa_build.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32]
+    L.debwt_fm_esa_fetch.restype = ctypes.c_int
+    L.debwt_fm_esa_fetch.argtypes = [vp, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p]
+    L.debwt_fm_esa_summary_get.restype = ctypes.c_int
+    L.debwt_fm_esa_summary_get.argtypes = [vp, ctypes.POINTER(DebwtFmEsaSummary)]
+    L.debwt_fm_esa_profile.restype = ctypes.c_int
+    L.debwt_fm_esa_profile.argtypes = [vp, ctypes.c_uint32, u64p]
+    L.debwt_fm_esa_release.restype = ctypes.c_int
+    L.debwt_fm_esa_release.argtypes = [vp]
+    L.debwt_fm_esa_stats_get.restype = ctypes.c_int
+    L.debwt_fm_esa_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmEsaStats)]
     u8p, edgep = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(DebwtFmEdge)
     L.debwt_fm_string_graph.restype = ctypes.c_int
     L.debwt_fm_string_graph.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u64p, edgep, ctypes.c_uint64]

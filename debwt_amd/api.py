@@ -538,6 +538,24 @@ class FMIndex:
         self._chk(self._L.debwt_fm_spectrum_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def esa(self, max_lcp=0, sa=False, da=False):
+        """Suffix array, LCP array and record array of the collection on the device (debwt_fm_esa_build, Definition 10):
+        lcp[r] is the common prefix of the suffixes of rows r - 1 and r, cut at the first separator of either and stored
+        as min(lcp, max_lcp) (max_lcp 0: no cap); sa and da keep the positions and the records of the rows as well.  The
+        text is restored first when none is attached.  The arrays stay on the device, counted in info()["device_bytes"],
+        until release() or the next esa(), which replaces them.  Returns an EsaResult."""
+        flags = (ESA_SA if sa else 0) | (ESA_DA if da else 0)
+        self._chk(self._L.debwt_fm_esa_build(self._h, int(max_lcp), flags))
+        return EsaResult(self)
+
+    def esa_stats(self):
+        """What the last esa() did (debwt_fm_esa_stats_get): walk items, LF steps and wave steps, chunks and the chunk
+        length in force (DEBWT_FM_ESA_CHUNK), symbols_compared and plcp_wave_steps of the PLCP kernel, bytes allocated by
+        the build and kept, ms per phase and wall ms."""
+        st = _lib.DebwtFmEsaStats()
+        self._chk(self._L.debwt_fm_esa_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def correct(self, patterns, k, min_count=3, rounds=4, strands="both"):
         """k-mer read correction on the device (debwt_fm_correct): per read and round, a run of weak k-mers (count below
         min_count) that has the signature of one substitution is fixed when exactly one other base makes the k-mer next
@@ -1035,6 +1053,7 @@ MAP_PROPER, MAP_RESCUED = 8, 16                        # MapResult.flags of FMIn
 MAP_FORWARD = 1                                        # option flag of debwt_fm_map
 OVERLAP_LONGEST = 2                                    # option flag of debwt_fm_overlaps
 OVERLAP_CONTAINS, OVERLAP_WHOLE = 1, 2                 # OverlapResult hit flags
+ESA_SA, ESA_DA = 1, 2                                  # flags of debwt_fm_esa_build
 CORRECT_SHORT, CORRECT_CLEAN, CORRECT_FIXED, CORRECT_WEAK = 1, 2, 4, 8   # flags of FMIndex.correct's info
 _CORRECT_DTYPE = np.dtype([("flags", np.uint32), ("fixes", np.uint32), ("weak_before", np.uint32), ("weak_after", np.uint32)])
 _TRIAL_DTYPE = np.dtype([("run_a", np.uint32), ("run_b", np.uint32), ("pos", np.uint32), ("window", np.uint32),
@@ -1506,6 +1525,52 @@ class SpectrumResult:
 
     def threshold(self):
         return spectrum_threshold(self.hist, self.total)
+
+
+class EsaResult:
+    """The arrays FMIndex.esa left on the device.  lcp(lo, hi), sa(lo, hi), da(lo, hi): rows [lo, hi) (all rows by
+    default) as uint32, uint64, uint32; sa and da raise DEBWT_ESTATE unless they were kept.  summary(): n, max, max_row,
+    sum, capped, pos_prev, pos (the two places of the longest repeat), cap.  profile(kmax): distinct[k - 1] = the number
+    of distinct k-mers inside records, k = 1 .. kmax <= min(cap, 4096).  The arrays belong to the index: the next esa()
+    replaces them and release() frees them, after which every method raises DEBWT_ESTATE."""
+
+    _ARRAYS = {"lcp": (0, np.uint32), "sa": (1, np.uint64), "da": (2, np.uint32)}
+
+    def __init__(self, index):
+        self._x = index
+
+    def _fetch(self, name, lo, hi):
+        which, dtype = self._ARRAYS[name]
+        x = self._x
+        lo = int(lo)
+        hi = x.info()["n"] if hi is None else int(hi)
+        if hi < lo:
+            raise ValueError("hi must not be below lo")
+        out = np.zeros(hi - lo, dtype=dtype)
+        x._chk(x._L.debwt_fm_esa_fetch(x._h, which, lo, hi - lo, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def lcp(self, lo=0, hi=None):
+        return self._fetch("lcp", lo, hi)
+
+    def sa(self, lo=0, hi=None):
+        return self._fetch("sa", lo, hi)
+
+    def da(self, lo=0, hi=None):
+        return self._fetch("da", lo, hi)
+
+    def summary(self):
+        out = _lib.DebwtFmEsaSummary()
+        self._x._chk(self._x._L.debwt_fm_esa_summary_get(self._x._h, ctypes.byref(out)))
+        return out.as_dict()
+
+    def profile(self, kmax):
+        out = np.zeros(max(int(kmax), 1), dtype=np.uint64)
+        self._x._chk(self._x._L.debwt_fm_esa_profile(self._x._h, int(kmax), _p64(out)))
+        return out[:int(kmax)]
+
+    def release(self):
+        self._x._chk(self._x._L.debwt_fm_esa_release(self._x._h))
 
 
 class OverlapResult:

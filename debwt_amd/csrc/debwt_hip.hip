@@ -35,6 +35,7 @@
 #include "fm_overlap_kernels.h"
 #include "fm_overlap_mm_kernels.h"
 #include "fm_extract_kernels.h"
+#include "fm_esa_kernels.h"
 #include "fm_kmer_kernels.h"
 #include "fm_spectrum_kernels.h"
 #include "fm_graph_kernels.h"
@@ -2997,6 +2998,11 @@ struct debwt_fm {
     debwt_fm_correct_stats c_stats{};
     DevBuf sp_front, sp_codes, sp_mults, sp_ctr, sp_hist, sp_gsum;   // spectrum: two frontiers, list staging, counters, histogram, granule sums
     debwt_fm_spectrum_stats sp_stats{};
+    DevBuf esa_lcp, esa_sa, esa_da;   // the kept arrays of debwt_fm_esa_build, allocated exactly (has_esa: counted in device_bytes)
+    bool has_esa = false;
+    debwt_fm_esa_summary esa_sum{};
+    std::vector<u64> esa_distinct;    // the profile of the build, k = 1 .. 4096
+    debwt_fm_esa_stats esa_stats{};
     DevBuf g_coff, g_state, g_hbase, g_raw, g_flag, g_deg, g_oseg, g_edges, g_eoff, g_len, g_keep, g_out, g_ctr;   // string graph
     debwt_fm_graph_stats g_stats{};
     DevBuf b_state, b_self, b_row, b_cnt, b_whb, b_rawbase, b_tbase, b_pos, b_aoff, b_mm, b_cur, b_cat, b_ctr;   // graph over both strands
@@ -3287,7 +3293,8 @@ extern "C" int debwt_fm_info_get(const debwt_fm *f, debwt_fm_info *out) {
     out->n = f->n; out->nrec = f->nrec; out->sa_sample = f->s; out->samples = f->nsamp;
     out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap + (f->has_text ? f->text.cap : 0) +
                         (f->has_otable ? f->o_table.cap : 0) + (f->has_anchors ? f->anchors.cap : 0) +
-                        (f->has_ktable ? f->k_table.cap : 0) + (f->has_ptable ? f->p_table.cap : 0);
+                        (f->has_ktable ? f->k_table.cap : 0) + (f->has_ptable ? f->p_table.cap : 0) +
+                        (f->has_esa ? f->esa_lcp.cap + f->esa_sa.cap + f->esa_da.cap : 0);
     out->ms_rank = f->ms_rank; out->ms_samples = f->ms_samples;
     for (int q = 0; q < 4; q++) out->census[q] = f->census[q];
     return DEBWT_OK;
@@ -6601,6 +6608,187 @@ extern "C" int debwt_fm_spectrum_stats_get(const debwt_fm *f, debwt_fm_spectrum_
     return DEBWT_OK;
 }
 
+// ---- suffix array, LCP array and record array (fm_esa_kernels.h) ---------------------------------------------------------
+// One build is a run of launches on the index's stream: the walk that writes the suffix array (synchronised: its chain
+// check decides whether anything is kept), then scatter, PLCP, rows and the first row of the maximum without a host round
+// trip.  Everything is allocated into temporaries that are released on every way out; the arrays to keep change hands
+// only after the last check.
+
+namespace {
+
+constexpr u64 FM_ESA_CHUNK = 256;                      // text positions per lane of the PLCP kernel
+
+void fm_esa_drop(debwt_fm *f) {
+    if (!f->has_esa && !f->esa_lcp.p && !f->esa_sa.p && !f->esa_da.p) return;
+    (void)hipSetDevice(f->device);
+    if (f->stream) (void)hipStreamSynchronize(f->stream);
+    for (DevBuf *b : {&f->esa_lcp, &f->esa_sa, &f->esa_da}) {
+        if (b->p) (void)hipFree(b->p);
+        b->p = nullptr; b->cap = 0;
+    }
+    f->has_esa = false;
+    f->esa_distinct.clear();
+}
+
+void fm_esa_keep(DevBuf &b, FmTmp &t, size_t bytes) { b.p = t.p; b.cap = bytes; t.p = nullptr; }
+
+}  // namespace
+
+extern "C" int debwt_fm_esa_build(debwt_fm *f, uint32_t max_lcp, uint32_t flags) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    f->esa_stats = debwt_fm_esa_stats{};
+    debwt_fm_esa_stats &st = f->esa_stats;
+    if (flags & ~(DEBWT_FM_ESA_SA | DEBWT_FM_ESA_DA)) { f->err = "debwt_fm_esa_build: unknown flags"; return DEBWT_EINVAL; }
+    const u64 n = f->n, nrec = f->nrec;
+    const bool keep_sa = flags & DEBWT_FM_ESA_SA, keep_da = flags & DEBWT_FM_ESA_DA;
+    if (keep_da && nrec >> 32) { f->err = "debwt_fm_esa_build: the record array holds u32, the index has 2^32 records or more"; return DEBWT_EINVAL; }
+    HIPCHK(f, hipSetDevice(f->device));
+    fm_esa_drop(f);
+    int rc;
+    if (!f->has_text) {
+        const auto t1 = std::chrono::steady_clock::now();
+        if ((rc = debwt_fm_restore_text(f))) return rc;
+        st.ms_text = (float)fm_ms_since(t1);
+    } else if ((rc = fm_anchors_build(f))) return rc;
+    const u64 cap = max_lcp ? max_lcp : 0xFFFFFFFFull;
+    const u64 chunk = fm_env_u64("DEBWT_FM_ESA_CHUNK", FM_ESA_CHUNK), nchunks = (n + chunk - 1) / chunk;
+    st.chunk_len = chunk; st.chunks = nchunks;
+    const size_t sbw = (size_t)((n + 63) >> 6) + 2, small_bytes = (size_t)(FM_ESA_NCTR + FM_ESA_NDIFF) * 8;
+    const u64 rkw = (n + 63) >> 6, rkc = (rkw + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;   // the rank over the bitmap
+    FmTmp sa, phi, plcp, lcp, da, sepbits, seps, wpre, csum, small;
+    HIPCHK(f, hipMalloc(&sa.p, (size_t)n * 8));
+    HIPCHK(f, hipMalloc(&phi.p, (size_t)n * 8));
+    HIPCHK(f, hipMalloc(&plcp.p, (size_t)n * 4));
+    HIPCHK(f, hipMalloc(&lcp.p, (size_t)n * 4));
+    if (keep_da) HIPCHK(f, hipMalloc(&da.p, (size_t)n * 4));
+    HIPCHK(f, hipMalloc(&sepbits.p, sbw * 8));
+    HIPCHK(f, hipMalloc(&seps.p, (size_t)nrec * 8));
+    HIPCHK(f, hipMalloc(&wpre.p, (size_t)rkw * 4));
+    HIPCHK(f, hipMalloc(&csum.p, (size_t)(rkc + 1) * 8));
+    HIPCHK(f, hipMalloc(&small.p, small_bytes));
+    st.build_bytes = n * 24 + (keep_da ? n * 4 : 0) + sbw * 8 + nrec * 8 + rkw * 4 + (rkc + 1) * 8 + small_bytes;
+    u64 *d_sa = reinterpret_cast<u64 *>(sa.p), *d_phi = reinterpret_cast<u64 *>(phi.p), *d_bits = reinterpret_cast<u64 *>(sepbits.p);
+    u64 *d_seps = reinterpret_cast<u64 *>(seps.p), *d_csum = reinterpret_cast<u64 *>(csum.p), *ctr = reinterpret_cast<u64 *>(small.p);
+    u32 *d_plcp = reinterpret_cast<u32 *>(plcp.p), *d_lcp = reinterpret_cast<u32 *>(lcp.p), *d_da = reinterpret_cast<u32 *>(da.p);
+
+    // the suffix array: one walk over every anchor gap; the extract statistics stay those of the last extract or restore
+    FM_ENSURE(f, f->e_ctr, 64);
+    const debwt_fm_extract_stats e_keep = f->e_stats;
+    f->e_stats = debwt_fm_extract_stats{};
+    u64 h[8];
+    rc = fm_extract_walk(f, FmExSa{d_sa}, f->na - 1, false, h);
+    st.walk_items = f->na - 1; st.walk_steps = f->e_stats.steps; st.walk_wave_steps = f->e_stats.wave_steps;
+    st.ms_walk = f->e_stats.ms_kernel;
+    f->e_stats = e_keep;
+    if (rc) return rc;
+    if (h[FM_EX_W_CHAIN] || h[FM_EX_W_BAD] || h[FM_EX_W_STEPS] != n - 1) {
+        f->err = "debwt_fm_esa_build: the samples are not those of the rows (" + std::to_string(h[FM_EX_W_CHAIN]) +
+                 " walks missed the row of their lower anchor or the '$' row at the text's start, " +
+                 std::to_string(h[FM_EX_W_BAD]) + " were refused, " + std::to_string(h[FM_EX_W_STEPS]) + " of " +
+                 std::to_string(n - 1) + " steps)";
+        return DEBWT_EINVAL;
+    }
+
+    std::vector<u64> hs(nrec);                                 // the separator positions
+    for (u64 r = 0; r < nrec; r++) hs[r] = (r + 1 < nrec ? f->rec_starts[r + 1] : n) - 1;
+    HIPCHK(f, hipMemcpyAsync(d_seps, hs.data(), (size_t)nrec * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(d_bits, 0, sbw * 8, f->stream));
+    HIPCHK(f, hipMemsetAsync(ctr, 0, small_bytes, f->stream));
+    HIPCHK(f, hipMemsetAsync(ctr + FM_ESA_C_MAXROW, 0xFF, 8, f->stream));
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct Ev { hipEvent_t *e; ~Ev() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int i = 0; i < 4; i++) HIPCHK(f, hipEventCreate(&ev[i]));
+    k_set_sepbits<<<grid_for(nrec, 256), 256, 0, f->stream>>>(d_seps, nrec, d_bits);
+    k_fm_anc_count<<<(u32)rkc, FM_EX_CHUNK_WORDS, 0, f->stream>>>(d_bits, rkw, reinterpret_cast<u32 *>(wpre.p), d_csum);
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(d_csum, rkc, d_csum + rkc);
+    (void)hipEventRecord(ev[0], f->stream);
+    k_fm_esa_phi<<<grid_for(n, 256), 256, 0, f->stream>>>(d_sa, n, d_phi);
+    (void)hipEventRecord(ev[1], f->stream);
+    k_fm_esa_plcp<<<grid_for(nchunks, 256), 256, 0, f->stream>>>(f->text.as<u64>(), d_bits, d_phi, n, chunk, nchunks, cap, d_plcp, ctr);
+    (void)hipEventRecord(ev[2], f->stream);
+    // few workgroups with many rows each: the per-wave sums and the flush of the LDS array are atomics on shared addresses
+    const u32 row_blocks = (u32)std::min<u64>(grid_for(n, 256), std::max<u64>(4096, (n >> 30) + 1));
+    k_fm_esa_rows<<<row_blocks, 256, 0, f->stream>>>(d_sa, d_plcp, d_bits, reinterpret_cast<const u32 *>(wpre.p), d_csum, d_seps,
+                                                     nrec, n, (u32)cap, max_lcp ? 1u : 0u, d_lcp, keep_da ? d_da : nullptr, ctr,
+                                                     ctr + FM_ESA_NCTR);
+    k_fm_esa_maxrow<<<grid_for(n, 256), 256, 0, f->stream>>>(d_lcp, n, ctr);
+    (void)hipEventRecord(ev[3], f->stream);
+    std::vector<u64> hc(FM_ESA_NCTR + FM_ESA_NDIFF);
+    HIPCHK(f, hipMemcpyAsync(hc.data(), ctr, small_bytes, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    (void)hipEventElapsedTime(&st.ms_scatter, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&st.ms_plcp, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&st.ms_rows, ev[2], ev[3]);
+    if (hc[FM_ESA_C_BADPHI] || hc[FM_ESA_C_MAXROW] >= n) {
+        f->err = "debwt_fm_esa_build: the suffix array is no permutation of the text positions";
+        return DEBWT_EINTERNAL;
+    }
+    st.symbols_compared = hc[FM_ESA_C_SYMBOLS]; st.plcp_wave_steps = hc[FM_ESA_C_WAVE];
+    debwt_fm_esa_summary &sm = f->esa_sum;
+    sm = debwt_fm_esa_summary{n, hc[FM_ESA_C_MAX], hc[FM_ESA_C_MAXROW], hc[FM_ESA_C_SUM], hc[FM_ESA_C_CAPPED], 0, 0, cap};
+    u64 pos[2] = {0, 0};
+    const u64 r0 = sm.max_row ? sm.max_row - 1 : 0;
+    HIPCHK(f, hipMemcpyAsync(pos, d_sa + r0, sm.max_row ? 16 : 8, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    sm.pos_prev = pos[0]; sm.pos = sm.max_row ? pos[1] : pos[0];
+    f->esa_distinct.assign(FM_ESA_KMAX, 0);                    // distinct[k - 1] = the sum of diff[1 .. k]
+    u64 run = 0;
+    for (u32 k = 1; k <= FM_ESA_KMAX; k++) { run += hc[FM_ESA_NCTR + k]; f->esa_distinct[k - 1] = run; }
+    fm_esa_keep(f->esa_lcp, lcp, (size_t)n * 4);
+    if (keep_sa) fm_esa_keep(f->esa_sa, sa, (size_t)n * 8);
+    if (keep_da) fm_esa_keep(f->esa_da, da, (size_t)n * 4);
+    f->has_esa = true;
+    st.kept_bytes = f->esa_lcp.cap + f->esa_sa.cap + f->esa_da.cap;
+    st.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_esa_fetch(debwt_fm *f, int which, uint64_t row_lo, uint64_t count, void *dst) {
+    if (!f) return DEBWT_EINVAL;
+    if (which != DEBWT_FM_ESA_LCP_ARRAY && which != DEBWT_FM_ESA_SA_ARRAY && which != DEBWT_FM_ESA_DA_ARRAY) {
+        f->err = "debwt_fm_esa_fetch: which must name the LCP, SA or DA array"; return DEBWT_EINVAL;
+    }
+    const DevBuf &b = which == DEBWT_FM_ESA_LCP_ARRAY ? f->esa_lcp : which == DEBWT_FM_ESA_SA_ARRAY ? f->esa_sa : f->esa_da;
+    if (!f->has_esa || !b.p) { f->err = "debwt_fm_esa_fetch: no build holds this array (debwt_fm_esa_build and its flags)"; return DEBWT_ESTATE; }
+    if (row_lo > f->n || count > f->n - row_lo) { f->err = "debwt_fm_esa_fetch: row_lo + count exceeds n"; return DEBWT_EINVAL; }
+    if (!count) return DEBWT_OK;
+    if (!dst) return DEBWT_EINVAL;
+    const size_t w = which == DEBWT_FM_ESA_SA_ARRAY ? 8 : 4;
+    HIPCHK(f, hipSetDevice(f->device));
+    HIPCHK(f, hipMemcpyAsync(dst, b.as<u8>() + (size_t)row_lo * w, (size_t)count * w, hipMemcpyDeviceToHost, f->stream));
+    return fm_sync(f);
+}
+
+extern "C" int debwt_fm_esa_summary_get(const debwt_fm *f, debwt_fm_esa_summary *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    if (!f->has_esa) return DEBWT_ESTATE;
+    *out = f->esa_sum;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_esa_profile(debwt_fm *f, uint32_t kmax, uint64_t *distinct) {
+    if (!f || !distinct) return DEBWT_EINVAL;
+    if (!f->has_esa) { f->err = "debwt_fm_esa_profile: no build (debwt_fm_esa_build)"; return DEBWT_ESTATE; }
+    if (!kmax || kmax > FM_ESA_KMAX || kmax > f->esa_sum.cap) {
+        f->err = "debwt_fm_esa_profile: kmax must be 1..4096 and at most the cap of the build"; return DEBWT_EINVAL;
+    }
+    memcpy(distinct, f->esa_distinct.data(), (size_t)kmax * 8);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_esa_release(debwt_fm *f) {
+    if (!f) return DEBWT_EINVAL;
+    fm_esa_drop(f);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_esa_stats_get(const debwt_fm *f, debwt_fm_esa_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->esa_stats;
+    return DEBWT_OK;
+}
+
 // ---- string graph of the indexed records, on one strand or on both (fm_graph_kernels.h, fm_bigraph_kernels.h) --------
 // debwt_fm_string_graph and debwt_fm_string_graph_both share one host path: fm_graph_found, then fm_graph_finish.
 // States come from one backward search per record over the attached text.  The kept records then go through the overlap
@@ -7733,7 +7921,7 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
                       &f->b_self, &f->b_row, &f->b_cnt, &f->b_whb, &f->b_rawbase, &f->b_tbase, &f->b_pos, &f->b_aoff, &f->b_mm,
                       &f->b_cur, &f->b_cat, &f->b_ctr, &f->cl_state, &f->cl_src, &f->cl_cnt, &f->cl_toff, &f->cl_tin, &f->cl_snap,
                       &f->cl_mark, &f->cl_ctr, &f->p_table, &f->p_codes, &f->p_aln, &f->p_coff, &f->p_cig, &f->p_span, &f->p_ctr,
-                      &f->p_sep, &f->p_calls, &f->p_vcnt, &f->p_vbase, &f->p_vars})
+                      &f->p_sep, &f->p_calls, &f->p_vcnt, &f->p_vbase, &f->p_vars, &f->esa_lcp, &f->esa_sa, &f->esa_da})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -1177,6 +1177,69 @@ typedef struct {
 } debwt_fm_spectrum_stats;
 int debwt_fm_spectrum_stats_get(const debwt_fm *fm, debwt_fm_spectrum_stats *out);
 
+/* ---- Definition 10 (enhanced suffix array): suffix array, LCP array and record array (fm_esa_kernels.h) ---------------
+ * The text T is r0 # r1 # ... $ with n symbols; the order is the index's: A < C < G < T < '#' < '$', all '#' equal,
+ * suffixes compared symbol by symbol through separators.  Rows are the rows of the BWT, r = 0 .. n - 1.
+ *   sa[r]   the text position of the suffix of row r, a u64: what debwt_fm_locate answers for that row.
+ *   da[r]   the record j with start_j <= sa[r] <= start_j + |S_j|, a u32: the separator behind a record, and the '$',
+ *           belong to that record.
+ *   d(p)    the number of bases from p up to the next separator; 0 when T[p] is a separator.
+ *   lcp[0]  = 0.  For r >= 1, lcp[r] is the largest h <= min(d(sa[r-1]), d(sa[r])) with T[sa[r-1] .. +h) = T[sa[r] .. +h):
+ *           the common prefix of the two suffixes, cut at the first separator of either, so a row whose suffix starts
+ *           with a separator has lcp 0.  Stored as u32: min(lcp, cap), cap = max_lcp, or 2^32 - 1 when max_lcp = 0.
+ * Three facts the kernels rest on (tests/esa_ref.py asserts them):
+ *   1. for rows a < b the cut common prefix of suffixes sa[a] and sa[b] is min(lcp[a+1 .. b]);
+ *   2. with plcp[i] = lcp[row of position i], plcp[i+1] >= plcp[i] - 1 (Kasai's carry), for the capped values too;
+ *   3. the number of distinct strings of k bases inside records is #{ r : lcp[r] < k <= d(sa[r]) }, exact for k <= cap.
+ * Summary: max = the largest stored value, max_row = the first row that holds it, sum = the sum of the stored values,
+ * capped = the rows whose stored value equals a non-zero max_lcp (0 when max_lcp = 0), pos_prev = sa[max_row - 1] and
+ * pos = sa[max_row], the two places of the longest repeat (both sa[0] when max_row = 0: every value is 0), cap = the cap
+ * in force.  Profile: distinct[k - 1] for k = 1 .. kmax is fact 3; kmax <= cap and kmax <= 4096.
+ *
+ * The build.  The text is restored first when none is attached (debwt_fm_restore_text).  The suffix array is written by
+ * one walk over the gaps between the anchors of the extract section, every row once, under the chain check of that walk:
+ * samples that are not the rows' give DEBWT_EINVAL and nothing is kept.  phi[sa[r]] = sa[r-1] is scattered, the text
+ * positions are cut into chunks of DEBWT_FM_ESA_CHUNK positions (environment, read per call; default 256) and one lane
+ * per chunk compares word-wise, 32 bases a step, carrying the match length minus one from a position to the next inside
+ * its chunk: the work is at most n + chunks x cap symbols plus two words per position, not the sum of the LCP values.  No
+ * result depends on the chunk length.  Device memory while building, beside the text ((n + 63) / 32 + 2 words) and the
+ * anchors: 8 n (sa) + 8 n (phi) + 4 n (plcp) + 4 n (lcp) + 4 n (da, when kept) + 3 n / 16 (separator bitmap and its rank) +
+ * 8 nrec + 33 KiB; kept afterwards, allocated exactly and counted in debwt_fm_info.device_bytes until released: 4 n (lcp), 8 n
+ * (sa) with DEBWT_FM_ESA_SA, 4 n (da) with DEBWT_FM_ESA_DA.  When an allocation fails the call answers DEBWT_ENOMEM and
+ * keeps nothing.  A second build replaces the first (which is released before the new one is made). */
+#define DEBWT_FM_ESA_SA 1u
+#define DEBWT_FM_ESA_DA 2u
+#define DEBWT_FM_ESA_LCP_ARRAY 0
+#define DEBWT_FM_ESA_SA_ARRAY  1
+#define DEBWT_FM_ESA_DA_ARRAY  2
+#define DEBWT_FM_ESA_MAX_K 4096u
+/* DEBWT_EINVAL for flags other than the two above, and for DEBWT_FM_ESA_DA on an index of 2^32 records or more */
+int debwt_fm_esa_build(debwt_fm *fm, uint32_t max_lcp, uint32_t flags);
+/* rows [row_lo, row_lo + count) of one array to the host: which = DEBWT_FM_ESA_LCP_ARRAY (u32), _SA_ARRAY (u64) or
+ * _DA_ARRAY (u32).  DEBWT_ESTATE without a build or for an array that was not kept, DEBWT_EINVAL for another `which`,
+ * row_lo + count > n, or a NULL dst with count > 0. */
+int debwt_fm_esa_fetch(debwt_fm *fm, int which, uint64_t row_lo, uint64_t count, void *dst);
+typedef struct { uint64_t n, max, max_row, sum, capped, pos_prev, pos, cap; } debwt_fm_esa_summary;
+/* DEBWT_ESTATE without a build */
+int debwt_fm_esa_summary_get(const debwt_fm *fm, debwt_fm_esa_summary *out);
+/* distinct receives kmax values (host; the difference array was reduced by the build).  DEBWT_ESTATE without a build,
+ * DEBWT_EINVAL for kmax = 0, kmax > cap and kmax > 4096. */
+int debwt_fm_esa_profile(debwt_fm *fm, uint32_t kmax, uint64_t *distinct);
+/* releases the kept arrays; DEBWT_OK without a build too */
+int debwt_fm_esa_release(debwt_fm *fm);
+/* what the last debwt_fm_esa_build did: walk items (anchor gaps), LF steps (n - 1) and wave steps of the walk (64 x the
+ * loop iterations per wave), chunks and the chunk length in force, symbols_compared (the symbol pairs the PLCP kernel
+ * examined, a whole word step counting 32), plcp_wave_steps (64 x the word steps of the longest lane of every wave:
+ * symbols_compared / 32 / plcp_wave_steps is the share of lanes busy), the device bytes allocated by the build and those
+ * kept, ms per phase (events: walk, scatter, PLCP, rows with the reductions), the wall time of a text restore (0 when
+ * a text was attached) and host wall time */
+typedef struct {
+    uint64_t walk_items, walk_steps, walk_wave_steps, chunks, chunk_len, symbols_compared, plcp_wave_steps, build_bytes,
+        kept_bytes;
+    float ms_walk, ms_scatter, ms_plcp, ms_rows, ms_text, ms_wall;
+} debwt_fm_esa_stats;
+int debwt_fm_esa_stats_get(const debwt_fm *fm, debwt_fm_esa_stats *out);
+
 /* ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
  * Records S_0 .. S_{nrec-1} are those of the index, numbered as in overlap hits; |S| is the length of S.
  * 1. state[i] = 1 (duplicate) iff some j < i has S_j == S_i; otherwise 2 (contained) iff S_i is a substring of a strictly
