@@ -110,6 +110,19 @@
  * at most C) K lines k<TAB>distinct follow, the number of distinct strings of k bases inside records for k = 1..K.  It
  * needs OUT, OUT.#, OUT.$ and OUT.sa only (the text is restored on the GPU) and takes no file argument.
  *
+ * repeats lists the repeats of the indexed collection from the LCP array (debwt_fm_repeats, Definition 11 of debwt_hip.h):
+ * the maximal repeats of at least L bases (--min-len, default 20) with A (--min-occ, default 2) to B (--max-occ, default
+ * no bound) occurrences inside records; --supermaximal lists the supermaximal ones, --intervals every interval of the LCP
+ * array, left-diverse or not.  It builds the arrays with the suffix array kept; with --max-lcp C the LCP values are capped
+ * at C and only repeats shorter than C are listed (L must be below C).  stdout: one line "# intervals=I maximal=M
+ * supermaximal=S reported=R longest=LEN" (TAB-separated; I, M and S count the intervals of at least L bases before the
+ * occurrence bounds and the kind are applied), then one line per repeat in the library's order: len, occ, S (supermaximal), M
+ * (maximal) or - (an interval that is not left-diverse), the occurrences behind A,C,G,T and at a record's start
+ * (a,c,g,t,s), and the first occurrence in row order as record:offset, TAB-separated.  --seq appends the string (read
+ * through debwt_fm_extract), --occurrences every occurrence as record:offset, comma-separated, in row order.  It needs OUT,
+ * OUT.#, OUT.$ and OUT.sa only (the text is restored on the GPU), takes no file argument and holds the suffix array (8 n
+ * bytes) on the host while it writes.
+ *
  * graph writes the string graph of the indexed records as GFA 1 (debwt_fm_string_graph): a record that equals an earlier one
  * is a duplicate, one that lies inside a longer record is contained, the others are kept.  One "S J * LN:i:len" line per
  * kept record J (the 0-based number, as extract names records), then one "L a + b + <L>M" line per edge: the longest
@@ -164,6 +177,8 @@ static void usage(void) {
             "       deBWT-query correct -i OUT -k K [--device D] [--min-count T|auto] [--rounds R] [--forward] [--report FILE] READS.fa|.fq\n"
             "       deBWT-query spectrum -i OUT -k K [--device D] [--forward] [--bins N] [--list FILE [--at-least A] [--at-most B]]\n"
             "       deBWT-query lcp    -i OUT [--device D] [--max-lcp C] [--lcp FILE] [--sa FILE] [--da FILE] [--profile K]\n"
+            "       deBWT-query repeats -i OUT [--device D] [--min-len L] [--min-occ A] [--max-occ B] [--supermaximal | --intervals]\n"
+            "                          [--max-lcp C] [--seq] [--occurrences]\n"
             "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]\n"
             "                          [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]\n"
             "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]\n"
@@ -206,6 +221,11 @@ static void usage(void) {
             "little-endian u32, u64 and u32 arrays of n entries (LCP values cut at separators and capped at C with --max-lcp C);\n"
             "stdout gets # n=N<TAB>max=M<TAB>max_row=R<TAB>prev=J:OFF<TAB>pos=J:OFF<TAB>mean=X and, with --profile K (1..4096, at\n"
             "most C), k<TAB>distinct for k = 1..K, the distinct strings of k bases inside records;\n"
+            "repeats lists the maximal repeats of at least L bases (default 20) with A (default 2) to B occurrences, from the\n"
+            "LCP array: # intervals=I<TAB>maximal=M<TAB>supermaximal=S<TAB>reported=R<TAB>longest=LEN, then per repeat\n"
+            "len<TAB>occ<TAB>S|M|-<TAB>a,c,g,t,s (occurrences behind A, C, G, T, at a record's start)<TAB>record:offset of the\n"
+            "first occurrence; --supermaximal lists the supermaximal repeats, --intervals every interval; --seq appends the\n"
+            "string, --occurrences every occurrence; --max-lcp C caps the LCP values (L below C);\n"
             "graph writes GFA 1: S lines for the records that are neither duplicates nor contained, L lines a + b + <L>M for the\n"
             "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
             "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained;\n"
@@ -1422,6 +1442,98 @@ done:
     return ret;
 }
 
+/* ---- repeats ----------------------------------------------------------------------------------------------------------- */
+
+struct repeat_args { uint32_t min_len, kind, max_lcp; uint64_t min_occ, max_occ; int seq, occurrences; };
+
+static int cmd_repeats(const char *out, int device, const struct repeat_args *A) {
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) return 1;
+    int ret = 1, rc;
+    debwt_fm_info fi;
+    debwt_fm_info_get(fm, &fi);
+    uint64_t *starts = malloc(fi.nrec * 8), *sa = malloc(fi.n * 8), *off = NULL, count = 0;
+    debwt_fm_repeat *rp = NULL;
+    debwt_fm_extract_job *jb = NULL;
+    char *bases = NULL;
+    uint64_t bcap = 0;
+    debwt_fm_repeat_opts o = {A->min_len, A->kind, A->min_occ, A->max_occ};
+    debwt_fm_repeat_stats st;
+    if (!starts || !sa) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (debwt_fm_record_starts(fm, starts, fi.nrec) || debwt_fm_esa_build(fm, A->max_lcp, DEBWT_FM_ESA_SA)) {
+        fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
+        goto done;
+    }
+    rc = debwt_fm_repeats(fm, &o, NULL, 0, &count);
+    if (rc && rc != DEBWT_ERANGE) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    rp = malloc((count ? count : 1) * sizeof *rp);
+    if (!rp) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (count && debwt_fm_repeats(fm, &o, rp, count, &count)) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    debwt_fm_repeat_stats_get(fm, &st);
+    for (uint64_t lo = 0; lo < fi.n; lo += 1ull << 22) {
+        const uint64_t cnt = fi.n - lo < (1ull << 22) ? fi.n - lo : (1ull << 22);
+        if (debwt_fm_esa_fetch(fm, DEBWT_FM_ESA_SA_ARRAY, lo, cnt, sa + lo)) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    }
+    printf("# intervals=%llu\tmaximal=%llu\tsupermaximal=%llu\treported=%llu\tlongest=%llu\n", (unsigned long long)st.intervals,
+           (unsigned long long)st.maximal, (unsigned long long)st.supermaximal, (unsigned long long)st.reported,
+           (unsigned long long)st.longest_len);
+    if (A->seq) {
+        off = malloc((EXTRACT_BATCH_JOBS + 1) * 8);
+        jb = malloc(EXTRACT_BATCH_JOBS * sizeof *jb);
+        if (!off || !jb) { fprintf(stderr, "out of memory\n"); goto done; }
+        if (fi.nrec >> 32) { fprintf(stderr, "repeats --seq: 2^32 records or more\n"); goto done; }
+    }
+    for (uint64_t j0 = 0; j0 < count;) {
+        uint64_t j1 = j0, bytes = 0;
+        while (j1 < count && j1 - j0 < EXTRACT_BATCH_JOBS) {      /* at least one repeat, however long */
+            if (j1 > j0 && bytes + rp[j1].len > EXTRACT_BATCH_BYTES) break;
+            if (A->seq) {
+                const uint64_t p = sa[rp[j1].row_lo], r = record_of(starts, fi.nrec, p);
+                jb[j1 - j0].record = (uint32_t)r; jb[j1 - j0].reserved = 0; jb[j1 - j0].offset = p - starts[r]; jb[j1 - j0].length = rp[j1].len;
+            }
+            bytes += rp[j1].len; j1++;
+        }
+        if (A->seq) {
+            if (bytes > bcap) {
+                free(bases);
+                bases = malloc(bytes);
+                bcap = bases ? bytes : 0;
+                if (!bases) { fprintf(stderr, "out of memory\n"); goto done; }
+            }
+            if (debwt_fm_extract(fm, jb, j1 - j0, off, bases, bcap)) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+        }
+        for (uint64_t j = j0; j < j1; j++) {
+            const debwt_fm_repeat *x = &rp[j];
+            const uint64_t p = sa[x->row_lo], r = record_of(starts, fi.nrec, p);
+            printf("%u\t%llu\t%c\t%llu,%llu,%llu,%llu,%llu\t%llu:%llu", x->len, (unsigned long long)x->count,
+                   x->flags & DEBWT_FM_REPEAT_IS_SUPERMAXIMAL ? 'S' : x->flags & DEBWT_FM_REPEAT_IS_MAXIMAL ? 'M' : '-',
+                   (unsigned long long)x->left[0], (unsigned long long)x->left[1], (unsigned long long)x->left[2],
+                   (unsigned long long)x->left[3], (unsigned long long)x->left[4], (unsigned long long)r,
+                   (unsigned long long)(p - starts[r]));
+            if (A->seq) { putchar('\t'); fwrite(bases + off[j - j0], 1, off[j - j0 + 1] - off[j - j0], stdout); }
+            if (A->occurrences)
+                for (uint64_t t = 0; t < x->count; t++) {
+                    const uint64_t q = sa[x->row_lo + t], rq = record_of(starts, fi.nrec, q);
+                    printf("%c%llu:%llu", t ? ',' : '\t', (unsigned long long)rq, (unsigned long long)(q - starts[rq]));
+                }
+            putchar('\n');
+        }
+        j0 = j1;
+    }
+    fprintf(stderr, "repeats: %llu rows, %llu intervals of at least %u bases (%llu maximal, %llu supermaximal, %llu capped), %llu "
+                    "reported, longest %llu; %llu levels of fanout %llu, %.2f reads per row searched; tree %.1f, search %.1f, "
+                    "write %.1f ms\n",
+            (unsigned long long)st.rows, (unsigned long long)st.intervals, A->min_len, (unsigned long long)st.maximal,
+            (unsigned long long)st.supermaximal, (unsigned long long)st.capped_intervals, (unsigned long long)st.reported,
+            (unsigned long long)st.longest_len, (unsigned long long)st.levels, (unsigned long long)st.fanout,
+            st.searched ? (double)st.search_steps / (double)st.searched : 0.0, st.ms_tree, st.ms_search, st.ms_write);
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(starts); free(sa); free(rp); free(off); free(jb); free(bases);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
 /* ---- graph / unitigs --------------------------------------------------------------------------------------------------- */
 
 /* the mirror of oriented node v of the both-strand graph: v ^ 1, or v itself for the one node of a self-rc read */
@@ -1579,7 +1691,7 @@ int main(int argc, char **argv) {
                !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
                !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : !strcmp(cmd, "graph") ? 9 :
                !strcmp(cmd, "unitigs") ? 10 : !strcmp(cmd, "pileup") ? 11 : !strcmp(cmd, "consensus") ? 12 :
-               !strcmp(cmd, "spectrum") ? 13 : !strcmp(cmd, "lcp") ? 14 : -1;
+               !strcmp(cmd, "spectrum") ? 13 : !strcmp(cmd, "lcp") ? 14 : !strcmp(cmd, "repeats") ? 15 : -1;
     const int mapping = mode == 4 || mode == 11 || mode == 12;   /* the commands that map reads first */
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
@@ -1601,6 +1713,8 @@ int main(int argc, char **argv) {
     int k_given = 0, all_edges = 0, graph_both = 0, clean = 0, auto_count = 0, filter_given = 0;
     const char *list = NULL, *lcp_file = NULL, *esa_sa_file = NULL, *da_file = NULL;
     uint64_t max_lcp = 0, profile_k = 0;
+    struct repeat_args ra = {20, DEBWT_FM_REPEAT_MAXIMAL, 0, 2, 0, 0, 0};
+    int kind_given = 0;
     uint64_t bins = 256, at_least = 1, at_most = 0xFFFFFFFFull;
     debwt_fm_clean_opts cl;
     debwt_fm_clean_defaults(&cl);
@@ -1624,6 +1738,13 @@ int main(int argc, char **argv) {
         if ((mode == 9 || mode == 10) && !strcmp(a, "--both-strands")) { graph_both = 1; continue; }
         if ((mode == 9 || mode == 10) && !strcmp(a, "--clean")) { clean = 1; continue; }
         if ((mode == 8 || mode == 13) && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
+        if (mode == 15 && (!strcmp(a, "--supermaximal") || !strcmp(a, "--intervals"))) {
+            if (kind_given) { fprintf(stderr, "--supermaximal, --intervals: one of the two\n"); return 1; }
+            ra.kind = a[2] == 's' ? DEBWT_FM_REPEAT_SUPERMAXIMAL : DEBWT_FM_REPEAT_INTERVALS; kind_given = 1;
+            continue;
+        }
+        if (mode == 15 && !strcmp(a, "--seq")) { ra.seq = 1; continue; }
+        if (mode == 15 && !strcmp(a, "--occurrences")) { ra.occurrences = 1; continue; }
         if (mapping && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mapping && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
         if (!mapping && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
@@ -1722,7 +1843,17 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &at_most) || at_most < 1 || at_most > 0xFFFFFFFFull) { fprintf(stderr, "--at-most: a multiplicity of at least 1\n"); return 1; }
             filter_given = 1;
         }
-        else if (mode == 14 && !strcmp(a, "--max-lcp")) {
+        else if (mode == 15 && !strcmp(a, "--min-len")) {
+            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
+            ra.min_len = (uint32_t)v64;
+        }
+        else if (mode == 15 && !strcmp(a, "--min-occ")) {
+            if (parse_u64(v, &ra.min_occ) || ra.min_occ < 2) { fprintf(stderr, "--min-occ: a number of occurrences of at least 2\n"); return 1; }
+        }
+        else if (mode == 15 && !strcmp(a, "--max-occ")) {
+            if (parse_u64(v, &ra.max_occ) || ra.max_occ < 2) { fprintf(stderr, "--max-occ: a number of occurrences of at least 2\n"); return 1; }
+        }
+        else if ((mode == 14 || mode == 15) && !strcmp(a, "--max-lcp")) {
             if (parse_u64(v, &max_lcp) || max_lcp < 1 || max_lcp > 0xFFFFFFFFull) { fprintf(stderr, "--max-lcp: a cap of at least 1\n"); return 1; }
         }
         else if (mode == 14 && !strcmp(a, "--lcp")) lcp_file = v;
@@ -1778,6 +1909,13 @@ int main(int argc, char **argv) {
         if (!out || file) { usage(); return 1; }
         if (max_lcp && profile_k > max_lcp) { fprintf(stderr, "--profile: above --max-lcp\n"); return 1; }
         return cmd_lcp(out, (int)device, (uint32_t)max_lcp, lcp_file, esa_sa_file, da_file, (uint32_t)profile_k);
+    }
+    if (mode == 15) {
+        if (!out || file) { usage(); return 1; }
+        if (ra.max_occ && ra.max_occ < ra.min_occ) { fprintf(stderr, "--max-occ: below --min-occ\n"); return 1; }
+        if (max_lcp && ra.min_len >= max_lcp) { fprintf(stderr, "--min-len: not below --max-lcp (repeats of the capped length are not listed)\n"); return 1; }
+        ra.max_lcp = (uint32_t)max_lcp;
+        return cmd_repeats(out, (int)device, &ra);
     }
     if (!out || !file) { usage(); return 1; }
     if (mapping) {

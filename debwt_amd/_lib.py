@@ -159,6 +159,21 @@ class DebwtFmEsaStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmRepeatOpts(ctypes.Structure):
+    _fields_ = [("min_len", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("min_occ", ctypes.c_uint64), ("max_occ", ctypes.c_uint64)]
+
+
+class DebwtFmRepeatStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("rows", "searched", "representatives", "intervals", "maximal", "supermaximal",
+                                                 "capped_intervals", "reported", "longest_len", "longest_row_lo", "levels",
+                                                 "fanout", "tree_bytes", "scratch_bytes", "search_steps", "wave_steps",
+                                                 "rank_lines")] +
+                [(n, ctypes.c_float) for n in ("ms_tree", "ms_search", "ms_write", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 CORRECT_MAX_ROUNDS = 16
 
 
@@ -408,7 +423,7 @@ SYMBOLS = [
     "debwt_fm_correct", "debwt_fm_correct_stats_get",
     "debwt_fm_spectrum", "debwt_fm_kmer_list", "debwt_fm_spectrum_threshold", "debwt_fm_spectrum_stats_get",
     "debwt_fm_esa_build", "debwt_fm_esa_fetch", "debwt_fm_esa_summary_get", "debwt_fm_esa_profile", "debwt_fm_esa_release",
-    "debwt_fm_esa_stats_get",
+    "debwt_fm_esa_stats_get", "debwt_fm_repeats", "debwt_fm_repeat_stats_get",
     "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
     "debwt_fm_string_graph_both", "debwt_fm_unitigs_both", "debwt_fm_graph_both_stats_get",
     "debwt_fm_clean_defaults", "debwt_fm_graph_clean", "debwt_fm_edges_compact", "debwt_fm_clean_stats_get",
@@ -733,6 +748,10 @@ def lib():
     L.debwt_fm_esa_release.argtypes = [vp]
     L.debwt_fm_esa_stats_get.restype = ctypes.c_int
     L.debwt_fm_esa_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmEsaStats)]
+    L.debwt_fm_repeats.restype = ctypes.c_int
+    L.debwt_fm_repeats.argtypes = [vp, ctypes.POINTER(DebwtFmRepeatOpts), ctypes.c_void_p, ctypes.c_uint64, u64p]
+    L.debwt_fm_repeat_stats_get.restype = ctypes.c_int
+    L.debwt_fm_repeat_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmRepeatStats)]
     u8p, edgep = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(DebwtFmEdge)
     L.debwt_fm_string_graph.restype = ctypes.c_int
     L.debwt_fm_string_graph.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u64p, edgep, ctypes.c_uint64]

@@ -556,6 +556,15 @@ class FMIndex:
         self._chk(self._L.debwt_fm_esa_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def repeat_stats(self):
+        """What the last EsaResult.repeats did (debwt_fm_repeat_stats_get): rows, rows searched, representatives, intervals,
+        maximal, supermaximal, capped_intervals, reported, the longest reported length and its row_lo, levels and fanout of
+        the hierarchy (DEBWT_FM_REPEAT_FANOUT), tree and scratch bytes, search_steps and wave_steps of the searches, rank
+        lines read, ms per phase and wall ms."""
+        st = _lib.DebwtFmRepeatStats()
+        self._chk(self._L.debwt_fm_repeat_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def correct(self, patterns, k, min_count=3, rounds=4, strands="both"):
         """k-mer read correction on the device (debwt_fm_correct): per read and round, a run of weak k-mers (count below
         min_count) that has the signature of one substitution is fixed when exactly one other base makes the k-mer next
@@ -1054,6 +1063,9 @@ MAP_FORWARD = 1                                        # option flag of debwt_fm
 OVERLAP_LONGEST = 2                                    # option flag of debwt_fm_overlaps
 OVERLAP_CONTAINS, OVERLAP_WHOLE = 1, 2                 # OverlapResult hit flags
 ESA_SA, ESA_DA = 1, 2                                  # flags of debwt_fm_esa_build
+REPEAT_KINDS = {"maximal": 0, "supermaximal": 1, "intervals": 2}                 # kind of debwt_fm_repeats
+REPEAT_IS_MAXIMAL, REPEAT_IS_SUPERMAXIMAL = 1, 2       # flags of a repeat
+REPEAT_DTYPE = np.dtype([("row_lo", "<u8"), ("count", "<u8"), ("left", "<u8", (5,)), ("len", "<u4"), ("flags", "<u4")])
 CORRECT_SHORT, CORRECT_CLEAN, CORRECT_FIXED, CORRECT_WEAK = 1, 2, 4, 8   # flags of FMIndex.correct's info
 _CORRECT_DTYPE = np.dtype([("flags", np.uint32), ("fixes", np.uint32), ("weak_before", np.uint32), ("weak_after", np.uint32)])
 _TRIAL_DTYPE = np.dtype([("run_a", np.uint32), ("run_b", np.uint32), ("pos", np.uint32), ("window", np.uint32),
@@ -1532,7 +1544,8 @@ class EsaResult:
     default) as uint32, uint64, uint32; sa and da raise DEBWT_ESTATE unless they were kept.  summary(): n, max, max_row,
     sum, capped, pos_prev, pos (the two places of the longest repeat), cap.  profile(kmax): distinct[k - 1] = the number
     of distinct k-mers inside records, k = 1 .. kmax <= min(cap, 4096).  The arrays belong to the index: the next esa()
-    replaces them and release() frees them, after which every method raises DEBWT_ESTATE."""
+    replaces them and release() frees them, after which every method raises DEBWT_ESTATE.  repeats(): the maximal
+    repeats, the supermaximal repeats or all intervals of the LCP array (Definition 11), from the LCP array alone."""
 
     _ARRAYS = {"lcp": (0, np.uint32), "sa": (1, np.uint64), "da": (2, np.uint32)}
 
@@ -1568,6 +1581,27 @@ class EsaResult:
         out = np.zeros(max(int(kmax), 1), dtype=np.uint64)
         self._x._chk(self._x._L.debwt_fm_esa_profile(self._x._h, int(kmax), _p64(out)))
         return out[:int(kmax)]
+
+    def repeats(self, min_len=20, min_occ=2, max_occ=None, kind="maximal"):
+        """The repeats of the collection (debwt_fm_repeats): the intervals of the LCP array with len >= min_len and
+        min_occ <= count <= max_occ (None: no bound) of kind "maximal", "supermaximal" or "intervals" (every interval, left-
+        diverse or not), ascending by representative row.  A structured array (REPEAT_DTYPE): row_lo and count name the
+        rows [row_lo, row_lo + count) -- sa(row_lo, row_lo + count) are the occurrences when sa was kept --, left the
+        occurrences behind A, C, G, T and at a record's start, len the length, flags REPEAT_IS_MAXIMAL and
+        REPEAT_IS_SUPERMAXIMAL.  With a capped build the intervals of the capped value are left out and counted in
+        repeat_stats()["capped_intervals"]."""
+        if kind not in REPEAT_KINDS:
+            raise ValueError('kind must be "maximal", "supermaximal" or "intervals"')
+        x = self._x
+        opts = _lib.DebwtFmRepeatOpts(int(min_len), REPEAT_KINDS[kind], int(min_occ), int(max_occ or 0))
+        n = ctypes.c_uint64(0)
+        rc = x._L.debwt_fm_repeats(x._h, ctypes.byref(opts), None, 0, ctypes.byref(n))     # the sizing call: ERANGE names the count
+        if rc != -5:
+            x._chk(rc)
+        out = np.zeros(n.value, dtype=REPEAT_DTYPE)
+        if n.value:
+            x._chk(x._L.debwt_fm_repeats(x._h, ctypes.byref(opts), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        return out[:n.value]
 
     def release(self):
         self._x._chk(self._x._L.debwt_fm_esa_release(self._x._h))

@@ -36,6 +36,7 @@
 #include "fm_overlap_mm_kernels.h"
 #include "fm_extract_kernels.h"
 #include "fm_esa_kernels.h"
+#include "fm_repeat_kernels.h"
 #include "fm_kmer_kernels.h"
 #include "fm_spectrum_kernels.h"
 #include "fm_graph_kernels.h"
@@ -3003,6 +3004,7 @@ struct debwt_fm {
     debwt_fm_esa_summary esa_sum{};
     std::vector<u64> esa_distinct;    // the profile of the build, k = 1 .. 4096
     debwt_fm_esa_stats esa_stats{};
+    debwt_fm_repeat_stats rp_stats{};
     DevBuf g_coff, g_state, g_hbase, g_raw, g_flag, g_deg, g_oseg, g_edges, g_eoff, g_len, g_keep, g_out, g_ctr;   // string graph
     debwt_fm_graph_stats g_stats{};
     DevBuf b_state, b_self, b_row, b_cnt, b_whb, b_rawbase, b_tbase, b_pos, b_aoff, b_mm, b_cur, b_cat, b_ctr;   // graph over both strands
@@ -6786,6 +6788,131 @@ extern "C" int debwt_fm_esa_release(debwt_fm *f) {
 extern "C" int debwt_fm_esa_stats_get(const debwt_fm *f, debwt_fm_esa_stats *out) {
     if (!f || !out) return DEBWT_EINVAL;
     *out = f->esa_stats;
+    return DEBWT_OK;
+}
+
+// ---- maximal and supermaximal repeats (fm_repeat_kernels.h) ------------------------------------------------------------
+// One call is a run of launches on the index's stream: the levels of the hierarchy, the search, and for a call that takes
+// the list the rank over the masks of the reported rows and the write.  Everything is allocated into temporaries that are
+// released on every way out; the kept arrays are only read.
+
+static_assert(sizeof(debwt_fm_repeat) == 64, "a record of debwt_fm_repeats is 64 bytes");
+
+extern "C" int debwt_fm_repeats(debwt_fm *f, const debwt_fm_repeat_opts *opts, debwt_fm_repeat *out, uint64_t capacity,
+                                uint64_t *count) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!opts || !count) { f->err = "debwt_fm_repeats: opts and count must not be NULL"; return DEBWT_EINVAL; }
+    if (!opts->min_len || opts->min_occ < 2 || (opts->max_occ && opts->max_occ < opts->min_occ)) {
+        f->err = "debwt_fm_repeats: min_len must be at least 1, min_occ at least 2 and max_occ 0 or at least min_occ";
+        return DEBWT_EINVAL;
+    }
+    if (opts->kind > DEBWT_FM_REPEAT_INTERVALS) { f->err = "debwt_fm_repeats: unknown kind"; return DEBWT_EINVAL; }
+    if (capacity && !out) { f->err = "debwt_fm_repeats: out is NULL with capacity > 0"; return DEBWT_EINVAL; }
+    if (!f->has_esa || !f->esa_lcp.p) { f->err = "debwt_fm_repeats: no build holds the LCP array (debwt_fm_esa_build)"; return DEBWT_ESTATE; }
+    const u64 F = fm_env_u64("DEBWT_FM_REPEAT_FANOUT", 64);
+    if (F < 2 || F > 64 || (F & (F - 1))) { f->err = "debwt_fm_repeats: DEBWT_FM_REPEAT_FANOUT must be a power of two in 2..64"; return DEBWT_EINVAL; }
+    u32 sh = 0;
+    while ((1ull << sh) < F) sh++;
+    f->rp_stats = debwt_fm_repeat_stats{};
+    debwt_fm_repeat_stats &st = f->rp_stats;
+    const u64 n = f->n;
+    HIPCHK(f, hipSetDevice(f->device));
+
+    // the level table: n_t, and where level t begins in the node buffer
+    std::vector<u64> lev{n, 0};
+    u64 nodes = 0;
+    for (u64 m = n; m > 1;) { m = (m + F - 1) >> sh; lev.push_back(m); lev.push_back(nodes); nodes += m; }
+    const u32 levels = (u32)(lev.size() / 2 - 1);
+    if (levels > FM_REP_MAXLEV) { f->err = "debwt_fm_repeats: more levels than the kernels hold"; return DEBWT_EINTERNAL; }
+    const bool list = capacity != 0;
+    const u64 nw = (n + 63) >> 6, rkc = (nw + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;
+    const u32 blocks = (u32)std::min<u64>(grid_for(n, 256), 4096);
+    const size_t small_bytes = (size_t)(FM_REP_NCTR + 2 * (FM_REP_MAXLEV + 1)) * 8, best_bytes = (size_t)blocks * 16;
+    FmTmp node, small, best, lo, hi, masks, wpre, csum, dout;
+    HIPCHK(f, hipMalloc(&node.p, (size_t)std::max<u64>(nodes, 1) * 8));
+    HIPCHK(f, hipMalloc(&small.p, small_bytes));
+    HIPCHK(f, hipMalloc(&best.p, best_bytes));
+    st.rows = n; st.levels = levels; st.fanout = F; st.tree_bytes = nodes * 8;
+    st.scratch_bytes = st.tree_bytes + small_bytes + best_bytes;
+    if (list) {
+        HIPCHK(f, hipMalloc(&lo.p, (size_t)n * 8));
+        HIPCHK(f, hipMalloc(&hi.p, (size_t)n * 8));
+        HIPCHK(f, hipMalloc(&masks.p, (size_t)nw * 24));
+        HIPCHK(f, hipMalloc(&wpre.p, (size_t)nw * 4));
+        HIPCHK(f, hipMalloc(&csum.p, (size_t)(rkc + 1) * 8));
+        st.scratch_bytes += n * 16 + nw * 28 + (rkc + 1) * 8;
+    }
+    u64 *ctr = reinterpret_cast<u64 *>(small.p), *d_lev = ctr + FM_REP_NCTR, *d_best = reinterpret_cast<u64 *>(best.p);
+    uint2 *d_node = reinterpret_cast<uint2 *>(node.p);
+    const u32 *d_lcp = f->esa_lcp.as<u32>();
+    u64 *d_masks = reinterpret_cast<u64 *>(masks.p), *d_csum = reinterpret_cast<u64 *>(csum.p);
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    struct Ev { hipEvent_t *e; ~Ev() { for (int i = 0; i < 4; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int i = 0; i < 4; i++) HIPCHK(f, hipEventCreate(&ev[i]));
+    HIPCHK(f, hipMemsetAsync(ctr, 0, FM_REP_NCTR * 8, f->stream));
+    HIPCHK(f, hipMemcpyAsync(d_lev, lev.data(), lev.size() * 8, hipMemcpyHostToDevice, f->stream));
+    (void)hipEventRecord(ev[0], f->stream);
+    for (u32 t = 0; t < levels; t++) {
+        const u64 nin = lev[2 * t], nout = lev[2 * t + 2];
+        const u32 g = (u32)std::min<u64>(grid_for(nin, 256), 1u << 20);
+        if (t == 0) k_fm_rep_level<true><<<g, 256, 0, f->stream>>>(d_lcp, nullptr, nin, sh, d_node + lev[3], nout);
+        else k_fm_rep_level<false><<<g, 256, 0, f->stream>>>(nullptr, d_node + lev[2 * t + 1], nin, sh, d_node + lev[2 * t + 3], nout);
+    }
+    (void)hipEventRecord(ev[1], f->stream);
+    const u32 cap = f->esa_sum.cap < 0xFFFFFFFFull ? (u32)f->esa_sum.cap : 0u;
+    const FmRepTree T{d_lcp, d_node, d_lev, levels, sh};
+    const FmRepOpts O{opts->min_len, opts->kind, cap, opts->min_occ, opts->max_occ};
+    k_fm_rep_search<<<blocks, 256, 0, f->stream>>>(f->V, T, O, reinterpret_cast<u64 *>(lo.p), reinterpret_cast<u64 *>(hi.p),
+                                                   list ? d_masks : nullptr, list ? d_masks + nw : nullptr,
+                                                   list ? d_masks + 2 * nw : nullptr, ctr, d_best);
+    (void)hipEventRecord(ev[2], f->stream);
+    u64 hc[FM_REP_NCTR];
+    std::vector<u64> hb((size_t)blocks * 2);
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(hb.data(), d_best, best_bytes, hipMemcpyDeviceToHost, f->stream));
+    int rc;
+    if ((rc = fm_sync(f))) return rc;
+    (void)hipEventElapsedTime(&st.ms_tree, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&st.ms_search, ev[1], ev[2]);
+    st.searched = hc[FM_REP_C_SEARCHED]; st.representatives = hc[FM_REP_C_REPS]; st.capped_intervals = hc[FM_REP_C_CAPPED];
+    st.intervals = st.representatives - st.capped_intervals;
+    st.maximal = hc[FM_REP_C_MAXIMAL]; st.supermaximal = hc[FM_REP_C_SUPER]; st.reported = hc[FM_REP_C_REPORTED];
+    st.search_steps = hc[FM_REP_C_STEPS]; st.wave_steps = hc[FM_REP_C_WAVE]; st.rank_lines = hc[FM_REP_C_LINES];
+    for (u32 b = 0; b < blocks; b++)
+        if (hb[2 * b] > st.longest_len || (hb[2 * b] && hb[2 * b] == st.longest_len && hb[2 * b + 1] < st.longest_row_lo)) {
+            st.longest_len = hb[2 * b]; st.longest_row_lo = hb[2 * b + 1];
+        }
+    *count = st.reported;
+    if (capacity < st.reported) {
+        st.ms_wall = (float)fm_ms_since(t0);
+        f->err = "debwt_fm_repeats: capacity below the repeats (count = " + std::to_string(st.reported) + ")";
+        return DEBWT_ERANGE;
+    }
+    if (st.reported) {
+        HIPCHK(f, hipMalloc(&dout.p, (size_t)st.reported * sizeof(debwt_fm_repeat)));
+        st.scratch_bytes += st.reported * sizeof(debwt_fm_repeat);
+        k_fm_anc_count<<<(u32)rkc, FM_EX_CHUNK_WORDS, 0, f->stream>>>(d_masks, nw, reinterpret_cast<u32 *>(wpre.p), d_csum);
+        k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(d_csum, rkc, d_csum + rkc);
+        k_fm_rep_write<<<(u32)std::min<u64>(grid_for(n, 256), 1u << 20), 256, 0, f->stream>>>(
+            f->V, d_lcp, n, reinterpret_cast<const u64 *>(lo.p), reinterpret_cast<const u64 *>(hi.p), d_masks, d_masks + nw,
+            d_masks + 2 * nw, reinterpret_cast<const u32 *>(wpre.p), d_csum, reinterpret_cast<debwt_fm_repeat *>(dout.p), st.reported);
+        (void)hipEventRecord(ev[3], f->stream);
+        u64 total = 0;
+        HIPCHK(f, hipMemcpyAsync(&total, d_csum + rkc, 8, hipMemcpyDeviceToHost, f->stream));
+        HIPCHK(f, hipMemcpyAsync(out, dout.p, (size_t)st.reported * sizeof(debwt_fm_repeat), hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+        (void)hipEventElapsedTime(&st.ms_write, ev[2], ev[3]);
+        st.rank_lines += 8 * st.reported;
+        if (total != st.reported) { f->err = "debwt_fm_repeats: the masks and the count of the reported rows differ"; return DEBWT_EINTERNAL; }
+    }
+    st.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_repeat_stats_get(const debwt_fm *f, debwt_fm_repeat_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->rp_stats;
     return DEBWT_OK;
 }
 

@@ -1240,6 +1240,66 @@ typedef struct {
 } debwt_fm_esa_stats;
 int debwt_fm_esa_stats_get(const debwt_fm *fm, debwt_fm_esa_stats *out);
 
+/* ---- Definition 11 (repeats): maximal and supermaximal repeats from the kept LCP array (fm_repeat_kernels.h) -----------
+ * Rows, sa, lcp, d() and the symbol order are those of Definition 10.  L[r] is the BWT symbol of row r, the symbol in
+ * front of sa[r]: A, C, G, T, '#' or '$' ('$' on the row with sa[r] = 0).
+ *   Interval.  A triple (l, i, j) with l >= 1, i < j, lcp[i] < l, (j = n - 1 or lcp[j + 1] < l) and min(lcp[i+1 .. j]) = l.
+ *     Its string w = T[sa[i] .. +l) holds bases only (lcp is cut at separators) and occurs j - i + 1 times inside records,
+ *     at sa[i .. j].  Its representative row is the smallest r in (i, j] with lcp[r] = l: every interval has exactly one,
+ *     and a row represents at most one interval.
+ *   Left counts.  left[c], c = 0..3: the rows of [i, j] whose L is base c; left[4]: those whose L is '#' or '$' (the
+ *     occurrence starts a record).  The five sum to j - i + 1.
+ *   Maximal repeat.  An interval with max(left[0..3]) < j - i + 1: occurrences that start a record count as pairwise
+ *     different on the left.
+ *   Supermaximal repeat.  An interval with every lcp[i+1 .. j] == l and every left[0..3] <= 1.  It is maximal.
+ *   Capped build (max_lcp = c != 0).  The intervals with l < c are exactly those of the uncapped array (capping keeps
+ *     values below c, and keeps values above l above l).  The intervals of stored value c are not reported; the statistics
+ *     count them as capped_intervals, whatever min_len is.
+ * The list: the intervals with len >= min_len, min_occ <= count (<= max_occ when max_occ != 0) and of the kind asked for,
+ * ascending by representative row.  A record names the interval by row_lo = i and count = j - i + 1; len = l; flags tells
+ * whether it is maximal and supermaximal, for every kind.  The occurrences are debwt_fm_esa_fetch(SA, row_lo, count) when
+ * the build kept sa; the call itself needs the LCP array alone and changes none of the kept arrays.
+ *
+ * The method.  A min/max hierarchy over lcp with fanout F (environment DEBWT_FM_REPEAT_FANOUT, read per call, a power of
+ * two in 2..64, default 64; DEBWT_EINVAL otherwise; no result depends on it): level 0 is lcp, entry b of level t + 1 holds
+ * min and max of entries [b F, (b + 1) F) of level t, n_0 = n and n_{t+1} = ceil(n_t / F) up to one entry: `levels` levels
+ * of tree_bytes = 8 (n_1 + .. + n_levels) bytes, below 8 n / (F - 1) + 8 levels.  One lane per row r with l = lcp[r] >=
+ * min_len searches the nearest p < r with lcp[p] <= l (r is a representative iff lcp[p] < l, and then i = p), the nearest
+ * q > r with lcp[q] < l (j = q - 1, q = n without one) and the nearest q' > r with lcp[q'] > l; the values of (i, r) are
+ * above l, so the interval is flat iff r = i + 1 and q' >= q (the third search runs only for r = i + 1 with every left[0..3]
+ * <= 1, where it decides).  Every search ascends while a node cannot hold a hit and
+ * descends into the first that can: at most 2 F entries per level, never a number that grows with the distance.  The left
+ * counts are two rank lines per base.  Order comes from the device: a wave's reported rows are a ballot, the rank over those
+ * masks is a row's place in the list.  Scratch, all released before the call returns: the tree, 1 KiB of counters and 16
+ * bytes per workgroup (at most 4096); a call with capacity > 0 adds 16 n + 28 ceil(n / 64) + 8 (ceil(n / 16384) + 1) bytes
+ * and 64 bytes per record.  A failed allocation is DEBWT_ENOMEM and leaves the kept arrays as they were. */
+#define DEBWT_FM_REPEAT_MAXIMAL       0u   /* kind */
+#define DEBWT_FM_REPEAT_SUPERMAXIMAL  1u
+#define DEBWT_FM_REPEAT_INTERVALS     2u   /* every interval, left-diverse or not */
+#define DEBWT_FM_REPEAT_IS_MAXIMAL      1u /* flags of a record */
+#define DEBWT_FM_REPEAT_IS_SUPERMAXIMAL 2u
+typedef struct { uint32_t min_len, kind; uint64_t min_occ, max_occ; } debwt_fm_repeat_opts;  /* max_occ 0 = no bound */
+typedef struct { uint64_t row_lo, count, left[5]; uint32_t len, flags; } debwt_fm_repeat;      /* 64 bytes */
+/* count is written first; DEBWT_ERANGE when capacity < count (the protocol of debwt_fm_kmer_list; capacity 0 with a NULL
+ * out is the sizing call).  DEBWT_ESTATE without a build or after debwt_fm_esa_release.  DEBWT_EINVAL for a NULL opts or
+ * count, min_len = 0, min_occ < 2, max_occ != 0 && max_occ < min_occ, an unknown kind, a NULL out with capacity > 0 and a
+ * fanout that is no power of two in 2..64. */
+int debwt_fm_repeats(debwt_fm *fm, const debwt_fm_repeat_opts *opts, debwt_fm_repeat *out, uint64_t capacity, uint64_t *count);
+/* what the last debwt_fm_repeats did: rows (n), rows searched (stored value >= min_len, capped rows included),
+ * representatives among them, intervals (representatives below the cap: len >= min_len, any count and kind), the maximal
+ * and the supermaximal of those, capped_intervals (representatives whose stored value is the cap), reported, the longest
+ * reported length and its row_lo (the lowest on ties; 0, 0 without a record), levels and the fanout in force, tree_bytes,
+ * scratch_bytes (everything the call allocated, the tree included), search_steps (hierarchy nodes and level-0 entries read by
+ * the three searches), wave_steps (64 x the reads of the longest lane of every wave: search_steps / wave_steps is the share
+ * of lanes busy), rank_lines (rank lines read for left counts, the write pass included), ms per phase (events: tree, search,
+ * write with its rank) and host wall time */
+typedef struct {
+    uint64_t rows, searched, representatives, intervals, maximal, supermaximal, capped_intervals, reported, longest_len,
+        longest_row_lo, levels, fanout, tree_bytes, scratch_bytes, search_steps, wave_steps, rank_lines;
+    float ms_tree, ms_search, ms_write, ms_wall;
+} debwt_fm_repeat_stats;
+int debwt_fm_repeat_stats_get(const debwt_fm *fm, debwt_fm_repeat_stats *out);
+
 /* ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
  * Records S_0 .. S_{nrec-1} are those of the index, numbered as in overlap hits; |S| is the length of S.
  * 1. state[i] = 1 (duplicate) iff some j < i has S_j == S_i; otherwise 2 (contained) iff S_i is a substring of a strictly
