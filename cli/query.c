@@ -3,7 +3,7 @@
  * libdebwt_hip.so (debwt_fm_*).
  *
  *   deBWT-query index  -i OUT [-t T] [--iupac SEED] [--device D] [--sa S] INPUT.fa[.gz]
- *   deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
+ *   deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] [--records] PATTERNS.fa|.fq
  *   deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq
  *   deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq
  *   deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self]
@@ -121,7 +121,17 @@
  * (a,c,g,t,s), and the first occurrence in row order as record:offset, TAB-separated.  --seq appends the string (read
  * through debwt_fm_extract), --occurrences every occurrence as record:offset, comma-separated, in row order.  It needs OUT,
  * OUT.#, OUT.$ and OUT.sa only (the text is restored on the GPU), takes no file argument and holds the suffix array (8 n
- * bytes) on the host while it writes.
+ * bytes) on the host while it writes.  --min-records Q, --max-records Q and --unique filter by the distinct records an
+ * interval occurs in (debwt_fm_repeats_records, Definition 12; --unique: no record holds the string twice): any of them
+ * keeps the record array too, builds the record prefix and adds the column rec behind occ.
+ *
+ * mums lists the multi-MUMs of the collection: the maximal repeats of at least L bases (--min-len, default 20) that occur
+ * exactly once in each of at least Q records (--min-records, default every record) and nowhere else.  stdout: one line
+ * "# mums=N min_records=Q longest=LEN", then per multi-MUM len and its occurrences as record:offset, comma-separated,
+ * ascending by record; --seq appends the string.  Files and memory as for repeats.
+ *
+ * count --records adds a column behind the count: the distinct records the pattern occurs in (debwt_fm_record_counts over
+ * an uncapped build with the record array; exact patterns on one strand only).
  *
  * graph writes the string graph of the indexed records as GFA 1 (debwt_fm_string_graph): a record that equals an earlier one
  * is a duplicate, one that lies inside a longer record is contained, the others are kept.  One "S J * LN:i:len" line per
@@ -161,7 +171,7 @@
 static void usage(void) {
     fprintf(stderr,
             "usage: deBWT-query index  -i OUT [-t T] [--iupac SEED] [--device D] [--sa S] INPUT.fa[.gz]\n"
-            "       deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
+            "       deBWT-query count  -i OUT [--device D] [--mismatches K] [--both-strands] [--best] [--records] PATTERNS.fa|.fq\n"
             "       deBWT-query locate -i OUT [--device D] [--max-hits M] [--mismatches K] [--both-strands] [--best] PATTERNS.fa|.fq\n"
             "       deBWT-query mems   -i OUT [--device D] [--min-len L] [--both-strands] [--max-hits M] READS.fa|.fq\n"
             "       deBWT-query overlaps -i OUT [--device D] [--min-overlap L] [--both-strands] [--longest] [--no-self]\n"
@@ -178,7 +188,8 @@ static void usage(void) {
             "       deBWT-query spectrum -i OUT -k K [--device D] [--forward] [--bins N] [--list FILE [--at-least A] [--at-most B]]\n"
             "       deBWT-query lcp    -i OUT [--device D] [--max-lcp C] [--lcp FILE] [--sa FILE] [--da FILE] [--profile K]\n"
             "       deBWT-query repeats -i OUT [--device D] [--min-len L] [--min-occ A] [--max-occ B] [--supermaximal | --intervals]\n"
-            "                          [--max-lcp C] [--seq] [--occurrences]\n"
+            "                          [--max-lcp C] [--seq] [--occurrences] [--min-records Q] [--max-records Q] [--unique]\n"
+            "       deBWT-query mums   -i OUT [--device D] [--min-len L] [--min-records Q] [--seq]\n"
             "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]\n"
             "                          [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]\n"
             "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]\n"
@@ -225,7 +236,13 @@ static void usage(void) {
             "LCP array: # intervals=I<TAB>maximal=M<TAB>supermaximal=S<TAB>reported=R<TAB>longest=LEN, then per repeat\n"
             "len<TAB>occ<TAB>S|M|-<TAB>a,c,g,t,s (occurrences behind A, C, G, T, at a record's start)<TAB>record:offset of the\n"
             "first occurrence; --supermaximal lists the supermaximal repeats, --intervals every interval; --seq appends the\n"
-            "string, --occurrences every occurrence; --max-lcp C caps the LCP values (L below C);\n"
+            "string, --occurrences every occurrence; --max-lcp C caps the LCP values (L below C); --min-records Q,\n"
+            "--max-records Q and --unique (no record holds the string twice) filter by the distinct records of a repeat and add\n"
+            "the column rec behind occ;\n"
+            "mums lists the multi-MUMs, the maximal repeats of at least L bases (default 20) that occur once in each of at least\n"
+            "Q records (default all) and nowhere else: # mums=N<TAB>min_records=Q<TAB>longest=LEN, then per multi-MUM\n"
+            "len<TAB>record:offset,... ascending by record; --seq appends the string;\n"
+            "count --records adds the distinct records a pattern occurs in behind its count;\n"
             "graph writes GFA 1: S lines for the records that are neither duplicates nor contained, L lines a + b + <L>M for the\n"
             "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
             "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained;\n"
@@ -483,19 +500,24 @@ static int cmp_u64(const void *a, const void *b) {
     return x < y ? -1 : x > y;
 }
 
-static int cmd_query(const char *out, const char *pfile, int device, int locate, uint64_t max_hits) {
+static int cmd_query(const char *out, const char *pfile, int device, int locate, uint64_t max_hits, int records) {
     struct patterns P;
     if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
     if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1;
     uint64_t *ranges = malloc((P.n ? P.n : 1) * 16), *oo = malloc((P.n + 1) * 8), *pos = NULL, *starts = NULL;
+    uint64_t *nrecs = records ? malloc((P.n ? P.n : 1) * 8) : NULL;
     debwt_fm_info info;
     debwt_fm_info_get(fm, &info);
     starts = malloc(info.nrec * 8);
-    if (!ranges || !oo || !starts) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (!ranges || !oo || !starts || (records && !nrecs)) { fprintf(stderr, "out of memory\n"); goto done; }
     int rc = debwt_fm_count(fm, P.seq, P.off, P.n, ranges);
     if (!rc) rc = debwt_fm_record_starts(fm, starts, info.nrec);
+    /* the range of a pattern is closed (Definition 12) on the uncapped array, whatever its length */
+    if (!rc && records) rc = debwt_fm_esa_build(fm, 0, DEBWT_FM_ESA_DA);
+    if (!rc && records) rc = debwt_fm_records_build(fm);
+    if (!rc && records) rc = debwt_fm_record_counts(fm, ranges, P.n, nrecs);
     if (!rc && locate) {
         uint64_t total = 0;
         for (uint64_t i = 0; i < P.n; i++) {
@@ -509,6 +531,7 @@ static int cmd_query(const char *out, const char *pfile, int device, int locate,
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     for (uint64_t i = 0; i < P.n; i++) {
         printf("%s\t%llu", P.name[i], (unsigned long long)(ranges[2 * i + 1] - ranges[2 * i]));
+        if (records) printf("\t%llu", (unsigned long long)nrecs[i]);
         if (locate) {
             uint64_t *a = pos + oo[i], m = oo[i + 1] - oo[i], rec = 0;
             qsort(a, m, 8, cmp_u64);
@@ -522,7 +545,7 @@ static int cmd_query(const char *out, const char *pfile, int device, int locate,
     }
     ret = fflush(stdout) ? 1 : 0;
 done:
-    free(ranges); free(oo); free(pos); free(starts);
+    free(ranges); free(oo); free(pos); free(starts); free(nrecs);
     debwt_fm_destroy(fm);
     free_patterns(&P);
     return ret;
@@ -1444,7 +1467,10 @@ done:
 
 /* ---- repeats ----------------------------------------------------------------------------------------------------------- */
 
-struct repeat_args { uint32_t min_len, kind, max_lcp; uint64_t min_occ, max_occ; int seq, occurrences; };
+/* by_record: --min-records, --max-records or --unique was given (a column `rec` then follows `occ`); mums: the subcommand
+ * mums, min_records 0 standing for every record of the index */
+struct repeat_args { uint32_t min_len, kind, max_lcp; uint64_t min_occ, max_occ; int seq, occurrences;
+                     uint64_t min_records, max_records; int unique, by_record, mums; };
 
 static int cmd_repeats(const char *out, int device, const struct repeat_args *A) {
     debwt_fm *fm = NULL;
@@ -1458,25 +1484,48 @@ static int cmd_repeats(const char *out, int device, const struct repeat_args *A)
     char *bases = NULL;
     uint64_t bcap = 0;
     debwt_fm_repeat_opts o = {A->min_len, A->kind, A->min_occ, A->max_occ};
+    debwt_fm_record_filter flt = {A->min_records ? A->min_records : 1, A->max_records, A->unique ? DEBWT_FM_RECORDS_UNIQUE : 0u, 0};
+    const int by_record = A->by_record || A->mums;
+    uint32_t *nrecs = NULL;
+    struct occ *oc = NULL;
     debwt_fm_repeat_stats st;
+    if (A->mums) {                                              /* maximal, once in each of at least q records, nowhere else */
+        flt.min_records = A->min_records ? A->min_records : fi.nrec;
+        flt.flags = DEBWT_FM_RECORDS_UNIQUE;
+        o.kind = DEBWT_FM_REPEAT_MAXIMAL; o.min_occ = flt.min_records > 2 ? flt.min_records : 2; o.max_occ = 0;
+    }
     if (!starts || !sa) { fprintf(stderr, "out of memory\n"); goto done; }
-    if (debwt_fm_record_starts(fm, starts, fi.nrec) || debwt_fm_esa_build(fm, A->max_lcp, DEBWT_FM_ESA_SA)) {
+    if (debwt_fm_record_starts(fm, starts, fi.nrec) ||
+        debwt_fm_esa_build(fm, A->max_lcp, DEBWT_FM_ESA_SA | (by_record ? DEBWT_FM_ESA_DA : 0u)) ||
+        (by_record && debwt_fm_records_build(fm))) {
         fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
         goto done;
     }
-    rc = debwt_fm_repeats(fm, &o, NULL, 0, &count);
+    rc = by_record ? debwt_fm_repeats_records(fm, &o, &flt, NULL, NULL, 0, &count) : debwt_fm_repeats(fm, &o, NULL, 0, &count);
     if (rc && rc != DEBWT_ERANGE) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     rp = malloc((count ? count : 1) * sizeof *rp);
-    if (!rp) { fprintf(stderr, "out of memory\n"); goto done; }
-    if (count && debwt_fm_repeats(fm, &o, rp, count, &count)) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    if (by_record) nrecs = malloc((count ? count : 1) * sizeof *nrecs);
+    if (!rp || (by_record && !nrecs)) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (count && (by_record ? debwt_fm_repeats_records(fm, &o, &flt, rp, nrecs, count, &count) : debwt_fm_repeats(fm, &o, rp, count, &count))) {
+        fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
+        goto done;
+    }
     debwt_fm_repeat_stats_get(fm, &st);
     for (uint64_t lo = 0; lo < fi.n; lo += 1ull << 22) {
         const uint64_t cnt = fi.n - lo < (1ull << 22) ? fi.n - lo : (1ull << 22);
         if (debwt_fm_esa_fetch(fm, DEBWT_FM_ESA_SA_ARRAY, lo, cnt, sa + lo)) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     }
-    printf("# intervals=%llu\tmaximal=%llu\tsupermaximal=%llu\treported=%llu\tlongest=%llu\n", (unsigned long long)st.intervals,
-           (unsigned long long)st.maximal, (unsigned long long)st.supermaximal, (unsigned long long)st.reported,
-           (unsigned long long)st.longest_len);
+    if (A->mums)
+        printf("# mums=%llu\tmin_records=%llu\tlongest=%llu\n", (unsigned long long)st.reported, (unsigned long long)flt.min_records,
+               (unsigned long long)st.longest_len);
+    else
+        printf("# intervals=%llu\tmaximal=%llu\tsupermaximal=%llu\treported=%llu\tlongest=%llu\n", (unsigned long long)st.intervals,
+               (unsigned long long)st.maximal, (unsigned long long)st.supermaximal, (unsigned long long)st.reported,
+               (unsigned long long)st.longest_len);
+    if (A->mums) {
+        oc = malloc((fi.nrec ? fi.nrec : 1) * sizeof *oc);      /* unique: a multi-MUM has at most one occurrence per record */
+        if (!oc) { fprintf(stderr, "out of memory\n"); goto done; }
+    }
     if (A->seq) {
         off = malloc((EXTRACT_BATCH_JOBS + 1) * 8);
         jb = malloc(EXTRACT_BATCH_JOBS * sizeof *jb);
@@ -1505,7 +1554,23 @@ static int cmd_repeats(const char *out, int device, const struct repeat_args *A)
         for (uint64_t j = j0; j < j1; j++) {
             const debwt_fm_repeat *x = &rp[j];
             const uint64_t p = sa[x->row_lo], r = record_of(starts, fi.nrec, p);
-            printf("%u\t%llu\t%c\t%llu,%llu,%llu,%llu,%llu\t%llu:%llu", x->len, (unsigned long long)x->count,
+            if (A->mums) {                                      /* len, then the occurrence in every record, ascending by record */
+                if (x->count > fi.nrec) { fprintf(stderr, "mums: more occurrences than records\n"); goto done; }
+                for (uint64_t t = 0; t < x->count; t++) {
+                    const uint64_t q = sa[x->row_lo + t], rq = record_of(starts, fi.nrec, q);
+                    oc[t].rec = rq; oc[t].off = q - starts[rq]; oc[t].strand = 0; oc[t].mm = 0;
+                }
+                qsort(oc, x->count, sizeof *oc, cmp_occ);
+                printf("%u", x->len);
+                for (uint64_t t = 0; t < x->count; t++)
+                    printf("%c%llu:%llu", t ? ',' : '\t', (unsigned long long)oc[t].rec, (unsigned long long)oc[t].off);
+                if (A->seq) { putchar('\t'); fwrite(bases + off[j - j0], 1, off[j - j0 + 1] - off[j - j0], stdout); }
+                putchar('\n');
+                continue;
+            }
+            printf("%u\t%llu\t", x->len, (unsigned long long)x->count);
+            if (by_record) printf("%u\t", nrecs[j]);
+            printf("%c\t%llu,%llu,%llu,%llu,%llu\t%llu:%llu",
                    x->flags & DEBWT_FM_REPEAT_IS_SUPERMAXIMAL ? 'S' : x->flags & DEBWT_FM_REPEAT_IS_MAXIMAL ? 'M' : '-',
                    (unsigned long long)x->left[0], (unsigned long long)x->left[1], (unsigned long long)x->left[2],
                    (unsigned long long)x->left[3], (unsigned long long)x->left[4], (unsigned long long)r,
@@ -1529,7 +1594,7 @@ static int cmd_repeats(const char *out, int device, const struct repeat_args *A)
             st.searched ? (double)st.search_steps / (double)st.searched : 0.0, st.ms_tree, st.ms_search, st.ms_write);
     ret = fflush(stdout) ? 1 : 0;
 done:
-    free(starts); free(sa); free(rp); free(off); free(jb); free(bases);
+    free(starts); free(sa); free(rp); free(off); free(jb); free(bases); free(nrecs); free(oc);
     debwt_fm_destroy(fm);
     return ret;
 }
@@ -1691,7 +1756,7 @@ int main(int argc, char **argv) {
                !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
                !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : !strcmp(cmd, "graph") ? 9 :
                !strcmp(cmd, "unitigs") ? 10 : !strcmp(cmd, "pileup") ? 11 : !strcmp(cmd, "consensus") ? 12 :
-               !strcmp(cmd, "spectrum") ? 13 : !strcmp(cmd, "lcp") ? 14 : !strcmp(cmd, "repeats") ? 15 : -1;
+               !strcmp(cmd, "spectrum") ? 13 : !strcmp(cmd, "lcp") ? 14 : !strcmp(cmd, "repeats") ? 15 : !strcmp(cmd, "mums") ? 16 : -1;
     const int mapping = mode == 4 || mode == 11 || mode == 12;   /* the commands that map reads first */
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
@@ -1713,8 +1778,8 @@ int main(int argc, char **argv) {
     int k_given = 0, all_edges = 0, graph_both = 0, clean = 0, auto_count = 0, filter_given = 0;
     const char *list = NULL, *lcp_file = NULL, *esa_sa_file = NULL, *da_file = NULL;
     uint64_t max_lcp = 0, profile_k = 0;
-    struct repeat_args ra = {20, DEBWT_FM_REPEAT_MAXIMAL, 0, 2, 0, 0, 0};
-    int kind_given = 0;
+    struct repeat_args ra = {20, DEBWT_FM_REPEAT_MAXIMAL, 0, 2, 0, 0, 0, 0, 0, 0, 0, 0};
+    int kind_given = 0, count_records = 0;
     uint64_t bins = 256, at_least = 1, at_most = 0xFFFFFFFFull;
     debwt_fm_clean_opts cl;
     debwt_fm_clean_defaults(&cl);
@@ -1743,7 +1808,9 @@ int main(int argc, char **argv) {
             ra.kind = a[2] == 's' ? DEBWT_FM_REPEAT_SUPERMAXIMAL : DEBWT_FM_REPEAT_INTERVALS; kind_given = 1;
             continue;
         }
-        if (mode == 15 && !strcmp(a, "--seq")) { ra.seq = 1; continue; }
+        if ((mode == 15 || mode == 16) && !strcmp(a, "--seq")) { ra.seq = 1; continue; }
+        if (mode == 15 && !strcmp(a, "--unique")) { ra.unique = 1; ra.by_record = 1; continue; }
+        if (mode == 1 && !strcmp(a, "--records")) { count_records = 1; continue; }
         if (mode == 15 && !strcmp(a, "--occurrences")) { ra.occurrences = 1; continue; }
         if (mapping && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mapping && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
@@ -1843,7 +1910,15 @@ int main(int argc, char **argv) {
             if (parse_u64(v, &at_most) || at_most < 1 || at_most > 0xFFFFFFFFull) { fprintf(stderr, "--at-most: a multiplicity of at least 1\n"); return 1; }
             filter_given = 1;
         }
-        else if (mode == 15 && !strcmp(a, "--min-len")) {
+        else if ((mode == 15 || mode == 16) && !strcmp(a, "--min-records")) {
+            if (parse_u64(v, &ra.min_records) || ra.min_records < 1) { fprintf(stderr, "--min-records: a number of records of at least 1\n"); return 1; }
+            ra.by_record = 1;
+        }
+        else if (mode == 15 && !strcmp(a, "--max-records")) {
+            if (parse_u64(v, &ra.max_records) || ra.max_records < 1) { fprintf(stderr, "--max-records: a number of records of at least 1\n"); return 1; }
+            ra.by_record = 1;
+        }
+        else if ((mode == 15 || mode == 16) && !strcmp(a, "--min-len")) {
             if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
             ra.min_len = (uint32_t)v64;
         }
@@ -1910,9 +1985,11 @@ int main(int argc, char **argv) {
         if (max_lcp && profile_k > max_lcp) { fprintf(stderr, "--profile: above --max-lcp\n"); return 1; }
         return cmd_lcp(out, (int)device, (uint32_t)max_lcp, lcp_file, esa_sa_file, da_file, (uint32_t)profile_k);
     }
-    if (mode == 15) {
+    if (mode == 15 || mode == 16) {
         if (!out || file) { usage(); return 1; }
+        ra.mums = mode == 16;
         if (ra.max_occ && ra.max_occ < ra.min_occ) { fprintf(stderr, "--max-occ: below --min-occ\n"); return 1; }
+        if (ra.max_records && ra.max_records < ra.min_records) { fprintf(stderr, "--max-records: below --min-records\n"); return 1; }
         if (max_lcp && ra.min_len >= max_lcp) { fprintf(stderr, "--min-len: not below --max-lcp (repeats of the capped length are not listed)\n"); return 1; }
         ra.max_lcp = (uint32_t)max_lcp;
         return cmd_repeats(out, (int)device, &ra);
@@ -1950,6 +2027,7 @@ int main(int argc, char **argv) {
                             (uint32_t)ovl_permille);
     }
     if (mode == 3) return cmd_mems(out, file, (int)device, max_hits, (uint32_t)min_len, flags);
+    if (search && count_records) { fprintf(stderr, "--records: only with exact patterns on one strand\n"); return 1; }
     if (search) return cmd_search(out, file, (int)device, mode == 2, max_hits, (uint32_t)K, flags);
-    return cmd_query(out, file, (int)device, mode == 2, max_hits);
+    return cmd_query(out, file, (int)device, mode == 2, max_hits, count_records);
 }

@@ -174,6 +174,20 @@ class DebwtFmRepeatStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmRecordFilter(ctypes.Structure):
+    _fields_ = [("min_records", ctypes.c_uint64), ("max_records", ctypes.c_uint64), ("flags", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+class DebwtFmRecordsStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("rows", "pairs", "records_present", "sort_passes", "levels", "fanout",
+                                                 "rmq_steps", "wave_steps", "build_bytes", "kept_bytes")] +
+                [(n, ctypes.c_float) for n in ("ms_sort", "ms_tree", "ms_pairs", "ms_scan", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 CORRECT_MAX_ROUNDS = 16
 
 
@@ -424,6 +438,8 @@ SYMBOLS = [
     "debwt_fm_spectrum", "debwt_fm_kmer_list", "debwt_fm_spectrum_threshold", "debwt_fm_spectrum_stats_get",
     "debwt_fm_esa_build", "debwt_fm_esa_fetch", "debwt_fm_esa_summary_get", "debwt_fm_esa_profile", "debwt_fm_esa_release",
     "debwt_fm_esa_stats_get", "debwt_fm_repeats", "debwt_fm_repeat_stats_get",
+    "debwt_fm_records_build", "debwt_fm_records_fetch", "debwt_fm_record_counts", "debwt_fm_repeats_records",
+    "debwt_fm_records_stats_get",
     "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
     "debwt_fm_string_graph_both", "debwt_fm_unitigs_both", "debwt_fm_graph_both_stats_get",
     "debwt_fm_clean_defaults", "debwt_fm_graph_clean", "debwt_fm_edges_compact", "debwt_fm_clean_stats_get",
@@ -752,6 +768,17 @@ def lib():
     L.debwt_fm_repeats.argtypes = [vp, ctypes.POINTER(DebwtFmRepeatOpts), ctypes.c_void_p, ctypes.c_uint64, u64p]
     L.debwt_fm_repeat_stats_get.restype = ctypes.c_int
     L.debwt_fm_repeat_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmRepeatStats)]
+    L.debwt_fm_records_build.restype = ctypes.c_int
+    L.debwt_fm_records_build.argtypes = [vp]
+    L.debwt_fm_records_fetch.restype = ctypes.c_int
+    L.debwt_fm_records_fetch.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint64, u64p]
+    L.debwt_fm_record_counts.restype = ctypes.c_int
+    L.debwt_fm_record_counts.argtypes = [vp, u64p, ctypes.c_uint64, u64p]
+    L.debwt_fm_repeats_records.restype = ctypes.c_int
+    L.debwt_fm_repeats_records.argtypes = [vp, ctypes.POINTER(DebwtFmRepeatOpts), ctypes.POINTER(DebwtFmRecordFilter),
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, u64p]
+    L.debwt_fm_records_stats_get.restype = ctypes.c_int
+    L.debwt_fm_records_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmRecordsStats)]
     u8p, edgep = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(DebwtFmEdge)
     L.debwt_fm_string_graph.restype = ctypes.c_int
     L.debwt_fm_string_graph.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u64p, edgep, ctypes.c_uint64]

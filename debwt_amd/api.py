@@ -565,6 +565,14 @@ class FMIndex:
         self._chk(self._L.debwt_fm_repeat_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def records_stats(self):
+        """What the last EsaResult.records_build did (debwt_fm_records_stats_get): rows, pairs (rows whose record occurs in
+        an earlier row), records_present, sort_passes, levels and fanout of the hierarchy (DEBWT_FM_REPEAT_FANOUT),
+        rmq_steps and wave_steps of the range minima, bytes allocated by the build and kept, ms per phase and wall ms."""
+        st = _lib.DebwtFmRecordsStats()
+        self._chk(self._L.debwt_fm_records_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def correct(self, patterns, k, min_count=3, rounds=4, strands="both"):
         """k-mer read correction on the device (debwt_fm_correct): per read and round, a run of weak k-mers (count below
         min_count) that has the signature of one substitution is fixed when exactly one other base makes the k-mer next
@@ -1064,6 +1072,7 @@ OVERLAP_LONGEST = 2                                    # option flag of debwt_fm
 OVERLAP_CONTAINS, OVERLAP_WHOLE = 1, 2                 # OverlapResult hit flags
 ESA_SA, ESA_DA = 1, 2                                  # flags of debwt_fm_esa_build
 REPEAT_KINDS = {"maximal": 0, "supermaximal": 1, "intervals": 2}                 # kind of debwt_fm_repeats
+RECORDS_UNIQUE = 1                                                                # flags of debwt_fm_record_filter
 REPEAT_IS_MAXIMAL, REPEAT_IS_SUPERMAXIMAL = 1, 2       # flags of a repeat
 REPEAT_DTYPE = np.dtype([("row_lo", "<u8"), ("count", "<u8"), ("left", "<u8", (5,)), ("len", "<u4"), ("flags", "<u4")])
 CORRECT_SHORT, CORRECT_CLEAN, CORRECT_FIXED, CORRECT_WEAK = 1, 2, 4, 8   # flags of FMIndex.correct's info
@@ -1545,7 +1554,9 @@ class EsaResult:
     sum, capped, pos_prev, pos (the two places of the longest repeat), cap.  profile(kmax): distinct[k - 1] = the number
     of distinct k-mers inside records, k = 1 .. kmax <= min(cap, 4096).  The arrays belong to the index: the next esa()
     replaces them and release() frees them, after which every method raises DEBWT_ESTATE.  repeats(): the maximal
-    repeats, the supermaximal repeats or all intervals of the LCP array (Definition 11), from the LCP array alone."""
+    repeats, the supermaximal repeats or all intervals of the LCP array (Definition 11), from the LCP array alone.
+    records_build() (needs da) adds the prefix array of Definition 12; record_counts(), repeats_by_record() and mums()
+    then answer in how many distinct records a row range or a repeat occurs."""
 
     _ARRAYS = {"lcp": (0, np.uint32), "sa": (1, np.uint64), "da": (2, np.uint32)}
 
@@ -1602,6 +1613,62 @@ class EsaResult:
         if n.value:
             x._chk(x._L.debwt_fm_repeats(x._h, ctypes.byref(opts), out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
         return out[:n.value]
+
+    def records_build(self):
+        """The prefix array of Definition 12 on the device (debwt_fm_records_build): after it record_counts,
+        repeats_by_record and mums answer in how many distinct records an interval occurs.  Needs esa(da=True); kept with
+        the arrays, counted in info()["device_bytes"], released with them."""
+        self._x._chk(self._x._L.debwt_fm_records_build(self._x._h))
+        return self
+
+    def dup_prefix(self, lo=0, hi=None):
+        """P[lo .. hi) of Definition 12 as uint64 (all rows by default)."""
+        x = self._x
+        lo = int(lo)
+        hi = x.info()["n"] if hi is None else int(hi)
+        if hi < lo:
+            raise ValueError("hi must not be below lo")
+        out = np.zeros(hi - lo, dtype=np.uint64)
+        x._chk(x._L.debwt_fm_records_fetch(x._h, lo, hi - lo, _p64(out)))
+        return out
+
+    def record_counts(self, ranges):
+        """The distinct records of each row range [lo, hi) (debwt_fm_record_counts), uint64: ranges is (k, 2), as
+        FMIndex.ranges answers.  Exact for closed ranges (every LCP interval, every pattern no longer than the cap of the
+        build); for other ranges the value of the formula of Definition 12, which is no record count."""
+        r = np.ascontiguousarray(np.asarray(ranges, dtype=np.uint64).reshape(-1, 2))
+        out = np.zeros(len(r), dtype=np.uint64)
+        if len(r):
+            self._x._chk(self._x._L.debwt_fm_record_counts(self._x._h, _p64(r), len(r), _p64(out)))
+        return out
+
+    def repeats_by_record(self, min_len=20, min_occ=2, max_occ=None, kind="maximal", min_records=1, max_records=None,
+                          unique=False):
+        """repeats() filtered by the distinct records of every interval (debwt_fm_repeats_records): min_records <= records
+        <= max_records (None: no bound), and count == records with unique (no record holds the string twice).  Returns
+        (the REPEAT_DTYPE array, the records of each entry as uint32).  Needs records_build()."""
+        if kind not in REPEAT_KINDS:
+            raise ValueError('kind must be "maximal", "supermaximal" or "intervals"')
+        x = self._x
+        opts = _lib.DebwtFmRepeatOpts(int(min_len), REPEAT_KINDS[kind], int(min_occ), int(max_occ or 0))
+        flt = _lib.DebwtFmRecordFilter(int(min_records), int(max_records or 0), RECORDS_UNIQUE if unique else 0, 0)
+        n = ctypes.c_uint64(0)
+        rc = x._L.debwt_fm_repeats_records(x._h, ctypes.byref(opts), ctypes.byref(flt), None, None, 0, ctypes.byref(n))
+        if rc != -5:                                           # the sizing call: ERANGE names the count
+            x._chk(rc)
+        out = np.zeros(n.value, dtype=REPEAT_DTYPE)
+        recs = np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            x._chk(x._L.debwt_fm_repeats_records(x._h, ctypes.byref(opts), ctypes.byref(flt), out.ctypes.data_as(ctypes.c_void_p),
+                                                 recs.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)))
+        return out[:n.value], recs[:n.value]
+
+    def mums(self, min_len=20, min_records=None):
+        """The multi-MUMs of the collection (Definition 12): maximal repeats of len >= min_len that occur once in each of
+        at least min_records records and nowhere else; min_records defaults to all records of the index.  Returns what
+        repeats_by_record returns."""
+        q = self._x.info()["nrec"] if min_records is None else int(min_records)
+        return self.repeats_by_record(min_len=min_len, min_occ=max(q, 2), kind="maximal", min_records=q, unique=True)
 
     def release(self):
         self._x._chk(self._x._L.debwt_fm_esa_release(self._x._h))

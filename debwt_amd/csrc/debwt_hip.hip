@@ -37,6 +37,7 @@
 #include "fm_extract_kernels.h"
 #include "fm_esa_kernels.h"
 #include "fm_repeat_kernels.h"
+#include "fm_record_kernels.h"
 #include "fm_kmer_kernels.h"
 #include "fm_spectrum_kernels.h"
 #include "fm_graph_kernels.h"
@@ -3005,6 +3006,8 @@ struct debwt_fm {
     std::vector<u64> esa_distinct;    // the profile of the build, k = 1 .. 4096
     debwt_fm_esa_stats esa_stats{};
     debwt_fm_repeat_stats rp_stats{};
+    DevBuf rec_P;                     // the kept prefix of debwt_fm_records_build, 8 n bytes exactly (counted in device_bytes)
+    debwt_fm_records_stats rc_stats{};
     DevBuf g_coff, g_state, g_hbase, g_raw, g_flag, g_deg, g_oseg, g_edges, g_eoff, g_len, g_keep, g_out, g_ctr;   // string graph
     debwt_fm_graph_stats g_stats{};
     DevBuf b_state, b_self, b_row, b_cnt, b_whb, b_rawbase, b_tbase, b_pos, b_aoff, b_mm, b_cur, b_cat, b_ctr;   // graph over both strands
@@ -3296,7 +3299,7 @@ extern "C" int debwt_fm_info_get(const debwt_fm *f, debwt_fm_info *out) {
     out->device_bytes = f->idx.cap + f->rowlists.cap + f->sa.cap + (f->has_text ? f->text.cap : 0) +
                         (f->has_otable ? f->o_table.cap : 0) + (f->has_anchors ? f->anchors.cap : 0) +
                         (f->has_ktable ? f->k_table.cap : 0) + (f->has_ptable ? f->p_table.cap : 0) +
-                        (f->has_esa ? f->esa_lcp.cap + f->esa_sa.cap + f->esa_da.cap : 0);
+                        (f->has_esa ? f->esa_lcp.cap + f->esa_sa.cap + f->esa_da.cap + f->rec_P.cap : 0);
     out->ms_rank = f->ms_rank; out->ms_samples = f->ms_samples;
     for (int q = 0; q < 4; q++) out->census[q] = f->census[q];
     return DEBWT_OK;
@@ -6621,10 +6624,10 @@ namespace {
 constexpr u64 FM_ESA_CHUNK = 256;                      // text positions per lane of the PLCP kernel
 
 void fm_esa_drop(debwt_fm *f) {
-    if (!f->has_esa && !f->esa_lcp.p && !f->esa_sa.p && !f->esa_da.p) return;
+    if (!f->has_esa && !f->esa_lcp.p && !f->esa_sa.p && !f->esa_da.p && !f->rec_P.p) return;
     (void)hipSetDevice(f->device);
     if (f->stream) (void)hipStreamSynchronize(f->stream);
-    for (DevBuf *b : {&f->esa_lcp, &f->esa_sa, &f->esa_da}) {
+    for (DevBuf *b : {&f->esa_lcp, &f->esa_sa, &f->esa_da, &f->rec_P}) {
         if (b->p) (void)hipFree(b->p);
         b->p = nullptr; b->cap = 0;
     }
@@ -6798,20 +6801,21 @@ extern "C" int debwt_fm_esa_stats_get(const debwt_fm *f, debwt_fm_esa_stats *out
 
 static_assert(sizeof(debwt_fm_repeat) == 64, "a record of debwt_fm_repeats is 64 bytes");
 
-extern "C" int debwt_fm_repeats(debwt_fm *f, const debwt_fm_repeat_opts *opts, debwt_fm_repeat *out, uint64_t capacity,
-                                uint64_t *count) {
-    if (!f) return DEBWT_EINVAL;
+// filter: null for debwt_fm_repeats (who names the call in messages); records: the records of every listed interval, or null
+static int fm_repeats_run(debwt_fm *f, const std::string &who, const debwt_fm_repeat_opts *opts, const debwt_fm_record_filter *filter,
+                          debwt_fm_repeat *out, uint32_t *records, uint64_t capacity, uint64_t *count) {
     const auto t0 = std::chrono::steady_clock::now();
-    if (!opts || !count) { f->err = "debwt_fm_repeats: opts and count must not be NULL"; return DEBWT_EINVAL; }
+    if (!opts || !count) { f->err = who + ": opts and count must not be NULL"; return DEBWT_EINVAL; }
     if (!opts->min_len || opts->min_occ < 2 || (opts->max_occ && opts->max_occ < opts->min_occ)) {
-        f->err = "debwt_fm_repeats: min_len must be at least 1, min_occ at least 2 and max_occ 0 or at least min_occ";
+        f->err = who + ": min_len must be at least 1, min_occ at least 2 and max_occ 0 or at least min_occ";
         return DEBWT_EINVAL;
     }
-    if (opts->kind > DEBWT_FM_REPEAT_INTERVALS) { f->err = "debwt_fm_repeats: unknown kind"; return DEBWT_EINVAL; }
-    if (capacity && !out) { f->err = "debwt_fm_repeats: out is NULL with capacity > 0"; return DEBWT_EINVAL; }
-    if (!f->has_esa || !f->esa_lcp.p) { f->err = "debwt_fm_repeats: no build holds the LCP array (debwt_fm_esa_build)"; return DEBWT_ESTATE; }
+    if (opts->kind > DEBWT_FM_REPEAT_INTERVALS) { f->err = who + ": unknown kind"; return DEBWT_EINVAL; }
+    if (capacity && !out) { f->err = who + ": out is NULL with capacity > 0"; return DEBWT_EINVAL; }
+    if (!f->has_esa || !f->esa_lcp.p) { f->err = who + ": no build holds the LCP array (debwt_fm_esa_build)"; return DEBWT_ESTATE; }
+    if (filter && !f->rec_P.p) { f->err = who + ": no records build (debwt_fm_records_build)"; return DEBWT_ESTATE; }
     const u64 F = fm_env_u64("DEBWT_FM_REPEAT_FANOUT", 64);
-    if (F < 2 || F > 64 || (F & (F - 1))) { f->err = "debwt_fm_repeats: DEBWT_FM_REPEAT_FANOUT must be a power of two in 2..64"; return DEBWT_EINVAL; }
+    if (F < 2 || F > 64 || (F & (F - 1))) { f->err = who + ": DEBWT_FM_REPEAT_FANOUT must be a power of two in 2..64"; return DEBWT_EINVAL; }
     u32 sh = 0;
     while ((1ull << sh) < F) sh++;
     f->rp_stats = debwt_fm_repeat_stats{};
@@ -6824,12 +6828,12 @@ extern "C" int debwt_fm_repeats(debwt_fm *f, const debwt_fm_repeat_opts *opts, d
     u64 nodes = 0;
     for (u64 m = n; m > 1;) { m = (m + F - 1) >> sh; lev.push_back(m); lev.push_back(nodes); nodes += m; }
     const u32 levels = (u32)(lev.size() / 2 - 1);
-    if (levels > FM_REP_MAXLEV) { f->err = "debwt_fm_repeats: more levels than the kernels hold"; return DEBWT_EINTERNAL; }
+    if (levels > FM_REP_MAXLEV) { f->err = who + ": more levels than the kernels hold"; return DEBWT_EINTERNAL; }
     const bool list = capacity != 0;
     const u64 nw = (n + 63) >> 6, rkc = (nw + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;
     const u32 blocks = (u32)std::min<u64>(grid_for(n, 256), 4096);
     const size_t small_bytes = (size_t)(FM_REP_NCTR + 2 * (FM_REP_MAXLEV + 1)) * 8, best_bytes = (size_t)blocks * 16;
-    FmTmp node, small, best, lo, hi, masks, wpre, csum, dout;
+    FmTmp node, small, best, lo, hi, masks, wpre, csum, dout, drec;
     HIPCHK(f, hipMalloc(&node.p, (size_t)std::max<u64>(nodes, 1) * 8));
     HIPCHK(f, hipMalloc(&small.p, small_bytes));
     HIPCHK(f, hipMalloc(&best.p, best_bytes));
@@ -6863,9 +6867,13 @@ extern "C" int debwt_fm_repeats(debwt_fm *f, const debwt_fm_repeat_opts *opts, d
     const u32 cap = f->esa_sum.cap < 0xFFFFFFFFull ? (u32)f->esa_sum.cap : 0u;
     const FmRepTree T{d_lcp, d_node, d_lev, levels, sh};
     const FmRepOpts O{opts->min_len, opts->kind, cap, opts->min_occ, opts->max_occ};
-    k_fm_rep_search<<<blocks, 256, 0, f->stream>>>(f->V, T, O, reinterpret_cast<u64 *>(lo.p), reinterpret_cast<u64 *>(hi.p),
-                                                   list ? d_masks : nullptr, list ? d_masks + nw : nullptr,
-                                                   list ? d_masks + 2 * nw : nullptr, ctr, d_best);
+    u64 *const d_lo = reinterpret_cast<u64 *>(lo.p), *const d_hi = reinterpret_cast<u64 *>(hi.p);
+    u64 *const m0 = list ? d_masks : nullptr, *const m1 = list ? d_masks + nw : nullptr, *const m2 = list ? d_masks + 2 * nw : nullptr;
+    if (filter)
+        k_fm_rep_search<true><<<blocks, 256, 0, f->stream>>>(f->V, T, O, d_lo, d_hi, m0, m1, m2, ctr, d_best, f->rec_P.as<u64>(),
+                                                             FmRecFilter{filter->min_records, filter->max_records, filter->flags});
+    else
+        k_fm_rep_search<false><<<blocks, 256, 0, f->stream>>>(f->V, T, O, d_lo, d_hi, m0, m1, m2, ctr, d_best, nullptr, FmRecFilter{});
     (void)hipEventRecord(ev[2], f->stream);
     u64 hc[FM_REP_NCTR];
     std::vector<u64> hb((size_t)blocks * 2);
@@ -6886,33 +6894,210 @@ extern "C" int debwt_fm_repeats(debwt_fm *f, const debwt_fm_repeat_opts *opts, d
     *count = st.reported;
     if (capacity < st.reported) {
         st.ms_wall = (float)fm_ms_since(t0);
-        f->err = "debwt_fm_repeats: capacity below the repeats (count = " + std::to_string(st.reported) + ")";
+        f->err = who + ": capacity below the repeats (count = " + std::to_string(st.reported) + ")";
         return DEBWT_ERANGE;
     }
     if (st.reported) {
         HIPCHK(f, hipMalloc(&dout.p, (size_t)st.reported * sizeof(debwt_fm_repeat)));
         st.scratch_bytes += st.reported * sizeof(debwt_fm_repeat);
+        if (records) {
+            HIPCHK(f, hipMalloc(&drec.p, (size_t)st.reported * 4));
+            st.scratch_bytes += st.reported * 4;
+        }
         k_fm_anc_count<<<(u32)rkc, FM_EX_CHUNK_WORDS, 0, f->stream>>>(d_masks, nw, reinterpret_cast<u32 *>(wpre.p), d_csum);
         k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(d_csum, rkc, d_csum + rkc);
         k_fm_rep_write<<<(u32)std::min<u64>(grid_for(n, 256), 1u << 20), 256, 0, f->stream>>>(
             f->V, d_lcp, n, reinterpret_cast<const u64 *>(lo.p), reinterpret_cast<const u64 *>(hi.p), d_masks, d_masks + nw,
-            d_masks + 2 * nw, reinterpret_cast<const u32 *>(wpre.p), d_csum, reinterpret_cast<debwt_fm_repeat *>(dout.p), st.reported);
+            d_masks + 2 * nw, reinterpret_cast<const u32 *>(wpre.p), d_csum, reinterpret_cast<debwt_fm_repeat *>(dout.p), st.reported,
+            records ? f->rec_P.as<u64>() : nullptr, reinterpret_cast<u32 *>(drec.p));
         (void)hipEventRecord(ev[3], f->stream);
         u64 total = 0;
         HIPCHK(f, hipMemcpyAsync(&total, d_csum + rkc, 8, hipMemcpyDeviceToHost, f->stream));
         HIPCHK(f, hipMemcpyAsync(out, dout.p, (size_t)st.reported * sizeof(debwt_fm_repeat), hipMemcpyDeviceToHost, f->stream));
+        if (records) HIPCHK(f, hipMemcpyAsync(records, drec.p, (size_t)st.reported * 4, hipMemcpyDeviceToHost, f->stream));
         if ((rc = fm_sync(f))) return rc;
         (void)hipEventElapsedTime(&st.ms_write, ev[2], ev[3]);
         st.rank_lines += 8 * st.reported;
-        if (total != st.reported) { f->err = "debwt_fm_repeats: the masks and the count of the reported rows differ"; return DEBWT_EINTERNAL; }
+        if (total != st.reported) { f->err = who + ": the masks and the count of the reported rows differ"; return DEBWT_EINTERNAL; }
     }
     st.ms_wall = (float)fm_ms_since(t0);
     return DEBWT_OK;
 }
 
+extern "C" int debwt_fm_repeats(debwt_fm *f, const debwt_fm_repeat_opts *opts, debwt_fm_repeat *out, uint64_t capacity,
+                                uint64_t *count) {
+    if (!f) return DEBWT_EINVAL;
+    return fm_repeats_run(f, "debwt_fm_repeats", opts, nullptr, out, nullptr, capacity, count);
+}
+
 extern "C" int debwt_fm_repeat_stats_get(const debwt_fm *f, debwt_fm_repeat_stats *out) {
     if (!f || !out) return DEBWT_EINVAL;
     *out = f->rp_stats;
+    return DEBWT_OK;
+}
+
+// ---- distinct records per LCP interval (fm_record_kernels.h) -----------------------------------------------------------
+// The build is one run of launches on the index's stream: keys, the stable passes over the record bits, the hierarchy of
+// the repeats section, one range minimum per pair, the prefix sum.  Everything is allocated into temporaries that are
+// released on every way out; the prefix changes hands only after the last check, so a failed build leaves an earlier
+// prefix in place.
+
+namespace {
+
+u32 fm_bits_of(u64 v) { u32 b = 0; while (b < 64 && (v >> b)) b++; return b; }    // the bits of v; 0 for v = 0
+
+template <typename DT>
+void fm_records_launch(debwt_fm *f, const FmRepTree &T, const u64 *keys, u32 rb, void *dup, u64 *ctr, u64 *tsum, u64 ntiles, u64 *P,
+                       hipEvent_t after_pairs) {
+    const u64 n = f->n;
+    DT *d_dup = reinterpret_cast<DT *>(dup);
+    k_fm_rec_pairs<DT><<<(u32)std::min<u64>(grid_for(n, 256), 4096), 256, 0, f->stream>>>(T, keys, rb, d_dup, ctr);
+    (void)hipEventRecord(after_pairs, f->stream);
+    k_fm_rec_tile_sums<DT><<<(u32)ntiles, FM_REC_TILE, 0, f->stream>>>(d_dup, n, tsum);
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(tsum, ntiles, tsum + ntiles);
+    k_fm_rec_scan<DT><<<(u32)ntiles, FM_REC_TILE, 0, f->stream>>>(d_dup, n, tsum, P);
+}
+
+}  // namespace
+
+extern "C" int debwt_fm_records_build(debwt_fm *f) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!f->has_esa || !f->esa_lcp.p || !f->esa_da.p) {
+        f->err = "debwt_fm_records_build: no build holds the record array (debwt_fm_esa_build with DEBWT_FM_ESA_DA)";
+        return DEBWT_ESTATE;
+    }
+    const u64 F = fm_env_u64("DEBWT_FM_REPEAT_FANOUT", 64);
+    if (F < 2 || F > 64 || (F & (F - 1))) { f->err = "debwt_fm_records_build: DEBWT_FM_REPEAT_FANOUT must be a power of two in 2..64"; return DEBWT_EINVAL; }
+    u32 sh = 0;
+    while ((1ull << sh) < F) sh++;
+    const u64 n = f->n, nrec = f->nrec;
+    const u32 rb = fm_bits_of(n - 1), db = fm_bits_of(nrec - 1);
+    if (rb + db > 64) { f->err = "debwt_fm_records_build: record and row do not fit one 64-bit key"; return DEBWT_EINVAL; }
+    if ((n + FM_REC_TILE - 1) / FM_REC_TILE > 0x7FFFFFFFull) { f->err = "debwt_fm_records_build: more rows than the scan's grid holds"; return DEBWT_EINVAL; }
+    debwt_fm_records_stats st{};
+    HIPCHK(f, hipSetDevice(f->device));
+
+    std::vector<u64> lev{n, 0};                                // the level table of debwt_fm_repeats
+    u64 nodes = 0;
+    for (u64 m = n; m > 1;) { m = (m + F - 1) >> sh; lev.push_back(m); lev.push_back(nodes); nodes += m; }
+    const u32 levels = (u32)(lev.size() / 2 - 1);
+    if (levels > FM_REP_MAXLEV) { f->err = "debwt_fm_records_build: more levels than the kernels hold"; return DEBWT_EINTERNAL; }
+    const bool wide = n >> 32;                                 // dup as u64
+    const u64 ntiles = (n + FM_REC_TILE - 1) / FM_REC_TILE;
+    const size_t small_bytes = (size_t)(FM_REC_NCTR + 2 * (FM_REP_MAXLEV + 1)) * 8, ws_bytes = radix_workspace_bytes(n),
+                 dup_bytes = (size_t)n * (wide ? 8 : 4), tsum_bytes = (size_t)(ntiles + 1) * 8;
+    FmTmp ka, kb, rws, node, small, dup, tsum, P;
+    HIPCHK(f, hipMalloc(&ka.p, (size_t)n * 8));
+    HIPCHK(f, hipMalloc(&kb.p, (size_t)n * 8));
+    HIPCHK(f, hipMalloc(&rws.p, ws_bytes));
+    HIPCHK(f, hipMalloc(&node.p, (size_t)std::max<u64>(nodes, 1) * 8));
+    HIPCHK(f, hipMalloc(&small.p, small_bytes));
+    HIPCHK(f, hipMalloc(&dup.p, dup_bytes));
+    HIPCHK(f, hipMalloc(&tsum.p, tsum_bytes));
+    HIPCHK(f, hipMalloc(&P.p, (size_t)n * 8));
+    st.rows = n; st.levels = levels; st.fanout = F; st.sort_passes = (db + 7) / 8;
+    st.kept_bytes = n * 8;
+    st.build_bytes = n * 16 + ws_bytes + std::max<u64>(nodes, 1) * 8 + small_bytes + dup_bytes + tsum_bytes + st.kept_bytes;
+    u64 *ctr = reinterpret_cast<u64 *>(small.p), *d_lev = ctr + FM_REC_NCTR;
+    uint2 *d_node = reinterpret_cast<uint2 *>(node.p);
+    const u32 *d_lcp = f->esa_lcp.as<u32>();
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct Ev { hipEvent_t *e; ~Ev() { for (int i = 0; i < 5; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int i = 0; i < 5; i++) HIPCHK(f, hipEventCreate(&ev[i]));
+    HIPCHK(f, hipMemsetAsync(ctr, 0, FM_REC_NCTR * 8, f->stream));
+    HIPCHK(f, hipMemsetAsync(dup.p, 0, dup_bytes, f->stream));
+    HIPCHK(f, hipMemcpyAsync(d_lev, lev.data(), lev.size() * 8, hipMemcpyHostToDevice, f->stream));
+    (void)hipEventRecord(ev[0], f->stream);
+    k_fm_rec_keys<<<(u32)std::min<u64>(grid_for(n, 256), 1u << 20), 256, 0, f->stream>>>(f->esa_da.as<u32>(), n, rb,
+                                                                                         reinterpret_cast<u64 *>(ka.p));
+    RadixWorkspace ws{};
+    ws.counts = reinterpret_cast<u32 *>(rws.p);                // chunk histograms only: no pair counts, no hybrid lists
+    hipError_t e = hipSuccess;
+    const u64 *sorted = radix_sort_bits(f->stream, reinterpret_cast<u64 *>(ka.p), reinterpret_cast<u64 *>(kb.p), n, (int)rb,
+                                        (int)(rb + db), ws, &e);
+    if (e != hipSuccess) { f->err = std::string("debwt_fm_records_build: the key sort: ") + hipGetErrorString(e); return DEBWT_EDEVICE; }
+    (void)hipEventRecord(ev[1], f->stream);
+    for (u32 t = 0; t < levels; t++) {
+        const u64 nin = lev[2 * t], nout = lev[2 * t + 2];
+        const u32 g = (u32)std::min<u64>(grid_for(nin, 256), 1u << 20);
+        if (t == 0) k_fm_rep_level<true><<<g, 256, 0, f->stream>>>(d_lcp, nullptr, nin, sh, d_node + lev[3], nout);
+        else k_fm_rep_level<false><<<g, 256, 0, f->stream>>>(nullptr, d_node + lev[2 * t + 1], nin, sh, d_node + lev[2 * t + 3], nout);
+    }
+    (void)hipEventRecord(ev[2], f->stream);
+    const FmRepTree T{d_lcp, d_node, d_lev, levels, sh};
+    if (wide) fm_records_launch<u64>(f, T, sorted, rb, dup.p, ctr, reinterpret_cast<u64 *>(tsum.p), ntiles, reinterpret_cast<u64 *>(P.p), ev[3]);
+    else fm_records_launch<u32>(f, T, sorted, rb, dup.p, ctr, reinterpret_cast<u64 *>(tsum.p), ntiles, reinterpret_cast<u64 *>(P.p), ev[3]);
+    (void)hipEventRecord(ev[4], f->stream);
+    u64 hc[FM_REC_NCTR], total = 0;
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(&total, reinterpret_cast<u64 *>(tsum.p) + ntiles, 8, hipMemcpyDeviceToHost, f->stream));
+    int rc;
+    if ((rc = fm_sync(f))) return rc;
+    (void)hipEventElapsedTime(&st.ms_sort, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&st.ms_tree, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&st.ms_pairs, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&st.ms_scan, ev[3], ev[4]);
+    st.pairs = hc[FM_REC_C_PAIRS]; st.records_present = n - st.pairs;
+    st.rmq_steps = hc[FM_REC_C_STEPS]; st.wave_steps = hc[FM_REC_C_WAVE];
+    if (hc[FM_REC_C_LOST] || total != st.pairs || st.pairs >= n) {
+        f->err = "debwt_fm_records_build: the pairs and the sum of dup differ (" + std::to_string(st.pairs) + " pairs, " +
+                 std::to_string(total) + " counted, " + std::to_string(hc[FM_REC_C_LOST]) + " without a minimum)";
+        return DEBWT_EINTERNAL;
+    }
+    if (f->rec_P.p) (void)hipFree(f->rec_P.p);                 // a second build replaces the first
+    fm_esa_keep(f->rec_P, P, (size_t)n * 8);
+    st.ms_wall = (float)fm_ms_since(t0);
+    f->rc_stats = st;
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_records_fetch(debwt_fm *f, uint64_t row_lo, uint64_t count, uint64_t *P) {
+    if (!f) return DEBWT_EINVAL;
+    if (!f->has_esa || !f->rec_P.p) { f->err = "debwt_fm_records_fetch: no records build (debwt_fm_records_build)"; return DEBWT_ESTATE; }
+    if (row_lo > f->n || count > f->n - row_lo) { f->err = "debwt_fm_records_fetch: row_lo + count exceeds n"; return DEBWT_EINVAL; }
+    if (!count) return DEBWT_OK;
+    if (!P) return DEBWT_EINVAL;
+    HIPCHK(f, hipSetDevice(f->device));
+    HIPCHK(f, hipMemcpyAsync(P, f->rec_P.as<u64>() + row_lo, (size_t)count * 8, hipMemcpyDeviceToHost, f->stream));
+    return fm_sync(f);
+}
+
+extern "C" int debwt_fm_record_counts(debwt_fm *f, const uint64_t *ranges, uint64_t nranges, uint64_t *records) {
+    if (!f) return DEBWT_EINVAL;
+    if (!f->has_esa || !f->rec_P.p) { f->err = "debwt_fm_record_counts: no records build (debwt_fm_records_build)"; return DEBWT_ESTATE; }
+    if (!nranges) return DEBWT_OK;
+    if (!ranges || !records) { f->err = "debwt_fm_record_counts: ranges and records must not be NULL"; return DEBWT_EINVAL; }
+    for (u64 k = 0; k < nranges; k++)
+        if (ranges[2 * k + 1] > f->n || ranges[2 * k] > ranges[2 * k + 1]) {
+            f->err = "debwt_fm_record_counts: range " + std::to_string(k) + " has hi > n or lo > hi"; return DEBWT_EINVAL;
+        }
+    HIPCHK(f, hipSetDevice(f->device));
+    FmTmp dr, dout;
+    HIPCHK(f, hipMalloc(&dr.p, (size_t)nranges * 16));
+    HIPCHK(f, hipMalloc(&dout.p, (size_t)nranges * 8));
+    HIPCHK(f, hipMemcpyAsync(dr.p, ranges, (size_t)nranges * 16, hipMemcpyHostToDevice, f->stream));
+    k_fm_rec_gather<<<(u32)std::min<u64>(grid_for(nranges, 256), 1u << 20), 256, 0, f->stream>>>(
+        f->rec_P.as<u64>(), f->n, reinterpret_cast<const u64 *>(dr.p), nranges, reinterpret_cast<u64 *>(dout.p));
+    HIPCHK(f, hipMemcpyAsync(records, dout.p, (size_t)nranges * 8, hipMemcpyDeviceToHost, f->stream));
+    return fm_sync(f);
+}
+
+extern "C" int debwt_fm_repeats_records(debwt_fm *f, const debwt_fm_repeat_opts *opts, const debwt_fm_record_filter *filter,
+                                        debwt_fm_repeat *out, uint32_t *records, uint64_t capacity, uint64_t *count) {
+    if (!f) return DEBWT_EINVAL;
+    if (!filter) { f->err = "debwt_fm_repeats_records: filter must not be NULL"; return DEBWT_EINVAL; }
+    if (!filter->min_records || (filter->max_records && filter->max_records < filter->min_records) ||
+        (filter->flags & ~DEBWT_FM_RECORDS_UNIQUE) || filter->reserved) {
+        f->err = "debwt_fm_repeats_records: min_records must be at least 1, max_records 0 or at least min_records, flags known and reserved 0";
+        return DEBWT_EINVAL;
+    }
+    return fm_repeats_run(f, "debwt_fm_repeats_records", opts, filter, out, records, capacity, count);
+}
+
+extern "C" int debwt_fm_records_stats_get(const debwt_fm *f, debwt_fm_records_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->rc_stats;
     return DEBWT_OK;
 }
 
@@ -8048,7 +8233,7 @@ extern "C" void debwt_fm_destroy(debwt_fm *f) {
                       &f->b_self, &f->b_row, &f->b_cnt, &f->b_whb, &f->b_rawbase, &f->b_tbase, &f->b_pos, &f->b_aoff, &f->b_mm,
                       &f->b_cur, &f->b_cat, &f->b_ctr, &f->cl_state, &f->cl_src, &f->cl_cnt, &f->cl_toff, &f->cl_tin, &f->cl_snap,
                       &f->cl_mark, &f->cl_ctr, &f->p_table, &f->p_codes, &f->p_aln, &f->p_coff, &f->p_cig, &f->p_span, &f->p_ctr,
-                      &f->p_sep, &f->p_calls, &f->p_vcnt, &f->p_vbase, &f->p_vars, &f->esa_lcp, &f->esa_sa, &f->esa_da})
+                      &f->p_sep, &f->p_calls, &f->p_vcnt, &f->p_vbase, &f->p_vars, &f->esa_lcp, &f->esa_sa, &f->esa_da, &f->rec_P})
         if (b->p) (void)hipFree(b->p);
     for (DevBuf &b : f->s_items)
         if (b.p) (void)hipFree(b.p);

@@ -138,6 +138,11 @@ __device__ __forceinline__ u64 fm_rep_left(const FmRepTree &T, const u64 *sn, co
     return pos;
 }
 
+struct FmRecFilter {
+    u64 min_records, max_records;         // max_records 0: no bound
+    u32 flags;                            // DEBWT_FM_RECORDS_UNIQUE
+};
+
 // the left counts of rows [i, j]: two rank lines per base, the separators by subtraction
 __device__ __forceinline__ void fm_rep_left_counts(const VIndex &V, u64 i, u64 j, u64 left[5]) {
     u64 sum = 0;
@@ -148,9 +153,13 @@ __device__ __forceinline__ void fm_rep_left_counts(const VIndex &V, u64 i, u64 j
 
 // One lane per row, a tile of 256 rows per workgroup and step of its stride.  lo, hi, rmask, mmask, smask: null for a call
 // that only counts.  best: 2 u64 per workgroup, the longest reported length and its row_lo (the lowest on ties).
+// REC: the record filter of Definition 12 on top, P the kept prefix of fm_record_kernels.h; without REC nothing of the
+// filter is compiled in and P, RF are not read.
+template <bool REC>
 __global__ __launch_bounds__(256) void k_fm_rep_search(VIndex V, FmRepTree T, FmRepOpts O, u64 *__restrict__ lo, u64 *__restrict__ hi,
                                                        u64 *__restrict__ rmask, u64 *__restrict__ mmask, u64 *__restrict__ smask,
-                                                       u64 *__restrict__ ctr, u64 *__restrict__ best) {
+                                                       u64 *__restrict__ ctr, u64 *__restrict__ best, const u64 *__restrict__ P,
+                                                       FmRecFilter RF) {
     __shared__ u64 sn[FM_REP_MAXLEV + 1], soff[FM_REP_MAXLEV + 1];
     __shared__ u64 sbest[2][4];
     for (u32 k = threadIdx.x; k <= T.levels; k += blockDim.x) { sn[k] = T.lev[2 * k]; soff[k] = T.lev[2 * k + 1]; }
@@ -191,6 +200,13 @@ __global__ __launch_bounds__(256) void k_fm_rep_search(VIndex V, FmRepTree T, Fm
                 rep = occ >= O.min_occ && (!O.max_occ || occ <= O.max_occ) &&
                       (O.kind == DEBWT_FM_REPEAT_INTERVALS ||
                        (flags & (O.kind == DEBWT_FM_REPEAT_MAXIMAL ? DEBWT_FM_REPEAT_IS_MAXIMAL : DEBWT_FM_REPEAT_IS_SUPERMAXIMAL)));
+                if constexpr (REC) {
+                    if (rep) {                                 // records(i, j + 1) of Definition 12: two reads
+                        const u64 recs = occ - (P[j] - P[i]);
+                        rep = recs >= RF.min_records && (!RF.max_records || recs <= RF.max_records) &&
+                              (!(RF.flags & DEBWT_FM_RECORDS_UNIQUE) || recs == occ);
+                    }
+                }
                 if (rep) {
                     reported++;
                     if (l > blen || (l == blen && i < blo)) { blen = l; blo = i; }
@@ -235,12 +251,14 @@ __global__ __launch_bounds__(256) void k_fm_rep_search(VIndex V, FmRepTree T, Fm
 }
 
 // One lane per row: a reported row writes its record at the rank of its bit.  wpre, csum: the rank over rmask in the
-// layout of k_fm_anc_count and k_fm_anc_scan.  cap: the records out holds.
+// layout of k_fm_anc_count and k_fm_anc_scan.  cap: the records out holds.  recs (with P, the kept prefix of Definition 12;
+// null for debwt_fm_repeats): the distinct records of every interval of the list, beside it.
 __global__ __launch_bounds__(256) void k_fm_rep_write(VIndex V, const u32 *__restrict__ lcp, u64 n, const u64 *__restrict__ lo,
                                                       const u64 *__restrict__ hi, const u64 *__restrict__ rmask,
                                                       const u64 *__restrict__ mmask, const u64 *__restrict__ smask,
                                                       const u32 *__restrict__ wpre, const u64 *__restrict__ csum,
-                                                      debwt_fm_repeat *__restrict__ out, u64 cap) {
+                                                      debwt_fm_repeat *__restrict__ out, u64 cap,
+                                                      const u64 *__restrict__ P, u32 *__restrict__ recs) {
     for (u64 r = (u64)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (u64)gridDim.x * blockDim.x) {
         const u64 w = r >> 6, bit = 1ull << (r & 63), m = rmask[w];
         if (!(m & bit)) continue;
@@ -256,5 +274,6 @@ __global__ __launch_bounds__(256) void k_fm_rep_write(VIndex V, const u32 *__res
         rec.len = lcp[r];
         rec.flags = (mmask[w] & bit ? DEBWT_FM_REPEAT_IS_MAXIMAL : 0u) | (smask[w] & bit ? DEBWT_FM_REPEAT_IS_SUPERMAXIMAL : 0u);
         out[k] = rec;
+        if (recs) recs[k] = (u32)(rec.count - (P[j] - P[i]));  // records(i, j + 1), as the search computed it
     }
 }

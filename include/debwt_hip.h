@@ -1300,6 +1300,68 @@ typedef struct {
 } debwt_fm_repeat_stats;
 int debwt_fm_repeat_stats_get(const debwt_fm *fm, debwt_fm_repeat_stats *out);
 
+/* ---- Definition 12 (records): distinct records per LCP interval, multi-MUMs (fm_record_kernels.h) ---------------------
+ * Rows, sa, da, lcp (the STORED array, capped or not) and intervals are those of Definitions 10 and 11.
+ *   prev[r]  the largest r' < r with da[r'] = da[r], or none.
+ *   dup      For every row r that has a prev, m(r) is the smallest row of (prev[r], r] that holds min(lcp[prev[r]+1 .. r]):
+ *            the leftmost argmin.  dup[m] is the number of rows r with m(r) = m.  The sum of dup is n minus the number of
+ *            records present in da.  P[r] = dup[0] + .. + dup[r].
+ *   Closed range.  Rows [lo, hi) are closed when hi - lo <= 1, or every value of lcp[lo+1 .. hi-1] is above lcp[lo], and
+ *            above lcp[hi] when hi < n.  Every interval (l, i, j) is the closed range [i, j + 1); so is the range
+ *            debwt_fm_count answers for a pattern of bases whose length is at most the cap of the build.
+ *   records(lo, hi)  0 for an empty range, else (hi - lo) - (P[hi-1] - P[lo]).
+ *   Fact 4 (tests/record_ref.py asserts it).  For a closed range records(lo, hi) is the number of distinct values of
+ *            da[lo .. hi).  A row r of the range with prev[r] >= lo is exactly a repeated record, and its m(r) lies in
+ *            (lo, hi).  Conversely, were m(r) in (lo, hi) with prev[r] < lo, then lo lies in (prev[r], r] and lcp[lo] >=
+ *            lcp[m(r)], but lcp[m(r)] is above lcp[lo]; r >= hi is ruled out the same way through lcp[hi].
+ *   Not closed.  For such a range the value is still the formula's, in u64 arithmetic (it may wrap below 0), and the
+ *            leftmost argmin makes it the same in every run, but it is NOT a record count.
+ *   multi-MUM.  A maximal interval (Definition 11) with count = records = the number of records of the index: its string
+ *            occurs exactly once in every record and can be extended on neither side.  With a bound q: count = records >= q.
+ *
+ * The build needs da (DEBWT_FM_ESA_DA) and lcp.  Keys da[r] << rb | r (rb the bits of n - 1) are sorted by the stable
+ * radix passes over the db bits of nrec - 1 (ceil(db / 8) passes; rb + db > 64 is DEBWT_EINVAL): neighbours with equal da
+ * are the pairs (prev[r], r).  One lane per pair finds the leftmost argmin on the min/max hierarchy of Definition 11 (same
+ * fanout, same DEBWT_FM_REPEAT_FANOUT; no result depends on it) -- an ascent from both ends of at most 2 (F - 1) entries
+ * per level and a descent of at most F per level, never a number that grows with r - prev[r] -- and adds 1 to dup[m] with
+ * an integer atomic, whose sum does not depend on the order of arrival.  dup is u32 for n < 2^32 and u64 above.  A prefix
+ * sum makes P, kept as plain u64: kept_bytes = 8 n, allocated exactly, counted in debwt_fm_info.device_bytes, released by
+ * debwt_fm_esa_release, by the next debwt_fm_esa_build and by debwt_fm_destroy.  Peak of the build beside the kept arrays:
+ * 16 n (keys and sort scratch) + 4 n (dup; 8 n above 2^32 rows) + the tree (below 8 n / (F - 1) + 8 levels) + 16 MiB
+ * (radix workspace) + n / 32 (tile sums) + 8 n (P); everything but P is freed before the call returns.  DEBWT_ENOMEM keeps
+ * nothing new and leaves the kept arrays, an earlier P included, as they were; a second successful call replaces the
+ * first.  DEBWT_ESTATE without a build or without a kept da. */
+int debwt_fm_records_build(debwt_fm *fm);
+/* P[row_lo .. row_lo + count) to the host as u64.  DEBWT_ESTATE without debwt_fm_records_build, DEBWT_EINVAL for
+ * row_lo + count > n or a NULL P with count > 0. */
+int debwt_fm_records_fetch(debwt_fm *fm, uint64_t row_lo, uint64_t count, uint64_t *P);
+/* records[k] = records(ranges[2k], ranges[2k + 1]), ranges as debwt_fm_count writes them.  DEBWT_EINVAL for hi > n or
+ * lo > hi in any range (nothing is written then), DEBWT_ESTATE without debwt_fm_records_build. */
+int debwt_fm_record_counts(debwt_fm *fm, const uint64_t *ranges, uint64_t nranges, uint64_t *records);
+#define DEBWT_FM_RECORDS_UNIQUE 1u         /* flags of a filter: count == records, no record holds the string twice */
+typedef struct { uint64_t min_records, max_records; uint32_t flags, reserved; } debwt_fm_record_filter;  /* max_records 0 = no bound */
+/* debwt_fm_repeats with a filter on the records of every interval: the list holds the intervals that debwt_fm_repeats
+ * lists for opts and whose records lie in [min_records, max_records] (and equal count with DEBWT_FM_RECORDS_UNIQUE), in
+ * the same order; records[k] (capacity entries, may be NULL) is the records of out[k].  Protocol and error codes are
+ * those of debwt_fm_repeats; DEBWT_EINVAL also for a NULL filter, min_records = 0, max_records != 0 && max_records <
+ * min_records, unknown flags and a non-zero reserved; DEBWT_ESTATE also without debwt_fm_records_build.  With the filter
+ * {1, 0, 0} the list equals that of debwt_fm_repeats byte for byte.  A lane of the search that has i and j reads P[j] and
+ * P[i] and applies the filter before the row is reported; the write pass reads the two again for records[] (4 bytes of
+ * scratch more per listed record, nothing per row).
+ * debwt_fm_repeat_stats_get describes this call too (its counters before `reported` do not depend on the filter). */
+int debwt_fm_repeats_records(debwt_fm *fm, const debwt_fm_repeat_opts *opts, const debwt_fm_record_filter *filter,
+                             debwt_fm_repeat *out, uint32_t *records, uint64_t capacity, uint64_t *count);
+/* what the last debwt_fm_records_build did: rows (n), pairs (rows with a prev), records_present (n - pairs: the distinct
+ * values of da), sort_passes, levels and the fanout in force, rmq_steps (hierarchy nodes and level-0 entries read by the
+ * range minima), wave_steps (64 x the reads of the longest lane of every wave: rmq_steps / wave_steps is the share of
+ * lanes busy), build_bytes (everything the call allocated, P included), kept_bytes, ms per phase (events: keys and sort,
+ * tree, pairs, scan) and host wall time */
+typedef struct {
+    uint64_t rows, pairs, records_present, sort_passes, levels, fanout, rmq_steps, wave_steps, build_bytes, kept_bytes;
+    float ms_sort, ms_tree, ms_pairs, ms_scan, ms_wall;
+} debwt_fm_records_stats;
+int debwt_fm_records_stats_get(const debwt_fm *fm, debwt_fm_records_stats *out);
+
 /* ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
  * Records S_0 .. S_{nrec-1} are those of the index, numbered as in overlap hits; |S| is the length of S.
  * 1. state[i] = 1 (duplicate) iff some j < i has S_j == S_i; otherwise 2 (contained) iff S_i is a substring of a strictly
