@@ -23,10 +23,23 @@ SMALL = 2000                   # up to here the suffixes are sorted as byte stri
 class Esa:
     def __init__(self, records, sa=None):
         self.records = [np.asarray(r, dtype=np.uint8) for r in records]
-        self.sym = F.text_symbols(self.records)
-        n = self.n = len(self.sym)
+        sym = F.text_symbols(self.records)
         if sa is None:
-            sa = F.definition_index(self.records)[1] if n <= SMALL else F.suffix_array(self.sym)
+            sa = F.definition_index(self.records)[1] if len(sym) <= SMALL else F.suffix_array(sym)
+        self._arrays(sym, sa)
+
+    @classmethod
+    def from_index(cls, sym, sa):
+        """The second way in: the text as codes 0..5 and its suffix array, for a collection of so many records that a
+        list of them is not made (many_records_ref).  records is None then; everything else is as __init__ leaves it."""
+        E = cls.__new__(cls)
+        E.records = None
+        E._arrays(np.asarray(sym, dtype=np.uint8), sa)
+        return E
+
+    def _arrays(self, sym, sa):
+        self.sym = sym
+        n = self.n = len(sym)
         self.sa = np.asarray(sa, dtype=np.int64)
         assert np.array_equal(np.sort(self.sa), np.arange(n))
         self.seppos = np.nonzero(self.sym > 3)[0].astype(np.int64)

@@ -7,8 +7,9 @@ last, so no suffix is a prefix of another and the suffix array of a text is uniq
 before suffix sa[r] (cyclically: '$' before position 0), packed as code min(symbol, 3) at bits 2 * (31 - r % 32) of word
 r // 32; the rows that hold '#' and the row that holds '$' are listed beside the words.
 
-Not covered by any collection here: the high 24 bits of the separators-before count of a rank line (more than 2^24
-records in front of a line), which needs a workload-sized input."""
+The high 24 bits of the separators-before count of a rank line (more than 2^24 records in front of a line) are beyond
+every collection here: many_records_ref.py makes the index of 2^24 + 300 one-base records in closed form, and
+test_fm_many_records_gpu.py runs the queries on it."""
 import bisect
 import functools
 
@@ -110,7 +111,11 @@ def samples(sa, s):
 def packed_text(records):
     """(words, sep) as debwt_fm_text_fetch documents them: ((n + 63) >> 5) + 2 words, base j at bits 2 * (31 - j % 32) of
     word j // 32, separators as 'T', 32 'T' behind position n - 1 and zeros behind; the nrec separator positions"""
-    sym = text_symbols(records)
+    return packed_text_of(text_symbols(records))
+
+
+def packed_text_of(sym):
+    """packed_text from the text's codes 0..5"""
     n = len(sym)
     nw = ((n + 63) >> 5) + 2
     code = np.zeros(nw * 32, dtype=np.uint64)

@@ -27,6 +27,11 @@ def members(strs, k, both, palindromes_twice=True, across_separators=False):
         occ = Counter(joined[j:j + k] for j in range(len(joined) - k + 1))
     else:
         occ = Counter(s[j:j + k] for s in strs for j in range(len(s) - k + 1))
+    return members_of(occ, both, palindromes_twice)
+
+
+def members_of(occ, both, palindromes_twice=True):
+    """{code: mult} of D from the occurrences of every k-mer inside records ({string: count})"""
     if not both:
         return {code_of(w): c for w, c in occ.items()}
     out = {}

@@ -5,8 +5,8 @@ and the collections outside the builder's domain, at sa_sample 1, 2, 32 and 1024
 locate walks through the '$' row, extract has little more than the free anchors).  Every answer is compared with the
 brute force over the record strings and the definition's suffix array; every comparison is exact.  The builder, the
 verifier and the sample walk are run on the cases the builder accepts.  tests/test_fm_geometry_selfcheck.py runs these
-assertions on the CPU against right and wrong answers.  Not covered: the high 24 bits of a line's separators-before
-count (see fm_definition)."""
+assertions on the CPU against right and wrong answers.  The high 24 bits of a line's separators-before count are covered
+by test_fm_many_records_gpu.py, on the index of many_records_ref.py."""
 import functools
 
 import numpy as np
