@@ -190,6 +190,7 @@ static void usage(void) {
             "       deBWT-query repeats -i OUT [--device D] [--min-len L] [--min-occ A] [--max-occ B] [--supermaximal | --intervals]\n"
             "                          [--max-lcp C] [--seq] [--occurrences] [--min-records Q] [--max-records Q] [--unique]\n"
             "       deBWT-query mums   -i OUT [--device D] [--min-len L] [--min-records Q] [--seq]\n"
+            "       deBWT-query dbg    -i OUT -k K [--device D] [--fasta]\n"
             "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]\n"
             "                          [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]\n"
             "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]\n"
@@ -243,6 +244,10 @@ static void usage(void) {
             "Q records (default all) and nowhere else: # mums=N<TAB>min_records=Q<TAB>longest=LEN, then per multi-MUM\n"
             "len<TAB>record:offset,... ascending by record; --seq appends the string;\n"
             "count --records adds the distinct records a pattern occurs in behind its count;\n"
+            "dbg writes the compacted de Bruijn graph of the K-mers of the collection (forward strand, K in 1..2^32-2) as GFA 1:\n"
+            "S<TAB>u<TAB>string<TAB>LN:i:len<TAB>KC:i:k-mer occurrences[<TAB>CL:Z:circular] per unitig, in the order of their first\n"
+            "K-mers, L<TAB>a<TAB>+<TAB>b<TAB>+<TAB><K-1>M per edge; --fasta writes the unitigs alone under >uJ nodes=N kc=C [circular];\n"
+            "stderr gets one # line with nodes, unitigs, edges, the longest unitig and N50;\n"
             "graph writes GFA 1: S lines for the records that are neither duplicates nor contained, L lines a + b + <L>M for the\n"
             "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
             "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained;\n"
@@ -1599,6 +1604,81 @@ done:
     return ret;
 }
 
+/* ---- dbg ------------------------------------------------------------------------------------------------------------------ */
+
+static int cmp_u64_desc(const void *a, const void *b) {
+    const uint64_t x = *(const uint64_t *)a, y = *(const uint64_t *)b;
+    return x < y ? 1 : x > y ? -1 : 0;
+}
+
+/* the largest L such that the strings of length >= L hold at least half of all bases; 0 without strings.  Sorts len. */
+static uint64_t n50_of(uint64_t *len, uint64_t count) {
+    uint64_t total = 0, run = 0;
+    for (uint64_t i = 0; i < count; i++) total += len[i];
+    qsort(len, count, sizeof *len, cmp_u64_desc);
+    for (uint64_t i = 0; i < count; i++) {
+        run += len[i];
+        if (run >= total - run) return len[i];
+    }
+    return 0;
+}
+
+/* the compacted de Bruijn graph of the collection's k-mers (Definition 13), as GFA 1 or as FASTA */
+static int cmd_dbg(const char *out, int device, uint32_t k, int fasta) {
+    debwt_fm *fm = NULL;
+    if (open_index(out, device, &fm)) return 1;
+    int ret = 1, rc;
+    debwt_fm_cdbg_sizes sz = {0, 0, 0};
+    debwt_fm_unitig *un = NULL;
+    debwt_fm_cdbg_edge *ed = NULL;
+    uint8_t *seq = NULL;
+    uint64_t *len = NULL;
+    debwt_fm_cdbg_stats st;
+    if (debwt_fm_esa_build(fm, k + 1, DEBWT_FM_ESA_SA | DEBWT_FM_ESA_DA)) {   /* the call tells lcp = k from lcp > k, no more */
+        fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
+        goto done;
+    }
+    rc = debwt_fm_cdbg(fm, k, 0, NULL, 0, NULL, 0, NULL, 0, &sz);
+    if (rc && rc != DEBWT_ERANGE) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    un = malloc((sz.unitigs ? sz.unitigs : 1) * sizeof *un);
+    ed = malloc((sz.edges ? sz.edges : 1) * sizeof *ed);
+    seq = malloc(sz.seq_bytes ? sz.seq_bytes : 1);
+    len = malloc((sz.unitigs ? sz.unitigs : 1) * sizeof *len);
+    if (!un || !ed || !seq || !len) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (sz.unitigs && debwt_fm_cdbg(fm, k, 0, un, sz.unitigs, seq, sz.seq_bytes, ed, sz.edges, &sz)) {
+        fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
+        goto done;
+    }
+    debwt_fm_cdbg_stats_get(fm, &st);
+    if (!fasta) printf("H\tVN:Z:1.0\n");
+    for (uint64_t u = 0; u < sz.unitigs; u++) {
+        const uint64_t m = (uint64_t)un[u].nodes + k - 1;
+        const int circular = (un[u].flags & DEBWT_FM_CDBG_CIRCULAR) != 0;
+        len[u] = m;
+        if (fasta) printf(">u%llu nodes=%u kc=%llu%s\n", (unsigned long long)u, un[u].nodes, (unsigned long long)un[u].kmer_count, circular ? " circular" : "");
+        else printf("S\t%llu\t", (unsigned long long)u);
+        fwrite(seq + un[u].seq_offset, 1, m, stdout);
+        if (fasta) putchar('\n');
+        else printf("\tLN:i:%llu\tKC:i:%llu%s\n", (unsigned long long)m, (unsigned long long)un[u].kmer_count, circular ? "\tCL:Z:circular" : "");
+    }
+    if (!fasta)
+        for (uint64_t e = 0; e < sz.edges; e++) printf("L\t%u\t+\t%u\t+\t%uM\n", ed[e].from, ed[e].to, k - 1);
+    {
+        uint64_t longest = 0;
+        for (uint64_t u = 0; u < sz.unitigs; u++) longest = len[u] > longest ? len[u] : longest;
+        fprintf(stderr, "# dbg\tk=%u\tnodes=%llu\tunitigs=%llu\tcircular=%llu\tedges=%llu\tlongest=%llu\tN50=%llu\trounds=%llu\t"
+                        "nodes %.1f, links %.1f, rank %.1f, write %.1f ms\n",
+                k, (unsigned long long)st.nodes, (unsigned long long)sz.unitigs, (unsigned long long)st.circular,
+                (unsigned long long)sz.edges, (unsigned long long)longest, (unsigned long long)n50_of(len, sz.unitigs),
+                (unsigned long long)st.jump_rounds, st.ms_nodes, st.ms_links, st.ms_rank, st.ms_write);
+    }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(un); free(ed); free(seq); free(len);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
 /* ---- graph / unitigs --------------------------------------------------------------------------------------------------- */
 
 /* the mirror of oriented node v of the both-strand graph: v ^ 1, or v itself for the one node of a self-rc read */
@@ -1756,7 +1836,8 @@ int main(int argc, char **argv) {
                !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
                !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : !strcmp(cmd, "graph") ? 9 :
                !strcmp(cmd, "unitigs") ? 10 : !strcmp(cmd, "pileup") ? 11 : !strcmp(cmd, "consensus") ? 12 :
-               !strcmp(cmd, "spectrum") ? 13 : !strcmp(cmd, "lcp") ? 14 : !strcmp(cmd, "repeats") ? 15 : !strcmp(cmd, "mums") ? 16 : -1;
+               !strcmp(cmd, "spectrum") ? 13 : !strcmp(cmd, "lcp") ? 14 : !strcmp(cmd, "repeats") ? 15 : !strcmp(cmd, "mums") ? 16 :
+               !strcmp(cmd, "dbg") ? 17 : -1;
     const int mapping = mode == 4 || mode == 11 || mode == 12;   /* the commands that map reads first */
     if (mode < 0) { usage(); return 1; }
     const char *out = NULL, *file = NULL, *ref = NULL;
@@ -1779,7 +1860,7 @@ int main(int argc, char **argv) {
     const char *list = NULL, *lcp_file = NULL, *esa_sa_file = NULL, *da_file = NULL;
     uint64_t max_lcp = 0, profile_k = 0;
     struct repeat_args ra = {20, DEBWT_FM_REPEAT_MAXIMAL, 0, 2, 0, 0, 0, 0, 0, 0, 0, 0};
-    int kind_given = 0, count_records = 0;
+    int kind_given = 0, count_records = 0, dbg_fasta = 0;
     uint64_t bins = 256, at_least = 1, at_most = 0xFFFFFFFFull;
     debwt_fm_clean_opts cl;
     debwt_fm_clean_defaults(&cl);
@@ -1812,6 +1893,7 @@ int main(int argc, char **argv) {
         if (mode == 15 && !strcmp(a, "--unique")) { ra.unique = 1; ra.by_record = 1; continue; }
         if (mode == 1 && !strcmp(a, "--records")) { count_records = 1; continue; }
         if (mode == 15 && !strcmp(a, "--occurrences")) { ra.occurrences = 1; continue; }
+        if (mode == 17 && !strcmp(a, "--fasta")) { dbg_fasta = 1; continue; }
         if (mapping && !strcmp(a, "--chain")) { chain = 1; continue; }
         if (mapping && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
         if (!mapping && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
@@ -1852,14 +1934,14 @@ int main(int argc, char **argv) {
             co.max_gap = (uint32_t)v64; gap_given = 1;
         }
         else if (mapping && !strcmp(a, "--mate")) mate = v;
-        else if (mode >= 11 && !strcmp(a, "--min-mapq")) { if (parse_u64(v, &pa.min_mapq) || pa.min_mapq > 60) { fprintf(stderr, "--min-mapq: a quality in 0..60\n"); return 1; } }
-        else if (mode >= 11 && !strcmp(a, "--region")) pa.region = v;
-        else if (mode >= 11 && !strcmp(a, "--window")) { if (parse_u64(v, &pa.window) || pa.window < 1 || pa.window > (1ull << 32)) { fprintf(stderr, "--window: positions per table, 1..2^32\n"); return 1; } }
-        else if (mode >= 11 && !strcmp(a, "--min-depth")) {
+        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--min-mapq")) { if (parse_u64(v, &pa.min_mapq) || pa.min_mapq > 60) { fprintf(stderr, "--min-mapq: a quality in 0..60\n"); return 1; } }
+        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--region")) pa.region = v;
+        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--window")) { if (parse_u64(v, &pa.window) || pa.window < 1 || pa.window > (1ull << 32)) { fprintf(stderr, "--window: positions per table, 1..2^32\n"); return 1; } }
+        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--min-depth")) {
             if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-depth: a depth of at least 0\n"); return 1; }
             pa.call.min_depth = (uint32_t)v64;
         }
-        else if (mode >= 11 && !strcmp(a, "--min-permille")) {
+        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--min-permille")) {
             if (parse_u64(v, &v64) || v64 > 1000) { fprintf(stderr, "--min-permille: a share in 0..1000\n"); return 1; }
             pa.call.min_permille = (uint32_t)v64;
         }
@@ -1896,6 +1978,10 @@ int main(int argc, char **argv) {
         }
         else if (mode == 13 && !strcmp(a, "-k")) {
             if (parse_u64(v, &v64) || v64 < 1 || v64 > 32) { fprintf(stderr, "-k: a k-mer length in 1..32\n"); return 1; }
+            ko.k = (uint32_t)v64; k_given = 1;
+        }
+        else if (mode == 17 && !strcmp(a, "-k")) {
+            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFEull) { fprintf(stderr, "-k: a k-mer length in 1..2^32-2\n"); return 1; }
             ko.k = (uint32_t)v64; k_given = 1;
         }
         else if (mode == 13 && !strcmp(a, "--bins")) {
@@ -1979,6 +2065,11 @@ int main(int argc, char **argv) {
         if (filter_given && !list) { fprintf(stderr, "--at-least, --at-most: only with --list\n"); return 1; }
         if (at_least > at_most) { fprintf(stderr, "--at-least: above --at-most\n"); return 1; }
         return cmd_spectrum(out, (int)device, ko.k, ko.flags, (uint32_t)bins, list, (uint32_t)at_least, (uint32_t)at_most);
+    }
+    if (mode == 17) {
+        if (!out || file) { usage(); return 1; }
+        if (!k_given) { fprintf(stderr, "%s: -k K is required\n", cmd); usage(); return 1; }
+        return cmd_dbg(out, (int)device, ko.k, dbg_fasta);
     }
     if (mode == 14) {
         if (!out || file) { usage(); return 1; }

@@ -565,6 +565,14 @@ class FMIndex:
         self._chk(self._L.debwt_fm_repeat_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def cdbg_stats(self):
+        """What the last EsaResult.cdbg did (debwt_fm_cdbg_stats_get): nodes, edge_strings, unitigs, circular, links, edges,
+        longest_nodes, seq_bytes, jump_rounds, jump_steps and jump_wave_steps of the ranking, rank lines read, scratch
+        bytes, ms per phase and wall ms."""
+        st = _lib.DebwtFmCdbgStats()
+        self._chk(self._L.debwt_fm_cdbg_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def records_stats(self):
         """What the last EsaResult.records_build did (debwt_fm_records_stats_get): rows, pairs (rows whose record occurs in
         an earlier row), records_present, sort_passes, levels and fanout of the hierarchy (DEBWT_FM_REPEAT_FANOUT),
@@ -1075,6 +1083,9 @@ REPEAT_KINDS = {"maximal": 0, "supermaximal": 1, "intervals": 2}                
 RECORDS_UNIQUE = 1                                                                # flags of debwt_fm_record_filter
 REPEAT_IS_MAXIMAL, REPEAT_IS_SUPERMAXIMAL = 1, 2       # flags of a repeat
 REPEAT_DTYPE = np.dtype([("row_lo", "<u8"), ("count", "<u8"), ("left", "<u8", (5,)), ("len", "<u4"), ("flags", "<u4")])
+CDBG_CIRCULAR = 1                                      # flags of a unitig of debwt_fm_cdbg
+UNITIG_DTYPE = np.dtype([("row_lo", "<u8"), ("seq_offset", "<u8"), ("kmer_count", "<u8"), ("nodes", "<u4"), ("flags", "<u4")])
+CDBG_EDGE_DTYPE = np.dtype([("from", "<u4"), ("to", "<u4")])
 CORRECT_SHORT, CORRECT_CLEAN, CORRECT_FIXED, CORRECT_WEAK = 1, 2, 4, 8   # flags of FMIndex.correct's info
 _CORRECT_DTYPE = np.dtype([("flags", np.uint32), ("fixes", np.uint32), ("weak_before", np.uint32), ("weak_after", np.uint32)])
 _TRIAL_DTYPE = np.dtype([("run_a", np.uint32), ("run_b", np.uint32), ("pos", np.uint32), ("window", np.uint32),
@@ -1670,8 +1681,38 @@ class EsaResult:
         q = self._x.info()["nrec"] if min_records is None else int(min_records)
         return self.repeats_by_record(min_len=min_len, min_occ=max(q, 2), kind="maximal", min_records=q, unique=True)
 
+    def cdbg(self, k):
+        """The compacted de Bruijn graph of the collection's k-mers, forward strand (debwt_fm_cdbg, Definition 13).  Needs
+        esa(sa=True, da=True) with max_lcp 0 or at least k + 1.  Returns a CdbgResult."""
+        x = self._x
+        sz = _lib.DebwtFmCdbgSizes()
+        rc = x._L.debwt_fm_cdbg(x._h, int(k), 0, None, 0, None, 0, None, 0, ctypes.byref(sz))   # the sizing call: ERANGE names the sizes
+        if rc != -5:
+            x._chk(rc)
+        un = np.zeros(sz.unitigs, dtype=UNITIG_DTYPE)
+        seq = np.zeros(sz.seq_bytes, dtype=np.uint8)
+        ed = np.zeros(sz.edges, dtype=CDBG_EDGE_DTYPE)
+        if sz.unitigs:
+            x._chk(x._L.debwt_fm_cdbg(x._h, int(k), 0, un.ctypes.data_as(ctypes.c_void_p), len(un),
+                                      seq.ctypes.data_as(ctypes.c_void_p), len(seq), ed.ctypes.data_as(ctypes.c_void_p), len(ed),
+                                      ctypes.byref(sz)))
+        return CdbgResult(int(k), un[:sz.unitigs], seq[:sz.seq_bytes], ed[:sz.edges])
+
     def release(self):
         self._x._chk(self._x._L.debwt_fm_esa_release(self._x._h))
+
+
+class CdbgResult:
+    """What EsaResult.cdbg returns: unitigs (UNITIG_DTYPE: row_lo, seq_offset, kmer_count, nodes, flags with CDBG_CIRCULAR),
+    numbered by the string order of their first k-mers; seq, the unitig strings as ASCII bytes packed in that order; edges
+    (CDBG_EDGE_DTYPE: from, to in unitig numbers, ascending).  strings() cuts seq into one str per unitig."""
+
+    def __init__(self, k, unitigs, seq, edges):
+        self.k, self.unitigs, self.seq, self.edges = k, unitigs, seq, edges
+
+    def strings(self):
+        s = self.seq.tobytes().decode()
+        return [s[int(u["seq_offset"]):int(u["seq_offset"]) + int(u["nodes"]) + self.k - 1] for u in self.unitigs]
 
 
 class OverlapResult:

@@ -38,6 +38,7 @@
 #include "fm_esa_kernels.h"
 #include "fm_repeat_kernels.h"
 #include "fm_record_kernels.h"
+#include "fm_cdbg_kernels.h"
 #include "fm_kmer_kernels.h"
 #include "fm_spectrum_kernels.h"
 #include "fm_graph_kernels.h"
@@ -3008,6 +3009,7 @@ struct debwt_fm {
     debwt_fm_repeat_stats rp_stats{};
     DevBuf rec_P;                     // the kept prefix of debwt_fm_records_build, 8 n bytes exactly (counted in device_bytes)
     debwt_fm_records_stats rc_stats{};
+    debwt_fm_cdbg_stats dbg_stats{};
     DevBuf g_coff, g_state, g_hbase, g_raw, g_flag, g_deg, g_oseg, g_edges, g_eoff, g_len, g_keep, g_out, g_ctr;   // string graph
     debwt_fm_graph_stats g_stats{};
     DevBuf b_state, b_self, b_row, b_cnt, b_whb, b_rawbase, b_tbase, b_pos, b_aoff, b_mm, b_cur, b_cat, b_ctr;   // graph over both strands
@@ -7098,6 +7100,237 @@ extern "C" int debwt_fm_repeats_records(debwt_fm *f, const debwt_fm_repeat_opts 
 extern "C" int debwt_fm_records_stats_get(const debwt_fm *f, debwt_fm_records_stats *out) {
     if (!f || !out) return DEBWT_EINVAL;
     *out = f->rc_stats;
+    return DEBWT_OK;
+}
+
+// ---- compacted de Bruijn graph (fm_cdbg_kernels.h) ----------------------------------------------------------------------
+// One call is a run of launches on the index's stream: the three bitmaps over the rows and their ranks, degrees and links
+// per piece, the ranking rounds (the host reads four counters after each: the list's length, the nodes finished, the
+// cycles found), the first nodes, and for a call that takes the graph the unitig records, the strings and the sorted edge
+// keys.  Everything is allocated into temporaries that are released on every way out; the kept arrays are only read.
+
+static_assert(sizeof(debwt_fm_unitig) == 32, "a record of debwt_fm_cdbg is 32 bytes");
+static_assert(sizeof(debwt_fm_cdbg_edge) == 8, "an edge of debwt_fm_cdbg is 8 bytes");
+
+extern "C" int debwt_fm_cdbg(debwt_fm *f, uint32_t k, uint32_t flags, debwt_fm_unitig *unitigs, uint64_t unitig_capacity,
+                             uint8_t *seq, uint64_t seq_capacity, debwt_fm_cdbg_edge *edges, uint64_t edge_capacity,
+                             debwt_fm_cdbg_sizes *sizes) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!sizes) { f->err = "debwt_fm_cdbg: sizes must not be NULL"; return DEBWT_EINVAL; }
+    if (!k) { f->err = "debwt_fm_cdbg: k must be at least 1"; return DEBWT_EINVAL; }
+    if (flags) { f->err = "debwt_fm_cdbg: unknown flags"; return DEBWT_EINVAL; }
+    if ((unitig_capacity && !unitigs) || (seq_capacity && !seq) || (edge_capacity && !edges)) {
+        f->err = "debwt_fm_cdbg: an array is NULL with capacity > 0"; return DEBWT_EINVAL;
+    }
+    if (!f->has_esa || !f->esa_lcp.p || !f->esa_sa.p || !f->esa_da.p) {
+        f->err = "debwt_fm_cdbg: no build holds lcp, sa and da (debwt_fm_esa_build with DEBWT_FM_ESA_SA | DEBWT_FM_ESA_DA)";
+        return DEBWT_ESTATE;
+    }
+    if ((u64)k + 1 > f->esa_sum.cap) {
+        f->err = "debwt_fm_cdbg: k + 1 is above the cap of the build (" + std::to_string(f->esa_sum.cap) + ")"; return DEBWT_EINVAL;
+    }
+    if (f->n >> 32) { f->err = "debwt_fm_cdbg: the index has 2^32 rows or more"; return DEBWT_EINVAL; }
+    f->dbg_stats = debwt_fm_cdbg_stats{};
+    debwt_fm_cdbg_stats &st = f->dbg_stats;
+    HIPCHK(f, hipSetDevice(f->device));
+    int rc;
+    if (!f->has_text && (rc = debwt_fm_restore_text(f))) return rc;
+    const u64 n = f->n, nrec = f->nrec;
+    auto grid = [](u64 m) { return (u32)std::min<u64>(std::max<u64>(grid_for(m, 256), 1), 1u << 20); };
+    // few workgroups with many items each where a kernel ends in atomics on shared counters or stages a list in LDS
+    auto few = [](u64 m, u64 per) { return (u32)std::min<u64>(std::max<u64>((m + per - 1) / per, 1), 4096); };
+    auto take = [&st](FmTmp &t, size_t bytes) { st.scratch_bytes += bytes; return hipMalloc(&t.p, std::max<size_t>(bytes, 8)); };
+
+    // rows: three bitmaps of one word more than the rows need, ranks over the start and the out bits
+    const u64 nbw = (n >> 6) + 1, rkc = (nbw + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;
+    FmTmp bits, wpre, csum, seps, small;
+    HIPCHK(f, take(bits, (size_t)nbw * 24));
+    HIPCHK(f, take(wpre, (size_t)nbw * 8));
+    HIPCHK(f, take(csum, (size_t)(rkc + 1) * 16));
+    HIPCHK(f, take(seps, (size_t)nrec * 8));
+    HIPCHK(f, take(small, FM_DBG_NCTR * 8));
+    u64 *const d_start = reinterpret_cast<u64 *>(bits.p), *const d_node = d_start + nbw, *const d_out = d_node + nbw;
+    u32 *const d_swpre = reinterpret_cast<u32 *>(wpre.p), *const d_owpre = d_swpre + nbw;
+    u64 *const d_scsum = reinterpret_cast<u64 *>(csum.p), *const d_ocsum = d_scsum + rkc + 1;
+    u64 *const d_seps = reinterpret_cast<u64 *>(seps.p), *const ctr = reinterpret_cast<u64 *>(small.p);
+    std::vector<u64> hs(nrec);                                 // the separator positions
+    for (u64 r = 0; r < nrec; r++) hs[r] = (r + 1 < nrec ? f->rec_starts[r + 1] : n) - 1;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    struct Ev { hipEvent_t *e; ~Ev() { for (int i = 0; i < 5; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int i = 0; i < 5; i++) HIPCHK(f, hipEventCreate(&ev[i]));
+    HIPCHK(f, hipMemcpyAsync(d_seps, hs.data(), (size_t)nrec * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(bits.p, 0, (size_t)nbw * 24, f->stream));
+    HIPCHK(f, hipMemsetAsync(ctr, 0, FM_DBG_NCTR * 8, f->stream));
+    (void)hipEventRecord(ev[0], f->stream);
+    k_fm_cdbg_rows<<<std::min<u32>(grid(n), 8192), 256, 0, f->stream>>>(f->esa_lcp.as<u32>(), f->esa_sa.as<u64>(), f->esa_da.as<u32>(),
+                                                                        d_seps, nrec, n, k, d_start, d_node, d_out, ctr);
+    k_fm_anc_count<<<(u32)rkc, FM_EX_CHUNK_WORDS, 0, f->stream>>>(d_start, nbw, d_swpre, d_scsum);
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(d_scsum, rkc, d_scsum + rkc);
+    k_fm_anc_count<<<(u32)rkc, FM_EX_CHUNK_WORDS, 0, f->stream>>>(d_out, nbw, d_owpre, d_ocsum);
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(d_ocsum, rkc, d_ocsum + rkc);
+    u64 hc[FM_DBG_NCTR], pieces = 0;
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(&pieces, d_scsum + rkc, 8, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    const u64 nodes = hc[FM_DBG_C_NODES], estr = hc[FM_DBG_C_ESTR];
+    st.nodes = nodes; st.edge_strings = estr;
+    if (!pieces || pieces > n || nodes > pieces) { f->err = "debwt_fm_cdbg: the start bits and their rank differ"; return DEBWT_EINTERNAL; }
+    if (!nodes) {                                              // every record is shorter than k
+        *sizes = debwt_fm_cdbg_sizes{0, 0, 0};
+        st.ms_wall = (float)fm_ms_since(t0);
+        return DEBWT_OK;
+    }
+
+    // pieces: first rows, degrees, links
+    const u32 P = (u32)pieces;
+    const u64 nbp = (pieces >> 6) + 1, rkp = (nbp + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;
+    FmTmp lo, od, link, hasnext, s0, s1, l0, l1, hbits, hwpre, hcsum;
+    HIPCHK(f, take(lo, (size_t)(pieces + 1) * 4));
+    HIPCHK(f, take(od, (size_t)pieces * 4));
+    HIPCHK(f, take(link, (size_t)pieces * 4));
+    HIPCHK(f, take(hasnext, (size_t)pieces));
+    HIPCHK(f, take(s0, (size_t)pieces * 16));
+    HIPCHK(f, take(s1, (size_t)pieces * 16));
+    HIPCHK(f, take(l0, (size_t)nodes * 4));
+    HIPCHK(f, take(l1, (size_t)nodes * 4));
+    HIPCHK(f, take(hbits, (size_t)nbp * 8));
+    HIPCHK(f, take(hwpre, (size_t)nbp * 4));
+    HIPCHK(f, take(hcsum, (size_t)(rkp + 1) * 8));
+    u32 *const d_lo = reinterpret_cast<u32 *>(lo.p), *const d_od = reinterpret_cast<u32 *>(od.p), *const d_link = reinterpret_cast<u32 *>(link.p);
+    u8 *const d_next = reinterpret_cast<u8 *>(hasnext.p);
+    uint4 *const d_s[2] = {reinterpret_cast<uint4 *>(s0.p), reinterpret_cast<uint4 *>(s1.p)};
+    u32 *const d_l[2] = {reinterpret_cast<u32 *>(l0.p), reinterpret_cast<u32 *>(l1.p)};
+    const FmDbgBits S{d_start, d_swpre, d_scsum}, O{d_out, d_owpre, d_ocsum};
+    const FmDbgBits H{reinterpret_cast<u64 *>(hbits.p), reinterpret_cast<u32 *>(hwpre.p), reinterpret_cast<u64 *>(hcsum.p)};
+    k_fm_cdbg_lo<<<grid(n), 256, 0, f->stream>>>(S, n, P, d_lo);
+    (void)hipEventRecord(ev[1], f->stream);
+    HIPCHK(f, hipMemsetAsync(d_next, 0, (size_t)pieces, f->stream));
+    k_fm_cdbg_degrees<<<few(pieces, 256), 256, 0, f->stream>>>(f->V, d_lo, P, d_node, S, O, d_od, d_link, ctr);
+    k_fm_cdbg_links<<<few(pieces, 256), 256, 0, f->stream>>>(d_od, d_link, d_next, P, ctr);
+    (void)hipEventRecord(ev[2], f->stream);
+    k_fm_cdbg_init<<<few(pieces, FM_DBG_CHUNK), 256, 0, f->stream>>>(d_link, P, d_s[0], d_s[1], d_l[0], ctr);
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    if (hc[FM_DBG_C_BAD] || hc[FM_DBG_C_LIST] != hc[FM_DBG_C_LINKS] || hc[FM_DBG_C_LINKS] > nodes) {
+        f->err = "debwt_fm_cdbg: " + std::to_string(hc[FM_DBG_C_BAD]) + " left extensions lie in no node, " +
+                 std::to_string(hc[FM_DBG_C_LINKS]) + " links, " + std::to_string(hc[FM_DBG_C_LIST]) + " listed";
+        return DEBWT_EINTERNAL;
+    }
+    const u64 links0 = hc[FM_DBG_C_LINKS];
+
+    // ranking: the first phase ends when every listed node is finished or on a cycle that was found; the second ranks the
+    // cycles after the cut
+    u64 cnt = links0, target = links0, fin = 0, cyclen = 0, cycles = 0;
+    int cur = 0, li = 0;
+    for (int phase = 0; phase < 2 && cnt; phase++) {
+        if (phase == 1) {
+            HIPCHK(f, hipMemsetAsync(ctr + FM_DBG_C_LIST, 0, 3 * 8, f->stream));   // the list, finished, cycle lengths
+            k_fm_cdbg_cut<<<few(cnt, FM_DBG_CHUNK), 256, 0, f->stream>>>(d_s[cur], d_link, d_od, d_next, d_l[li], cnt, d_s[0], d_s[1], d_l[1 - li], ctr);
+            HIPCHK(f, hipMemcpyAsync(&cnt, ctr + FM_DBG_C_LIST, 8, hipMemcpyDeviceToHost, f->stream));
+            if ((rc = fm_sync(f))) return rc;
+            li ^= 1; target = cnt; fin = 0; cyclen = 0;
+        }
+        while (fin + cyclen < target) {
+            u64 h4[4];
+            HIPCHK(f, hipMemsetAsync(ctr + FM_DBG_C_LIST, 0, 8, f->stream));
+            k_fm_cdbg_jump<<<few(cnt, FM_DBG_CHUNK), 256, 0, f->stream>>>(d_s[cur], d_s[1 - cur], d_l[li], cnt, d_l[1 - li], ctr);
+            HIPCHK(f, hipMemcpyAsync(h4, ctr + FM_DBG_C_LIST, sizeof h4, hipMemcpyDeviceToHost, f->stream));
+            if ((rc = fm_sync(f))) return rc;
+            st.jump_rounds++; st.jump_steps += cnt; st.jump_wave_steps += (cnt + 63) / 64 * 64;
+            if (h4[0] > cnt || st.jump_rounds > 80) { f->err = "debwt_fm_cdbg: the ranking does not end"; return DEBWT_EINTERNAL; }
+            cnt = h4[0]; fin = h4[1]; cyclen = h4[2];
+            if (phase == 0) cycles = h4[3];
+            cur ^= 1; li ^= 1;
+        }
+        if (!cycles) break;
+    }
+    (void)hipEventRecord(ev[3], f->stream);
+    if (cycles > links0) return DEBWT_EINTERNAL;
+    const u64 links = links0 - cycles;                         // the link into the first node of a cycle is an edge
+    HIPCHK(f, hipMemsetAsync(hbits.p, 0, (size_t)nbp * 8, f->stream));
+    k_fm_cdbg_heads<<<std::min<u32>(grid(pieces), 8192), 256, 0, f->stream>>>(d_s[cur], d_od, d_link, P, reinterpret_cast<u64 *>(hbits.p), ctr);
+    k_fm_anc_count<<<(u32)rkp, FM_EX_CHUNK_WORDS, 0, f->stream>>>(H.bits, nbp, reinterpret_cast<u32 *>(hwpre.p), reinterpret_cast<u64 *>(hcsum.p));
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(reinterpret_cast<u64 *>(hcsum.p), rkp, reinterpret_cast<u64 *>(hcsum.p) + rkp);
+    u64 U = 0;
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(&U, H.csum + rkp, 8, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    (void)hipEventElapsedTime(&st.ms_nodes, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&st.ms_links, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&st.ms_rank, ev[2], ev[3]);
+    if (U != nodes - links || estr < links) {
+        f->err = "debwt_fm_cdbg: " + std::to_string(U) + " first nodes, " + std::to_string(nodes) + " nodes and " + std::to_string(links) + " links";
+        return DEBWT_EINTERNAL;
+    }
+    const u64 E = estr - links, seq_bytes = nodes + U * ((u64)k - 1);
+    st.unitigs = U; st.circular = cycles; st.links = links; st.edges = E; st.longest_nodes = hc[FM_DBG_C_LONGEST];
+    st.seq_bytes = seq_bytes; st.rank_lines = hc[FM_DBG_C_LINES];
+    *sizes = debwt_fm_cdbg_sizes{U, seq_bytes, E};
+    if (unitig_capacity < U || seq_capacity < seq_bytes || edge_capacity < E) {
+        st.ms_wall = (float)fm_ms_since(t0);
+        f->err = "debwt_fm_cdbg: a capacity is below its size (" + std::to_string(U) + " unitigs, " + std::to_string(seq_bytes) +
+                 " bytes, " + std::to_string(E) + " edges)";
+        return DEBWT_ERANGE;
+    }
+
+    // the write pass
+    const u64 ntiles = (U + FM_REC_TILE - 1) / FM_REC_TILE;
+    FmTmp dun, dlen, dP, tsum, dseq, ka, kb, rws, dedge;
+    HIPCHK(f, take(dun, (size_t)U * sizeof(debwt_fm_unitig)));
+    HIPCHK(f, take(dlen, (size_t)U * 8));
+    HIPCHK(f, take(dP, (size_t)U * 8));
+    HIPCHK(f, take(tsum, (size_t)(ntiles + 1) * 8));
+    HIPCHK(f, take(dseq, (size_t)seq_bytes));
+    debwt_fm_unitig *const d_un = reinterpret_cast<debwt_fm_unitig *>(dun.p);
+    u64 *const d_len = reinterpret_cast<u64 *>(dlen.p), *const d_P = reinterpret_cast<u64 *>(dP.p), *const d_tsum = reinterpret_cast<u64 *>(tsum.p);
+    HIPCHK(f, hipMemsetAsync(dun.p, 0, (size_t)U * sizeof(debwt_fm_unitig), f->stream));
+    k_fm_cdbg_unitigs<<<std::min<u32>(grid(pieces), 8192), 256, 0, f->stream>>>(d_s[cur], d_od, d_link, d_next, d_lo, P, H, U, k, d_un, d_len);
+    k_fm_rec_tile_sums<u64><<<(u32)ntiles, FM_REC_TILE, 0, f->stream>>>(d_len, U, d_tsum);
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(d_tsum, ntiles, d_tsum + ntiles);
+    k_fm_rec_scan<u64><<<(u32)ntiles, FM_REC_TILE, 0, f->stream>>>(d_len, U, d_tsum, d_P);
+    k_fm_cdbg_seq<<<grid(pieces), 256, 0, f->stream>>>(d_s[cur], d_od, d_link, d_lo, P, H, U, k, d_P, d_len, f->esa_sa.as<u64>(),
+                                                       f->text.as<u64>(), n, d_un, reinterpret_cast<u8 *>(dseq.p), seq_bytes);
+    if (E) {
+        const u32 ub = std::max<u32>(fm_bits_of(U - 1), 1);
+        const size_t ws_bytes = radix_workspace_bytes(E);
+        HIPCHK(f, take(ka, (size_t)E * 8));
+        HIPCHK(f, take(kb, (size_t)E * 8));
+        HIPCHK(f, take(rws, ws_bytes));
+        HIPCHK(f, take(dedge, (size_t)E * sizeof(debwt_fm_cdbg_edge)));
+        k_fm_cdbg_edges<<<few(pieces, 256), 256, 0, f->stream>>>(f->V, d_s[cur], d_od, d_link, d_lo, P, S, H, ub, reinterpret_cast<u64 *>(ka.p), E, ctr);
+        const u64 *sorted = reinterpret_cast<u64 *>(ka.p);
+        if (E >= 2) {
+            RadixWorkspace ws{};
+            ws.counts = reinterpret_cast<u32 *>(rws.p);        // chunk histograms only, as debwt_fm_records_build sorts
+            hipError_t e = hipSuccess;
+            sorted = radix_sort_bits(f->stream, reinterpret_cast<u64 *>(ka.p), reinterpret_cast<u64 *>(kb.p), E, 0, (int)(2 * ub), ws, &e);
+            if (e != hipSuccess) { f->err = std::string("debwt_fm_cdbg: the key sort: ") + hipGetErrorString(e); return DEBWT_EDEVICE; }
+        }
+        k_fm_cdbg_edge_out<<<grid(E), 256, 0, f->stream>>>(sorted, E, ub, reinterpret_cast<debwt_fm_cdbg_edge *>(dedge.p));
+        HIPCHK(f, hipMemcpyAsync(edges, dedge.p, (size_t)E * sizeof(debwt_fm_cdbg_edge), hipMemcpyDeviceToHost, f->stream));
+    }
+    (void)hipEventRecord(ev[4], f->stream);
+    u64 total = 0;
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(&total, d_tsum + ntiles, 8, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(unitigs, dun.p, (size_t)U * sizeof(debwt_fm_unitig), hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(seq, dseq.p, (size_t)seq_bytes, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    (void)hipEventElapsedTime(&st.ms_write, ev[3], ev[4]);
+    st.rank_lines = hc[FM_DBG_C_LINES];
+    if (total != seq_bytes || hc[FM_DBG_C_EDGES] != E) {
+        f->err = "debwt_fm_cdbg: the write pass made " + std::to_string(total) + " bytes and " + std::to_string(hc[FM_DBG_C_EDGES]) +
+                 " edges, the count said " + std::to_string(seq_bytes) + " and " + std::to_string(E);
+        return DEBWT_EINTERNAL;
+    }
+    st.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_cdbg_stats_get(const debwt_fm *f, debwt_fm_cdbg_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->dbg_stats;
     return DEBWT_OK;
 }
 

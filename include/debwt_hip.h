@@ -1362,6 +1362,73 @@ typedef struct {
 } debwt_fm_records_stats;
 int debwt_fm_records_stats_get(const debwt_fm *fm, debwt_fm_records_stats *out);
 
+/* ---- Definition 13 (compacted de Bruijn graph): unitigs and edges of the k-mers of the collection (fm_cdbg_kernels.h) --
+ * Rows, sa, da, lcp (the STORED array), d(), L[r] and the symbol order are those of Definitions 10 and 11.  k >= 1.
+ * Forward strand only: a k-mer and its reverse complement are two nodes, and nothing joins them (bidirected unitigs over
+ * canonical k-mers are not built here).
+ *   Node.  A string W of k bases with occ W > 0 inside records: Definition 9, forward, for any k.  Its interval is [i, e)
+ *     with lcp[i] < k <= d(sa[i]) and e the next row with lcp < k, or n; occ W = e - i.  A row with d(sa[r]) < k always has
+ *     lcp[r] < k: it starts a piece that is no node.
+ *   Edge string.  A string of k + 1 bases with occ > 0 inside records; it runs from its first k bases to its last k.
+ *     out(W) is the number of rows r of [i, e) with (r = i or lcp[r] = k) and d(sa[r]) >= k + 1.  in(W) is the number of
+ *     bases c with a row of [i, e) whose L is c (an occurrence that starts a record adds nothing); the node that enters W
+ *     by c holds row C[c] + occ(c, i).
+ *   Link.  u -> v iff out(u) = 1, v is u's only successor, in(v) = 1 and u != v (the rule of Definition 4).
+ *   Unitig.  A maximal chain of links; every node is in exactly one.  A node with no incoming link starts one.  A
+ *     component in which every node has an incoming link is a cycle: it starts at its node of the lowest row and is flagged
+ *     DEBWT_FM_CDBG_CIRCULAR, and the link into that node counts as an edge, not as a member link.  Unitigs are numbered by
+ *     ascending row of their first node, the string order of their first k-mers.  The string is the first node's k bases
+ *     and the last base of every later node, nodes + k - 1 bases; kmer_count is the sum of occ over the nodes.
+ *   Edge.  Every edge string that is no member link runs from the LAST node of a unitig to the FIRST node of one (the
+ *     same one, perhaps).  The list holds (from, to) in unitig numbers, ascending by (from, to); no pair occurs twice.
+ * Three facts (tests/cdbg_ref.py asserts them), distinct[] as debwt_fm_esa_profile answers:
+ *   1. the sum of nodes over the unitigs = distinct[k - 1];
+ *   2. the sum of (nodes - 1) over the unitigs + the number of edges = distinct[k], the distinct (k+1)-mers;
+ *   3. the sum of kmer_count = the sum over the records S of max(0, |S| - k + 1).
+ * A record: row_lo = the first row of the first node's interval; seq_offset = where the unitig's string begins in seq,
+ * ASCII A, C, G, T, the strings packed in unitig order (seq_bytes = the sum of nodes + k - 1).
+ *
+ * The method.  Needs a build with DEBWT_FM_ESA_SA and DEBWT_FM_ESA_DA whose cap is 0 or at least k + 1 (the call must tell
+ * lcp = k from lcp > k), and the text (restored when none is attached); it changes none of the kept arrays.  Limit: an
+ * index of fewer than 2^32 rows.  One lane per row writes a start bit (lcp < k), a node bit and an out bit; a rank over the
+ * start bits numbers the pieces, out() is a difference of ranks over the out bits, in() and the predecessor come from
+ * the rank line(s) of the two ends of the interval.  The chains are ranked by pointer doubling towards the first node over
+ * a compacted list of the unfinished nodes, states in two buffers so that no lane reads what another writes in the round; a
+ * cycle shows when the span of its lowest node comes back to it, with its length, so an input without cycles ends when
+ * its longest chain is ranked, and one with cycles ranks them in a second phase after the cut: at most ceil(log2(longest))
+ * + 1 rounds a phase.  Unitig numbers are the rank over a bitmap of first nodes; kmer_count is summed inside a wave before
+ * one lane adds to the unitig (integer adds); the edge keys are ordered by the stable radix passes of
+ * debwt_fm_records_build.  No result depends on launch geometry or on the order in which atomics arrive.
+ * Scratch, all released before the call returns, pieces = the rows with lcp < k, nodes <= pieces: n / 2 bytes (three
+ * bitmaps over the rows, the ranks of two), 8 nrec (separators), 45 bytes per piece (lo, out, link, successor mark, two
+ * states of 16 bytes) + 3 pieces / 16 (first nodes and their rank) + 8 bytes per node (two lists); a call that writes
+ * adds 48 bytes per unitig + 8 per 256 unitigs, seq_bytes, and 24 bytes per edge + 16 MiB (keys, sort scratch, the list;
+ * radix workspace).  A failed allocation is DEBWT_ENOMEM and leaves the kept arrays as they were. */
+#define DEBWT_FM_CDBG_CIRCULAR 1u
+typedef struct { uint64_t row_lo, seq_offset, kmer_count; uint32_t nodes, flags; } debwt_fm_unitig;   /* 32 bytes */
+typedef struct { uint32_t from, to; } debwt_fm_cdbg_edge;
+typedef struct { uint64_t unitigs, seq_bytes, edges; } debwt_fm_cdbg_sizes;
+/* sizes is written first; DEBWT_ERANGE when any capacity is below its size (the protocol of debwt_fm_repeats; all
+ * capacities 0 with NULL arrays is the sizing call, which skips the write pass).  flags: none defined, must be 0.  An index
+ * whose records are all shorter than k answers DEBWT_OK with all sizes 0.  DEBWT_EINVAL for k = 0, unknown flags, a NULL
+ * sizes, a NULL array with capacity > 0, k + 1 above the cap of a capped build and an index of 2^32 rows or more;
+ * DEBWT_ESTATE without a build or with a build that kept no sa or no da. */
+int debwt_fm_cdbg(debwt_fm *fm, uint32_t k, uint32_t flags, debwt_fm_unitig *unitigs, uint64_t unitig_capacity,
+                  uint8_t *seq, uint64_t seq_capacity, debwt_fm_cdbg_edge *edges, uint64_t edge_capacity,
+                  debwt_fm_cdbg_sizes *sizes);
+/* what the last debwt_fm_cdbg did: nodes, edge strings (the sum of out()), unitigs, the circular ones, links (member
+ * links: edge_strings = links + edges), edges, the nodes of the longest unitig, seq_bytes, jump_rounds (rounds of both
+ * ranking phases), jump_steps (node visits of those rounds), jump_wave_steps (64 x the waves the rounds launched:
+ * jump_steps / jump_wave_steps is the share of lanes busy), rank_lines (rank lines read for left counts, the edges of a
+ * write pass included), scratch_bytes (everything the call allocated), ms per phase (events: nodes = bits, ranks and lo;
+ * links = degrees and links; rank = the rounds; write = unitigs, strings and edges) and host wall time */
+typedef struct {
+    uint64_t nodes, edge_strings, unitigs, circular, links, edges, longest_nodes, seq_bytes, jump_rounds, jump_steps,
+        jump_wave_steps, rank_lines, scratch_bytes;
+    float ms_nodes, ms_links, ms_rank, ms_write, ms_wall;
+} debwt_fm_cdbg_stats;
+int debwt_fm_cdbg_stats_get(const debwt_fm *fm, debwt_fm_cdbg_stats *out);
+
 /* ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
  * Records S_0 .. S_{nrec-1} are those of the index, numbered as in overlap hits; |S| is the length of S.
  * 1. state[i] = 1 (duplicate) iff some j < i has S_j == S_i; otherwise 2 (contained) iff S_i is a substring of a strictly
