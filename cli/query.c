@@ -157,6 +157,7 @@
  * count, 6 zero words -- then the samples.  OUT does not carry n (its last word is padded): the header does, and a header
  * that does not match OUT, OUT.# and OUT.$ is refused.
  */
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -167,6 +168,33 @@
 
 #define SA_MAGIC 0x3141534657424544ull   /* "DEBWFSA1" */
 #define SA_HEADER_WORDS 16
+
+/* the subcommands; bit c of an option's mask (struct option, below) stands for command c */
+enum cmd { CMD_INDEX, CMD_COUNT, CMD_LOCATE, CMD_MEMS, CMD_MAP, CMD_PILEUP, CMD_CONSENSUS, CMD_OVERLAPS, CMD_EXTRACT, CMD_KMERS,
+           CMD_CORRECT, CMD_SPECTRUM, CMD_LCP, CMD_REPEATS, CMD_MUMS, CMD_DBG, CMD_GRAPH, CMD_UNITIGS };
+
+/* everything the command line says: set_defaults() fills it, the option table writes into it, the commands read it */
+struct query_args {
+    enum cmd cmd; const char *name;                                         /* the subcommand */
+    const char *out, *file;                                                 /* -i, and the argument that is no option */
+    int device;
+    uint64_t threads, seed, sa_sample; int iupac;                           /* index, and --ref of the commands that map */
+    uint64_t max_hits; uint32_t mismatches, mem_len, flags;                 /* count, locate, mems, overlaps, kmers */
+    int search, count_records;                                              /* search: an option of debwt_fm_search was given */
+    uint32_t min_overlap, ovl_k, ovl_permille; int no_self, ovl_mm, permille_given;       /* overlaps; min_overlap: graph too */
+    const char *ref, *mate; int chain, gap_given, insert_given, no_rescue;  /* map, pileup, consensus */
+    debwt_fm_map_opts mo; debwt_fm_chain_opts co; debwt_fm_pair_opts po;
+    const char *region, *variants; uint64_t window, min_mapq; debwt_fm_pile_opts call;    /* pileup, consensus */
+    int all;                                                                /* extract */
+    debwt_fm_correct_opts ko; int k_given, auto_count; const char *report;  /* kmers, correct, spectrum, dbg: ko.k, ko.flags */
+    uint32_t bins, at_least, at_most; const char *list; int filter_given;   /* spectrum */
+    uint32_t max_lcp, profile_k; const char *lcp_file, *sa_file, *da_file;  /* lcp; max_lcp: repeats too */
+    /* repeats, mums.  by_record: --min-records, --max-records or --unique was given (a column `rec` then follows `occ`);
+     * min_records 0 stands for 1, and under mums for every record of the index */
+    uint32_t min_len, kind; uint64_t min_occ, max_occ, min_records, max_records; int seq, occurrences, unique, by_record, kind_given;
+    int fasta;                                                              /* dbg */
+    int all_edges, both, clean; const char *states; debwt_fm_clean_opts cl; /* graph, unitigs */
+};
 
 static void usage(void) {
     fprintf(stderr,
@@ -319,14 +347,14 @@ static int read_rows(const char *out, struct rows *r) {
 
 /* ---- index ---------------------------------------------------------------------------------------------------------- */
 
-static int cmd_index(const char *out, const char *input, uint64_t threads, int iupac, uint64_t seed, int device, uint64_t s) {
-    debwt_config cfg = {32, device, 0, 0};
+static int cmd_index(const struct query_args *A) {
+    debwt_config cfg = {32, A->device, 0, 0};
     debwt_ctx *ctx = NULL;
     int rc = debwt_create(&cfg, &ctx);
     if (rc) { fprintf(stderr, "debwt_create: %s\n", debwt_strerror(rc)); return 1; }
-    rc = debwt_load_fasta_opts(ctx, input, (int)threads, iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, seed);
+    rc = debwt_load_fasta_opts(ctx, A->file, (int)A->threads, A->iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, A->seed);
     if (rc) {
-        fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", input,
+        fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", A->file,
                 debwt_last_error(ctx));
         debwt_destroy(ctx);
         return 1;
@@ -334,15 +362,15 @@ static int cmd_index(const char *out, const char *input, uint64_t threads, int i
     debwt_stats st;
     debwt_get_stats(ctx, &st);
     struct rows r;
-    if (read_rows(out, &r)) { debwt_destroy(ctx); return 1; }
+    if (read_rows(A->out, &r)) { debwt_destroy(ctx); return 1; }
     debwt_fm *fm = NULL;
     if (r.nwords != (st.n + 31) / 32 || r.nhash != st.nrec - 1) {
-        fprintf(stderr, "%s is not the BWT of %s: %llu rows / %llu '#' rows expected\n", out, input,
+        fprintf(stderr, "%s is not the BWT of %s: %llu rows / %llu '#' rows expected\n", A->out, A->file,
                 (unsigned long long)st.n, (unsigned long long)(st.nrec - 1));
         rc = DEBWT_EINVAL;
     } else {
-        rc = debwt_fm_create(ctx, r.words, r.hash, r.dollar, (uint32_t)s, &fm);
-        if (rc) fprintf(stderr, "%s is not the BWT of %s: %s\n", out, input, debwt_last_error(ctx));
+        rc = debwt_fm_create(ctx, r.words, r.hash, r.dollar, (uint32_t)A->sa_sample, &fm);
+        if (rc) fprintf(stderr, "%s is not the BWT of %s: %s\n", A->out, A->file, debwt_last_error(ctx));
     }
     debwt_destroy(ctx);                                   /* the index keeps what it needs */
     int ret = rc ? 1 : 0;
@@ -350,7 +378,7 @@ static int cmd_index(const char *out, const char *input, uint64_t threads, int i
         debwt_fm_info info;
         debwt_fm_info_get(fm, &info);
         uint64_t *buf = malloc((SA_HEADER_WORDS + info.samples) * 8);
-        char *psa = with_suffix(out, ".sa");
+        char *psa = with_suffix(A->out, ".sa");
         FILE *f = psa ? fopen(psa, "wb") : NULL;
         if (buf && f) {
             memset(buf, 0, SA_HEADER_WORDS * 8);
@@ -505,38 +533,39 @@ static int cmp_u64(const void *a, const void *b) {
     return x < y ? -1 : x > y;
 }
 
-static int cmd_query(const char *out, const char *pfile, int device, int locate, uint64_t max_hits, int records) {
+static int cmd_query(const struct query_args *A) {
+    const int locate = A->cmd == CMD_LOCATE;
     struct patterns P;
-    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1;
     uint64_t *ranges = malloc((P.n ? P.n : 1) * 16), *oo = malloc((P.n + 1) * 8), *pos = NULL, *starts = NULL;
-    uint64_t *nrecs = records ? malloc((P.n ? P.n : 1) * 8) : NULL;
+    uint64_t *nrecs = A->count_records ? malloc((P.n ? P.n : 1) * 8) : NULL;
     debwt_fm_info info;
     debwt_fm_info_get(fm, &info);
     starts = malloc(info.nrec * 8);
-    if (!ranges || !oo || !starts || (records && !nrecs)) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (!ranges || !oo || !starts || (A->count_records && !nrecs)) { fprintf(stderr, "out of memory\n"); goto done; }
     int rc = debwt_fm_count(fm, P.seq, P.off, P.n, ranges);
     if (!rc) rc = debwt_fm_record_starts(fm, starts, info.nrec);
     /* the range of a pattern is closed (Definition 12) on the uncapped array, whatever its length */
-    if (!rc && records) rc = debwt_fm_esa_build(fm, 0, DEBWT_FM_ESA_DA);
-    if (!rc && records) rc = debwt_fm_records_build(fm);
-    if (!rc && records) rc = debwt_fm_record_counts(fm, ranges, P.n, nrecs);
+    if (!rc && A->count_records) rc = debwt_fm_esa_build(fm, 0, DEBWT_FM_ESA_DA);
+    if (!rc && A->count_records) rc = debwt_fm_records_build(fm);
+    if (!rc && A->count_records) rc = debwt_fm_record_counts(fm, ranges, P.n, nrecs);
     if (!rc && locate) {
         uint64_t total = 0;
         for (uint64_t i = 0; i < P.n; i++) {
             uint64_t c = ranges[2 * i + 1] - ranges[2 * i];
-            total += max_hits && c > max_hits ? max_hits : c;
+            total += A->max_hits && c > A->max_hits ? A->max_hits : c;
         }
         pos = malloc((total ? total : 1) * 8);
         if (!pos) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = debwt_fm_locate(fm, ranges, P.n, max_hits, oo, pos, total);
+        rc = debwt_fm_locate(fm, ranges, P.n, A->max_hits, oo, pos, total);
     }
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     for (uint64_t i = 0; i < P.n; i++) {
         printf("%s\t%llu", P.name[i], (unsigned long long)(ranges[2 * i + 1] - ranges[2 * i]));
-        if (records) printf("\t%llu", (unsigned long long)nrecs[i]);
+        if (A->count_records) printf("\t%llu", (unsigned long long)nrecs[i]);
         if (locate) {
             uint64_t *a = pos + oo[i], m = oo[i + 1] - oo[i], rec = 0;
             qsort(a, m, 8, cmp_u64);
@@ -566,12 +595,12 @@ static int cmp_occ(const void *a, const void *b) {
     return (x->strand > y->strand) - (x->strand < y->strand);
 }
 
-static int cmd_search(const char *out, const char *pfile, int device, int locate, uint64_t max_hits, uint32_t K,
-                      uint32_t flags) {
+static int cmd_search(const struct query_args *A) {
+    const int locate = A->cmd == CMD_LOCATE;
     struct patterns P;
-    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1, rc;
     uint64_t cap = 4 * P.n + 16, *hoff = malloc((P.n + 1) * 8), *ranges = NULL, *oo = NULL, *pos = NULL, *starts = NULL;
     uint32_t *info = NULL;
@@ -584,7 +613,7 @@ static int cmd_search(const char *out, const char *pfile, int device, int locate
         free(ranges); free(info);
         ranges = malloc(cap * 16); info = malloc(cap * 4);
         if (!ranges || !info) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = debwt_fm_search(fm, P.seq, P.off, P.n, K, flags, hoff, ranges, info, cap);
+        rc = debwt_fm_search(fm, P.seq, P.off, P.n, A->mismatches, A->flags, hoff, ranges, info, cap);
         if (rc == DEBWT_ERANGE && hoff[P.n] > cap) { cap = hoff[P.n]; continue; }
         break;
     }
@@ -606,7 +635,7 @@ static int cmd_search(const char *out, const char *pfile, int device, int locate
         }
         printf("%s\t%llu\t", P.name[i], (unsigned long long)t);
         if (!locate) {
-            for (uint32_t k = 0; k <= K; k++) printf("%s%llu", k ? "," : "", (unsigned long long)per[k]);
+            for (uint32_t k = 0; k <= A->mismatches; k++) printf("%s%llu", k ? "," : "", (unsigned long long)per[k]);
         } else {
             uint64_t m = 0;
             for (uint64_t h = hoff[i]; h < hoff[i + 1]; h++)
@@ -617,7 +646,7 @@ static int cmd_search(const char *out, const char *pfile, int device, int locate
                     m++;
                 }
             qsort(occ, m, sizeof *occ, cmp_occ);
-            if (max_hits && m > max_hits) m = max_hits;
+            if (A->max_hits && m > A->max_hits) m = A->max_hits;
             for (uint64_t j = 0; j < m; j++)
                 printf("%s%llu:%llu:%c:%u", j ? "," : "", (unsigned long long)occ[j].rec, (unsigned long long)occ[j].off,
                        occ[j].strand ? '-' : '+', occ[j].mm);
@@ -632,11 +661,11 @@ done:
     return ret;
 }
 
-static int cmd_mems(const char *out, const char *pfile, int device, uint64_t max_hits, uint32_t min_len, uint32_t flags) {
+static int cmd_mems(const struct query_args *A) {
     struct patterns P;
-    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1, rc;
     uint64_t cap = 4 * P.n + 16, *moff = malloc((P.n + 1) * 8), *ranges = NULL, *oo = NULL, *pos = NULL, *starts = NULL;
     uint32_t *spans = NULL;
@@ -649,7 +678,7 @@ static int cmd_mems(const char *out, const char *pfile, int device, uint64_t max
         free(spans); free(ranges); free(strand);
         spans = malloc(cap * 8); ranges = malloc(cap * 16); strand = malloc(cap);
         if (!spans || !ranges || !strand) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = debwt_fm_mems(fm, P.seq, P.off, P.n, min_len, flags, moff, spans, ranges, strand, cap);
+        rc = debwt_fm_mems(fm, P.seq, P.off, P.n, A->mem_len, A->flags, moff, spans, ranges, strand, cap);
         if (rc == DEBWT_ERANGE && moff[P.n] > cap) { cap = moff[P.n]; continue; }
         break;
     }
@@ -658,12 +687,12 @@ static int cmd_mems(const char *out, const char *pfile, int device, uint64_t max
     uint64_t total = 0;
     for (uint64_t h = 0; h < nm; h++) {
         const uint64_t c = ranges[2 * h + 1] - ranges[2 * h];
-        total += max_hits && c > max_hits ? max_hits : c;
+        total += A->max_hits && c > A->max_hits ? A->max_hits : c;
     }
     if (!rc) {
         oo = malloc((nm + 1) * 8); pos = malloc((total ? total : 1) * 8);
         if (!oo || !pos) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = debwt_fm_locate(fm, ranges, nm, max_hits, oo, pos, total);
+        rc = debwt_fm_locate(fm, ranges, nm, A->max_hits, oo, pos, total);
     }
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     for (uint64_t i = 0; i < P.n; i++)
@@ -687,12 +716,11 @@ done:
 }
 
 /* mm: --max-mismatches was given (the call with a mismatch budget and the sixth column) */
-static int cmd_overlaps(const char *out, const char *pfile, int device, uint32_t min_overlap, uint32_t flags, int no_self,
-                        int mm, uint32_t K, uint32_t permille) {
+static int cmd_overlaps(const struct query_args *A) {
     struct patterns P;
-    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1, rc;
     uint64_t cap = 4 * P.n + 16, *hoff = malloc((P.n + 1) * 8);
     debwt_fm_overlap *hits = NULL;
@@ -701,8 +729,8 @@ static int cmd_overlaps(const char *out, const char *pfile, int device, uint32_t
         free(hits);
         hits = malloc(cap * sizeof *hits);
         if (!hits) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = mm ? debwt_fm_overlaps_mm(fm, P.seq, P.off, P.n, min_overlap, K, permille, flags, hoff, hits, cap)
-                : debwt_fm_overlaps(fm, P.seq, P.off, P.n, min_overlap, flags, hoff, hits, cap);
+        rc = A->ovl_mm ? debwt_fm_overlaps_mm(fm, P.seq, P.off, P.n, A->min_overlap, A->ovl_k, A->ovl_permille, A->flags, hoff, hits, cap)
+                : debwt_fm_overlaps(fm, P.seq, P.off, P.n, A->min_overlap, A->flags, hoff, hits, cap);
         if (rc == DEBWT_ERANGE && hoff[P.n] > cap) { cap = hoff[P.n]; continue; }
         break;
     }
@@ -711,11 +739,11 @@ static int cmd_overlaps(const char *out, const char *pfile, int device, uint32_t
         const uint64_t m = P.off[i + 1] - P.off[i];
         for (uint64_t h = hoff[i]; h < hoff[i + 1]; h++) {
             const debwt_fm_overlap *o = hits + h;
-            if (no_self && !o->strand && o->record == i && o->length == m) continue;
+            if (A->no_self && !o->strand && o->record == i && o->length == m) continue;
             printf("%s\t%c\t%u\t%u\t%s", P.name[i], o->strand ? '-' : '+', o->record, o->length,
                    (o->flags & 3u) == 3u ? "CW" : (o->flags & DEBWT_FM_OVERLAP_CONTAINS) ? "C" :
                    (o->flags & DEBWT_FM_OVERLAP_WHOLE) ? "W" : ".");
-            if (mm) printf("\t%u", DEBWT_FM_OVERLAP_MM(o->flags));
+            if (A->ovl_mm) printf("\t%u", DEBWT_FM_OVERLAP_MM(o->flags));
             putchar('\n');
         }
     }
@@ -749,8 +777,8 @@ static void paf_line(const char *name, uint64_t m, const debwt_fm_hit *h, const 
 
 /* the text the mappers read: --ref packed as index packs it and checked against the index, or, without --ref, restored
  * from the index itself */
-static int map_text(debwt_fm *fm, const char *out, const char *ref, uint64_t threads, int iupac, uint64_t seed,
-                    const debwt_fm_info *fi, debwt_packed_text *pt) {
+static int map_text(debwt_fm *fm, const struct query_args *A, const debwt_fm_info *fi, debwt_packed_text *pt) {
+    const char *out = A->out, *ref = A->ref;
     char err[256] = "";
     int rc;
     if (!ref) {
@@ -758,7 +786,7 @@ static int map_text(debwt_fm *fm, const char *out, const char *ref, uint64_t thr
         if (rc) fprintf(stderr, "%s.sa does not restore the text of %s: %s\n", out, out, debwt_fm_last_error(fm));
         return rc ? -1 : 0;
     }
-    rc = debwt_pack_fasta_opts(ref, (int)threads, iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, seed, pt, err, sizeof err);
+    rc = debwt_pack_fasta_opts(ref, (int)A->threads, A->iupac ? DEBWT_FASTA_IUPAC_RANDOM : 0u, A->seed, pt, err, sizeof err);
     if (rc) {
         fprintf(stderr, "%s: %s (sequence must be ACGT only unless --iupac is given, records > 32 bases)\n", ref, err);
         return -1;
@@ -773,12 +801,11 @@ static int map_text(debwt_fm *fm, const char *out, const char *ref, uint64_t thr
     return 0;
 }
 
-static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t threads, int iupac, uint64_t seed, int device,
-                   const debwt_fm_map_opts *opts, int chain, uint32_t max_gap) {
+static int cmd_map(const struct query_args *A) {
     struct patterns P;
-    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1, rc;
     debwt_packed_text pt;
     memset(&pt, 0, sizeof pt);
@@ -789,19 +816,19 @@ static int cmd_map(const char *out, const char *ref, const char *pfile, uint64_t
     debwt_fm_info_get(fm, &fi);
     starts = malloc((fi.nrec + 1) * 8);
     if (!coff || !hits || !starts) { fprintf(stderr, "out of memory\n"); goto done; }
-    if (map_text(fm, out, ref, threads, iupac, seed, &fi, &pt)) goto done;
+    if (map_text(fm, A, &fi, &pt)) goto done;
     for (;;) {                                            /* grow to the exact op count on DEBWT_ERANGE */
         free(cig);
         cig = malloc(cap * 4);
         if (!cig) { fprintf(stderr, "out of memory\n"); goto done; }
-        if (chain) {
+        if (A->chain) {
             debwt_fm_chain_opts co;
             debwt_fm_chain_defaults(&co);
-            co.map = *opts;
-            co.max_gap = max_gap;
+            co.map = A->mo;
+            co.max_gap = A->co.max_gap;
             rc = debwt_fm_map_chained(fm, P.seq, P.off, P.n, &co, hits, coff, cig, cap, NULL, NULL, 0);
         } else {
-            rc = debwt_fm_map(fm, P.seq, P.off, P.n, opts, hits, coff, cig, cap);
+            rc = debwt_fm_map(fm, P.seq, P.off, P.n, &A->mo, hits, coff, cig, cap);
         }
         if (rc == DEBWT_ERANGE && coff[P.n] > cap) { cap = coff[P.n]; continue; }
         break;
@@ -825,21 +852,29 @@ done:
 
 /* ---- map --mate: paired ends ----------------------------------------------------------------------------------------- */
 
-static int cmd_map_pairs(const char *out, const char *ref, const char *pfile, const char *mfile, uint64_t threads, int iupac,
-                         uint64_t seed, int device, const debwt_fm_pair_opts *opts) {
+/* the pair options of the command line: they carry the map options, and --no-rescue rescues no mate */
+static debwt_fm_pair_opts pair_opts(const struct query_args *A) {
+    debwt_fm_pair_opts po = A->po;
+    po.map = A->mo;
+    if (A->no_rescue) po.max_rescue = 0;
+    return po;
+}
+
+static int cmd_map_pairs(const struct query_args *A) {
+    const debwt_fm_pair_opts po = pair_opts(A);
     struct patterns P, M, B;                              /* mates 1, mates 2, both interleaved (names stay in P and M) */
     memset(&P, 0, sizeof P); memset(&M, 0, sizeof M); memset(&B, 0, sizeof B);
-    if (read_patterns(pfile, &P)) return 1;
-    if (read_patterns(mfile, &M)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) return 1;
+    if (read_patterns(A->mate, &M)) { free_patterns(&P); return 1; }
     if (P.n != M.n) {
-        fprintf(stderr, "--mate: %s holds %llu reads, %s holds %llu: read i of one is the mate of read i of the other\n", mfile,
-                (unsigned long long)M.n, pfile, (unsigned long long)P.n);
+        fprintf(stderr, "--mate: %s holds %llu reads, %s holds %llu: read i of one is the mate of read i of the other\n", A->mate,
+                (unsigned long long)M.n, A->file, (unsigned long long)P.n);
         free_patterns(&P); free_patterns(&M);
         return 1;
     }
     const uint64_t np = P.n, nr = 2 * np;
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); free_patterns(&M); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); free_patterns(&M); return 1; }
     int ret = 1, rc;
     debwt_packed_text pt;
     memset(&pt, 0, sizeof pt);
@@ -861,12 +896,12 @@ static int cmd_map_pairs(const char *out, const char *ref, const char *pfile, co
         memcpy(B.seq + B.off[2 * i + 1], M.seq + M.off[i], l2);
         B.off[2 * i + 2] = B.off[2 * i + 1] + l2;
     }
-    if (map_text(fm, out, ref, threads, iupac, seed, &fi, &pt)) goto done;
+    if (map_text(fm, A, &fi, &pt)) goto done;
     for (;;) {                                            /* grow to the exact op count on DEBWT_ERANGE */
         free(cig);
         cig = malloc(cap * 4);
         if (!cig) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = debwt_fm_map_pairs(fm, B.seq, B.off, np, opts, hits, info, coff, cig, cap);
+        rc = debwt_fm_map_pairs(fm, B.seq, B.off, np, &po, hits, info, coff, cig, cap);
         if (rc == DEBWT_ERANGE && coff[nr] > cap) { cap = coff[nr]; continue; }
         break;
     }
@@ -932,7 +967,7 @@ static int parse_region(const char *s, uint64_t *rec, uint64_t *beg, uint64_t *e
     return 0;
 }
 
-static int cmd_extract(const char *out, const char *rfile, int device) {
+static int cmd_extract(const struct query_args *A) {
     debwt_fm *fm = NULL;
     struct regions R;
     memset(&R, 0, sizeof R);
@@ -940,8 +975,8 @@ static int cmd_extract(const char *out, const char *rfile, int device) {
     uint64_t *starts = NULL, *off = NULL;
     char *bases = NULL, *line = NULL;
     FILE *f = NULL;
-    if (rfile && !(f = fopen(rfile, "r"))) { fprintf(stderr, "cannot open %s\n", rfile); return 1; }
-    if (open_index(out, device, &fm)) { if (f) fclose(f); return 1; }
+    if (A->file && !(f = fopen(A->file, "r"))) { fprintf(stderr, "cannot open %s\n", A->file); return 1; }
+    if (open_index(A->out, A->device, &fm)) { if (f) fclose(f); return 1; }
     debwt_fm_info fi;
     debwt_fm_info_get(fm, &fi);
     starts = malloc((fi.nrec + 1) * 8);
@@ -961,13 +996,13 @@ static int cmd_extract(const char *out, const char *rfile, int device) {
             uint64_t rec = 0, beg = 0, end = 0;
             int whole = 0;
             if (parse_region(line, &rec, &beg, &end, &whole)) {
-                fprintf(stderr, "%s:%llu: '%s' is not a region (J or J:BEG-END)\n", rfile, (unsigned long long)lineno, line);
+                fprintf(stderr, "%s:%llu: '%s' is not a region (J or J:BEG-END)\n", A->file, (unsigned long long)lineno, line);
                 goto done;
             }
             const uint64_t len = rec < fi.nrec ? starts[rec + 1] - 1 - starts[rec] : 0;
             if (whole) end = len;
             if (rec >= fi.nrec || beg > end || end > len) {
-                fprintf(stderr, "%s:%llu: region '%s' lies outside its record (%llu records; record %llu holds %llu bases)\n", rfile,
+                fprintf(stderr, "%s:%llu: region '%s' lies outside its record (%llu records; record %llu holds %llu bases)\n", A->file,
                         (unsigned long long)lineno, line, (unsigned long long)fi.nrec, (unsigned long long)rec, (unsigned long long)len);
                 goto done;
             }
@@ -1017,31 +1052,23 @@ done:
 
 #define PILE_BATCH_ALNS (1ull << 20)
 
-struct pile_args {
-    const char *ref, *mate, *region, *variants;
-    uint64_t threads, seed, window, min_mapq;
-    int iupac, chain, consensus;
-    uint32_t max_gap;
-    const debwt_fm_map_opts *mo;
-    const debwt_fm_pair_opts *po;
-    debwt_fm_pile_opts call;
-};
-
 /* reads -> alignments once (map, map --chain or map --mate), kept on the host; then the text is walked in windows of
  * --window positions: the alignments are piled up in batches with DEBWT_FM_PILE_ADD, the table is fetched (pileup) or
  * called and turned into consensus and variants (consensus) */
-static int cmd_pile(const char *out, const char *pfile, int device, const struct pile_args *A) {
+static int cmd_pile(const struct query_args *A) {
+    const int consensus = A->cmd == CMD_CONSENSUS;
+    const debwt_fm_pair_opts po = pair_opts(A);
     struct patterns P, M, B;
     memset(&P, 0, sizeof P); memset(&M, 0, sizeof M); memset(&B, 0, sizeof B);
-    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) { free_patterns(&P); return 1; }
     if (A->mate && read_patterns(A->mate, &M)) { free_patterns(&P); free_patterns(&M); return 1; }
     if (A->mate && P.n != M.n) {
-        fprintf(stderr, "--mate: %s holds %llu reads, %s holds %llu\n", A->mate, (unsigned long long)M.n, pfile, (unsigned long long)P.n);
+        fprintf(stderr, "--mate: %s holds %llu reads, %s holds %llu\n", A->mate, (unsigned long long)M.n, A->file, (unsigned long long)P.n);
         free_patterns(&P); free_patterns(&M);
         return 1;
     }
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); free_patterns(&M); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); free_patterns(&M); return 1; }
     int ret = 1, rc = 0;
     debwt_packed_text pt;
     memset(&pt, 0, sizeof pt);
@@ -1077,19 +1104,19 @@ static int cmd_pile(const char *out, const char *pfile, int device, const struct
         }
         seq = B.seq; off = B.off;
     }
-    if (map_text(fm, out, A->ref, A->threads, A->iupac, A->seed, &fi, &pt)) goto done;
+    if (map_text(fm, A, &fi, &pt)) goto done;
     for (;;) {                                            /* grow to the exact op count on DEBWT_ERANGE */
         free(cig);
         cig = malloc(cap * 4);
         if (!cig) { fprintf(stderr, "out of memory\n"); goto done; }
-        if (A->mate) rc = debwt_fm_map_pairs(fm, seq, off, P.n, A->po, hits, info, coff, cig, cap);
+        if (A->mate) rc = debwt_fm_map_pairs(fm, seq, off, P.n, &po, hits, info, coff, cig, cap);
         else if (A->chain) {
             debwt_fm_chain_opts co;
             debwt_fm_chain_defaults(&co);
-            co.map = *A->mo;
-            co.max_gap = A->max_gap;
+            co.map = A->mo;
+            co.max_gap = A->co.max_gap;
             rc = debwt_fm_map_chained(fm, seq, off, nr, &co, hits, coff, cig, cap, NULL, NULL, 0);
-        } else rc = debwt_fm_map(fm, seq, off, nr, A->mo, hits, coff, cig, cap);
+        } else rc = debwt_fm_map(fm, seq, off, nr, &A->mo, hits, coff, cig, cap);
         if (rc == DEBWT_ERANGE && coff[nr] > cap) { cap = coff[nr]; continue; }
         break;
     }
@@ -1126,8 +1153,8 @@ static int cmd_pile(const char *out, const char *pfile, int device, const struct
     }
     const uint64_t W = A->window < gend - gbeg ? A->window : gend - gbeg;
     calls = malloc(W); refb = malloc(W);
-    counts = A->consensus ? NULL : malloc(W * 32);
-    if (!calls || !refb || (!A->consensus && !counts)) { fprintf(stderr, "out of memory\n"); goto done; }
+    counts = consensus ? NULL : malloc(W * 32);
+    if (!calls || !refb || (!consensus && !counts)) { fprintf(stderr, "out of memory\n"); goto done; }
     if (A->variants && !(vf = fopen(A->variants, "w"))) { fprintf(stderr, "cannot write %s\n", A->variants); goto done; }
     uint64_t vcap = 0, ecap = 0, ccap = 0, open_rec = ~0ull;
     for (uint64_t wb = gbeg; wb < gend; wb += W) {
@@ -1149,7 +1176,7 @@ static int cmd_pile(const char *out, const char *pfile, int device, const struct
             rc = debwt_fm_pile_call(fm, &A->call, calls, refb, vars, vcap, &nv);
         }
         if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
-        if (!A->consensus) {
+        if (!consensus) {
             uint64_t win[2];
             rc = debwt_fm_pile_fetch(fm, win, counts, W);
             if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
@@ -1242,7 +1269,7 @@ static int cmd_pile(const char *out, const char *pfile, int device, const struct
             }
         }
     }
-    if (A->consensus && open_rec != ~0ull) putchar('\n');
+    if (consensus && open_rec != ~0ull) putchar('\n');
     ret = fflush(stdout) ? 1 : 0;
     if (vf && fflush(vf)) ret = 1;
 done:
@@ -1258,20 +1285,20 @@ done:
 
 /* ---- kmers / correct -------------------------------------------------------------------------------------------------- */
 
-static int cmd_kmers(const char *out, const char *pfile, int device, uint32_t k, uint32_t flags) {
+static int cmd_kmers(const struct query_args *A) {
     struct patterns P;
-    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1;
     uint64_t total = 0, *coff = malloc((P.n + 1) * 8);
     for (uint64_t i = 0; i < P.n; i++) {
         uint64_t m = P.off[i + 1] - P.off[i];
-        total += m >= k ? m - k + 1 : 0;
+        total += m >= A->ko.k ? m - A->ko.k + 1 : 0;
     }
     uint32_t *cnt = malloc((total ? total : 1) * 4);
     if (!coff || !cnt) { fprintf(stderr, "out of memory\n"); goto done; }
-    int rc = debwt_fm_kmer_counts(fm, P.seq, P.off, P.n, k, flags, coff, cnt, total);
+    int rc = debwt_fm_kmer_counts(fm, P.seq, P.off, P.n, A->ko.k, A->flags, coff, cnt, total);
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     for (uint64_t i = 0; i < P.n; i++) {
         printf("%s\t", P.name[i]);
@@ -1287,19 +1314,18 @@ done:
     return ret;
 }
 
-static int cmd_correct(const char *out, const char *pfile, int device, const debwt_fm_correct_opts *opts, int auto_count,
-                       const char *report) {
+static int cmd_correct(const struct query_args *A) {
     struct patterns P;
-    if (read_patterns(pfile, &P)) { free_patterns(&P); return 1; }
+    if (read_patterns(A->file, &P)) { free_patterns(&P); return 1; }
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) { free_patterns(&P); return 1; }
+    if (open_index(A->out, A->device, &fm)) { free_patterns(&P); return 1; }
     int ret = 1, rc;
-    debwt_fm_correct_opts ko = *opts, *o = &ko;
+    debwt_fm_correct_opts ko = A->ko, *o = &ko;
     char *fixed = malloc(P.len ? P.len : 1);
     debwt_fm_correct_info *info = malloc((P.n ? P.n : 1) * sizeof *info);
     FILE *rf = NULL;
     if (!fixed || !info) { fprintf(stderr, "out of memory\n"); goto done; }
-    if (auto_count) {                                     /* the valley of the spectrum at this K and these strands */
+    if (A->auto_count) {                                  /* the valley of the spectrum at this K and these strands */
         uint64_t hist[256];
         debwt_fm_spectrum_totals tot;
         debwt_fm_spectrum_summary sum;
@@ -1316,7 +1342,7 @@ static int cmd_correct(const char *out, const char *pfile, int device, const deb
     }
     rc = debwt_fm_correct(fm, P.seq, P.off, P.n, o, fixed, info);
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
-    if (report && !(rf = fopen(report, "w"))) { fprintf(stderr, "cannot write %s\n", report); goto done; }
+    if (A->report && !(rf = fopen(A->report, "w"))) { fprintf(stderr, "cannot write %s\n", A->report); goto done; }
     for (uint64_t i = 0; i < P.n; i++) {
         printf(">%s\n", P.name[i]);
         fwrite(fixed + P.off[i], 1, P.off[i + 1] - P.off[i], stdout);
@@ -1328,7 +1354,7 @@ static int cmd_correct(const char *out, const char *pfile, int device, const deb
                     info[i].fixes, info[i].weak_before, info[i].weak_after);
         }
     }
-    if (rf && fclose(rf)) { rf = NULL; fprintf(stderr, "cannot write %s\n", report); goto done; }
+    if (rf && fclose(rf)) { rf = NULL; fprintf(stderr, "cannot write %s\n", A->report); goto done; }
     rf = NULL;
     debwt_fm_correct_stats st;
     debwt_fm_correct_stats_get(fm, &st);
@@ -1347,42 +1373,42 @@ done:
 
 /* ---- spectrum ---------------------------------------------------------------------------------------------------------- */
 
-static int cmd_spectrum(const char *out, int device, uint32_t k, uint32_t flags, uint32_t bins, const char *list,
-                        uint32_t at_least, uint32_t at_most) {
+static int cmd_spectrum(const struct query_args *A) {
+    const uint32_t k = A->ko.k, flags = A->ko.flags;
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) return 1;
+    if (open_index(A->out, A->device, &fm)) return 1;
     int ret = 1;
-    uint64_t *hist = calloc(bins, 8), *codes = NULL, count = 0;
+    uint64_t *hist = calloc(A->bins, 8), *codes = NULL, count = 0;
     uint32_t *mults = NULL;
     FILE *lf = NULL;
     debwt_fm_spectrum_totals tot;
     debwt_fm_spectrum_summary sum;
     if (!hist) { fprintf(stderr, "out of memory\n"); goto done; }
-    int rc = debwt_fm_spectrum(fm, k, flags, bins, hist, &tot);
+    int rc = debwt_fm_spectrum(fm, k, flags, A->bins, hist, &tot);
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
-    debwt_fm_spectrum_threshold(hist, bins, tot.total, &sum);
+    debwt_fm_spectrum_threshold(hist, A->bins, tot.total, &sum);
     printf("# k\t%u\n# strands\t%s\n# distinct\t%llu\n# total\t%llu\n# valley\t%llu\n# peak\t%llu\n# est_size\t%llu\n", k,
            flags & DEBWT_FM_BOTH_STRANDS ? "both" : "forward", (unsigned long long)tot.distinct, (unsigned long long)tot.total,
            (unsigned long long)sum.valley, (unsigned long long)sum.peak, (unsigned long long)sum.est_size);
-    for (uint32_t c = 1; c < bins; c++)
-        if (hist[c]) printf("%s%u\t%llu\n", c == bins - 1 ? ">=" : "", c, (unsigned long long)hist[c]);
-    if (list) {
-        rc = debwt_fm_kmer_list(fm, k, flags, at_least, at_most, NULL, NULL, 0, &count);
+    for (uint32_t c = 1; c < A->bins; c++)
+        if (hist[c]) printf("%s%u\t%llu\n", c == A->bins - 1 ? ">=" : "", c, (unsigned long long)hist[c]);
+    if (A->list) {
+        rc = debwt_fm_kmer_list(fm, k, flags, A->at_least, A->at_most, NULL, NULL, 0, &count);
         if (rc && rc != DEBWT_ERANGE) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
         codes = malloc((count ? count : 1) * 8); mults = malloc((count ? count : 1) * 4);
         if (!codes || !mults) { fprintf(stderr, "out of memory\n"); goto done; }
-        if (count && (rc = debwt_fm_kmer_list(fm, k, flags, at_least, at_most, codes, mults, count, &count))) {
+        if (count && (rc = debwt_fm_kmer_list(fm, k, flags, A->at_least, A->at_most, codes, mults, count, &count))) {
             fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
             goto done;
         }
-        if (!(lf = fopen(list, "w"))) { fprintf(stderr, "cannot write %s\n", list); goto done; }
+        if (!(lf = fopen(A->list, "w"))) { fprintf(stderr, "cannot write %s\n", A->list); goto done; }
         char w[33];
         w[k] = 0;
         for (uint64_t i = 0; i < count; i++) {
             for (uint32_t j = 0; j < k; j++) w[j] = "ACGT"[(codes[i] >> (2 * (k - 1 - j))) & 3];
             fprintf(lf, "%s\t%u\n", w, mults[i]);
         }
-        if (fclose(lf)) { lf = NULL; fprintf(stderr, "cannot write %s\n", list); goto done; }
+        if (fclose(lf)) { lf = NULL; fprintf(stderr, "cannot write %s\n", A->list); goto done; }
         lf = NULL;
     }
     debwt_fm_spectrum_stats st;
@@ -1431,32 +1457,31 @@ static uint64_t record_of(const uint64_t *starts, uint64_t nrec, uint64_t p) {
     return lo;
 }
 
-static int cmd_lcp(const char *out, int device, uint32_t max_lcp, const char *lcp_file, const char *sa_file, const char *da_file,
-                   uint32_t kmax) {
+static int cmd_lcp(const struct query_args *A) {
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) return 1;
+    if (open_index(A->out, A->device, &fm)) return 1;
     int ret = 1;
     debwt_fm_info fi;
     debwt_fm_info_get(fm, &fi);
-    uint64_t *starts = malloc(fi.nrec * 8), *distinct = calloc(kmax ? kmax : 1, 8);
+    uint64_t *starts = malloc(fi.nrec * 8), *distinct = calloc(A->profile_k ? A->profile_k : 1, 8);
     debwt_fm_esa_summary sm;
     debwt_fm_esa_stats st;
     if (!starts || !distinct) { fprintf(stderr, "out of memory\n"); goto done; }
     if (debwt_fm_record_starts(fm, starts, fi.nrec) ||
-        debwt_fm_esa_build(fm, max_lcp, (sa_file ? DEBWT_FM_ESA_SA : 0u) | (da_file ? DEBWT_FM_ESA_DA : 0u)) ||
-        debwt_fm_esa_summary_get(fm, &sm) || (kmax && debwt_fm_esa_profile(fm, kmax, distinct))) {
+        debwt_fm_esa_build(fm, A->max_lcp, (A->sa_file ? DEBWT_FM_ESA_SA : 0u) | (A->da_file ? DEBWT_FM_ESA_DA : 0u)) ||
+        debwt_fm_esa_summary_get(fm, &sm) || (A->profile_k && debwt_fm_esa_profile(fm, A->profile_k, distinct))) {
         fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
         goto done;
     }
-    if (lcp_file && write_esa_array(fm, DEBWT_FM_ESA_LCP_ARRAY, 4, fi.n, lcp_file)) goto done;
-    if (sa_file && write_esa_array(fm, DEBWT_FM_ESA_SA_ARRAY, 8, fi.n, sa_file)) goto done;
-    if (da_file && write_esa_array(fm, DEBWT_FM_ESA_DA_ARRAY, 4, fi.n, da_file)) goto done;
+    if (A->lcp_file && write_esa_array(fm, DEBWT_FM_ESA_LCP_ARRAY, 4, fi.n, A->lcp_file)) goto done;
+    if (A->sa_file && write_esa_array(fm, DEBWT_FM_ESA_SA_ARRAY, 8, fi.n, A->sa_file)) goto done;
+    if (A->da_file && write_esa_array(fm, DEBWT_FM_ESA_DA_ARRAY, 4, fi.n, A->da_file)) goto done;
     const uint64_t ra = record_of(starts, fi.nrec, sm.pos_prev), rb = record_of(starts, fi.nrec, sm.pos);
     printf("# n=%llu\tmax=%llu\tmax_row=%llu\tprev=%llu:%llu\tpos=%llu:%llu\tmean=%.6f\n", (unsigned long long)sm.n,
            (unsigned long long)sm.max, (unsigned long long)sm.max_row, (unsigned long long)ra,
            (unsigned long long)(sm.pos_prev - starts[ra]), (unsigned long long)rb, (unsigned long long)(sm.pos - starts[rb]),
            (double)sm.sum / (double)sm.n);
-    for (uint32_t k = 1; k <= kmax; k++) printf("%u\t%llu\n", k, (unsigned long long)distinct[k - 1]);
+    for (uint32_t k = 1; k <= A->profile_k; k++) printf("%u\t%llu\n", k, (unsigned long long)distinct[k - 1]);
     debwt_fm_esa_stats_get(fm, &st);
     fprintf(stderr, "lcp: %llu rows, max %llu at row %llu, %llu capped; %llu chunks of %llu, %.2f symbols compared per position; "
                     "walk %.1f, scatter %.1f, plcp %.1f, rows %.1f ms, %.1f ms in all\n",
@@ -1472,14 +1497,10 @@ done:
 
 /* ---- repeats ----------------------------------------------------------------------------------------------------------- */
 
-/* by_record: --min-records, --max-records or --unique was given (a column `rec` then follows `occ`); mums: the subcommand
- * mums, min_records 0 standing for every record of the index */
-struct repeat_args { uint32_t min_len, kind, max_lcp; uint64_t min_occ, max_occ; int seq, occurrences;
-                     uint64_t min_records, max_records; int unique, by_record, mums; };
-
-static int cmd_repeats(const char *out, int device, const struct repeat_args *A) {
+static int cmd_repeats(const struct query_args *A) {
+    const int mums = A->cmd == CMD_MUMS;
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) return 1;
+    if (open_index(A->out, A->device, &fm)) return 1;
     int ret = 1, rc;
     debwt_fm_info fi;
     debwt_fm_info_get(fm, &fi);
@@ -1490,11 +1511,11 @@ static int cmd_repeats(const char *out, int device, const struct repeat_args *A)
     uint64_t bcap = 0;
     debwt_fm_repeat_opts o = {A->min_len, A->kind, A->min_occ, A->max_occ};
     debwt_fm_record_filter flt = {A->min_records ? A->min_records : 1, A->max_records, A->unique ? DEBWT_FM_RECORDS_UNIQUE : 0u, 0};
-    const int by_record = A->by_record || A->mums;
+    const int by_record = A->by_record || mums;
     uint32_t *nrecs = NULL;
     struct occ *oc = NULL;
     debwt_fm_repeat_stats st;
-    if (A->mums) {                                              /* maximal, once in each of at least q records, nowhere else */
+    if (mums) {                                                 /* maximal, once in each of at least q records, nowhere else */
         flt.min_records = A->min_records ? A->min_records : fi.nrec;
         flt.flags = DEBWT_FM_RECORDS_UNIQUE;
         o.kind = DEBWT_FM_REPEAT_MAXIMAL; o.min_occ = flt.min_records > 2 ? flt.min_records : 2; o.max_occ = 0;
@@ -1520,14 +1541,14 @@ static int cmd_repeats(const char *out, int device, const struct repeat_args *A)
         const uint64_t cnt = fi.n - lo < (1ull << 22) ? fi.n - lo : (1ull << 22);
         if (debwt_fm_esa_fetch(fm, DEBWT_FM_ESA_SA_ARRAY, lo, cnt, sa + lo)) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     }
-    if (A->mums)
+    if (mums)
         printf("# mums=%llu\tmin_records=%llu\tlongest=%llu\n", (unsigned long long)st.reported, (unsigned long long)flt.min_records,
                (unsigned long long)st.longest_len);
     else
         printf("# intervals=%llu\tmaximal=%llu\tsupermaximal=%llu\treported=%llu\tlongest=%llu\n", (unsigned long long)st.intervals,
                (unsigned long long)st.maximal, (unsigned long long)st.supermaximal, (unsigned long long)st.reported,
                (unsigned long long)st.longest_len);
-    if (A->mums) {
+    if (mums) {
         oc = malloc((fi.nrec ? fi.nrec : 1) * sizeof *oc);      /* unique: a multi-MUM has at most one occurrence per record */
         if (!oc) { fprintf(stderr, "out of memory\n"); goto done; }
     }
@@ -1559,7 +1580,7 @@ static int cmd_repeats(const char *out, int device, const struct repeat_args *A)
         for (uint64_t j = j0; j < j1; j++) {
             const debwt_fm_repeat *x = &rp[j];
             const uint64_t p = sa[x->row_lo], r = record_of(starts, fi.nrec, p);
-            if (A->mums) {                                      /* len, then the occurrence in every record, ascending by record */
+            if (mums) {                                         /* len, then the occurrence in every record, ascending by record */
                 if (x->count > fi.nrec) { fprintf(stderr, "mums: more occurrences than records\n"); goto done; }
                 for (uint64_t t = 0; t < x->count; t++) {
                     const uint64_t q = sa[x->row_lo + t], rq = record_of(starts, fi.nrec, q);
@@ -1624,9 +1645,10 @@ static uint64_t n50_of(uint64_t *len, uint64_t count) {
 }
 
 /* the compacted de Bruijn graph of the collection's k-mers (Definition 13), as GFA 1 or as FASTA */
-static int cmd_dbg(const char *out, int device, uint32_t k, int fasta) {
+static int cmd_dbg(const struct query_args *A) {
+    const uint32_t k = A->ko.k;
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) return 1;
+    if (open_index(A->out, A->device, &fm)) return 1;
     int ret = 1, rc;
     debwt_fm_cdbg_sizes sz = {0, 0, 0};
     debwt_fm_unitig *un = NULL;
@@ -1650,18 +1672,18 @@ static int cmd_dbg(const char *out, int device, uint32_t k, int fasta) {
         goto done;
     }
     debwt_fm_cdbg_stats_get(fm, &st);
-    if (!fasta) printf("H\tVN:Z:1.0\n");
+    if (!A->fasta) printf("H\tVN:Z:1.0\n");
     for (uint64_t u = 0; u < sz.unitigs; u++) {
         const uint64_t m = (uint64_t)un[u].nodes + k - 1;
         const int circular = (un[u].flags & DEBWT_FM_CDBG_CIRCULAR) != 0;
         len[u] = m;
-        if (fasta) printf(">u%llu nodes=%u kc=%llu%s\n", (unsigned long long)u, un[u].nodes, (unsigned long long)un[u].kmer_count, circular ? " circular" : "");
+        if (A->fasta) printf(">u%llu nodes=%u kc=%llu%s\n", (unsigned long long)u, un[u].nodes, (unsigned long long)un[u].kmer_count, circular ? " circular" : "");
         else printf("S\t%llu\t", (unsigned long long)u);
         fwrite(seq + un[u].seq_offset, 1, m, stdout);
-        if (fasta) putchar('\n');
+        if (A->fasta) putchar('\n');
         else printf("\tLN:i:%llu\tKC:i:%llu%s\n", (unsigned long long)m, (unsigned long long)un[u].kmer_count, circular ? "\tCL:Z:circular" : "");
     }
-    if (!fasta)
+    if (!A->fasta)
         for (uint64_t e = 0; e < sz.edges; e++) printf("L\t%u\t+\t%u\t+\t%uM\n", ed[e].from, ed[e].to, k - 1);
     {
         uint64_t longest = 0;
@@ -1686,10 +1708,11 @@ static uint32_t mirror_node(const uint8_t *state, uint32_t v) {
     return state[v & ~1u] == 0 && state[v | 1u] == 1 ? v : v ^ 1u;
 }
 
-static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_edges, const char *states, int want_unitigs,
-                     int both, const debwt_fm_clean_opts *clean) {
+static int cmd_graph(const struct query_args *A) {
+    const int want_unitigs = A->cmd == CMD_UNITIGS, both = A->both;
+    const debwt_fm_clean_opts *clean = A->clean ? &A->cl : NULL;
     debwt_fm *fm = NULL;
-    if (open_index(out, device, &fm)) return 1;
+    if (open_index(A->out, A->device, &fm)) return 1;
     int ret = 1, rc = 0;
     debwt_fm_info fi;
     debwt_fm_info_get(fm, &fi);
@@ -1705,14 +1728,14 @@ static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_
     rc = debwt_fm_record_starts(fm, starts, nrec);
     if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     starts[nrec] = fi.n;                                  /* record r holds starts[r + 1] - 1 - starts[r] bases */
-    const uint32_t flags = all_edges ? DEBWT_FM_GRAPH_ALL_EDGES : 0u;
+    const uint32_t flags = A->all_edges ? DEBWT_FM_GRAPH_ALL_EDGES : 0u;
     uint64_t cap = 4 * nn + 16;                           /* first estimate; the exact count on DEBWT_ERANGE */
     for (;;) {
         free(edges);
         edges = malloc(cap * sizeof *edges);
         if (!edges) { fprintf(stderr, "out of memory\n"); goto done; }
-        rc = both ? debwt_fm_string_graph_both(fm, min_overlap, flags, state, eoff, edges, cap)
-                  : debwt_fm_string_graph(fm, min_overlap, flags, state, eoff, edges, cap);
+        rc = both ? debwt_fm_string_graph_both(fm, A->min_overlap, flags, state, eoff, edges, cap)
+                  : debwt_fm_string_graph(fm, A->min_overlap, flags, state, eoff, edges, cap);
         if (rc == DEBWT_ERANGE && eoff[nn] > cap) { cap = eoff[nn]; continue; }
         break;
     }
@@ -1727,13 +1750,13 @@ static int cmd_graph(const char *out, int device, uint32_t min_overlap, int all_
         free(keep);
         if (rc) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
     }
-    if (states) {
-        if (!(sf = fopen(states, "w"))) { fprintf(stderr, "cannot write %s\n", states); goto done; }
+    if (A->states) {
+        if (!(sf = fopen(A->states, "w"))) { fprintf(stderr, "cannot write %s\n", A->states); goto done; }
         for (uint64_t i = 0; i < nrec; i++) {
             const uint8_t x = state[both ? 2 * i : i];        /* per read: the state of its first node */
             fprintf(sf, "%llu\t%s\n", (unsigned long long)i, x == 0 ? "kept" : x == 1 ? "duplicate" : x == 2 ? "contained" : x == DEBWT_FM_NODE_CLIPPED ? "clipped" : "popped");
         }
-        if (fclose(sf)) { sf = NULL; fprintf(stderr, "cannot write %s\n", states); goto done; }
+        if (fclose(sf)) { sf = NULL; fprintf(stderr, "cannot write %s\n", A->states); goto done; }
         sf = NULL;
     }
     debwt_fm_graph_stats st;
@@ -1829,296 +1852,271 @@ done:
     return ret;
 }
 
-int main(int argc, char **argv) {
-    if (argc < 2) { usage(); return 1; }
-    const char *cmd = argv[1];
-    int mode = !strcmp(cmd, "index") ? 0 : !strcmp(cmd, "count") ? 1 : !strcmp(cmd, "locate") ? 2 : !strcmp(cmd, "mems") ? 3 :
-               !strcmp(cmd, "map") ? 4 : !strcmp(cmd, "overlaps") ? 5 : !strcmp(cmd, "extract") ? 6 :
-               !strcmp(cmd, "kmers") ? 7 : !strcmp(cmd, "correct") ? 8 : !strcmp(cmd, "graph") ? 9 :
-               !strcmp(cmd, "unitigs") ? 10 : !strcmp(cmd, "pileup") ? 11 : !strcmp(cmd, "consensus") ? 12 :
-               !strcmp(cmd, "spectrum") ? 13 : !strcmp(cmd, "lcp") ? 14 : !strcmp(cmd, "repeats") ? 15 : !strcmp(cmd, "mums") ? 16 :
-               !strcmp(cmd, "dbg") ? 17 : -1;
-    const int mapping = mode == 4 || mode == 11 || mode == 12;   /* the commands that map reads first */
-    if (mode < 0) { usage(); return 1; }
-    const char *out = NULL, *file = NULL, *ref = NULL;
-    uint64_t threads = 8, seed = 0, device = 0, s = 32, max_hits = 0, K = 0, min_len = 19, min_overlap = 20, v64 = 0;
-    uint64_t ovl_k = 0, ovl_permille = 0;
-    int ovl_mm = 0, permille_given = 0;
-    debwt_fm_map_opts mo;
-    debwt_fm_map_defaults(&mo);
-    debwt_fm_chain_opts co;
-    debwt_fm_chain_defaults(&co);
-    debwt_fm_pair_opts po;
-    debwt_fm_pair_defaults(&po);
-    const char *mate = NULL;
-    int iupac = 0, search = 0, chain = 0, gap_given = 0, insert_given = 0, no_rescue = 0, no_self = 0, all = 0;
-    uint32_t flags = 0;
-    debwt_fm_correct_opts ko;
-    debwt_fm_correct_defaults(&ko);
-    const char *report = NULL, *states = NULL;
-    int k_given = 0, all_edges = 0, graph_both = 0, clean = 0, auto_count = 0, filter_given = 0;
-    const char *list = NULL, *lcp_file = NULL, *esa_sa_file = NULL, *da_file = NULL;
-    uint64_t max_lcp = 0, profile_k = 0;
-    struct repeat_args ra = {20, DEBWT_FM_REPEAT_MAXIMAL, 0, 2, 0, 0, 0, 0, 0, 0, 0, 0};
-    int kind_given = 0, count_records = 0, dbg_fasta = 0;
-    uint64_t bins = 256, at_least = 1, at_most = 0xFFFFFFFFull;
-    debwt_fm_clean_opts cl;
-    debwt_fm_clean_defaults(&cl);
-    struct pile_args pa;
-    memset(&pa, 0, sizeof pa);
-    pa.window = 1ull << 26; pa.min_mapq = 20;
-    debwt_fm_pile_defaults(&pa.call);
+/* ---- the command line -------------------------------------------------------------------------------------------------- */
+
+/* what a command checks across its options before it runs, and which of its forms runs */
+static int run_count(const struct query_args *A) {                          /* count, locate */
+    if (A->search && A->count_records) { fprintf(stderr, "--records: only with exact patterns on one strand\n"); return 1; }
+    return A->search ? cmd_search(A) : cmd_query(A);
+}
+
+static int run_overlaps(const struct query_args *A) {
+    if (A->permille_given && !A->ovl_mm) { fprintf(stderr, "--max-error-permille: only with --max-mismatches\n"); usage(); return 1; }
+    return cmd_overlaps(A);
+}
+
+static int run_map(const struct query_args *A) {                            /* map, pileup, consensus */
+    if (!A->ref) fprintf(stderr, "%s: no --ref INPUT.fa[.gz]: the text is restored from %s.sa and the BWT\n", A->name, A->out);
+    if (A->gap_given && !A->chain) { fprintf(stderr, "--max-gap: only with --chain\n"); return 1; }
+    if (A->mate && A->chain) { fprintf(stderr, "--mate: not with --chain (pairs are mapped with the fixed band)\n"); return 1; }
+    if (A->insert_given && !A->mate) { fprintf(stderr, "--insert: only with --mate\n"); return 1; }
+    if (A->no_rescue && !A->mate) { fprintf(stderr, "--no-rescue: only with --mate\n"); return 1; }
+    return A->cmd != CMD_MAP ? cmd_pile(A) : A->mate ? cmd_map_pairs(A) : cmd_map(A);
+}
+
+static int run_spectrum(const struct query_args *A) {
+    if (A->filter_given && !A->list) { fprintf(stderr, "--at-least, --at-most: only with --list\n"); return 1; }
+    if (A->at_least > A->at_most) { fprintf(stderr, "--at-least: above --at-most\n"); return 1; }
+    return cmd_spectrum(A);
+}
+
+static int run_lcp(const struct query_args *A) {
+    if (A->max_lcp && A->profile_k > A->max_lcp) { fprintf(stderr, "--profile: above --max-lcp\n"); return 1; }
+    return cmd_lcp(A);
+}
+
+static int run_repeats(const struct query_args *A) {                        /* repeats, mums */
+    if (A->max_occ && A->max_occ < A->min_occ) { fprintf(stderr, "--max-occ: below --min-occ\n"); return 1; }
+    if (A->max_records && A->max_records < A->min_records) { fprintf(stderr, "--max-records: below --min-records\n"); return 1; }
+    if (A->max_lcp && A->min_len >= A->max_lcp) { fprintf(stderr, "--min-len: not below --max-lcp (repeats of the capped length are not listed)\n"); return 1; }
+    return cmd_repeats(A);
+}
+
+static int run_graph(const struct query_args *A) {                          /* graph, unitigs */
+    if (A->clean && A->all_edges) { usage(); return 1; }
+    if (A->clean && !A->cl.max_tip && !A->cl.max_bubble) { fprintf(stderr, "--clean: --max-tip and --max-bubble are both 0\n"); return 1; }
+    return cmd_graph(A);
+}
+
+/* one row per subcommand.  file: the argument that is no option; maps: the command maps reads first and takes map's options */
+enum file_rule { FILE_NEEDED, FILE_NONE, FILE_OR_ALL };                     /* FILE_OR_ALL: exactly one of --all and REGIONS */
+static const struct command {
+    const char *name; enum cmd cmd; enum file_rule file; int need_k, maps;
+    int (*run)(const struct query_args *);
+} commands[] = {
+    {"index",     CMD_INDEX,     FILE_NEEDED, 0, 0, cmd_index},
+    {"count",     CMD_COUNT,     FILE_NEEDED, 0, 0, run_count},
+    {"locate",    CMD_LOCATE,    FILE_NEEDED, 0, 0, run_count},
+    {"mems",      CMD_MEMS,      FILE_NEEDED, 0, 0, cmd_mems},
+    {"map",       CMD_MAP,       FILE_NEEDED, 0, 1, run_map},
+    {"pileup",    CMD_PILEUP,    FILE_NEEDED, 0, 1, run_map},
+    {"consensus", CMD_CONSENSUS, FILE_NEEDED, 0, 1, run_map},
+    {"overlaps",  CMD_OVERLAPS,  FILE_NEEDED, 0, 0, run_overlaps},
+    {"extract",   CMD_EXTRACT,   FILE_OR_ALL, 0, 0, cmd_extract},
+    {"kmers",     CMD_KMERS,     FILE_NEEDED, 1, 0, cmd_kmers},
+    {"correct",   CMD_CORRECT,   FILE_NEEDED, 1, 0, cmd_correct},
+    {"spectrum",  CMD_SPECTRUM,  FILE_NONE,   1, 0, run_spectrum},
+    {"lcp",       CMD_LCP,       FILE_NONE,   0, 0, run_lcp},
+    {"repeats",   CMD_REPEATS,   FILE_NONE,   0, 0, run_repeats},
+    {"mums",      CMD_MUMS,      FILE_NONE,   0, 0, run_repeats},
+    {"dbg",       CMD_DBG,       FILE_NONE,   1, 0, cmd_dbg},
+    {"graph",     CMD_GRAPH,     FILE_NONE,   0, 0, run_graph},
+    {"unitigs",   CMD_UNITIGS,   FILE_NONE,   0, 0, run_graph},
+};
+
+/* one row per option and meaning: the commands that take it (bit c: command c; MAPS: every command whose row says maps; PAIR:
+ * any other command answers "only with map"), its kind, where the value goes in struct query_args (at) and which int
+ * becomes 1 beside it (mark, 0: none).  FLAG sets an int, BITS ors lo into a u32, U32 and U64 (NUM: by the member's width)
+ * take a number in [lo, hi] or print err, STR keeps the argument; FLAG and BITS take no value.  fn, where a row has one,
+ * stands in for take(). */
+enum kind { FLAG, BITS, U32, U64, STR };
+struct option {
+    const char *name; uint32_t cmds; enum kind kind; size_t at, mark; uint64_t lo, hi; const char *err;
+    int (*fn)(struct query_args *, const struct option *, const char *);
+};
+
+static int take(struct query_args *A, const struct option *o, const char *v) {
+    void *p = (char *)A + o->at;
+    uint64_t x = 0;
+    if ((o->kind == U32 || o->kind == U64) && (parse_u64(v, &x) || x < o->lo || x > o->hi)) { fprintf(stderr, "%s: %s\n", o->name, o->err); return 1; }
+    if (o->kind == FLAG) *(int *)p = 1;
+    else if (o->kind == BITS) *(uint32_t *)p |= (uint32_t)o->lo;
+    else if (o->kind == U32) *(uint32_t *)p = (uint32_t)x;
+    else if (o->kind == U64) *(uint64_t *)p = x;
+    else *(const char **)p = v;
+    if (o->mark) *(int *)((char *)A + o->mark) = 1;
+    return 0;
+}
+
+static int opt_threads(struct query_args *A, const struct option *o, const char *v) {
+    if (take(A, o, v)) return 1;
+    if (A->threads > 256) A->threads = 256;
+    return 0;
+}
+
+static int opt_sa_sample(struct query_args *A, const struct option *o, const char *v) {
+    if (take(A, o, v)) return 1;
+    if (A->sa_sample & (A->sa_sample - 1)) { fprintf(stderr, "%s: %s\n", o->name, o->err); return 1; }
+    return 0;
+}
+
+static int opt_insert(struct query_args *A, const struct option *o, const char *v) {
+    uint64_t lo = 0, hi = 0;
+    char buf[48];
+    const char *comma = strchr(v, ',');
+    if (!comma || (size_t)(comma - v) >= sizeof buf) { fprintf(stderr, "--insert: LO,HI, two template lengths\n"); return 1; }
+    memcpy(buf, v, (size_t)(comma - v)); buf[comma - v] = 0;
+    if (parse_u64(buf, &lo) || parse_u64(comma + 1, &hi) || lo > hi || hi < 1 || hi > DEBWT_FM_INSERT_MAX) {
+        fprintf(stderr, "--insert: LO,HI with LO <= HI, HI in 1..%u\n", DEBWT_FM_INSERT_MAX);
+        return 1;
+    }
+    A->po.ins_lo = (uint32_t)lo; A->po.ins_hi = (uint32_t)hi; A->insert_given = 1;
+    return 0;
+}
+
+static int opt_min_count(struct query_args *A, const struct option *o, const char *v) {
+    A->auto_count = !strcmp(v, "auto");
+    return A->auto_count ? 0 : take(A, o, v);
+}
+
+static int opt_forward(struct query_args *A, const struct option *o, const char *v) {
+    A->ko.flags &= ~DEBWT_FM_BOTH_STRANDS;
+    return 0;
+}
+
+static int opt_kind(struct query_args *A, const struct option *o, const char *v) {          /* --supermaximal, --intervals */
+    if (A->kind_given) { fprintf(stderr, "--supermaximal, --intervals: one of the two\n"); return 1; }
+    A->kind = (uint32_t)o->lo; A->kind_given = 1;
+    return 0;
+}
+
+#define AT(member) offsetof(struct query_args, member)
+#define NUM(member) (sizeof ((struct query_args *)0)->member == 8 ? U64 : U32), AT(member)   /* as wide as the member is */
+#define C(c) (1u << CMD_##c)
+#define MAPS (1u << 31)
+#define PAIR (1u << 30)
+#define PILES (C(PILEUP) | C(CONSENSUS))
+#define GRAPHS (C(GRAPH) | C(UNITIGS))
+_Static_assert(DEBWT_FM_CORRECT_MAX_ROUNDS == 16 && DEBWT_FM_ESA_MAX_K == 4096, "the texts of --rounds and --profile name them");
+static const struct option options[] = {
+    {"-i", ~PAIR, STR, AT(out)},
+    {"--device", ~PAIR, NUM(device), 0, 0, 255, "a GPU ordinal"},
+    {"-t", C(INDEX) | MAPS, NUM(threads), 0, 1, UINT64_MAX, "thread number must be a positive integer", opt_threads},
+    {"--iupac", C(INDEX) | MAPS, NUM(seed), AT(iupac), 0, UINT64_MAX, "a seed"},
+    {"--sa", C(INDEX), NUM(sa_sample), 0, 1, 1024, "a power of two in 1..1024", opt_sa_sample},
+    {"--sa", C(LCP), STR, AT(sa_file)},
+    {"--both-strands", C(COUNT) | C(LOCATE) | C(MEMS) | C(OVERLAPS) | C(KMERS), BITS, AT(flags), AT(search), DEBWT_FM_BOTH_STRANDS},
+    {"--both-strands", GRAPHS, FLAG, AT(both)},
+    {"--best", C(COUNT) | C(LOCATE), BITS, AT(flags), AT(search), DEBWT_FM_BEST_ONLY},
+    {"--mismatches", C(COUNT) | C(LOCATE), NUM(mismatches), AT(search), 0, 4, "a count in 0..4"},
+    {"--records", C(COUNT), FLAG, AT(count_records)},
+    {"--max-hits", C(LOCATE) | C(MEMS), NUM(max_hits), 0, 0, UINT64_MAX, "a count"},
+    {"--min-len", C(MEMS), NUM(mem_len), 0, 1, UINT32_MAX, "a length of at least 1"},
+    {"--min-len", MAPS, NUM(mo.min_len), 0, 1, UINT32_MAX, "a length of at least 1"},
+    {"--min-len", C(REPEATS) | C(MUMS), NUM(min_len), 0, 1, UINT32_MAX, "a length of at least 1"},
+    {"--ref", MAPS, STR, AT(ref)},
+    {"--band", MAPS, NUM(mo.band), 0, 0, 63, "a half-width in 0..63"},
+    {"--max-occ", MAPS, NUM(mo.max_occ), 0, 1, UINT32_MAX, "a count of at least 1"},
+    {"--max-occ", C(REPEATS), NUM(max_occ), 0, 2, UINT64_MAX, "a number of occurrences of at least 2"},
+    {"--min-score", MAPS, NUM(mo.min_score), 0, 0, 0x7FFFFFFF, "a score of at least 0"},
+    {"--chain", MAPS, FLAG, AT(chain)},
+    {"--max-gap", MAPS, NUM(co.max_gap), AT(gap_given), 0, UINT32_MAX, "a length of at least 0"},
+    {"--mate", MAPS | PAIR, STR, AT(mate)},
+    {"--insert", MAPS | PAIR, STR, 0, 0, 0, 0, NULL, opt_insert},
+    {"--no-rescue", MAPS | PAIR, FLAG, AT(no_rescue)},
+    {"--min-mapq", PILES, NUM(min_mapq), 0, 0, 60, "a quality in 0..60"},
+    {"--region", PILES, STR, AT(region)},
+    {"--window", PILES, NUM(window), 0, 1, 1ull << 32, "positions per table, 1..2^32"},
+    {"--min-depth", PILES, NUM(call.min_depth), 0, 0, UINT32_MAX, "a depth of at least 0"},
+    {"--min-permille", PILES, NUM(call.min_permille), 0, 0, 1000, "a share in 0..1000"},
+    {"--variants", C(CONSENSUS), STR, AT(variants)},
+    {"--min-overlap", C(OVERLAPS) | GRAPHS, NUM(min_overlap), 0, 1, UINT32_MAX, "a length of at least 1"},
+    {"--longest", C(OVERLAPS), BITS, AT(flags), 0, DEBWT_FM_OVERLAP_LONGEST},
+    {"--no-self", C(OVERLAPS), FLAG, AT(no_self)},
+    {"--max-mismatches", C(OVERLAPS), NUM(ovl_k), AT(ovl_mm), 0, 4, "a count in 0..4"},
+    {"--max-error-permille", C(OVERLAPS), NUM(ovl_permille), AT(permille_given), 0, 1000, "a rate in 0..1000"},
+    {"--all", C(EXTRACT), FLAG, AT(all)},
+    {"-k", C(KMERS) | C(CORRECT), NUM(ko.k), AT(k_given), 1, UINT32_MAX, "a k-mer length of at least 1"},
+    {"-k", C(SPECTRUM), NUM(ko.k), AT(k_given), 1, 32, "a k-mer length in 1..32"},
+    {"-k", C(DBG), NUM(ko.k), AT(k_given), 1, UINT32_MAX - 1, "a k-mer length in 1..2^32-2"},
+    {"--min-count", C(CORRECT), NUM(ko.min_count), 0, 1, UINT32_MAX, "a count of at least 1", opt_min_count},
+    {"--rounds", C(CORRECT), NUM(ko.max_rounds), 0, 1, DEBWT_FM_CORRECT_MAX_ROUNDS, "a number in 1..16"},
+    {"--forward", C(CORRECT) | C(SPECTRUM), FLAG, 0, 0, 0, 0, NULL, opt_forward},
+    {"--report", C(CORRECT), STR, AT(report)},
+    {"--bins", C(SPECTRUM), NUM(bins), 0, 2, 4096, "a number of bins in 2..4096"},
+    {"--list", C(SPECTRUM), STR, AT(list)},
+    {"--at-least", C(SPECTRUM), NUM(at_least), AT(filter_given), 1, UINT32_MAX, "a multiplicity of at least 1"},
+    {"--at-most", C(SPECTRUM), NUM(at_most), AT(filter_given), 1, UINT32_MAX, "a multiplicity of at least 1"},
+    {"--max-lcp", C(LCP) | C(REPEATS), NUM(max_lcp), 0, 1, UINT32_MAX, "a cap of at least 1"},
+    {"--lcp", C(LCP), STR, AT(lcp_file)},
+    {"--da", C(LCP), STR, AT(da_file)},
+    {"--profile", C(LCP), NUM(profile_k), 0, 1, DEBWT_FM_ESA_MAX_K, "a length in 1..4096"},
+    {"--min-occ", C(REPEATS), NUM(min_occ), 0, 2, UINT64_MAX, "a number of occurrences of at least 2"},
+    {"--supermaximal", C(REPEATS), FLAG, 0, 0, DEBWT_FM_REPEAT_SUPERMAXIMAL, 0, NULL, opt_kind},
+    {"--intervals", C(REPEATS), FLAG, 0, 0, DEBWT_FM_REPEAT_INTERVALS, 0, NULL, opt_kind},
+    {"--seq", C(REPEATS) | C(MUMS), FLAG, AT(seq)},
+    {"--occurrences", C(REPEATS), FLAG, AT(occurrences)},
+    {"--min-records", C(REPEATS) | C(MUMS), NUM(min_records), AT(by_record), 1, UINT64_MAX, "a number of records of at least 1"},
+    {"--max-records", C(REPEATS), NUM(max_records), AT(by_record), 1, UINT64_MAX, "a number of records of at least 1"},
+    {"--unique", C(REPEATS), FLAG, AT(unique), AT(by_record)},
+    {"--fasta", C(DBG), FLAG, AT(fasta)},
+    {"--all-edges", C(GRAPH), FLAG, AT(all_edges)},
+    {"--states", GRAPHS, STR, AT(states)},
+    {"--clean", GRAPHS, FLAG, AT(clean)},
+    {"--max-tip", GRAPHS, NUM(cl.max_tip), AT(clean), 0, UINT32_MAX, "a number of reads of at least 0"},
+    {"--max-bubble", GRAPHS, NUM(cl.max_bubble), AT(clean), 0, UINT32_MAX, "a number of reads of at least 0"},
+    {"--clean-rounds", GRAPHS, NUM(cl.max_rounds), AT(clean), 1, UINT32_MAX, "a number of at least 1"},
+};
+
+/* the row of option `name` for a command of mask `cmds`, or NULL */
+static const struct option *find_option(const char *name, uint32_t cmds) {
+    for (size_t j = 0; j < sizeof options / sizeof *options; j++)
+        if ((options[j].cmds & cmds) && !strcmp(options[j].name, name)) return options + j;
+    return NULL;
+}
+
+/* the defaults of every command, before its options are read */
+static void set_defaults(struct query_args *A, const struct command *c) {
+    memset(A, 0, sizeof *A);
+    A->cmd = c->cmd; A->name = c->name;
+    A->threads = 8; A->sa_sample = 32; A->mem_len = 19; A->min_overlap = 20; A->window = 1ull << 26; A->min_mapq = 20;
+    A->bins = 256; A->at_least = 1; A->at_most = UINT32_MAX; A->min_len = 20; A->kind = DEBWT_FM_REPEAT_MAXIMAL; A->min_occ = 2;
+    debwt_fm_map_defaults(&A->mo); debwt_fm_chain_defaults(&A->co); debwt_fm_pair_defaults(&A->po);
+    debwt_fm_pile_defaults(&A->call); debwt_fm_correct_defaults(&A->ko); debwt_fm_clean_defaults(&A->cl);
+}
+
+/* reads the arguments behind the command into A.  0: done; 1: an option has said what is wrong with it; 2: the usage text does */
+static int parse_options(struct query_args *A, const struct command *c, int argc, char **argv) {
+    const uint32_t me = 1u << c->cmd | (c->maps ? MAPS : 0);
     for (int i = 2; i < argc; i++) {
-        const char *a = argv[i];
+        const char *a = argv[i], *v = NULL;
         if (a[0] != '-' || !a[1]) {
-            if (file) { usage(); return 1; }
-            file = a;
+            if (A->file) return 2;
+            A->file = a;
             continue;
         }
-        if (((mode >= 1 && mode <= 3) || mode == 5 || mode == 7) && !strcmp(a, "--both-strands")) { flags |= DEBWT_FM_BOTH_STRANDS; search = 1; continue; }
-        if ((mode == 1 || mode == 2) && !strcmp(a, "--best")) { flags |= DEBWT_FM_BEST_ONLY; search = 1; continue; }
-        if (mode == 5 && !strcmp(a, "--longest")) { flags |= DEBWT_FM_OVERLAP_LONGEST; continue; }
-        if (mode == 5 && !strcmp(a, "--no-self")) { no_self = 1; continue; }
-        if (mode == 6 && !strcmp(a, "--all")) { all = 1; continue; }
-        if (mode == 9 && !strcmp(a, "--all-edges")) { all_edges = 1; continue; }
-        if ((mode == 9 || mode == 10) && !strcmp(a, "--both-strands")) { graph_both = 1; continue; }
-        if ((mode == 9 || mode == 10) && !strcmp(a, "--clean")) { clean = 1; continue; }
-        if ((mode == 8 || mode == 13) && !strcmp(a, "--forward")) { ko.flags &= ~DEBWT_FM_BOTH_STRANDS; continue; }
-        if (mode == 15 && (!strcmp(a, "--supermaximal") || !strcmp(a, "--intervals"))) {
-            if (kind_given) { fprintf(stderr, "--supermaximal, --intervals: one of the two\n"); return 1; }
-            ra.kind = a[2] == 's' ? DEBWT_FM_REPEAT_SUPERMAXIMAL : DEBWT_FM_REPEAT_INTERVALS; kind_given = 1;
-            continue;
+        const struct option *o = find_option(a, me);
+        if (!o && find_option(a, PAIR)) { fprintf(stderr, "%s: only with map\n", a); return 1; }
+        if (!o || o->kind >= U32) {                       /* a value follows; an option that is none of this command's ends here */
+            if (i + 1 >= argc || !o) return 2;
+            v = argv[++i];
         }
-        if ((mode == 15 || mode == 16) && !strcmp(a, "--seq")) { ra.seq = 1; continue; }
-        if (mode == 15 && !strcmp(a, "--unique")) { ra.unique = 1; ra.by_record = 1; continue; }
-        if (mode == 1 && !strcmp(a, "--records")) { count_records = 1; continue; }
-        if (mode == 15 && !strcmp(a, "--occurrences")) { ra.occurrences = 1; continue; }
-        if (mode == 17 && !strcmp(a, "--fasta")) { dbg_fasta = 1; continue; }
-        if (mapping && !strcmp(a, "--chain")) { chain = 1; continue; }
-        if (mapping && !strcmp(a, "--no-rescue")) { no_rescue = 1; continue; }
-        if (!mapping && (!strcmp(a, "--mate") || !strcmp(a, "--insert") || !strcmp(a, "--no-rescue"))) {
-            fprintf(stderr, "%s: only with map\n", a);
-            return 1;
-        }
-        if (i + 1 >= argc) { usage(); return 1; }
-        const char *v = argv[++i];
-        if (!strcmp(a, "-i")) out = v;
-        else if (!strcmp(a, "--device")) { if (parse_u64(v, &device) || device > 255) { fprintf(stderr, "--device: a GPU ordinal\n"); return 1; } }
-        else if ((mode == 0 || mapping) && !strcmp(a, "-t")) {
-            if (parse_u64(v, &threads) || threads < 1) { fprintf(stderr, "-t: thread number must be a positive integer\n"); return 1; }
-            if (threads > 256) threads = 256;
-        }
-        else if ((mode == 0 || mapping) && !strcmp(a, "--iupac")) { if (parse_u64(v, &seed)) { fprintf(stderr, "--iupac: a seed\n"); return 1; } iupac = 1; }
-        else if (mode == 0 && !strcmp(a, "--sa")) {
-            if (parse_u64(v, &s) || s < 1 || s > 1024 || (s & (s - 1))) { fprintf(stderr, "--sa: a power of two in 1..1024\n"); return 1; }
-        }
-        else if ((mode == 1 || mode == 2) && !strcmp(a, "--mismatches")) {
-            if (parse_u64(v, &K) || K > 4) { fprintf(stderr, "--mismatches: a count in 0..4\n"); return 1; }
-            search = 1;
-        }
-        else if (mapping && !strcmp(a, "--ref")) ref = v;
-        else if (mapping && !strcmp(a, "--band")) {
-            if (parse_u64(v, &v64) || v64 > 63) { fprintf(stderr, "--band: a half-width in 0..63\n"); return 1; }
-            mo.band = (uint32_t)v64;
-        }
-        else if (mapping && !strcmp(a, "--max-occ")) {
-            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-occ: a count of at least 1\n"); return 1; }
-            mo.max_occ = (uint32_t)v64;
-        }
-        else if (mapping && !strcmp(a, "--min-score")) {
-            if (parse_u64(v, &v64) || v64 > 0x7FFFFFFFull) { fprintf(stderr, "--min-score: a score of at least 0\n"); return 1; }
-            mo.min_score = (int32_t)v64;
-        }
-        else if (mapping && !strcmp(a, "--max-gap")) {
-            if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-gap: a length of at least 0\n"); return 1; }
-            co.max_gap = (uint32_t)v64; gap_given = 1;
-        }
-        else if (mapping && !strcmp(a, "--mate")) mate = v;
-        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--min-mapq")) { if (parse_u64(v, &pa.min_mapq) || pa.min_mapq > 60) { fprintf(stderr, "--min-mapq: a quality in 0..60\n"); return 1; } }
-        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--region")) pa.region = v;
-        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--window")) { if (parse_u64(v, &pa.window) || pa.window < 1 || pa.window > (1ull << 32)) { fprintf(stderr, "--window: positions per table, 1..2^32\n"); return 1; } }
-        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--min-depth")) {
-            if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-depth: a depth of at least 0\n"); return 1; }
-            pa.call.min_depth = (uint32_t)v64;
-        }
-        else if (mode >= 11 && mode <= 16 && !strcmp(a, "--min-permille")) {
-            if (parse_u64(v, &v64) || v64 > 1000) { fprintf(stderr, "--min-permille: a share in 0..1000\n"); return 1; }
-            pa.call.min_permille = (uint32_t)v64;
-        }
-        else if (mode == 12 && !strcmp(a, "--variants")) pa.variants = v;
-        else if (mapping && !strcmp(a, "--insert")) {
-            uint64_t lo = 0, hi = 0;
-            char buf[48];
-            const char *comma = strchr(v, ',');
-            if (!comma || (size_t)(comma - v) >= sizeof buf) { fprintf(stderr, "--insert: LO,HI, two template lengths\n"); return 1; }
-            memcpy(buf, v, (size_t)(comma - v)); buf[comma - v] = 0;
-            if (parse_u64(buf, &lo) || parse_u64(comma + 1, &hi) || lo > hi || hi < 1 || hi > DEBWT_FM_INSERT_MAX) {
-                fprintf(stderr, "--insert: LO,HI with LO <= HI, HI in 1..%u\n", DEBWT_FM_INSERT_MAX);
-                return 1;
-            }
-            po.ins_lo = (uint32_t)lo; po.ins_hi = (uint32_t)hi; insert_given = 1;
-        }
-        else if ((mode == 3 || mapping) && !strcmp(a, "--min-len")) {
-            if (parse_u64(v, &min_len) || min_len < 1 || min_len > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
-        }
-        else if ((mode == 5 || mode == 9 || mode == 10) && !strcmp(a, "--min-overlap")) {
-            if (parse_u64(v, &min_overlap) || min_overlap < 1 || min_overlap > 0xFFFFFFFFull) { fprintf(stderr, "--min-overlap: a length of at least 1\n"); return 1; }
-        }
-        else if (mode == 5 && !strcmp(a, "--max-mismatches")) {
-            if (parse_u64(v, &ovl_k) || ovl_k > 4) { fprintf(stderr, "--max-mismatches: a count in 0..4\n"); return 1; }
-            ovl_mm = 1;
-        }
-        else if (mode == 5 && !strcmp(a, "--max-error-permille")) {
-            if (parse_u64(v, &ovl_permille) || ovl_permille > 1000) { fprintf(stderr, "--max-error-permille: a rate in 0..1000\n"); return 1; }
-            permille_given = 1;
-        }
-        else if ((mode == 7 || mode == 8) && !strcmp(a, "-k")) {
-            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "-k: a k-mer length of at least 1\n"); return 1; }
-            ko.k = (uint32_t)v64; k_given = 1;
-        }
-        else if (mode == 13 && !strcmp(a, "-k")) {
-            if (parse_u64(v, &v64) || v64 < 1 || v64 > 32) { fprintf(stderr, "-k: a k-mer length in 1..32\n"); return 1; }
-            ko.k = (uint32_t)v64; k_given = 1;
-        }
-        else if (mode == 17 && !strcmp(a, "-k")) {
-            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFEull) { fprintf(stderr, "-k: a k-mer length in 1..2^32-2\n"); return 1; }
-            ko.k = (uint32_t)v64; k_given = 1;
-        }
-        else if (mode == 13 && !strcmp(a, "--bins")) {
-            if (parse_u64(v, &bins) || bins < 2 || bins > 4096) { fprintf(stderr, "--bins: a number of bins in 2..4096\n"); return 1; }
-        }
-        else if (mode == 13 && !strcmp(a, "--list")) list = v;
-        else if (mode == 13 && !strcmp(a, "--at-least")) {
-            if (parse_u64(v, &at_least) || at_least < 1 || at_least > 0xFFFFFFFFull) { fprintf(stderr, "--at-least: a multiplicity of at least 1\n"); return 1; }
-            filter_given = 1;
-        }
-        else if (mode == 13 && !strcmp(a, "--at-most")) {
-            if (parse_u64(v, &at_most) || at_most < 1 || at_most > 0xFFFFFFFFull) { fprintf(stderr, "--at-most: a multiplicity of at least 1\n"); return 1; }
-            filter_given = 1;
-        }
-        else if ((mode == 15 || mode == 16) && !strcmp(a, "--min-records")) {
-            if (parse_u64(v, &ra.min_records) || ra.min_records < 1) { fprintf(stderr, "--min-records: a number of records of at least 1\n"); return 1; }
-            ra.by_record = 1;
-        }
-        else if (mode == 15 && !strcmp(a, "--max-records")) {
-            if (parse_u64(v, &ra.max_records) || ra.max_records < 1) { fprintf(stderr, "--max-records: a number of records of at least 1\n"); return 1; }
-            ra.by_record = 1;
-        }
-        else if ((mode == 15 || mode == 16) && !strcmp(a, "--min-len")) {
-            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-len: a length of at least 1\n"); return 1; }
-            ra.min_len = (uint32_t)v64;
-        }
-        else if (mode == 15 && !strcmp(a, "--min-occ")) {
-            if (parse_u64(v, &ra.min_occ) || ra.min_occ < 2) { fprintf(stderr, "--min-occ: a number of occurrences of at least 2\n"); return 1; }
-        }
-        else if (mode == 15 && !strcmp(a, "--max-occ")) {
-            if (parse_u64(v, &ra.max_occ) || ra.max_occ < 2) { fprintf(stderr, "--max-occ: a number of occurrences of at least 2\n"); return 1; }
-        }
-        else if ((mode == 14 || mode == 15) && !strcmp(a, "--max-lcp")) {
-            if (parse_u64(v, &max_lcp) || max_lcp < 1 || max_lcp > 0xFFFFFFFFull) { fprintf(stderr, "--max-lcp: a cap of at least 1\n"); return 1; }
-        }
-        else if (mode == 14 && !strcmp(a, "--lcp")) lcp_file = v;
-        else if (mode == 14 && !strcmp(a, "--sa")) esa_sa_file = v;
-        else if (mode == 14 && !strcmp(a, "--da")) da_file = v;
-        else if (mode == 14 && !strcmp(a, "--profile")) {
-            if (parse_u64(v, &profile_k) || profile_k < 1 || profile_k > DEBWT_FM_ESA_MAX_K) { fprintf(stderr, "--profile: a length in 1..%u\n", DEBWT_FM_ESA_MAX_K); return 1; }
-        }
-        else if (mode == 8 && !strcmp(a, "--min-count") && !strcmp(v, "auto")) auto_count = 1;
-        else if (mode == 8 && !strcmp(a, "--min-count")) {
-            auto_count = 0;
-            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--min-count: a count of at least 1\n"); return 1; }
-            ko.min_count = (uint32_t)v64;
-        }
-        else if (mode == 8 && !strcmp(a, "--rounds")) {
-            if (parse_u64(v, &v64) || v64 < 1 || v64 > DEBWT_FM_CORRECT_MAX_ROUNDS) { fprintf(stderr, "--rounds: a number in 1..%d\n", DEBWT_FM_CORRECT_MAX_ROUNDS); return 1; }
-            ko.max_rounds = (uint32_t)v64;
-        }
-        else if (mode == 8 && !strcmp(a, "--report")) report = v;
-        else if ((mode == 9 || mode == 10) && !strcmp(a, "--states")) states = v;
-        else if ((mode == 9 || mode == 10) && !strcmp(a, "--max-tip")) {
-            if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-tip: a number of reads of at least 0\n"); return 1; }
-            cl.max_tip = (uint32_t)v64; clean = 1;
-        }
-        else if ((mode == 9 || mode == 10) && !strcmp(a, "--max-bubble")) {
-            if (parse_u64(v, &v64) || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--max-bubble: a number of reads of at least 0\n"); return 1; }
-            cl.max_bubble = (uint32_t)v64; clean = 1;
-        }
-        else if ((mode == 9 || mode == 10) && !strcmp(a, "--clean-rounds")) {
-            if (parse_u64(v, &v64) || v64 < 1 || v64 > 0xFFFFFFFFull) { fprintf(stderr, "--clean-rounds: a number of at least 1\n"); return 1; }
-            cl.max_rounds = (uint32_t)v64; clean = 1;
-        }
-        else if ((mode == 2 || mode == 3) && !strcmp(a, "--max-hits")) { if (parse_u64(v, &max_hits)) { fprintf(stderr, "--max-hits: a count\n"); return 1; } }
-        else { usage(); return 1; }
+        if (o->fn ? o->fn(A, o, v) : take(A, o, v)) return 1;
     }
-    if (mode == 6) {
-        if (!out || (all != 0) == (file != NULL)) { usage(); return 1; }
-        return cmd_extract(out, file, (int)device);
-    }
-    if (mode == 9 || mode == 10) {
-        if (!out || file || (clean && all_edges)) { usage(); return 1; }
-        if (clean && !cl.max_tip && !cl.max_bubble) { fprintf(stderr, "--clean: --max-tip and --max-bubble are both 0\n"); return 1; }
-        return cmd_graph(out, (int)device, (uint32_t)min_overlap, all_edges, states, mode == 10, graph_both, clean ? &cl : NULL);
-    }
-    if (mode == 13) {
-        if (!out || file) { usage(); return 1; }
-        if (!k_given) { fprintf(stderr, "%s: -k K is required\n", cmd); usage(); return 1; }
-        if (filter_given && !list) { fprintf(stderr, "--at-least, --at-most: only with --list\n"); return 1; }
-        if (at_least > at_most) { fprintf(stderr, "--at-least: above --at-most\n"); return 1; }
-        return cmd_spectrum(out, (int)device, ko.k, ko.flags, (uint32_t)bins, list, (uint32_t)at_least, (uint32_t)at_most);
-    }
-    if (mode == 17) {
-        if (!out || file) { usage(); return 1; }
-        if (!k_given) { fprintf(stderr, "%s: -k K is required\n", cmd); usage(); return 1; }
-        return cmd_dbg(out, (int)device, ko.k, dbg_fasta);
-    }
-    if (mode == 14) {
-        if (!out || file) { usage(); return 1; }
-        if (max_lcp && profile_k > max_lcp) { fprintf(stderr, "--profile: above --max-lcp\n"); return 1; }
-        return cmd_lcp(out, (int)device, (uint32_t)max_lcp, lcp_file, esa_sa_file, da_file, (uint32_t)profile_k);
-    }
-    if (mode == 15 || mode == 16) {
-        if (!out || file) { usage(); return 1; }
-        ra.mums = mode == 16;
-        if (ra.max_occ && ra.max_occ < ra.min_occ) { fprintf(stderr, "--max-occ: below --min-occ\n"); return 1; }
-        if (ra.max_records && ra.max_records < ra.min_records) { fprintf(stderr, "--max-records: below --min-records\n"); return 1; }
-        if (max_lcp && ra.min_len >= max_lcp) { fprintf(stderr, "--min-len: not below --max-lcp (repeats of the capped length are not listed)\n"); return 1; }
-        ra.max_lcp = (uint32_t)max_lcp;
-        return cmd_repeats(out, (int)device, &ra);
-    }
-    if (!out || !file) { usage(); return 1; }
-    if (mapping) {
-        if (!ref) fprintf(stderr, "%s: no --ref INPUT.fa[.gz]: the text is restored from %s.sa and the BWT\n", cmd, out);
-        if (gap_given && !chain) { fprintf(stderr, "--max-gap: only with --chain\n"); return 1; }
-        if (mate && chain) { fprintf(stderr, "--mate: not with --chain (pairs are mapped with the fixed band)\n"); return 1; }
-        if (insert_given && !mate) { fprintf(stderr, "--insert: only with --mate\n"); return 1; }
-        if (no_rescue && !mate) { fprintf(stderr, "--no-rescue: only with --mate\n"); return 1; }
-        mo.min_len = (uint32_t)min_len;
-        if (mate) { po.map = mo; if (no_rescue) po.max_rescue = 0; }
-        if (mode >= 11) {
-            pa.ref = ref; pa.mate = mate; pa.threads = threads; pa.seed = seed; pa.iupac = iupac; pa.chain = chain;
-            pa.consensus = mode == 12; pa.max_gap = co.max_gap; pa.mo = &mo; pa.po = &po;
-            return cmd_pile(out, file, (int)device, &pa);
-        }
-        if (mate) {
-            po.map = mo;
-            if (no_rescue) po.max_rescue = 0;
-            return cmd_map_pairs(out, ref, file, mate, threads, iupac, seed, (int)device, &po);
-        }
-        return cmd_map(out, ref, file, threads, iupac, seed, (int)device, &mo, chain, co.max_gap);
-    }
-    if (mode == 0) return cmd_index(out, file, threads, iupac, seed, (int)device, s);
-    if (mode == 7 || mode == 8) {
-        if (!k_given) { fprintf(stderr, "%s: -k K is required\n", cmd); usage(); return 1; }
-        if (mode == 7) return cmd_kmers(out, file, (int)device, ko.k, flags);
-        return cmd_correct(out, file, (int)device, &ko, auto_count, report);
-    }
-    if (mode == 5) {
-        if (permille_given && !ovl_mm) { fprintf(stderr, "--max-error-permille: only with --max-mismatches\n"); usage(); return 1; }
-        return cmd_overlaps(out, file, (int)device, (uint32_t)min_overlap, flags, no_self, ovl_mm, (uint32_t)ovl_k,
-                            (uint32_t)ovl_permille);
-    }
-    if (mode == 3) return cmd_mems(out, file, (int)device, max_hits, (uint32_t)min_len, flags);
-    if (search && count_records) { fprintf(stderr, "--records: only with exact patterns on one strand\n"); return 1; }
-    if (search) return cmd_search(out, file, (int)device, mode == 2, max_hits, (uint32_t)K, flags);
-    return cmd_query(out, file, (int)device, mode == 2, max_hits, count_records);
+    return 0;
+}
+
+int main(int argc, char **argv) {
+    const struct command *c = NULL;
+    for (size_t j = 0; argc >= 2 && j < sizeof commands / sizeof *commands; j++)
+        if (!strcmp(commands[j].name, argv[1])) c = commands + j;
+    if (!c) { usage(); return 1; }
+    struct query_args A;
+    set_defaults(&A, c);
+    const int rc = parse_options(&A, c, argc, argv);
+    if (rc == 1) return 1;
+    const int file_ok = c->file == FILE_NEEDED ? A.file != NULL : c->file == FILE_NONE ? !A.file : !A.all != !A.file;
+    if (rc || !A.out || !file_ok) { usage(); return 1; }
+    if (c->need_k && !A.k_given) { fprintf(stderr, "%s: -k K is required\n", c->name); usage(); return 1; }
+    return c->run(&A);
 }
