@@ -2802,6 +2802,30 @@ extern "C" int debwt_special_compare(debwt_ctx *c, uint64_t mismatch[6]) {
     return DEBWT_OK;
 }
 
+// The checks every entry point that takes outside row lists makes before it reads a row (debwt_verify_device,
+// fm_build_rank, debwt_verify_inverse): the '$' row and nrec - 1 strictly ascending '#' rows, all below n, the '$' row
+// not among the '#' rows.  Returns the reason of a refusal, or NULL with *sr = the separator rows ('#' rows and the
+// '$' row) ascending.
+static const char *row_lists_refusal(u64 n, u64 nrec, const std::vector<u64> &hr, u64 dollar_row, std::vector<u64> *sr) {
+    if (dollar_row >= n) return "'$' row outside the BWT";
+    if (hr.size() != nrec - 1) return "'#' rows: nrec - 1 rows expected";
+    for (size_t i = 0; i < hr.size(); i++)
+        if (hr[i] >= n || (i && hr[i] <= hr[i - 1]) || hr[i] == dollar_row) return "'#' rows are not ascending rows of the BWT";
+    if (sr) {
+        *sr = hr;
+        sr->insert(std::upper_bound(sr->begin(), sr->end(), dollar_row), dollar_row);
+    }
+    return nullptr;
+}
+// After the rank build: tot[0..3] rows per code, tot[4] separator rows, tot[5] listed rows whose code is not 3
+// (k_vlisted_codes).  With that count zero every occ('T') is a difference of two counts of which the first is the
+// larger, and C[3] + occ('T') stays at or below C[4].
+static const char *row_census_refusal(const u64 tot[6], u64 n, u64 nrec) {
+    if (tot[5]) return "a '#' row or the '$' row holds a code other than 3";
+    if (tot[4] != nrec || tot[0] + tot[1] + tot[2] + tot[3] != n || tot[3] < nrec) return "rank structure: row census is inconsistent";
+    return nullptr;
+}
+
 // Inverse BWT on the device (verify_kernels.h): rank structure over the packed rows, backward search for the segment
 // boundaries, one LF walk per segment against the text in HBM.
 extern "C" int debwt_verify_device(debwt_ctx *c, const uint64_t *d_words, const uint64_t *hash_rows, uint64_t dollar_row,
@@ -2823,11 +2847,8 @@ extern "C" int debwt_verify_device(debwt_ctx *c, const uint64_t *d_words, const 
         if (nrec > 1 && !hash_rows) return DEBWT_EINVAL;
         hr.assign(hash_rows, hash_rows + (nrec - 1));
     }
-    if (dollar_row >= n) { c->err = "'$' row outside the BWT"; return DEBWT_EINVAL; }
-    for (size_t i = 0; i < hr.size(); i++)
-        if (hr[i] >= n || (i && hr[i] <= hr[i - 1])) { c->err = "'#' rows are not ascending rows of the BWT"; return DEBWT_EINVAL; }
-    std::vector<u64> sr(hr);
-    sr.insert(std::upper_bound(sr.begin(), sr.end(), dollar_row), dollar_row);
+    std::vector<u64> sr;
+    if (const char *why = row_lists_refusal(n, nrec, hr, dollar_row, &sr)) { c->err = why; return DEBWT_EINVAL; }
     // rank structure
     const u64 nlines = n / VB_ROWS + 1, nchunks = (nlines + VB_CHUNK - 1) / VB_CHUNK;
     const size_t idx_bytes = (size_t)nlines * VB_LINE * 8;
@@ -2855,11 +2876,12 @@ extern "C" int debwt_verify_device(debwt_ctx *c, const uint64_t *d_words, const 
     k_vidx_count<<<(u32)nchunks, VB_CHUNK, 0, c->stream>>>(bw, n, nlines, d_srows, sr.size(), csum);
     k_vidx_scan<<<1, 1024, 0, c->stream>>>(csum, nchunks, totals);
     k_vidx_write<<<(u32)nchunks, VB_CHUNK, 0, c->stream>>>(bw, n, nlines, d_srows, sr.size(), csum, idx);
-    u64 tot[5];
-    HIPCHK(c, hipMemcpyAsync(tot, totals, 40, hipMemcpyDeviceToHost, c->stream));
+    k_vlisted_codes<<<grid_for(sr.size(), 256), 256, 0, c->stream>>>(bw, d_srows, sr.size(), totals + 5);
+    u64 tot[6];
+    HIPCHK(c, hipMemcpyAsync(tot, totals, 48, hipMemcpyDeviceToHost, c->stream));
     int rc = sync_check(c);
     if (rc) { drop_events(); return rc; }
-    if (tot[4] != nrec || tot[0] + tot[1] + tot[2] + tot[3] != n) { drop_events(); c->err = "rank structure: row census is inconsistent"; return DEBWT_EINTERNAL; }
+    if (const char *why = row_census_refusal(tot, n, nrec)) { drop_events(); c->err = why; return DEBWT_EINVAL; }
     VIndex V{};
     V.idx = idx; V.hash = d_hash; V.srows = d_srows; V.nhash = hr.size(); V.nsep = sr.size(); V.n = n;
     V.C[0] = 0; V.C[1] = tot[0]; V.C[2] = tot[0] + tot[1]; V.C[3] = V.C[2] + tot[2];
@@ -2907,10 +2929,15 @@ extern "C" int debwt_verify_inverse(const uint64_t *bwt, uint64_t n, const uint6
     // dependent steps; here every record is walked by its own thread: the walk that starts at the row of
     // the j-th '#' suffix (row n - nrec + j) spells the record in front of that '#' backwards and stops at the row that
     // carries the previous separator, which names the walk that precedes it in the text.
-    if (!bwt || !sym_out || n < 2 || nrec < 1 || dollar_row >= n) return DEBWT_EINVAL;
+    if (!bwt || !sym_out || n < 2 || nrec < 1 || nrec > n || (nrec > 1 && !hash_rows)) return DEBWT_EINVAL;
+    std::vector<u64> hr, sr;
+    if (nrec > 1) hr.assign(hash_rows, hash_rows + (nrec - 1));
+    if (row_lists_refusal(n, nrec, hr, dollar_row, &sr)) return DEBWT_EINVAL;
     std::vector<uint8_t> L(n);
     for (uint64_t j = 0; j < n; j++) L[j] = (uint8_t)((bwt[j >> 5] >> ((31 - (j & 31)) << 1)) & 3);
-    for (uint64_t h = 0; h + 1 < nrec; h++) { if (hash_rows[h] >= n) return DEBWT_EINVAL; L[hash_rows[h]] = 4; }
+    for (u64 r : sr)
+        if (L[r] != 3) return DEBWT_EINVAL;                    // the format stores code 3 under '#' and '$' (k_vlisted_codes)
+    for (u64 r : hr) L[r] = 4;
     L[dollar_row] = 5;
     uint64_t C[7] = {0}, cnt[6] = {0}, seen[6] = {0};
     for (uint64_t i = 0; i < n; i++) cnt[L[i]]++;
@@ -3082,12 +3109,8 @@ int fm_new(int device, u64 n, u64 nrec, u32 sa_sample, debwt_fm **out, std::stri
 // rank structure of packed rows in HBM (d_words, n rows) with the given '#' rows and '$' row: f->idx, f->rowlists, f->V
 int fm_build_rank(debwt_fm *f, const u64 *d_words, const std::vector<u64> &hr, u64 dollar_row) {
     const u64 n = f->n, nrec = f->nrec;
-    if (dollar_row >= n) { f->err = "'$' row outside the BWT"; return DEBWT_EINVAL; }
-    if (hr.size() != nrec - 1) { f->err = "'#' rows: nrec - 1 rows expected"; return DEBWT_EINVAL; }
-    for (size_t i = 0; i < hr.size(); i++)
-        if (hr[i] >= n || (i && hr[i] <= hr[i - 1]) || hr[i] == dollar_row) { f->err = "'#' rows are not ascending rows of the BWT"; return DEBWT_EINVAL; }
-    std::vector<u64> sr(hr);
-    sr.insert(std::upper_bound(sr.begin(), sr.end(), dollar_row), dollar_row);
+    std::vector<u64> sr;
+    if (const char *why = row_lists_refusal(n, nrec, hr, dollar_row, &sr)) { f->err = why; return DEBWT_EINVAL; }
     const u64 nlines = n / VB_ROWS + 1, nchunks = (nlines + VB_CHUNK - 1) / VB_CHUNK;
     FM_ENSURE(f, f->idx, (size_t)nlines * VB_LINE * 8);
     FM_ENSURE(f, f->rowlists, (size_t)(2 * nrec + 1) * 8);
@@ -3106,15 +3129,14 @@ int fm_build_rank(debwt_fm *f, const u64 *d_words, const std::vector<u64> &hr, u
     k_vidx_scan<<<1, 1024, 0, f->stream>>>(csum, nchunks, totals);
     k_vidx_write<<<(u32)nchunks, VB_CHUNK, 0, f->stream>>>(d_words, n, nlines, d_srows, sr.size(), csum, f->idx.as<u64>());
     (void)hipEventRecord(e1, f->stream);
-    u64 tot[5];
-    HIPCHK(f, hipMemcpyAsync(tot, totals, 40, hipMemcpyDeviceToHost, f->stream));
+    k_vlisted_codes<<<grid_for(sr.size(), 256), 256, 0, f->stream>>>(d_words, d_srows, sr.size(), totals + 5);
+    u64 tot[6];
+    HIPCHK(f, hipMemcpyAsync(tot, totals, 48, hipMemcpyDeviceToHost, f->stream));
     int rc = fm_sync(f);
     if (!rc) (void)hipEventElapsedTime(&f->ms_rank, e0, e1);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (rc) return rc;
-    if (tot[4] != nrec || tot[0] + tot[1] + tot[2] + tot[3] != n || tot[3] < nrec) {
-        f->err = "rank structure: row census is inconsistent"; return DEBWT_EINVAL;
-    }
+    if (const char *why = row_census_refusal(tot, n, nrec)) { f->err = why; return DEBWT_EINVAL; }
     for (int q = 0; q < 4; q++) f->census[q] = tot[q];
     VIndex &V = f->V;
     V = VIndex{};

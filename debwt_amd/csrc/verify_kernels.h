@@ -130,6 +130,16 @@ __global__ __launch_bounds__(VB_CHUNK) void k_vidx_write(const u64 *__restrict__
     for (u32 t = 0; t < VB_WORDS; t++) line[4 + t] = r0 + (u64)t * 32 < n ? bwt[(r0 >> 5) + t] : 0ull;
 }
 
+// The format stores code 3 under every '#' row and the '$' row, and C[] is derived from the census under that rule:
+// *bad += the listed rows (all below n, checked on the host) that hold another code
+__global__ __launch_bounds__(256) void k_vlisted_codes(const u64 *__restrict__ bwt, const u64 *__restrict__ srows, u64 nsep,
+                                                       u64 *__restrict__ bad) {
+    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nsep) return;
+    const u64 r = srows[j];
+    if (((bwt[r >> 5] >> (2 * (31 - (r & 31)))) & 3ull) != 3ull) atomicAdd(bad, 1ull);
+}
+
 struct VIndex {
     const u64 *idx;        // nlines lines
     const u64 *hash;       // rows that hold '#', ascending (nhash)

@@ -452,7 +452,7 @@ int debwt_special_compare(debwt_ctx *ctx, uint64_t mismatch[6]);
 
 /* Verification tool standing in for the dead LFsearch path (src/LFsearch.c:14-48): inverse BWT
  * by LF walk on the host from a fetched result; writes the n symbols (0..5).  Returns 0 when the
- * walk closes. */
+ * walk closes; DEBWT_EINVAL for row lists or listed rows that debwt_verify_device refuses (below). */
 int debwt_verify_inverse(const uint64_t *bwt, uint64_t n, const uint64_t *hash_rows, uint64_t nrec,
                          uint64_t dollar_row, uint8_t *sym_out);
 
@@ -463,7 +463,16 @@ int debwt_verify_inverse(const uint64_t *bwt, uint64_t n, const uint64_t *hash_r
  * compared symbol by symbol with the loaded text and required to end on the row the previous segment starts from --
  * together one chain over all n rows.  d_words: DEVICE packed rows (NULL: the context's own result, with its row
  * lists); hash_rows / dollar_row: OUT.# / OUT.$ (host).  segments 0 = default.  ok = 1: the inverse BWT of the rows is
- * the loaded text. */
+ * the loaded text.
+ * Refused with DEBWT_EINVAL and a reason in debwt_last_error, before any search or walk (debwt_fm_create and
+ * debwt_fm_open make the same checks):
+ *   - dollar_row >= n, or a '#' row >= n;
+ *   - '#' rows that are not strictly ascending (descending or repeated rows);
+ *   - the '$' row among the '#' rows;
+ *   - a '#' row or the '$' row whose stored code is not 3 (the format puts code 3 under both, see debwt_bwt_census);
+ *   - a census with fewer code-3 rows than records.
+ * Rows that pass are walked with a C[] table taken from their own census, so every LF step stays inside [0, n)
+ * whatever the rows hold; bits of the last word beyond row n - 1 are never read as rows. */
 typedef struct {
     uint64_t segments, steps, mismatches, broken_links, search_failures, search_steps;
     float ms_index, ms_search, ms_walk;

@@ -63,11 +63,18 @@ def test_verify_device_agrees_with_host_walk_and_rejects_corruption(api):
         t = torch.from_numpy(bad.view(np.int64)).cuda()
         r = d.verify_device(t.data_ptr(), hrows, drow, segments=64)
         assert not r["inverse_bwt_ok"], (trial, i, j, r)
-    # (b) a wrong '#' row, (c) a wrong '$' row
+    # (b) a wrong '#' row, (c) a wrong '$' row: a failed walk, or -- where the moved entry lands on the other list's row
+    # or on a row whose code is not 3 -- DEBWT_EINVAL before any walk (tests/test_gpu_verify_mutants.py has every such move)
+    def refused(hash_rows, dollar_row):
+        try:
+            return not d.verify_device(good.data_ptr(), hash_rows, dollar_row, segments=64)["inverse_bwt_ok"]
+        except api.DebwtError as e:
+            return e.code == -1
     h2 = hrows.copy()
     h2[1] = h2[1] + 1 if h2[1] + 1 < h2[2] else h2[1] - 1
-    assert not d.verify_device(good.data_ptr(), h2, drow, segments=64)["inverse_bwt_ok"]
-    assert not d.verify_device(good.data_ptr(), hrows, (drow + 5) % n, segments=64)["inverse_bwt_ok"]
+    assert refused(h2, drow)
+    assert refused(hrows, (drow + 5) % n)
+    assert d.verify_device(good.data_ptr(), hrows, drow, segments=64)["inverse_bwt_ok"]       # and no refusal leaves a trace
     d.close()
 
 
