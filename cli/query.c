@@ -171,7 +171,7 @@
 
 /* the subcommands; bit c of an option's mask (struct option, below) stands for command c */
 enum cmd { CMD_INDEX, CMD_COUNT, CMD_LOCATE, CMD_MEMS, CMD_MAP, CMD_PILEUP, CMD_CONSENSUS, CMD_OVERLAPS, CMD_EXTRACT, CMD_KMERS,
-           CMD_CORRECT, CMD_SPECTRUM, CMD_LCP, CMD_REPEATS, CMD_MUMS, CMD_DBG, CMD_GRAPH, CMD_UNITIGS };
+           CMD_CORRECT, CMD_SPECTRUM, CMD_LCP, CMD_REPEATS, CMD_MUMS, CMD_DBG, CMD_GRAPH, CMD_UNITIGS, CMD_BIDBG };
 
 /* everything the command line says: set_defaults() fills it, the option table writes into it, the commands read it */
 struct query_args {
@@ -192,7 +192,7 @@ struct query_args {
     /* repeats, mums.  by_record: --min-records, --max-records or --unique was given (a column `rec` then follows `occ`);
      * min_records 0 stands for 1, and under mums for every record of the index */
     uint32_t min_len, kind; uint64_t min_occ, max_occ, min_records, max_records; int seq, occurrences, unique, by_record, kind_given;
-    int fasta;                                                              /* dbg */
+    int fasta;                                                              /* dbg, bidbg */
     int all_edges, both, clean; const char *states; debwt_fm_clean_opts cl; /* graph, unitigs */
 };
 
@@ -219,6 +219,7 @@ static void usage(void) {
             "                          [--max-lcp C] [--seq] [--occurrences] [--min-records Q] [--max-records Q] [--unique]\n"
             "       deBWT-query mums   -i OUT [--device D] [--min-len L] [--min-records Q] [--seq]\n"
             "       deBWT-query dbg    -i OUT -k K [--device D] [--fasta]\n"
+            "       deBWT-query bidbg  -i OUT -k K [--device D] [--fasta]\n"
             "       deBWT-query graph  -i OUT [--device D] [--min-overlap L] [--all-edges] [--both-strands] [--states FILE]\n"
             "                          [--clean] [--max-tip N] [--max-bubble N] [--clean-rounds R]\n"
             "       deBWT-query unitigs -i OUT [--device D] [--min-overlap L] [--both-strands] [--states FILE]\n"
@@ -276,6 +277,9 @@ static void usage(void) {
             "S<TAB>u<TAB>string<TAB>LN:i:len<TAB>KC:i:k-mer occurrences[<TAB>CL:Z:circular] per unitig, in the order of their first\n"
             "K-mers, L<TAB>a<TAB>+<TAB>b<TAB>+<TAB><K-1>M per edge; --fasta writes the unitigs alone under >uJ nodes=N kc=C [circular];\n"
             "stderr gets one # line with nodes, unitigs, edges, the longest unitig and N50;\n"
+            "bidbg writes the graph over both strands (odd K): a K-mer and its reverse complement are one node, S lines in the\n"
+            "order of their lowest K-mer that occurs, L<TAB>a<TAB>+|-<TAB>b<TAB>+|-<TAB><K-1>M per edge (- reads the unitig reverse-\n"
+            "complemented; an edge and its mirror are both listed), and the # line counts the refused hairpins too;\n"
             "graph writes GFA 1: S lines for the records that are neither duplicates nor contained, L lines a + b + <L>M for the\n"
             "longest overlaps of at least L bases (default 20) that no two other edges explain (--all-edges: all of them);\n"
             "unitigs writes the unbranched paths of that graph as FASTA; --states FILE gets J<TAB>kept|duplicate|contained;\n"
@@ -1701,6 +1705,66 @@ done:
     return ret;
 }
 
+/* the compacted de Bruijn graph over both strands (Definition 14), as GFA 1 or as FASTA: cmd_dbg with oriented edge ends */
+static int cmd_bidbg(const struct query_args *A) {
+    const uint32_t k = A->ko.k;
+    if (!(k & 1u)) { fprintf(stderr, "-k: bidbg takes an odd k-mer length (an even one can be its own reverse complement)\n"); return 1; }
+    debwt_fm *fm = NULL;
+    if (open_index(A->out, A->device, &fm)) return 1;
+    int ret = 1, rc;
+    debwt_fm_cdbg_sizes sz = {0, 0, 0};
+    debwt_fm_unitig *un = NULL;
+    debwt_fm_cdbg_edge *ed = NULL;
+    uint8_t *seq = NULL;
+    uint64_t *len = NULL;
+    debwt_fm_cdbg_both_stats st;
+    if (debwt_fm_esa_build(fm, k + 1, DEBWT_FM_ESA_SA | DEBWT_FM_ESA_DA)) {   /* the call tells lcp = k from lcp > k, no more */
+        fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
+        goto done;
+    }
+    rc = debwt_fm_cdbg_both(fm, k, 0, NULL, 0, NULL, 0, NULL, 0, &sz);
+    if (rc && rc != DEBWT_ERANGE) { fprintf(stderr, "%s\n", debwt_fm_last_error(fm)); goto done; }
+    un = malloc((sz.unitigs ? sz.unitigs : 1) * sizeof *un);
+    ed = malloc((sz.edges ? sz.edges : 1) * sizeof *ed);
+    seq = malloc(sz.seq_bytes ? sz.seq_bytes : 1);
+    len = malloc((sz.unitigs ? sz.unitigs : 1) * sizeof *len);
+    if (!un || !ed || !seq || !len) { fprintf(stderr, "out of memory\n"); goto done; }
+    if (sz.unitigs && debwt_fm_cdbg_both(fm, k, 0, un, sz.unitigs, seq, sz.seq_bytes, ed, sz.edges, &sz)) {
+        fprintf(stderr, "%s\n", debwt_fm_last_error(fm));
+        goto done;
+    }
+    debwt_fm_cdbg_both_stats_get(fm, &st);
+    if (!A->fasta) printf("H\tVN:Z:1.0\n");
+    for (uint64_t u = 0; u < sz.unitigs; u++) {
+        const uint64_t m = (uint64_t)un[u].nodes + k - 1;
+        const int circular = (un[u].flags & DEBWT_FM_CDBG_CIRCULAR) != 0;
+        len[u] = m;
+        if (A->fasta) printf(">u%llu nodes=%u kc=%llu%s\n", (unsigned long long)u, un[u].nodes, (unsigned long long)un[u].kmer_count, circular ? " circular" : "");
+        else printf("S\t%llu\t", (unsigned long long)u);
+        fwrite(seq + un[u].seq_offset, 1, m, stdout);
+        if (A->fasta) putchar('\n');
+        else printf("\tLN:i:%llu\tKC:i:%llu%s\n", (unsigned long long)m, (unsigned long long)un[u].kmer_count, circular ? "\tCL:Z:circular" : "");
+    }
+    if (!A->fasta)
+        for (uint64_t e = 0; e < sz.edges; e++)
+            printf("L\t%u\t%c\t%u\t%c\t%uM\n", ed[e].from >> 1, ed[e].from & 1u ? '-' : '+', ed[e].to >> 1, ed[e].to & 1u ? '-' : '+', k - 1);
+    {
+        uint64_t longest = 0;
+        for (uint64_t u = 0; u < sz.unitigs; u++) longest = len[u] > longest ? len[u] : longest;
+        fprintf(stderr, "# bidbg\tk=%u\tnodes=%llu\tunitigs=%llu\tcircular=%llu\tedges=%llu\thairpins=%llu\tlongest=%llu\tN50=%llu\t"
+                        "rounds=%llu\tnodes %.1f, mates %.1f, links %.1f, rank %.1f, write %.1f ms\n",
+                k, (unsigned long long)st.nodes, (unsigned long long)sz.unitigs, (unsigned long long)st.circular,
+                (unsigned long long)sz.edges, (unsigned long long)st.hairpins, (unsigned long long)longest,
+                (unsigned long long)n50_of(len, sz.unitigs), (unsigned long long)st.jump_rounds, st.ms_nodes, st.ms_mates,
+                st.ms_links, st.ms_rank, st.ms_write);
+    }
+    ret = fflush(stdout) ? 1 : 0;
+done:
+    free(un); free(ed); free(seq); free(len);
+    debwt_fm_destroy(fm);
+    return ret;
+}
+
 /* ---- graph / unitigs --------------------------------------------------------------------------------------------------- */
 
 /* the mirror of oriented node v of the both-strand graph: v ^ 1, or v itself for the one node of a self-rc read */
@@ -1922,6 +1986,7 @@ static const struct command {
     {"dbg",       CMD_DBG,       FILE_NONE,   1, 0, cmd_dbg},
     {"graph",     CMD_GRAPH,     FILE_NONE,   0, 0, run_graph},
     {"unitigs",   CMD_UNITIGS,   FILE_NONE,   0, 0, run_graph},
+    {"bidbg",     CMD_BIDBG,     FILE_NONE,   1, 0, cmd_bidbg},
 };
 
 /* one row per option and meaning: the commands that take it (bit c: command c; MAPS: every command whose row says maps; PAIR:
@@ -2038,7 +2103,7 @@ static const struct option options[] = {
     {"--all", C(EXTRACT), FLAG, AT(all)},
     {"-k", C(KMERS) | C(CORRECT), NUM(ko.k), AT(k_given), 1, UINT32_MAX, "a k-mer length of at least 1"},
     {"-k", C(SPECTRUM), NUM(ko.k), AT(k_given), 1, 32, "a k-mer length in 1..32"},
-    {"-k", C(DBG), NUM(ko.k), AT(k_given), 1, UINT32_MAX - 1, "a k-mer length in 1..2^32-2"},
+    {"-k", C(DBG) | C(BIDBG), NUM(ko.k), AT(k_given), 1, UINT32_MAX - 1, "a k-mer length in 1..2^32-2"},
     {"--min-count", C(CORRECT), NUM(ko.min_count), 0, 1, UINT32_MAX, "a count of at least 1", opt_min_count},
     {"--rounds", C(CORRECT), NUM(ko.max_rounds), 0, 1, DEBWT_FM_CORRECT_MAX_ROUNDS, "a number in 1..16"},
     {"--forward", C(CORRECT) | C(SPECTRUM), FLAG, 0, 0, 0, 0, NULL, opt_forward},
@@ -2059,7 +2124,7 @@ static const struct option options[] = {
     {"--min-records", C(REPEATS) | C(MUMS), NUM(min_records), AT(by_record), 1, UINT64_MAX, "a number of records of at least 1"},
     {"--max-records", C(REPEATS), NUM(max_records), AT(by_record), 1, UINT64_MAX, "a number of records of at least 1"},
     {"--unique", C(REPEATS), FLAG, AT(unique), AT(by_record)},
-    {"--fasta", C(DBG), FLAG, AT(fasta)},
+    {"--fasta", C(DBG) | C(BIDBG), FLAG, AT(fasta)},
     {"--all-edges", C(GRAPH), FLAG, AT(all_edges)},
     {"--states", GRAPHS, STR, AT(states)},
     {"--clean", GRAPHS, FLAG, AT(clean)},

@@ -202,6 +202,16 @@ class DebwtFmCdbgStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DebwtFmCdbgBothStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_uint64) for n in ("nodes", "edge_strings", "unitigs", "circular", "links", "edges", "longest_nodes",
+                                                 "seq_bytes", "present", "mated", "hairpins", "jump_rounds", "jump_steps",
+                                                 "jump_wave_steps", "rank_lines", "mate_steps", "edge_keys", "scratch_bytes")] +
+                [(n, ctypes.c_float) for n in ("ms_nodes", "ms_mates", "ms_links", "ms_rank", "ms_write", "ms_wall")])
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 CORRECT_MAX_ROUNDS = 16
 
 
@@ -453,7 +463,8 @@ SYMBOLS = [
     "debwt_fm_esa_build", "debwt_fm_esa_fetch", "debwt_fm_esa_summary_get", "debwt_fm_esa_profile", "debwt_fm_esa_release",
     "debwt_fm_esa_stats_get", "debwt_fm_repeats", "debwt_fm_repeat_stats_get",
     "debwt_fm_records_build", "debwt_fm_records_fetch", "debwt_fm_record_counts", "debwt_fm_repeats_records",
-    "debwt_fm_records_stats_get", "debwt_fm_cdbg", "debwt_fm_cdbg_stats_get",
+    "debwt_fm_records_stats_get", "debwt_fm_cdbg", "debwt_fm_cdbg_stats_get", "debwt_fm_cdbg_both",
+    "debwt_fm_cdbg_both_stats_get",
     "debwt_fm_string_graph", "debwt_fm_edges_reduce", "debwt_fm_unitigs", "debwt_fm_graph_stats_get",
     "debwt_fm_string_graph_both", "debwt_fm_unitigs_both", "debwt_fm_graph_both_stats_get",
     "debwt_fm_clean_defaults", "debwt_fm_graph_clean", "debwt_fm_edges_compact", "debwt_fm_clean_stats_get",
@@ -798,6 +809,10 @@ def lib():
                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(DebwtFmCdbgSizes)]
     L.debwt_fm_cdbg_stats_get.restype = ctypes.c_int
     L.debwt_fm_cdbg_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmCdbgStats)]
+    L.debwt_fm_cdbg_both.restype = ctypes.c_int
+    L.debwt_fm_cdbg_both.argtypes = L.debwt_fm_cdbg.argtypes
+    L.debwt_fm_cdbg_both_stats_get.restype = ctypes.c_int
+    L.debwt_fm_cdbg_both_stats_get.argtypes = [vp, ctypes.POINTER(DebwtFmCdbgBothStats)]
     u8p, edgep = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(DebwtFmEdge)
     L.debwt_fm_string_graph.restype = ctypes.c_int
     L.debwt_fm_string_graph.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, u8p, u64p, edgep, ctypes.c_uint64]

@@ -573,6 +573,14 @@ class FMIndex:
         self._chk(self._L.debwt_fm_cdbg_stats_get(self._h, ctypes.byref(st)))
         return st.as_dict()
 
+    def cdbg_both_stats(self):
+        """What the last EsaResult.cdbg(k, strands="both") did (debwt_fm_cdbg_both_stats_get): the counting fields of
+        cdbg_stats over reported unitigs and canonical nodes, present, mated, hairpins, the ranking's rounds and steps, rank
+        lines, mate_steps, edge_keys, scratch bytes, ms per phase and wall ms."""
+        st = _lib.DebwtFmCdbgBothStats()
+        self._chk(self._L.debwt_fm_cdbg_both_stats_get(self._h, ctypes.byref(st)))
+        return st.as_dict()
+
     def records_stats(self):
         """What the last EsaResult.records_build did (debwt_fm_records_stats_get): rows, pairs (rows whose record occurs in
         an earlier row), records_present, sort_passes, levels and fanout of the hierarchy (DEBWT_FM_REPEAT_FANOUT),
@@ -1681,22 +1689,27 @@ class EsaResult:
         q = self._x.info()["nrec"] if min_records is None else int(min_records)
         return self.repeats_by_record(min_len=min_len, min_occ=max(q, 2), kind="maximal", min_records=q, unique=True)
 
-    def cdbg(self, k):
-        """The compacted de Bruijn graph of the collection's k-mers, forward strand (debwt_fm_cdbg, Definition 13).  Needs
-        esa(sa=True, da=True) with max_lcp 0 or at least k + 1.  Returns a CdbgResult."""
+    def cdbg(self, k, strands="forward"):
+        """The compacted de Bruijn graph of the collection's k-mers.  strands="forward": Definition 13 (debwt_fm_cdbg), a
+        k-mer and its reverse complement are two nodes.  strands="both": Definition 14 (debwt_fm_cdbg_both), bidirected
+        unitigs over canonical k-mers, k odd; an edge end is 2 * unitig + orientation.  Needs esa(sa=True, da=True) with
+        max_lcp 0 or at least k + 1.  Returns a CdbgResult."""
+        if strands not in ("forward", "both"):
+            raise ValueError('strands must be "forward" or "both"')
         x = self._x
+        call = x._L.debwt_fm_cdbg_both if strands == "both" else x._L.debwt_fm_cdbg
         sz = _lib.DebwtFmCdbgSizes()
-        rc = x._L.debwt_fm_cdbg(x._h, int(k), 0, None, 0, None, 0, None, 0, ctypes.byref(sz))   # the sizing call: ERANGE names the sizes
+        rc = call(x._h, int(k), 0, None, 0, None, 0, None, 0, ctypes.byref(sz))   # the sizing call: ERANGE names the sizes
         if rc != -5:
             x._chk(rc)
         un = np.zeros(sz.unitigs, dtype=UNITIG_DTYPE)
         seq = np.zeros(sz.seq_bytes, dtype=np.uint8)
         ed = np.zeros(sz.edges, dtype=CDBG_EDGE_DTYPE)
         if sz.unitigs:
-            x._chk(x._L.debwt_fm_cdbg(x._h, int(k), 0, un.ctypes.data_as(ctypes.c_void_p), len(un),
-                                      seq.ctypes.data_as(ctypes.c_void_p), len(seq), ed.ctypes.data_as(ctypes.c_void_p), len(ed),
-                                      ctypes.byref(sz)))
-        return CdbgResult(int(k), un[:sz.unitigs], seq[:sz.seq_bytes], ed[:sz.edges])
+            x._chk(call(x._h, int(k), 0, un.ctypes.data_as(ctypes.c_void_p), len(un),
+                        seq.ctypes.data_as(ctypes.c_void_p), len(seq), ed.ctypes.data_as(ctypes.c_void_p), len(ed),
+                        ctypes.byref(sz)))
+        return CdbgResult(int(k), un[:sz.unitigs], seq[:sz.seq_bytes], ed[:sz.edges], strands)
 
     def release(self):
         self._x._chk(self._x._L.debwt_fm_esa_release(self._x._h))
@@ -1705,10 +1718,12 @@ class EsaResult:
 class CdbgResult:
     """What EsaResult.cdbg returns: unitigs (UNITIG_DTYPE: row_lo, seq_offset, kmer_count, nodes, flags with CDBG_CIRCULAR),
     numbered by the string order of their first k-mers; seq, the unitig strings as ASCII bytes packed in that order; edges
-    (CDBG_EDGE_DTYPE: from, to in unitig numbers, ascending).  strings() cuts seq into one str per unitig."""
+    (CDBG_EDGE_DTYPE: from, to in unitig numbers, ascending).  strings() cuts seq into one str per unitig.  With strands =
+    "both" the unitigs are numbered by the row of w* (Definition 14) and an edge end is 2 * unitig + orientation, orientation 1
+    for the unitig read reverse-complemented."""
 
-    def __init__(self, k, unitigs, seq, edges):
-        self.k, self.unitigs, self.seq, self.edges = k, unitigs, seq, edges
+    def __init__(self, k, unitigs, seq, edges, strands="forward"):
+        self.k, self.unitigs, self.seq, self.edges, self.strands = k, unitigs, seq, edges, strands
 
     def strings(self):
         s = self.seq.tobytes().decode()

@@ -39,6 +39,7 @@
 #include "fm_repeat_kernels.h"
 #include "fm_record_kernels.h"
 #include "fm_cdbg_kernels.h"
+#include "fm_bicdbg_kernels.h"
 #include "fm_kmer_kernels.h"
 #include "fm_spectrum_kernels.h"
 #include "fm_graph_kernels.h"
@@ -3037,6 +3038,7 @@ struct debwt_fm {
     DevBuf rec_P;                     // the kept prefix of debwt_fm_records_build, 8 n bytes exactly (counted in device_bytes)
     debwt_fm_records_stats rc_stats{};
     debwt_fm_cdbg_stats dbg_stats{};
+    debwt_fm_cdbg_both_stats bidbg_stats{};
     DevBuf g_coff, g_state, g_hbase, g_raw, g_flag, g_deg, g_oseg, g_edges, g_eoff, g_len, g_keep, g_out, g_ctr;   // string graph
     debwt_fm_graph_stats g_stats{};
     DevBuf b_state, b_self, b_row, b_cnt, b_whb, b_rawbase, b_tbase, b_pos, b_aoff, b_mm, b_cur, b_cat, b_ctr;   // graph over both strands
@@ -7353,6 +7355,271 @@ extern "C" int debwt_fm_cdbg(debwt_fm *f, uint32_t k, uint32_t flags, debwt_fm_u
 extern "C" int debwt_fm_cdbg_stats_get(const debwt_fm *f, debwt_fm_cdbg_stats *out) {
     if (!f || !out) return DEBWT_EINVAL;
     *out = f->dbg_stats;
+    return DEBWT_OK;
+}
+
+// ---- compacted de Bruijn graph over both strands (fm_bicdbg_kernels.h) ------------------------------------------------
+// The launches of debwt_fm_cdbg up to lo[], then mates, masks and links over the 2 x pieces oriented ids, the ranking
+// rounds of debwt_fm_cdbg over those ids, the chain minima and the reported chains, and for a call that takes the graph
+// the unitig records, the strings, and the edge keys sorted and made distinct.
+
+static_assert(FM_BD_NCTR > FM_BD_C_CIRC && FM_BD_C_MATED > FM_DBG_C_EDGES, "the counters of both headers share one array");
+
+extern "C" int debwt_fm_cdbg_both(debwt_fm *f, uint32_t k, uint32_t flags, debwt_fm_unitig *unitigs, uint64_t unitig_capacity,
+                                  uint8_t *seq, uint64_t seq_capacity, debwt_fm_cdbg_edge *edges, uint64_t edge_capacity,
+                                  debwt_fm_cdbg_sizes *sizes) {
+    if (!f) return DEBWT_EINVAL;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!sizes) { f->err = "debwt_fm_cdbg_both: sizes must not be NULL"; return DEBWT_EINVAL; }
+    if (!k) { f->err = "debwt_fm_cdbg_both: k must be at least 1"; return DEBWT_EINVAL; }
+    if (!(k & 1u)) {
+        f->err = "debwt_fm_cdbg_both: k must be odd (a k-mer of even length can be its own reverse complement, a node that is its own mirror)";
+        return DEBWT_EINVAL;
+    }
+    if (flags) { f->err = "debwt_fm_cdbg_both: unknown flags"; return DEBWT_EINVAL; }
+    if ((unitig_capacity && !unitigs) || (seq_capacity && !seq) || (edge_capacity && !edges)) {
+        f->err = "debwt_fm_cdbg_both: an array is NULL with capacity > 0"; return DEBWT_EINVAL;
+    }
+    if (!f->has_esa || !f->esa_lcp.p || !f->esa_sa.p || !f->esa_da.p) {
+        f->err = "debwt_fm_cdbg_both: no build holds lcp, sa and da (debwt_fm_esa_build with DEBWT_FM_ESA_SA | DEBWT_FM_ESA_DA)";
+        return DEBWT_ESTATE;
+    }
+    if ((u64)k + 1 > f->esa_sum.cap) {
+        f->err = "debwt_fm_cdbg_both: k + 1 is above the cap of the build (" + std::to_string(f->esa_sum.cap) + ")"; return DEBWT_EINVAL;
+    }
+    if (f->n >> 31) { f->err = "debwt_fm_cdbg_both: the index has 2^31 rows or more (an oriented id needs one more bit)"; return DEBWT_EINVAL; }
+    f->bidbg_stats = debwt_fm_cdbg_both_stats{};
+    debwt_fm_cdbg_both_stats &st = f->bidbg_stats;
+    HIPCHK(f, hipSetDevice(f->device));
+    int rc;
+    if (!f->has_text && (rc = debwt_fm_restore_text(f))) return rc;
+    const u64 n = f->n, nrec = f->nrec;
+    auto grid = [](u64 m) { return (u32)std::min<u64>(std::max<u64>(grid_for(m, 256), 1), 1u << 20); };
+    auto few = [](u64 m, u64 per) { return (u32)std::min<u64>(std::max<u64>((m + per - 1) / per, 1), 4096); };
+    auto take = [&st](FmTmp &t, size_t bytes) { st.scratch_bytes += bytes; return hipMalloc(&t.p, std::max<size_t>(bytes, 8)); };
+
+    // rows: as debwt_fm_cdbg
+    const u64 nbw = (n >> 6) + 1, rkc = (nbw + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;
+    FmTmp bits, wpre, csum, seps, small;
+    HIPCHK(f, take(bits, (size_t)nbw * 24));
+    HIPCHK(f, take(wpre, (size_t)nbw * 4));
+    HIPCHK(f, take(csum, (size_t)(rkc + 1) * 8));
+    HIPCHK(f, take(seps, (size_t)nrec * 8));
+    HIPCHK(f, take(small, FM_BD_NCTR * 8));
+    u64 *const d_start = reinterpret_cast<u64 *>(bits.p), *const d_node = d_start + nbw, *const d_out = d_node + nbw;
+    u64 *const d_seps = reinterpret_cast<u64 *>(seps.p), *const ctr = reinterpret_cast<u64 *>(small.p);
+    const FmDbgBits S{d_start, reinterpret_cast<u32 *>(wpre.p), reinterpret_cast<u64 *>(csum.p)};
+    std::vector<u64> hs(nrec);                                 // the separator positions
+    for (u64 r = 0; r < nrec; r++) hs[r] = (r + 1 < nrec ? f->rec_starts[r + 1] : n) - 1;
+    const int NEV = 6;
+    hipEvent_t ev[NEV] = {};
+    struct Ev { hipEvent_t *e; ~Ev() { for (int i = 0; i < NEV; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evg{ev};
+    for (int i = 0; i < NEV; i++) HIPCHK(f, hipEventCreate(&ev[i]));
+    HIPCHK(f, hipMemcpyAsync(d_seps, hs.data(), (size_t)nrec * 8, hipMemcpyHostToDevice, f->stream));
+    HIPCHK(f, hipMemsetAsync(bits.p, 0, (size_t)nbw * 24, f->stream));
+    HIPCHK(f, hipMemsetAsync(ctr, 0, FM_BD_NCTR * 8, f->stream));
+    (void)hipEventRecord(ev[0], f->stream);
+    k_fm_cdbg_rows<<<std::min<u32>(grid(n), 8192), 256, 0, f->stream>>>(f->esa_lcp.as<u32>(), f->esa_sa.as<u64>(), f->esa_da.as<u32>(),
+                                                                        d_seps, nrec, n, k, d_start, d_node, d_out, ctr);
+    k_fm_anc_count<<<(u32)rkc, FM_EX_CHUNK_WORDS, 0, f->stream>>>(d_start, nbw, const_cast<u32 *>(S.wpre), const_cast<u64 *>(S.csum));
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(const_cast<u64 *>(S.csum), rkc, const_cast<u64 *>(S.csum) + rkc);
+    u64 hc[FM_BD_NCTR], pieces = 0;
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(&pieces, S.csum + rkc, 8, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    const u64 present = hc[FM_DBG_C_NODES], estr = hc[FM_DBG_C_ESTR];
+    st.present = present;
+    if (!pieces || pieces > n || present > pieces) { f->err = "debwt_fm_cdbg_both: the start bits and their rank differ"; return DEBWT_EINTERNAL; }
+    if (!present) {                                            // every record is shorter than k
+        *sizes = debwt_fm_cdbg_sizes{0, 0, 0};
+        st.ms_wall = (float)fm_ms_since(t0);
+        return DEBWT_OK;
+    }
+
+    // oriented ids: mates, masks, links
+    const u32 P = (u32)pieces;
+    const u64 ids = 2 * pieces;
+    const u64 nbp = (pieces >> 6) + 1, rkp = (nbp + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;
+    FmTmp lo, mate, od, link, hasnext, s0, s1, l0, l1, cmin, wbits, wwpre, wcsum;
+    HIPCHK(f, take(lo, (size_t)(pieces + 1) * 4));
+    HIPCHK(f, take(mate, (size_t)pieces * 4));
+    HIPCHK(f, take(od, (size_t)ids * 4));
+    HIPCHK(f, take(link, (size_t)ids * 4));
+    HIPCHK(f, take(hasnext, (size_t)ids));
+    HIPCHK(f, take(s0, (size_t)ids * 16));
+    HIPCHK(f, take(s1, (size_t)ids * 16));
+    HIPCHK(f, take(l0, (size_t)present * 8));
+    HIPCHK(f, take(l1, (size_t)present * 8));
+    HIPCHK(f, take(cmin, (size_t)ids * 4));
+    HIPCHK(f, take(wbits, (size_t)nbp * 8));
+    HIPCHK(f, take(wwpre, (size_t)nbp * 4));
+    HIPCHK(f, take(wcsum, (size_t)(rkp + 1) * 8));
+    u32 *const d_lo = reinterpret_cast<u32 *>(lo.p), *const d_mate = reinterpret_cast<u32 *>(mate.p), *const d_od = reinterpret_cast<u32 *>(od.p);
+    u32 *const d_link = reinterpret_cast<u32 *>(link.p), *const d_cmin = reinterpret_cast<u32 *>(cmin.p);
+    u8 *const d_next = reinterpret_cast<u8 *>(hasnext.p);
+    uint4 *const d_s[2] = {reinterpret_cast<uint4 *>(s0.p), reinterpret_cast<uint4 *>(s1.p)};
+    u32 *const d_l[2] = {reinterpret_cast<u32 *>(l0.p), reinterpret_cast<u32 *>(l1.p)};
+    const FmDbgBits W{reinterpret_cast<u64 *>(wbits.p), reinterpret_cast<u32 *>(wwpre.p), reinterpret_cast<u64 *>(wcsum.p)};
+    k_fm_cdbg_lo<<<grid(n), 256, 0, f->stream>>>(S, n, P, d_lo);
+    (void)hipEventRecord(ev[1], f->stream);
+    k_fm_bicdbg_mates<<<grid(pieces), 256, 0, f->stream>>>(f->V, d_lo, P, d_node, S, f->esa_sa.as<u64>(), f->text.as<u64>(), k, d_mate, d_od, ctr);
+    (void)hipEventRecord(ev[2], f->stream);
+    HIPCHK(f, hipMemsetAsync(d_next, 0, (size_t)ids, f->stream));
+    HIPCHK(f, hipMemsetAsync(d_link, 0xFF, (size_t)ids * 4, f->stream));
+    HIPCHK(f, hipMemsetAsync(d_cmin, 0xFF, (size_t)ids * 4, f->stream));
+    k_fm_bicdbg_degrees<<<few(pieces, 256), 256, 0, f->stream>>>(f->V, d_lo, P, d_node, S, f->esa_sa.as<u64>(), f->text.as<u64>(), k, d_mate, d_od, d_link, ctr);
+    k_fm_bicdbg_links<<<few(ids, 256), 256, 0, f->stream>>>(d_od, d_mate, d_link, d_next, P, ctr);
+    (void)hipEventRecord(ev[3], f->stream);
+    k_fm_cdbg_init<<<few(ids, FM_DBG_CHUNK), 256, 0, f->stream>>>(d_link, (u32)ids, d_s[0], d_s[1], d_l[0], ctr);
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    const u64 mated = hc[FM_BD_C_MATED], valid = 2 * present - mated, oestr = hc[FM_BD_C_OESTR], links0 = hc[FM_DBG_C_LINKS];
+    if (hc[FM_DBG_C_BAD] || mated > present || (mated & 1) || hc[FM_DBG_C_LIST] != links0 || links0 > valid || (links0 & 1) || oestr > 2 * estr) {
+        f->err = "debwt_fm_cdbg_both: " + std::to_string(hc[FM_DBG_C_BAD]) + " mates or extensions lie in no node, " + std::to_string(mated) +
+                 " mated, " + std::to_string(links0) + " links, " + std::to_string(hc[FM_DBG_C_LIST]) + " listed, " + std::to_string(oestr) +
+                 " oriented edge strings";
+        return DEBWT_EINTERNAL;
+    }
+    st.mated = mated; st.nodes = present - mated / 2; st.edge_strings = oestr; st.hairpins = hc[FM_BD_C_HAIRPINS];
+    st.mate_steps = hc[FM_BD_C_STEPS];
+
+    // ranking: the rounds of debwt_fm_cdbg over the oriented ids
+    u64 cnt = links0, target = links0, fin = 0, cyclen = 0, cycles = 0;
+    int cur = 0, li = 0;
+    for (int phase = 0; phase < 2 && cnt; phase++) {
+        if (phase == 1) {
+            HIPCHK(f, hipMemsetAsync(ctr + FM_DBG_C_LIST, 0, 3 * 8, f->stream));   // the list, finished, cycle lengths
+            k_fm_cdbg_cut<<<few(cnt, FM_DBG_CHUNK), 256, 0, f->stream>>>(d_s[cur], d_link, d_od, d_next, d_l[li], cnt, d_s[0], d_s[1], d_l[1 - li], ctr);
+            HIPCHK(f, hipMemcpyAsync(&cnt, ctr + FM_DBG_C_LIST, 8, hipMemcpyDeviceToHost, f->stream));
+            if ((rc = fm_sync(f))) return rc;
+            li ^= 1; target = cnt; fin = 0; cyclen = 0;
+        }
+        while (fin + cyclen < target) {
+            u64 h4[4];
+            HIPCHK(f, hipMemsetAsync(ctr + FM_DBG_C_LIST, 0, 8, f->stream));
+            k_fm_cdbg_jump<<<few(cnt, FM_DBG_CHUNK), 256, 0, f->stream>>>(d_s[cur], d_s[1 - cur], d_l[li], cnt, d_l[1 - li], ctr);
+            HIPCHK(f, hipMemcpyAsync(h4, ctr + FM_DBG_C_LIST, sizeof h4, hipMemcpyDeviceToHost, f->stream));
+            if ((rc = fm_sync(f))) return rc;
+            st.jump_rounds++; st.jump_steps += cnt; st.jump_wave_steps += (cnt + 63) / 64 * 64;
+            if (h4[0] > cnt || st.jump_rounds > 80) { f->err = "debwt_fm_cdbg_both: the ranking does not end"; return DEBWT_EINTERNAL; }
+            cnt = h4[0]; fin = h4[1]; cyclen = h4[2];
+            if (phase == 0) cycles = h4[3];
+            cur ^= 1; li ^= 1;
+        }
+        if (!cycles) break;
+    }
+    (void)hipEventRecord(ev[4], f->stream);
+    if (cycles > links0 || (cycles & 1)) { f->err = "debwt_fm_cdbg_both: " + std::to_string(cycles) + " oriented cycles"; return DEBWT_EINTERNAL; }
+    const u64 links = (links0 - cycles) / 2;                   // member links of the reported unitigs; the cut links are edges
+    HIPCHK(f, hipMemsetAsync(wbits.p, 0, (size_t)nbp * 8, f->stream));
+    k_fm_bicdbg_mins<<<std::min<u32>(grid(ids), 8192), 256, 0, f->stream>>>(d_s[cur], d_od, P, d_cmin);
+    k_fm_bicdbg_pairs<<<few(ids, 256), 256, 0, f->stream>>>(d_s[cur], d_od, d_link, d_mate, d_cmin, P, const_cast<u64 *>(W.bits), ctr);
+    k_fm_anc_count<<<(u32)rkp, FM_EX_CHUNK_WORDS, 0, f->stream>>>(W.bits, nbp, const_cast<u32 *>(W.wpre), const_cast<u64 *>(W.csum));
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(const_cast<u64 *>(W.csum), rkp, const_cast<u64 *>(W.csum) + rkp);
+    u64 U = 0;
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(&U, W.csum + rkp, 8, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    (void)hipEventElapsedTime(&st.ms_nodes, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&st.ms_mates, ev[1], ev[2]);
+    (void)hipEventElapsedTime(&st.ms_links, ev[2], ev[3]);
+    (void)hipEventElapsedTime(&st.ms_rank, ev[3], ev[4]);
+    if (hc[FM_DBG_C_BAD] || 2 * U != valid - 2 * links || hc[FM_BD_C_REPORTED] != U || oestr < 2 * links || (hc[FM_BD_C_CIRC] * 2 != cycles)) {
+        f->err = "debwt_fm_cdbg_both: " + std::to_string(U) + " reported unitigs, " + std::to_string(hc[FM_BD_C_REPORTED]) + " reported chains, " +
+                 std::to_string(valid) + " oriented nodes, " + std::to_string(links) + " links, " + std::to_string(cycles) + " oriented cycles";
+        return DEBWT_EINTERNAL;
+    }
+    const u64 E = oestr - 2 * links, seq_bytes = st.nodes + U * ((u64)k - 1);
+    st.unitigs = U; st.circular = cycles / 2; st.links = links; st.edges = E; st.longest_nodes = hc[FM_DBG_C_LONGEST];
+    st.seq_bytes = seq_bytes; st.rank_lines = hc[FM_DBG_C_LINES];
+    *sizes = debwt_fm_cdbg_sizes{U, seq_bytes, E};
+    if (unitig_capacity < U || seq_capacity < seq_bytes || edge_capacity < E) {
+        st.ms_wall = (float)fm_ms_since(t0);
+        f->err = "debwt_fm_cdbg_both: a capacity is below its size (" + std::to_string(U) + " unitigs, " + std::to_string(seq_bytes) +
+                 " bytes, " + std::to_string(E) + " edges)";
+        return DEBWT_ERANGE;
+    }
+
+    // the write pass
+    const u64 ntiles = (U + FM_REC_TILE - 1) / FM_REC_TILE;
+    FmTmp dun, dlen, dP, tsum, dseq, ka, kb, rws, dedge, qbits, qwpre, qcsum;
+    HIPCHK(f, take(dun, (size_t)U * sizeof(debwt_fm_unitig)));
+    HIPCHK(f, take(dlen, (size_t)U * 8));
+    HIPCHK(f, take(dP, (size_t)U * 8));
+    HIPCHK(f, take(tsum, (size_t)(ntiles + 1) * 8));
+    HIPCHK(f, take(dseq, (size_t)seq_bytes));
+    debwt_fm_unitig *const d_un = reinterpret_cast<debwt_fm_unitig *>(dun.p);
+    u64 *const d_len = reinterpret_cast<u64 *>(dlen.p), *const d_P = reinterpret_cast<u64 *>(dP.p), *const d_tsum = reinterpret_cast<u64 *>(tsum.p);
+    HIPCHK(f, hipMemsetAsync(dun.p, 0, (size_t)U * sizeof(debwt_fm_unitig), f->stream));
+    k_fm_bicdbg_unitigs<<<std::min<u32>(grid(ids), 8192), 256, 0, f->stream>>>(d_s[cur], d_od, d_mate, d_next, d_lo, d_cmin, P, W, U, k, d_un, d_len);
+    k_fm_rec_tile_sums<u64><<<(u32)ntiles, FM_REC_TILE, 0, f->stream>>>(d_len, U, d_tsum);
+    k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(d_tsum, ntiles, d_tsum + ntiles);
+    k_fm_rec_scan<u64><<<(u32)ntiles, FM_REC_TILE, 0, f->stream>>>(d_len, U, d_tsum, d_P);
+    k_fm_bicdbg_seq<<<grid(ids), 256, 0, f->stream>>>(d_s[cur], d_od, d_lo, d_cmin, P, W, U, k, d_P, d_len, f->esa_sa.as<u64>(),
+                                                      f->text.as<u64>(), n, d_un, reinterpret_cast<u8 *>(dseq.p), seq_bytes);
+    u64 M = 0, distinct = 0;
+    if (E) {
+        const u64 cap = 2 * estr;                              // every forward edge string and its mirror, at most
+        const u32 ub = std::max<u32>(fm_bits_of(2 * U - 1), 1);
+        HIPCHK(f, take(ka, (size_t)cap * 8));
+        HIPCHK(f, take(kb, (size_t)cap * 8));
+        HIPCHK(f, take(rws, radix_workspace_bytes(cap)));
+        HIPCHK(f, take(dedge, (size_t)E * sizeof(debwt_fm_cdbg_edge)));
+        k_fm_bicdbg_edges<<<few(pieces, 256), 256, 0, f->stream>>>(f->V, d_s[cur], d_od, d_mate, d_link, d_lo, d_cmin, P, d_node, S, W, ub,
+                                                                  reinterpret_cast<u64 *>(ka.p), cap, ctr);
+        HIPCHK(f, hipMemcpyAsync(&M, ctr + FM_DBG_C_EDGES, 8, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+        if (M < E || M > cap) {
+            f->err = "debwt_fm_cdbg_both: " + std::to_string(M) + " edge keys for " + std::to_string(E) + " edges and room for " + std::to_string(cap);
+            return DEBWT_EINTERNAL;
+        }
+        const u64 *sorted = reinterpret_cast<u64 *>(ka.p);
+        if (M >= 2) {
+            RadixWorkspace ws{};
+            ws.counts = reinterpret_cast<u32 *>(rws.p);        // chunk histograms only, as debwt_fm_records_build sorts
+            hipError_t e = hipSuccess;
+            sorted = radix_sort_bits(f->stream, reinterpret_cast<u64 *>(ka.p), reinterpret_cast<u64 *>(kb.p), M, 0, (int)(2 * ub), ws, &e);
+            if (e != hipSuccess) { f->err = std::string("debwt_fm_cdbg_both: the key sort: ") + hipGetErrorString(e); return DEBWT_EDEVICE; }
+        }
+        const u64 nbq = (M >> 6) + 1, rkq = (nbq + FM_EX_CHUNK_WORDS - 1) / FM_EX_CHUNK_WORDS;
+        HIPCHK(f, take(qbits, (size_t)nbq * 8));
+        HIPCHK(f, take(qwpre, (size_t)nbq * 4));
+        HIPCHK(f, take(qcsum, (size_t)(rkq + 1) * 8));
+        const FmDbgBits Q{reinterpret_cast<u64 *>(qbits.p), reinterpret_cast<u32 *>(qwpre.p), reinterpret_cast<u64 *>(qcsum.p)};
+        HIPCHK(f, hipMemsetAsync(qbits.p, 0, (size_t)nbq * 8, f->stream));
+        k_fm_bicdbg_uniq<<<std::min<u32>(grid(M), 8192), 256, 0, f->stream>>>(sorted, M, const_cast<u64 *>(Q.bits));
+        k_fm_anc_count<<<(u32)rkq, FM_EX_CHUNK_WORDS, 0, f->stream>>>(Q.bits, nbq, const_cast<u32 *>(Q.wpre), const_cast<u64 *>(Q.csum));
+        k_fm_anc_scan<<<1, 1024, 0, f->stream>>>(const_cast<u64 *>(Q.csum), rkq, const_cast<u64 *>(Q.csum) + rkq);
+        k_fm_bicdbg_edge_out<<<grid(M), 256, 0, f->stream>>>(sorted, M, Q, ub, E, reinterpret_cast<debwt_fm_cdbg_edge *>(dedge.p));
+        HIPCHK(f, hipMemcpyAsync(&distinct, Q.csum + rkq, 8, hipMemcpyDeviceToHost, f->stream));
+        if ((rc = fm_sync(f))) return rc;
+        if (distinct != E) {
+            f->err = "debwt_fm_cdbg_both: " + std::to_string(distinct) + " distinct edge keys, the count said " + std::to_string(E);
+            return DEBWT_EINTERNAL;
+        }
+        HIPCHK(f, hipMemcpyAsync(edges, dedge.p, (size_t)E * sizeof(debwt_fm_cdbg_edge), hipMemcpyDeviceToHost, f->stream));
+    }
+    (void)hipEventRecord(ev[5], f->stream);
+    u64 total = 0;
+    HIPCHK(f, hipMemcpyAsync(hc, ctr, sizeof hc, hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(&total, d_tsum + ntiles, 8, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    if (total != seq_bytes) {
+        f->err = "debwt_fm_cdbg_both: the write pass made " + std::to_string(total) + " bytes, the count said " + std::to_string(seq_bytes);
+        return DEBWT_EINTERNAL;
+    }
+    HIPCHK(f, hipMemcpyAsync(unitigs, dun.p, (size_t)U * sizeof(debwt_fm_unitig), hipMemcpyDeviceToHost, f->stream));
+    HIPCHK(f, hipMemcpyAsync(seq, dseq.p, (size_t)seq_bytes, hipMemcpyDeviceToHost, f->stream));
+    if ((rc = fm_sync(f))) return rc;
+    (void)hipEventElapsedTime(&st.ms_write, ev[4], ev[5]);
+    st.rank_lines = hc[FM_DBG_C_LINES]; st.edge_keys = M;
+    st.ms_wall = (float)fm_ms_since(t0);
+    return DEBWT_OK;
+}
+
+extern "C" int debwt_fm_cdbg_both_stats_get(const debwt_fm *f, debwt_fm_cdbg_both_stats *out) {
+    if (!f || !out) return DEBWT_EINVAL;
+    *out = f->bidbg_stats;
     return DEBWT_OK;
 }
 

@@ -1373,8 +1373,8 @@ int debwt_fm_records_stats_get(const debwt_fm *fm, debwt_fm_records_stats *out);
 
 /* ---- Definition 13 (compacted de Bruijn graph): unitigs and edges of the k-mers of the collection (fm_cdbg_kernels.h) --
  * Rows, sa, da, lcp (the STORED array), d(), L[r] and the symbol order are those of Definitions 10 and 11.  k >= 1.
- * Forward strand only: a k-mer and its reverse complement are two nodes, and nothing joins them (bidirected unitigs over
- * canonical k-mers are not built here).
+ * Forward strand only: a k-mer and its reverse complement are two nodes, and nothing joins them; the bidirected unitigs
+ * over canonical k-mers are Definition 14, debwt_fm_cdbg_both, below.
  *   Node.  A string W of k bases with occ W > 0 inside records: Definition 9, forward, for any k.  Its interval is [i, e)
  *     with lcp[i] < k <= d(sa[i]) and e the next row with lcp < k, or n; occ W = e - i.  A row with d(sa[r]) < k always has
  *     lcp[r] < k: it starts a piece that is no node.
@@ -1437,6 +1437,83 @@ typedef struct {
     float ms_nodes, ms_links, ms_rank, ms_write, ms_wall;
 } debwt_fm_cdbg_stats;
 int debwt_fm_cdbg_stats_get(const debwt_fm *fm, debwt_fm_cdbg_stats *out);
+
+/* ---- Definition 14 (compacted de Bruijn graph over both strands): bidirected unitigs over canonical k-mers
+ * (fm_bicdbg_kernels.h) ------------------------------------------------------------------------------------------------
+ * Let D = (S_0, rc S_0, S_1, rc S_1, ...) be the doubled collection.  D is never built: rows, intervals and occ are those of
+ * the index of S.  k must be odd, so that no k-mer is its own reverse complement.
+ *   Oriented node.  A string W of k bases such that W or rc W occurs inside a record of S (a node of Definition 13).
+ *     mirror(W) = rc W.  W is present when it occurs itself, and mated when rc W occurs too.
+ *   Oriented edge string.  A string E of k + 1 bases such that E or rc E occurs inside a record; it runs from its first k
+ *     bases to its last k.  out2(W) and in2(W) count the distinct oriented edge strings that leave and enter W: the
+ *     successors of W are the right extensions of W in S and the complemented left extensions of rc W in S, the
+ *     predecessors symmetrically, so in2(W) = out2(rc W).
+ *   Link.  u -> w iff out2(u) = 1, w is u's only successor, in2(w) = 1, w != u and w != mirror(u).  The last clause refuses
+ *     a hairpin: an edge string that is its own reverse complement joins a node to its own mirror.  `hairpins` counts the
+ *     edge strings that this clause alone keeps from being links.  Links are closed under u -> w |-> mirror(w) -> mirror(u),
+ *     and no maximal chain or cycle of links holds a node together with its mirror: oriented unitigs come in mirror
+ *     pairs U, U'.
+ *   Reported orientation.  Let w* be the k-mer of the lowest row among the members of U and U' that occur in S; there is
+ *     one, and it lies in exactly one of the two.  The orientation that holds w* is reported, pairs are numbered by
+ *     ascending row of w*, and row_lo is the first row of w*'s interval: strictly ascending.  (w* need not be the first
+ *     node of a linear unitig.)
+ *   Cycle.  A component in which every oriented node has an incoming link.  The reported one starts at w* and is flagged
+ *     DEBWT_FM_CDBG_CIRCULAR; the link into its first node counts as an edge, and so does the mirror of that link.
+ *   Record.  debwt_fm_unitig as it is.  nodes: the canonical k-mers of the chain; kmer_count: the sum over them of
+ *     occ W + occ rc W in S; the string is the first node's k bases and the last base of every later node in the reported
+ *     orientation, a member that does not occur in S spelled as the reverse complement of its mirror's occurrence;
+ *     seq_offset and seq_bytes as in Definition 13.
+ *   Edge.  from = 2a + oa, to = 2b + ob: unitig a is traversed as reported when o = 0 and reverse-complemented when o = 1.
+ *     Every oriented edge string that is no member link runs from the last node of an oriented unitig to the first node of
+ *     one.  The list holds every such pair once, ascending by (from, to), and is closed under (x, y) |-> (y ^ 1, x ^ 1); an
+ *     edge string and its reverse complement that both occur in S give one pair.  A refused hairpin at the end of unitig a
+ *     is the pair (2a, 2a + 1), its own mirror image.
+ * Facts (tests/bicdbg_ref.py asserts them):
+ *   1. the sum of nodes = the distinct canonical k-mers; for k <= 32, debwt_fm_spectrum(k, DEBWT_FM_BOTH_STRANDS).distinct;
+ *   2. 2 x the sum of (nodes - 1) + the number of edges = the number of oriented edge strings;
+ *   3. the sum of kmer_count = the sum over the records S of max(0, |S| - k + 1);
+ *   4. where hairpins = 0 the answer is Definition 13 applied to D with each mirror pair folded into one record.
+ *
+ * The method.  Preconditions as debwt_fm_cdbg: a build with DEBWT_FM_ESA_SA and DEBWT_FM_ESA_DA whose cap is 0 or at least
+ * k + 1, and the text (restored when none is attached); none of the kept arrays changes.  Limit: an index of fewer than
+ * 2^31 rows, since an oriented id needs one bit more than a piece.  Row bits, piece ranks and lo[] are those of Definition
+ * 13.  A present node v has oriented id v, the mirror of an unmated v has id pieces + v, the mirror of a mated v is
+ * mate[v].  Mates: one lane per present node searches its reverse complement backward, reading itself forward from the
+ * text and stepping with the complement, k rank steps.  Degrees: every forward edge string is met once from its target
+ * and ORs itself and its mirror into two 4-bit masks per oriented id (successor bases, predecessor bases), the single
+ * predecessor id beside them.  Links: one lane per oriented id; then the ranking rounds of Definition 13 unchanged over
+ * the 2 x pieces ids.  Pairs: the lowest id of a chain by an atomic minimum aggregated inside a wave; a chain is reported
+ * iff its minimum is below that of the chain of its first node's mirror; the unitig number is the rank over a bitmap with
+ * one bit at each w*.  The unreported chain of a pair is never walked: its ends, and for a cycle the place of its cut,
+ * are read from the reported one through the mirror.  Edges: every forward edge string and its mirror that are no member
+ * links go out as keys, ordered by the stable radix passes, and equal neighbours are dropped by a rank over the bitmap of
+ * the keys that differ from the one before; the number of edges is known before, oriented edge strings - 2 links.  No
+ * result depends on launch geometry or on the order in which atomics arrive (OR, minimum and integer adds).
+ * Scratch, all released before the call returns: 3 n / 8 + n / 16 bytes (three bitmaps over the rows, the rank of one),
+ * 8 nrec, per piece 8 (lo, mate) + 2 x 45 (masks, link, successor mark, chain minimum, two states of 16 bytes) + 3 / 16
+ * bytes, 16 bytes per present node (two lists); a call that writes adds 48 bytes per unitig, seq_bytes, 32 bytes per
+ * forward edge string (two key buffers of 2 x edge strings) + their bitmap, 8 bytes per edge and the radix workspace.
+ * A failed allocation is DEBWT_ENOMEM and leaves the kept arrays as they were.
+ *
+ * Arrays, capacities, the sizing call and the return codes are those of debwt_fm_cdbg; DEBWT_EINVAL in addition for an even
+ * k (debwt_fm_last_error says why) and for an index of 2^31 rows or more.  flags: none defined, must be 0. */
+int debwt_fm_cdbg_both(debwt_fm *fm, uint32_t k, uint32_t flags, debwt_fm_unitig *unitigs, uint64_t unitig_capacity,
+                       uint8_t *seq, uint64_t seq_capacity, debwt_fm_cdbg_edge *edges, uint64_t edge_capacity,
+                       debwt_fm_cdbg_sizes *sizes);
+/* what the last debwt_fm_cdbg_both did.  The counting fields of debwt_fm_cdbg_stats over reported unitigs and canonical
+ * nodes: nodes (canonical k-mers), edge_strings (oriented edge strings = 2 links + edges), unitigs, circular, links (member
+ * links of the reported unitigs), edges, longest_nodes, seq_bytes; present (nodes of S's forward graph), mated (present
+ * nodes whose reverse complement is present too), hairpins; jump_rounds, jump_steps, jump_wave_steps as in
+ * debwt_fm_cdbg_stats over the oriented ids; rank_lines (rank lines read for left counts), mate_steps (rank steps of the
+ * mate search, at most k x present), edge_keys (keys sorted before equal neighbours were dropped; 0 for a sizing call),
+ * scratch_bytes; ms per phase (events: nodes = bits, rank and lo; mates; links = masks and links; rank = the rounds;
+ * write = minima, pairs, unitigs, strings and edges) and host wall time */
+typedef struct {
+    uint64_t nodes, edge_strings, unitigs, circular, links, edges, longest_nodes, seq_bytes, present, mated, hairpins,
+        jump_rounds, jump_steps, jump_wave_steps, rank_lines, mate_steps, edge_keys, scratch_bytes;
+    float ms_nodes, ms_mates, ms_links, ms_rank, ms_write, ms_wall;
+} debwt_fm_cdbg_both_stats;
+int debwt_fm_cdbg_both_stats_get(const debwt_fm *fm, debwt_fm_cdbg_both_stats *out);
 
 /* ---- string graph of the indexed records (fm_graph_kernels.h) --------------------------------------------------------
  * Records S_0 .. S_{nrec-1} are those of the index, numbered as in overlap hits; |S| is the length of S.
